@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- NKA accel_update throughput on MI355X (the BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--vlen 100000000] [--mvec 20]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--vlen 100000000] [--mvec 20] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for every N.  In the plain form with N > 1 this process touches no GPU: it starts
@@ -18,6 +18,17 @@ With N>1 the SAME global vector is sharded by contiguous slices (strong
 scaling, BASELINE configs[3]); the only exchanges are two small RCCL all-reduces
 per update on the kernel stream -- the norm (1 double), then both Gram rows (1+2*mvec)
 -- or ONE of 2+2*mvec doubles in the opt-in fast sum mode (--sums blocked).
+
+A plain run sets up, warms up, times exactly --steps updates and prints the line: the driver's keys
+(`value`, `ms_per_step` = milliseconds per timed update, ...), `roofline` from the events of those
+steps and, with N > 1, the replica check and the per-rank record.  Everything else described below
+(cpu_baseline and the reference-order twin beside it, probe_ceiling, same-run PMC traffic,
+also_f08_rounding, with_drops, out_of_place_entry, sum_mode_*, config2_n1e7_m10, host_array_entry,
+config5_abstract_vector, the exchange latency of a sharded run) is measured with --full only.
+--dump-outputs DIR writes what the last timed update returned to its caller: DIR/f.npy (fp64), all
+of f up to 2^20 elements, else a sample of 2^20 drawn with a fixed seed, whose global indices are
+DIR/f_index.npy.  The inputs depend only on the arguments, so two builds can be compared output for
+output.
 
 Prints ONE JSON line (rank 0) with the driver's keys plus
   roofline     : PHYSICAL fractions only.  Top level = the dominant kernel (PB
@@ -91,6 +102,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
 SEED = 12345
+DUMP_SAMPLE = 1 << 20    # elements of f that --dump-outputs writes at most (8 MB of fp64, + their indices)
 
 
 def parse(argv=None):
@@ -130,7 +142,28 @@ def parse(argv=None):
                     help="plain form, N > 1: seconds the parent waits for the ranks before it kills their process group")
     ap.add_argument("--no-fallback", action="store_true",
                     help="plain form, N > 1: no second attempt with the host-staged all-reduce after a failed one")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the CPU baseline and the compiled "
+                         "reference beside it, the other rounding and sum mode, the other entries and workloads, configs 2 "
+                         "and 5, the probe ceilings, same-run PMC traffic and the exchange latency of a sharded run.  "
+                         "Without it a run sets up, warms up, times --steps updates and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed update returned to its caller (f, in place) "
+                         "as DIR/<name>.npy: all of it up to %d elements, else a fixed seeded sample of that many, with "
+                         "their global indices" % DUMP_SAMPLE)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_index(n_global: int):
+    """The global indices of f that --dump-outputs writes: all of them up to DUMP_SAMPLE elements, else a sample of
+    DUMP_SAMPLE drawn with a fixed seed (the same for every run at this n), ascending."""
+    import numpy as np
+    if n_global <= DUMP_SAMPLE:
+        return np.arange(n_global, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(n_global, DUMP_SAMPLE, replace=False))
 
 
 def host_mem_available_gb():
@@ -870,10 +903,26 @@ def main(argv=None):
     k_steady = m if args.workload == "full" else min(m, args.drop_dim)     # vectors the subspace holds in steady state
     steady = (nv == k_steady)
 
+    if args.dump_outputs:
+        # what the last timed update handed back to its caller: f, accelerated in place in its input row (before any
+        # extra of --full refills the rows)
+        import numpy as np
+        idx = dump_index(n_global)
+        mine = idx[(idx >= lo) & (idx < hi)] - lo
+        vals = pool[(W_all + K - 1) % P][torch.from_numpy(mine).to(dev)].cpu().numpy()
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, vals)          # control plane; the slices are contiguous and in rank order
+            vals = np.concatenate(parts)
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "f.npy"), vals.astype(np.float64))
+            np.save(os.path.join(args.dump_outputs, "f_index.npy"), idx.astype(np.float64))
+
     # an exchange of a sharded update by itself: 2 + 2 mvec doubles through the installed hook (the larger of the default's two), back to back on the kernel
     # stream (device events; max over ranks) -- the latency figure that decides between RCCL and the peer-to-peer exchange
     exchange = None
-    if world > 1 or hook_box[0] != "none":
+    if args.full and (world > 1 or hook_box[0] != "none"):
         # (every rank passes the same two barriers whatever happens locally)
         err, us_local = None, 0.0
         reps = 200 if hook_box[0] != "staged" else 20
@@ -1110,7 +1159,8 @@ def main(argv=None):
             a6.delete()
 
     drops = None
-    headline = world == 1 and (n_global, m) == (10**8, 20) and args.workload == "full" and not args.no_cpu_baseline
+    # everything below that is not the headline figure runs with --full only
+    headline = args.full and world == 1 and (n_global, m) == (10**8, 20) and args.workload == "full" and not args.no_cpu_baseline
     if headline and os.environ.get("NKA_BENCH_SECONDARY", "1") != "0":
         try:
             drops = with_drops_extra()
@@ -1132,7 +1182,7 @@ def main(argv=None):
     # Secondary figure in the same run: the src-F08 rounding (two stored vectors
     # per pair, bit-faithful to F08:397), same workload, same protocol.
     also = None
-    if flavor == "c" and args.workload == "full" and os.environ.get("NKA_BENCH_SECONDARY", "1") != "0":
+    if args.full and flavor == "c" and args.workload == "full" and os.environ.get("NKA_BENCH_SECONDARY", "1") != "0":
         acc.delete()
         acc = make_acc("f08")
         e2, mean2, nv2, nv2_end, _, stats2 = measure(acc)
@@ -1206,14 +1256,14 @@ def main(argv=None):
                     out["config2_n1e7_m10"] = c2
             except Exception as exc:       # an extra, never the measured path
                 out["config2_n1e7_m10"] = {"error": repr(exc)}
-        lean = args.no_cpu_baseline or world > 1            # lean runs skip the CPU leg and the child-process extras
+        lean = not args.full or args.no_cpu_baseline or world > 1      # lean runs skip the CPU leg and the child-process extras
         host_arr = None
         if headline and os.environ.get("NKA_BENCH_SECONDARY", "1") != "0":
             try:
                 host_arr = host_array_extra()
             except Exception as exc:       # an extra, never the measured path
                 host_arr = {"error": repr(exc)}
-        if world > 1 and not args.no_cpu_baseline and os.environ.get("NKA_BENCH_PROBE", "1") != "0":
+        if args.full and world > 1 and not args.no_cpu_baseline and os.environ.get("NKA_BENCH_PROBE", "1") != "0":
             # N > 1: rank 0 adds the same-run streaming ceilings at ITS shard size (a child process on rank 0's GPU after
             # the timed region, while the other ranks wait in the final barrier: ~10 s), so that a scaling record carries
             # what this memory system gives the shard's mixes next to the event-time fractions

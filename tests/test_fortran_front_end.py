@@ -343,6 +343,15 @@ def test_user_dot_product_through_every_front_end(fortran_build, oracle, tmp_pat
 # executables travel to the GPU box with oracle/_ref/).
 # ---------------------------------------------------------------------------
 REFDIR = os.path.join(ROOT, "oracle", "_ref")
+
+
+def _ours_env():
+    """The drop-ins that link libnka_hip.so run against THIS tree's build of it, wherever oracle/_ref was built or put
+    (their run path $ORIGIN/../../nka_amd follows a symlinked oracle/_ref to the directory it points to)."""
+    lib_dir = os.path.join(ROOT, "nka_amd")
+    return dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(d for d in (lib_dir, os.environ.get("LD_LIBRARY_PATH")) if d))
+
+
 CASES = [([], "f08"), (["--nka-vec", "5"], "f08 --nka-vec 5"), (["--sweeps", "4", "--nka-vec", "5"], "f08 --sweeps 4 --nka-vec 5")]
 
 
@@ -368,7 +377,7 @@ def test_reference_array_caller_against_our_module_on_gpu(tmp_path, args, key):
     place of the reference's: every accel_update runs on the MI355X and the
     printed tables equal the compiled reference's."""
     p = subprocess.run([os.path.join(REFDIR, "dropin_example_f08")] + args, cwd=tmp_path, capture_output=True,
-                       text=True, timeout=300)
+                       text=True, timeout=300, env=_ours_env())
     assert p.returncode == 0, p.stdout + p.stderr
     assert p.stdout.splitlines() == _tables()[key]
 
@@ -427,7 +436,8 @@ def test_reference_c_caller_links_unchanged_against_the_c_drop_in_library(tmp_pa
     header untouched -- linked with libnka_c_compat.so (the nine reference symbols over libnka_hip.so) in place of
     nonlinear_krylov_accelerator.c: every nka_accel_update runs on the MI355X and the program prints the
     reference's 403-line reference_output (the accelerated AND the unaccelerated solve) line for line."""
-    p = subprocess.run([os.path.join(REFDIR, "dropin_example_c")], cwd=tmp_path, capture_output=True, text=True, timeout=300)
+    p = subprocess.run([os.path.join(REFDIR, "dropin_example_c")], cwd=tmp_path, capture_output=True, text=True, timeout=300,
+                       env=_ours_env())
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr
     want = open(os.path.join(S.GOLD, "reference_output_C.txt")).read().splitlines()
     got = p.stdout.splitlines()
@@ -441,7 +451,8 @@ def test_reference_f95_caller_against_our_f95_module_on_gpu(tmp_path):
     """Reference src-F95/nka_example.F90, unchanged, with OUR procedural module nka_type (nka_init,
     nka_accel_update, nka_delete over libnka_hip.so) in place of the reference's: the program prints
     src-F95/reference_output (byte-identical to src-C/reference_output: SURVEY.md 4), 403 lines."""
-    p = subprocess.run([os.path.join(REFDIR, "dropin_example_f95")], cwd=tmp_path, capture_output=True, text=True, timeout=300)
+    p = subprocess.run([os.path.join(REFDIR, "dropin_example_f95")], cwd=tmp_path, capture_output=True, text=True, timeout=300,
+                       env=_ours_env())
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr
     want = open(os.path.join(S.GOLD, "reference_output_C.txt")).read().splitlines()
     got = p.stdout.splitlines()
@@ -461,7 +472,7 @@ def test_reference_array_caller_at_other_problem_sizes_against_the_compiled_refe
     norm to 7 digits, reduction, rate) equal to within one unit of its last printed digit (a long run does pass
     through values like 6.9125005 whose seventh digit a difference in the sixteenth decides)."""
     ours = subprocess.run([os.path.join(REFDIR, "dropin_example_f08")] + args, cwd=tmp_path, capture_output=True, text=True,
-                          timeout=600)
+                          timeout=600, env=_ours_env())
     ref = subprocess.run([os.path.join(REFDIR, "nka_example_f08")] + args, cwd=tmp_path, capture_output=True, text=True,
                          timeout=600)
     assert ours.returncode == 0 and ref.returncode == 0, ours.stdout[-500:] + ours.stderr + ref.stderr

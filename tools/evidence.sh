@@ -5,7 +5,7 @@
 # Every step writes under gpurun_out/ (scratch); copy what is to be judged into profiles/rNN/.  A step that is killed by its
 # own timeout starts nothing further (exit code >= 124 is passed on).
 #
-#   suite                       pytest -m gpu, smoke(), default bench.py                       (tools/gpu_check.sh)
+#   suite                       pytest -m gpu, smoke(), bench.py --full                        (tools/gpu_check.sh)
 #   rocprof TAG                 rocprofv3 kernel stats + PMC traffic of bench.py: compact, src-F08 rounding, drops workload
 #   soak MODE SECONDS SEED [W]  tools/fuzz_gpu.py: MODE = array | vector | hostdot | sharded | vector-sharded, W ranks
 #   soak-paired MODE "F:N ..." [W]  the same seeds once per fast sum mode (NKA_FUZZ_FORCE_SUMS)   (tools/soak_compare.py)

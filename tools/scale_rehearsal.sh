@@ -19,7 +19,7 @@ for N in 1 2 4 8; do
   NL=$((100000000 / N))
   PORT=$((PORT + 1))
   NKA_BENCH_FORCE_HOOK=1 NKA_BENCH_SECONDARY=0 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-      --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus 1 --vlen $NL --steps 40 --no-cpu-baseline --allreduce $HOOK --sums $SUMS 2>/dev/null | grep '^{' | tail -1 > /tmp/scale_$N.json
+      --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus 1 --vlen $NL --steps 40 --full --no-cpu-baseline --allreduce $HOOK --sums $SUMS 2>/dev/null | grep '^{' | tail -1 > /tmp/scale_$N.json
   python3 - "$N" /tmp/scale_$N.json <<'PY' | tee -a "$OUT"
 import json, sys
 N, path = int(sys.argv[1]), sys.argv[2]
