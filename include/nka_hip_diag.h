@@ -1,7 +1,7 @@
 /*
  * nka_hip_diag.h -- entry points that exist ONLY in the diagnostic build of the library
- * (nka_amd/libnka_hip_diag.so, compiled with -DNKA_DIAGNOSTIC by `make diag`; the phase stamps additionally
- * need -DNKA_SOLVE_STAMPS, `make stamps`).  The product, libnka_hip.so, does not export them: every choice they
+ * (nka_amd/libnka_hip_diag.so: the product's objects linked with nka_amd/csrc/lab.hip by `make diag`; the phase stamps
+ * additionally need -DNKA_SOLVE_STAMPS, `make stamps`).  The product, libnka_hip.so, does not export them: every choice they
  * override is made automatically there.  They serve in-process A/B measurements
  * (tools/ab_inproc.py: same allocations, same thermal state) and the tests that hold every kernel variant to
  * the same bits.  Same ABI otherwise: include nka_hip.h first.
@@ -32,10 +32,9 @@ extern "C" {
  * Results are bit-identical across variants.
  * "list_word" = 0/1: 0 ignores (and stops publishing) the list word -- the host's own count of the list length
  * only, the behaviour before round 4 (nka_hip_list_bound).
- * Round 5: "pb_reverse" = 0/1: the rolling-window PB walks its tiles from the END of the vectors, the reverse of PA's order
- * (the Infinity-Cache study, profiles/r05/ab_mall_reuse.txt).  "prime_pad": list lengths 23, 29, 31 are primes, the only
- * ring of their window kernels is the whole width (up to 311 VGPRs and scratch in PA): -1 automatic (= 1) both passes run them
- * at the next width with one dead ring slot; 0 = exact widths everywhere (profiles/r05/multipass.txt).  Same bits.
+ * "prime_pad": list lengths 23, 29, 31 are primes, the only ring of their window kernels is the whole width (up to 311 VGPRs
+ * and scratch in PA): -1 automatic (= 1) both passes run them at the next width with one dead ring slot; 0 = exact widths
+ * everywhere (profiles/r05/multipass.txt).  Same bits.
  * "fail_after_solve" = 1: the NEXT update returns NKA_HIP_EHIP right behind its enqueued scalar step, as a failing HIP call
  * there would: the handle must then be poisoned (every later call but destroy: NKA_HIP_ESTATE).
  * "chain_many" = -1/0/1: reference-order sums of the longest vectors by the whole device (k_chain_blocks / _predict / _apply): -1 automatic

@@ -120,7 +120,7 @@ SIGNATURES.update({
 })
 
 
-# include/nka_hip_diag.h: only in the diagnostic build libnka_hip_diag.so (-DNKA_DIAGNOSTIC)
+# include/nka_hip_diag.h: only in the diagnostic build libnka_hip_diag.so (the product's objects + nka_amd/csrc/lab.hip)
 DIAG_SIGNATURES = {
     "nka_hip_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "nka_hip_set_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -159,7 +159,7 @@ _EXTRA = {}
 
 
 def load_diag_at(path: str) -> C.CDLL:
-    """Another build of the diagnostic ABI (e.g. libnka_hip_diag_ft.so, `make -C nka_amd/csrc ftemporal`) as one more
+    """Another build of the diagnostic ABI (e.g. libnka_hip_diag_w4.so, `make -C nka_amd/csrc w4`) as one more
     independent copy of the library in the process: tools/ab_libs.py alternates two builds on the same inputs."""
     path = os.path.abspath(path)
     if path not in _EXTRA:

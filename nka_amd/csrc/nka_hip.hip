@@ -2,22 +2,15 @@
 //
 // The accelerator object (reference: `type nka`, src-F08/nka_type.F90:154-181)
 // keeps ALL of its state on the device: the 2*(mvec+1) slot vectors, the Gram /
-// Cholesky matrix h, the linked lists and the flags.  accel_update enqueues
-//   PA k_dots -> k_finalize_dots -> [all-reduce 2+2*mvec] -> k_solve -> PB k_combine
-// on one HIP stream and returns; nothing is read back.  The host only tracks what
+// Cholesky matrix h, the linked lists and the flags.  By default accel_update enqueues
+//   k_norm_diff -> k_norm_fin -> [all-reduce 1] -> PA k_dots_win -> k_finalize_dots
+//   -> [all-reduce 1+2*mvec] -> k_solve_rows -> PB k_combine_win
+// on one HIP stream and returns; nothing is read back.  The norm pass runs while a
+// pair is pending, the two exchanges only when sharded (sums_rounded; the other
+// forms of the sums: pick_sums_stage).  The host only tracks what
 // it can know without looking: whether a pair is pending, and an upper bound on
 // the list length (used to pick the unroll width of PA/PB).
-#include "../../include/nka_hip.h"
-#include "../../include/nka_hip_ext.h"
-#include "../../include/nka_hip_vec.h"
-#ifdef NKA_DIAGNOSTIC
-#include "../../include/nka_hip_diag.h"
-#endif
-#include "nka_kernels.hpp"
-#include "host_logic.hpp"
-
-#include <hip/hip_runtime.h>
-#include "rccl_dl.hpp"
+#include "handles.hpp"
 
 #include <dlfcn.h>
 
@@ -37,29 +30,15 @@
 using namespace nka;
 
 namespace {
-
 thread_local std::string g_err;
-
-int fail(int code, const std::string &msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      (void)hipGetLastError(); /* reported here: do not leave it for a later hipGetLastError() to find */ \
-      return fail(e_ == hipErrorOutOfMemory ? NKA_HIP_ENOMEM : NKA_HIP_EHIP,                \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                       \
-    }                                                                                       \
-  } while (0)
-
 }  // namespace
 
 namespace nka_detail {
-// shared with vec_ops.hip: one thread-local error string per library
-int set_error(int code, const std::string &msg) { return fail(code, msg); }
+// shared with vec_ops.hip and lab.hip (fail, handles.hpp): one thread-local error string per library
+int set_error(int code, const std::string &msg) {
+  g_err = msg;
+  return code;
+}
 std::string last_error() { return g_err; }
 bool &span_check_failed() {
   thread_local bool flag = false;
@@ -172,108 +151,11 @@ int env_int(const char *name, int dflt) {
 }
 
 using nka_detail::rccl;   // rccl_dl.hpp: RCCL bound at first use, one copy per process
+using nka_detail::chain_many_ready;   // (defined below, declared in handles.hpp: the lab calls them too)
+using nka_detail::chain_many_stage;
+using nka_detail::enqueue_pa;
 
 }  // namespace
-
-struct nka_hip_state {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int64_t n = 0;
-  int32_t mvec = 0;
-  double vtol = 0.01;
-  int flavor = NKA_HIP_FLAVOR_F08;
-  Vecs vs{};
-  Ctl ctl{};
-  double *partials = nullptr;
-  unsigned *tickets = nullptr; // tile-ticket counters of the rolling-window PB (kTicketWords, zero between launches)
-  double *f_stage = nullptr;  // device staging for the host-array entry point
-  double *hd_scratch = nullptr;  // device vector for the operands of a user host dot product (set_host_dot)
-  // what the host knows without reading the device back
-  bool pending = false;
-  int list_ub = 0;            // upper bound on the list length
-  // ... and what the device tells it without being asked: the list word (Ctl::hw, nka_kernels.hpp), one 64-bit word
-  // in pinned host memory that PB of update number u overwrites with (u, list length at its exit).
-  unsigned long long *list_word = nullptr;
-  int64_t seq = 0;            // updates enqueued so far; the next one is number seq + 1
-  int64_t word_valid_after = 0;      // words of updates numbered <= this are stale (restart; a word of 0 = none yet)
-  std::vector<int64_t> relaxed_after;  // relax() calls that dropped a pending pair, by the number of the update before them
-  bool word_off = false;      // the handle's stream was seen capturing (replays change the list behind the word), or
-                              // the diagnostic switch "list_word" = 0
-  // out-of-place updates (nka_hip_accel_update_swap): the slot -> buffer tables live on the device (Ctl::pc); the host
-  // knows only the two buffers it can hand out next
-  bool swapped = false;       // a table entry may differ from base + (slot-1)*stride: host-side accessors read the tables
-  double *spare_w = nullptr, *spare_v = nullptr;   // free buffers the host knows of (given away by the next swap update)
-  bool swap_pending = false;  // the buffers the last swap update displaced have not been collected yet (record word 3)
-  int64_t swap_seq = 0;       // number of that update
-  const double *last_acc = nullptr;   // the accelerated f lent by the last out-of-place update (read only for the caller)
-  std::vector<void *> extra_allocs;   // the two spare buffers allocated at the first swap update (freed at destroy)
-  // Who holds which buffer, as far as the HOST can know it: `taken` = every buffer outside the two slot-major
-  // allocations that a table entry may name (callers' buffers handed in, the two extra allocations); `lent` = the free
-  // buffers handed to the caller for its NEXT input (they may lie anywhere, the slot-major allocations included).  A
-  // buffer may enter an update only if the library does not hold it: it is lent, or it is foreign to both.
-  nka_host::BufferBook book;          // .taken / .lent (host_logic.hpp)
-  bool captured = false;      // the handle's stream was seen capturing: replays re-issue the scalar step with the ARGUMENTS of
-                              // the capture, so from then on it loads the slot -> buffer tables instead of computing them
-  bool solve63_raised = false;   // k_solve_rows<63> has its dynamic-LDS limit raised on this handle's device
-  bool poisoned = false;      // a HIP call failed AFTER the scalar step of an update was enqueued: the lists on the device
-                              // are ahead of the vectors; every later call but destroy returns NKA_HIP_ESTATE
-  // launch geometry
-  int num_cu = 256;
-  int bpc[2] = {0, 0};        // blocks per CU of PA, PB; 0 = automatic (see grid_for)
-  char devname[64] = {0};
-  int pa_pipe = -1;           // form of PA: 0 = k_dots (every load of a tile in flight; any list length), 201..204 = k_dots_win
-                              // (rolling window) with 1..4 blocks per CU, -1 = automatic (see enqueue_pa)
-  int pb_pipe = -1;           // form of PB: 0 = k_combine, 201..204 = k_combine_win, -1 = automatic (see enqueue_pb)
-  int pb_flags = 0;           // kPbNoStoreW | kPbNoStoreF while an out-of-place update is being enqueued, else 0
-  int pb_tile = -1;           // tile width of the rolling-window PB for short lists: -1 automatic (double-width tiles
-                              // when the tickets apply), 1 = 512 elements, 2 = 1024 elements
-  int pb_tickets = -1;        // tile tickets of the rolling-window PB: -1 automatic, 0 static tile mapping,
-                              // 1, 2, 4, 8 = that many ticket counters (see k_combine_win)
-  double *chain_pred = nullptr;   // reference-order sums of the longest vectors (k_chain_blocks ...): per sum and block of 1024, the block
-  void *chain_summ = nullptr;     // sum / the predicted running sum, and the block's summary; allocated at the first such update
-  long long chain_cap = 0;        // (sums x blocks the two arrays hold)
-  int chain_many = -1;            // diagnostic switch "chain_many": -1 automatic (from kChainManyMin elements on), 0 never, 1 whenever blocks exist
-  int chain_walk = 0;         // diagnostic switch "chain_walk": k_chain_sums walks every block element after element (A/B of chain_block_summary / _apply)
-  int pb_reverse = 0;         // diagnostic switch "pb_reverse": the rolling-window PB walks its tiles from the end (kPbReverse)
-  int fail_after_solve = 0;   // diagnostic switch "fail_after_solve": the next update fails as if a HIP call behind its scalar step had
-                              // (the test of the poisoned-handle path: the failure itself cannot be provoked from outside)
-  int prime_pad = -1;         // list lengths 23, 29, 31 (primes: the only ring of their window kernels is the whole width -- up to 311
-                              // VGPRs and scratch in PA, every load of a tile in flight in PB) run the next width with ONE dead ring
-                              // slot: -1 / 1 on (automatic), 0 off.  In-process A/B at n = 1e7 (profiles/r05/multipass.txt): update
-                              // -12.7 % at m = 31, -3.4 % at 29, -0.3 % at 23 (compact); -11 / -4.4 / -2.9 % in the src-F08 rounding
-  bool state_in_global = false;  // mvec > 140: h, c and the links no longer fit the LDS of one CU; the one-lane
-                                 // scalar kernels then work on the control block in global memory (slow, unlimited)
-  bool serial_solve = false;  // NKA_HIP_SERIAL_SOLVE=1: reference loops verbatim on one lane
-  int sum_order = NKA_HIP_SUMS_AUTO;   // nka_hip_set_sum_order: reference-order sums (k_dots_ordered) within one tile / always / never
-  bool debug = false;         // NKA_HIP_DEBUG=1: check defined() on entry of every update, like the
-                              // reference built without -DNDEBUG (F08:257); synchronises
-  // distribution hook
-  nka_hip_allreduce_fn allreduce = nullptr;
-  void *allreduce_ctx = nullptr;
-  ncclComm_t comm = nullptr;
-  // peer-to-peer exchange (nka_hip_p2p_export / _attach; nka_kernels.hpp: struct P2P)
-  P2P p2p{};                          // base == nullptr: none
-  void *p2p_mail = nullptr;           // this rank's mailbox (fine-grained device memory, exported through hipIpc)
-  std::vector<void *> p2p_opened;     // the peers' mailboxes as mapped here (hipIpcCloseMemHandle at detach)
-  void *p2p_dev = nullptr;            // offsets table, exchange counter, status word
-  int p2p_ranks = 0;                  // ranks the mailbox was sized for
-  bool p2p_fused = false;             // the PA being enqueued sends its sums itself (update_impl)
-  int pa_normed = 0;                  // the PA being enqueued sums on the ROUNDED w1' (NKA_HIP_SUMS_BLOCKED_ROUNDED): 0 no, 1 d/s, 3 (1/s)*d
-  int shard_rank = -1, shard_n = 0;   // position of this rank's slice in the global vector (nka_hip_set_shard; set by
-                                      // nka_hip_comm_init_rank too): only the sharded reference-order sums need it
-  bool needs_comm = false;    // a deep copy of an accelerator that reduced through the built-in RCCL communicator: the
-                              // communicator belongs to the original, and rank-local sums would be silently wrong
-  nka_hip_host_dot_fn host_dot = nullptr;   // user dot product on host copies (compatibility path)
-  void *host_dot_ctx = nullptr;
-  // instrumentation
-  // kTimingEvents events per update, in a ring of timing_cap updates
-  int timing_cap = 0;
-  int64_t timing_count = 0;   // updates recorded since set_timing
-  int timing_stride = 1;      // record the events of every stride-th update only (tuning key "timing_stride"):
-  int64_t update_seq = 0;     // four event records widen the kernel boundaries of an update by ~15 us
-  bool timing_this = false;   // the update in progress is a recorded one
-  std::vector<hipEvent_t> ev;
-};
 
 // Entries of the address block (Ctl::pc) are offsets in doubles from vs.w (nka_kernels.hpp).
 static inline long long buffer_offset(const nka_hip_state *a, const double *p) {
@@ -425,9 +307,7 @@ int launch_combine_w(int maxk, const nka_hip_state *a, double *f, int pass, int 
   // serves it beyond that (passes of 32) -- any other width reaches it only through the diagnostic switch pb_pipe = 0
   // and is padded to 32 (same bits).  The two-vector flavours use every width below the ticket threshold (enqueue_pb).
   if constexpr (COMB == 2) {
-#ifdef NKA_DIAGNOSTIC      // (the automatic rule sends every compact list of <= 32 pairs to the window kernel)
     if (maxk <= 4) return launch_combine_1<4, VEC, COMB>(a, f, pass, last);
-#endif
     return launch_combine_1<32, VEC, COMB>(a, f, pass, last);
   }
 #define CASE(K) \
@@ -992,9 +872,11 @@ static int enqueue_solve(nka_hip_t a, int mode, long long swap_w = kNoBuffer, lo
   return 0;
 }
 
+}  // extern "C"
+
 // PA: all inner products in one pure-read pass (F08:266-267, 286-290, 371).
 // Unaligned f (not 16-B aligned) takes scalar loads with the narrow unroll.
-static void enqueue_pa(nka_hip_t a, const double *f, int vec, int older_ub) {
+void nka_detail::enqueue_pa(nka_hip_t a, const double *f, int vec, int older_ub) {
   const int maxl = (vec == 1) ? 4 : (older_ub > kMaxPerPass ? kMaxPerPass : round_up4(older_ub));
   const int npass = std::max(1, (older_ub + maxl - 1) / maxl);
   // Automatic choice, from in-process A/B runs (tools/ab_inproc.py, profiles/r02/ab_inproc_*.txt):
@@ -1026,6 +908,8 @@ static void enqueue_pa(nka_hip_t a, const double *f, int vec, int older_ub) {
     }
   }
 }
+
+extern "C" {
 
 // PB: normalise + combine + ring stores (F08:282-283, 361, 395-404).
 // After the subspace update the list holds at most min(list_ub, mvec) vectors.
@@ -1229,19 +1113,13 @@ static bool held_by_library(const nka_hip_state *a, const double *p) {
   return a->book.held(p, a->n, a->vs.w, a->vs.v, a->vs.stride * (int64_t)(a->mvec + 1));
 }
 
-// Reference-order sums of a SHARDED accelerator (validation mode, VERDICT r4 item 5).  The reference's sum over the global
-// vector is ONE chain of additions through the slices in rank order (its dp is a global dot product, F08:209-219; summed
-// sequentially over the whole vector that is what a single-rank run of the reference computes).  So the ranks take turns:
-// in round r rank r continues the running sums from the prefix over ranks 0..r-1 (k_dots_ordered, carry) while every other
-// rank contributes zeros, and the installed all-reduce hands the new prefix to everybody -- x + 0 + ... + 0 is exact in any
-// order, so ANY hook that sums serves as the chain's transport.  N rounds for the norm (the Gram row needs the GLOBAL s
-// before w1' = d/s can be rounded), N rounds for the rows: 2N small exchanges and the serial walk of the whole global
-// vector per update -- validation speed, bits of the single-rank compiled reference.
+}  // extern "C"
+
 // The longest vectors: the block summaries of every sum by the whole device, then one wavefront per sum applies them
 // (k_chain_blocks / k_chain_predict / k_chain_apply, nka_kernels.hpp).  false: not this way (short vectors, no memory for the
 // block arrays, a capture in progress before they exist) -- the caller takes one compute unit per sum.
 constexpr long long kChainManyMin = 1 << 19;
-static bool chain_many_ready(nka_hip_t a, int nsum_max, long long n = -1) {
+bool nka_detail::chain_many_ready(nka_hip_t a, int nsum_max, long long n) {
   if (n < 0) n = a->n;
   const long long nfull = n / kChainBlock;
   if (a->chain_many == 0 || nfull < 1 || (a->chain_many < 0 && n < kChainManyMin)) return false;
@@ -1261,8 +1139,8 @@ static bool chain_many_ready(nka_hip_t a, int nsum_max, long long n = -1) {
   a->chain_pred = static_cast<double *>(p); a->chain_summ = q; a->chain_cap = need;
   return true;
 }
-static int chain_many_stage(nka_hip_t a, const double *f, int rcp, int set, int with_f, int ub, int nsum, const double *probe = nullptr,
-                            long long n_probe = -1) {
+int nka_detail::chain_many_stage(nka_hip_t a, const double *f, int rcp, int set, int with_f, int ub, int nsum, const double *probe,
+                                 long long n_probe) {
   hipStream_t s = a->stream;
   Vecs vs = a->vs;
   if (n_probe >= 0) vs.n = n_probe;                    // (the diagnostic entry sums arrays of its own length)
@@ -1282,9 +1160,25 @@ static int chain_many_stage(nka_hip_t a, const double *f, int rcp, int set, int 
   return 0;
 }
 
+void nka_detail::chain_sum_probe(nka_hip_t a, const double *x, const double *y, long long n, int walk) {
+  Vecs vs = a->vs;
+  vs.n = n;
+  hipLaunchKernelGGL(k_chain_sums, dim3(1), dim3(kChainThreads), kChainLdsBytes, a->stream, a->ctl, vs, x, 0, (int)kChainProbe, 1, 0, walk, y);
+}
+
+extern "C" {
+
 // (beyond one chunk of k_dots_ordered: one workgroup per sum, k_chain_sums)
 static bool chain_per_sum(const nka_hip_state *a, int rows) { return a->n > ord_chunk(rows); }
 
+// Reference-order sums of a SHARDED accelerator (validation mode, VERDICT r4 item 5).  The reference's sum over the global
+// vector is ONE chain of additions through the slices in rank order (its dp is a global dot product, F08:209-219; summed
+// sequentially over the whole vector that is what a single-rank run of the reference computes).  So the ranks take turns:
+// in round r rank r continues the running sums from the prefix over ranks 0..r-1 (k_dots_ordered, carry) while every other
+// rank contributes zeros, and the installed all-reduce hands the new prefix to everybody -- x + 0 + ... + 0 is exact in any
+// order, so ANY hook that sums serves as the chain's transport.  N rounds for the norm (the Gram row needs the GLOBAL s
+// before w1' = d/s can be rounded), N rounds for the rows: 2N small exchanges and the serial walk of the whole global
+// vector per update -- validation speed, bits of the single-rank compiled reference.
 static int ordered_chain(nka_hip_t a, const double *f, int mode, int older_ub) {
   hipStream_t s = a->stream;
   const int N = a->shard_n, me = a->shard_rank;
@@ -1540,12 +1434,10 @@ static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_
     bool armed = true;
     ~Poison() { if (armed) a->poisoned = true; }
   } poison{a};
-#ifdef NKA_DIAGNOSTIC
-  if (a->fail_after_solve) {
+  if (a->fail_after_solve) {      // (set only through the lab, lab.hip)
     a->fail_after_solve = 0;
-    return fail(NKA_HIP_EHIP, "accel_update: injected failure behind the scalar step (diagnostic switch fail_after_solve)");
+    return fail(NKA_HIP_EHIP, "accel_update: injected failure behind the scalar step (lab switch fail_after_solve)");
   }
-#endif
   if (int rc = record(a, 2)) return rc;
 
   const int comb_ub = a->pending ? std::min(a->list_ub, (int)a->mvec) : a->list_ub;
@@ -1554,7 +1446,7 @@ static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_
     Ctl &c = a->ctl;
     unsigned long long *const hw = c.hw;
     if (a->word_off) c.hw = nullptr;
-    a->pb_flags = (swap_w != kNoBuffer ? (kPbNoStoreW | kPbNoStoreF) : 0) | (a->pb_reverse ? kPbReverse : 0);
+    a->pb_flags = (swap_w != kNoBuffer ? (kPbNoStoreW | kPbNoStoreF) : 0);
     const int rc = enqueue_pb(a, f, vec, comb_ub);
     a->pb_flags = 0;
     c.hw = hw;
@@ -1747,17 +1639,6 @@ int nka_hip_get_state(nka_hip_t a, int32_t *subspace, int32_t *pending, int32_t 
       for (int i = 1; i <= m1; i++) h[(i - 1) + (size_t)(j - 1) * m1] = hh[i * (m1 + 1) + j];
   return 0;
 }
-
-#ifdef NKA_DIAGNOSTIC
-// Diagnostic builds (-DNKA_SOLVE_STAMPS): the s_memtime stamps of the last scalar step.
-int nka_hip_get_stamps(nka_hip_t a, double *out16) {
-  if (!a || !out16) return fail(NKA_HIP_EINVAL, "null argument");
-  HIP_TRY(hipSetDevice(a->device));
-  HIP_TRY(hipMemcpyAsync(out16, a->ctl.stamps(), sizeof(double) * kStamps, hipMemcpyDeviceToHost, a->stream));
-  HIP_TRY(hipStreamSynchronize(a->stream));
-  return 0;
-}
-#endif  // NKA_DIAGNOSTIC
 
 int nka_hip_get_reductions(nka_hip_t a, double *red_out) {
   if (!a || !red_out) return fail(NKA_HIP_EINVAL, "null argument");
@@ -2141,128 +2022,6 @@ int nka_hip_set_timing_stride(nka_hip_t a, int32_t stride) {
   a->update_seq = 0;
   return 0;
 }
-
-#ifdef NKA_DIAGNOSTIC      // ---- the builder's lab: only in libnka_hip_diag.so (include/nka_hip_diag.h) ----
-int nka_hip_set_grid(nka_hip_t a, int32_t pa, int32_t pb) {
-  if (!a) return fail(NKA_HIP_EINVAL, "null handle");
-  const int32_t v[2] = {pa, pb};
-  for (int i = 0; i < 2; i++) {
-    if (v[i] < 0 || v[i] * a->num_cu > kMaxGrid) return fail(NKA_HIP_EINVAL, "blocks per CU out of range");
-    a->bpc[i] = v[i];   // 0 = automatic
-  }
-  return 0;
-}
-
-// start + x[0]*y[0] + x[1]*y[1] + ... as the per-sum reference-order kernel forms it (k_chain_sums on one workgroup),
-// over ANY two device arrays: the test bench of chain_block_summary / _apply (walk = 1: every block element after element).
-int nka_hip_debug_chain_sum(nka_hip_t a, const double *x, const double *y, int64_t n, double start, int32_t walk, double *sum,
-                            float *ms) {
-  if (!a || !sum || n < 0 || (n > 0 && (!x || !y))) return fail(NKA_HIP_EINVAL, "bad argument");
-  HIP_TRY(hipSetDevice(a->device));
-  Vecs vs = a->vs;
-  vs.n = n;
-  double *slot = a->ctl.red() + 2 + a->mvec;
-  struct Events {          // (destroyed on EVERY exit)
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) hipEventDestroy(x); }
-  } ev;
-  hipEvent_t &e0 = ev.e[0], &e1 = ev.e[1];
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  HIP_TRY(hipMemcpyAsync(slot, &start, sizeof(double), hipMemcpyHostToDevice, a->stream));
-  HIP_TRY(hipStreamSynchronize(a->stream));
-  const bool many = (walk & 2) != 0;                    // (bit 1: through k_chain_blocks / _predict / _apply)
-  if (many) {
-    const int keep = a->chain_many;
-    a->chain_many = 1;
-    const bool ready = chain_many_ready(a, 1, n);
-    a->chain_many = keep;
-    if (!ready) return fail(NKA_HIP_EINVAL, "debug_chain_sum: no full block, or no memory for the block arrays");
-  }
-  HIP_TRY(hipEventRecord(e0, a->stream));
-  if (many) {
-    const int keepw = a->chain_walk;
-    a->chain_walk = walk & 1;
-    const int rc = chain_many_stage(a, x, 0, (int)kChainProbe, 1, 0, 1, y, n);
-    a->chain_walk = keepw;
-    if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL(k_chain_sums, dim3(1), dim3(kChainThreads), kChainLdsBytes, a->stream, a->ctl, vs, x, 0, (int)kChainProbe, 1, 0, (int)(walk & 1), y);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e1, a->stream));
-  HIP_TRY(hipMemcpyAsync(sum, slot, sizeof(double), hipMemcpyDeviceToHost, a->stream));
-  HIP_TRY(hipStreamSynchronize(a->stream));
-  if (ms) HIP_TRY(hipEventElapsedTime(ms, e0, e1));
-  return 0;
-}
-
-// Measurement aid: the PA launches of the NEXT update, `reps` times back to back on the
-// handle's stream, timed with HIP events (mean ms per repetition).  PA only writes
-// scratch (partials, red[]), so the state is unchanged.
-int nka_hip_debug_time_pa(nka_hip_t a, const double *f, int32_t reps, float *ms_mean) {
-  if (!a || !f || !ms_mean || reps < 1) return fail(NKA_HIP_EINVAL, "bad argument");
-  HIP_TRY(hipSetDevice(a->device));
-  if (int rc = nka_detail::check_device_span(f, a->n, "debug_time_pa: f")) return rc;
-  const int vec = (reinterpret_cast<uintptr_t>(f) % 16) == 0 ? 2 : 1;
-  const int older_ub = a->pending ? std::max(a->list_ub - 1, 0) : a->list_ub;
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  enqueue_pa(a, f, vec, older_ub);   // warm
-  HIP_TRY(hipEventRecord(e0, a->stream));
-  for (int r = 0; r < reps; r++) enqueue_pa(a, f, vec, older_ub);
-  HIP_TRY(hipEventRecord(e1, a->stream));
-  HIP_TRY(hipStreamSynchronize(a->stream));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  *ms_mean = ms / reps;
-  return 0;
-}
-
-int nka_hip_set_tuning(nka_hip_t a, const char *key, int32_t value) {
-  if (!a || !key) return fail(NKA_HIP_EINVAL, "null argument");
-  const std::string k(key);
-  if (k == "pb_pipe") {
-    if (value != -1 && value != 0 && !(value > 200 && value <= 204))
-      return fail(NKA_HIP_EINVAL, "pb_pipe: -1 (auto), 0 (every load of a tile in flight), 201..204 (rolling window, 1..4 blocks per CU)");
-    a->pb_pipe = value;
-  } else if (k == "pa_pipe") {
-    if (value != -1 && value != 0 && !(value > 200 && value <= 204))
-      return fail(NKA_HIP_EINVAL, "pa_pipe: -1 (auto), 0 (every load of a tile in flight), 201..204 (rolling window, 1..4 blocks per CU)");
-    a->pa_pipe = value;
-  } else if (k == "pb_tile") {
-    if (value != -1 && value != 1 && value != 2) return fail(NKA_HIP_EINVAL, "pb_tile: -1 (auto), 1, 2");
-    a->pb_tile = value;
-  } else if (k == "pb_tickets") {
-    if (value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
-      return fail(NKA_HIP_EINVAL, "pb_tickets: -1 (auto), 0 (static tile mapping), 1, 2, 4, 8 (ticket counters)");
-    a->pb_tickets = value;
-  } else if (k == "fail_after_solve") {   // 1: the NEXT update returns NKA_HIP_EHIP right behind its enqueued scalar step
-    a->fail_after_solve = value != 0;
-  } else if (k == "prime_pad") {      // -1 automatic = 1: list lengths 23 / 29 / 31 run the next width (one dead ring slot); 0: exact widths
-    if (value < -1 || value > 1) return fail(NKA_HIP_EINVAL, "prime_pad: -1, 0, 1");
-    a->prime_pad = value;
-  } else if (k == "chain_many") {     // -1 automatic, 0: one compute unit per reference-order sum at every length, 1: many wherever blocks exist
-    if (value < -1 || value > 1) return fail(NKA_HIP_EINVAL, "chain_many: -1, 0, 1");
-    a->chain_many = value;
-  } else if (k == "chain_walk") {     // 1: the per-sum reference-order kernel walks every block (no summaries): same bits, for A/B
-    a->chain_walk = value != 0;
-  } else if (k == "pb_reverse") {     // 1: the rolling-window PB walks its tiles in the reverse of PA's order (round-5 A/B)
-    a->pb_reverse = value != 0;
-  } else if (k == "serial_solve") {
-    a->serial_solve = value != 0;
-  } else if (k == "list_word") {       // 0: the host's own bound only (the behaviour before round 4), for A/B runs
-    a->word_off = value == 0;
-
-  } else {
-    return fail(NKA_HIP_EINVAL, "unknown tuning key: " + k);
-  }
-  return 0;
-}
-#endif  // NKA_DIAGNOSTIC
 
 int nka_hip_device_info(nka_hip_t a, char *name64, int32_t *num_cu) {
   if (!a) return fail(NKA_HIP_EINVAL, "null handle");

@@ -43,28 +43,6 @@
 #error "nka_kernels.hpp is written for gfx950 (CDNA4) only: v_permlane32_swap / v_permlane16_swap reductions, 160 KiB LDS, tile shapes measured on MI355X.  Build with --offload-arch=gfx950."
 #endif
 
-#ifndef NKA_NT_LOADS
-#define NKA_NT_LOADS 1      // streaming reads: non-temporal (nt) loads
-#endif
-#ifndef NKA_F_TEMPORAL
-// != 0 (bit 0: in PA, bit 1: in PB) = the vectors BOTH passes of an update read (f and the raw w of the pending pair: PA reads them, PB reads them again
-// a fraction of a millisecond later) are loaded with the default cache policy instead of nt, in the hope that the 256 MiB
-// Infinity Cache still holds them for PB at shard sizes (n_local <= 1.25e7: 200 MB).  Measured in round 5 (in-process A/B
-// of two builds, tools/ab_libs.py; profiles/r05/ab_mall_reuse.txt) together with PB walking its tiles in the reverse of
-// PA's order (kPbReverse); 0 = every streaming load nt, the product.
-#define NKA_F_TEMPORAL 0
-#endif
-#ifndef NKA_DEAD_SLOT_TILE0
-// A launch wider than the list (the host's bound is one too high in the update that takes a dependence drop, and too high
-// by more for a caller that never synchronises) has DEAD ring slots.  In PB they re-read f: 1 = always its first tile (4 KiB
-// that stay in the caches), 0 = the tile at hand, as before round 4 -- half of which came from HBM again (PMC: 19.55 words
-// per element where the list needs 19; PB -2.5 % with the first tile, neutral without dead slots).
-#define NKA_DEAD_SLOT_TILE0 1
-#endif
-#ifndef NKA_STORE_POLICY
-#define NKA_STORE_POLICY 1  // 0 plain, 1 nt (default: +2-3% on the mixed pass), 2 write-through "sc0 sc1 nt" (inline asm)
-#endif
-
 namespace nka {
 
 constexpr int kBlock = 256;  // 4 wavefronts of 64
@@ -364,48 +342,19 @@ __device__ __forceinline__ void block_reduce_store(const double (&acc)[NACC], do
 }
 
 // ---- 8-B / 16-B per lane streaming accesses ---------------------------------------
+// Non-temporal (nt) loads and stores (nt stores: +2-3 % on the mixed pass against plain ones).
 typedef double d2 __attribute__((ext_vector_type(2)));
 template <int VEC> struct VecT;
 template <> struct VecT<1> { using type = double; };
 template <> struct VecT<2> { using type = d2; };
 
 template <int VEC> __device__ __forceinline__ typename VecT<VEC>::type ld(const double *p);
-template <> __device__ __forceinline__ double ld<1>(const double *p) {
-#if NKA_NT_LOADS
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
+template <> __device__ __forceinline__ double ld<1>(const double *p) { return __builtin_nontemporal_load(p); }
 template <> __device__ __forceinline__ d2 ld<2>(const double *p) {
-#if NKA_NT_LOADS
   return __builtin_nontemporal_load(reinterpret_cast<const d2 *>(p));
-#else
-  return *reinterpret_cast<const d2 *>(p);
-#endif
 }
-// loads of the vectors that PA and PB both read (see NKA_F_TEMPORAL: bit 0 = in PA, bit 1 = in PB)
-template <int VEC, int PASS_BIT> __device__ __forceinline__ typename VecT<VEC>::type ld_keep(const double *p) {
-  if constexpr ((NKA_F_TEMPORAL & PASS_BIT) != 0) return *reinterpret_cast<const typename VecT<VEC>::type *>(p);
-  else return ld<VEC>(p);
-}
-__device__ __forceinline__ void st(double *p, double x) {
-#if NKA_STORE_POLICY == 1
-  __builtin_nontemporal_store(x, p);
-#else
-  *p = x;
-#endif
-}
-__device__ __forceinline__ void st(double *p, d2 x) {
-#if NKA_STORE_POLICY == 1
-  __builtin_nontemporal_store(x, reinterpret_cast<d2 *>(p));
-#elif NKA_STORE_POLICY == 2
-  // write-through streaming store; a store needs no later wait in this wave
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(p), "v"(x) : "memory");
-#else
-  *reinterpret_cast<d2 *>(p) = x;
-#endif
-}
+__device__ __forceinline__ void st(double *p, double x) { __builtin_nontemporal_store(x, p); }
+__device__ __forceinline__ void st(double *p, d2 x) { __builtin_nontemporal_store(x, reinterpret_cast<d2 *>(p)); }
 
 __device__ __forceinline__ double ex(double x, int) { return x; }
 __device__ __forceinline__ double ex(d2 x, int i) { return x[i]; }
@@ -602,7 +551,7 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
 
   const int64_t ntile = vs.n / (kBlock * VEC);
   // (dead ring slots -- a launch wider than the list -- re-read f at the tile at hand here.  Sending them to f's first
-  //  tile, as PB does (NKA_DEAD_SLOT_TILE0), was measured in this pass too: 25 more VGPRs for the per-slot offsets and
+  //  tile, as PB does (k_combine_win), was measured in this pass too: 25 more VGPRs for the per-slot offsets and
   //  +2...5 % of PA with NO dead slot, which is every launch of a caller that synchronises once per iteration, since PA
   //  then runs at exactly the list length; profiles/r04/ab_dead_slot.txt)
 #define DEAD_OFF(live, off) (off)
@@ -610,8 +559,8 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
   int64_t t = blockIdx.x;
   if (t < ntile) {
     const int64_t e = t * (kBlock * VEC) + threadIdx.x * VEC;
-    fv = ld_keep<VEC, 1>(f + e);
-    w1v = ld_keep<VEC, 1>(w1 + e);
+    fv = ld<VEC>(f + e);
+    w1v = ld<VEC>(w1 + e);
 #pragma unroll
     for (int j = 0; j < W; j++) ring[j] = ld<VEC>(wk[j] + (DEAD_OFF(j < nolder, e)));
   }
@@ -629,8 +578,8 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
       acc[1] = fma(fq[q], dq[q], acc[1]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    fv = ld_keep<VEC, 1>(f + en);
-    w1v = ld_keep<VEC, 1>(w1 + en);
+    fv = ld<VEC>(f + en);
+    w1v = ld<VEC>(w1 + en);
 #pragma unroll
     for (int j = 0; j < MAXL; j++) {
       const V x = ring[j % W];
@@ -1654,10 +1603,8 @@ static __global__ __launch_bounds__(64) __attribute__((unused)) void k_chain_app
 // w1' = (w1-f)/s, v1' = v1/s formed in registers and stored back.  The last pass
 // stores v_new = f_out.
 enum { kPbNoStoreW = 1, kPbNoStoreF = 2,     // `flags` of PB in an out-of-place update (nka_hip_accel_update_swap)
-       kPbNotFirst = 8, kPbNotLast = 16,      // rolling-window PB over a list longer than kMaxPerPass: not the first / not the
+       kPbNotFirst = 8, kPbNotLast = 16 };    // rolling-window PB over a list longer than kMaxPerPass: not the first / not the
                                               // last of its passes (enqueue_pb; in place only)
-       kPbReverse = 4 };                      // rolling-window PB: walk the tiles from the END of the vectors, i.e. in the
-                                              // reverse of PA's order (diagnostic builds only, see NKA_F_TEMPORAL)
 
 template <int COMB>
 __device__ __forceinline__ double comb1(double x, double c, double w, double v) {
@@ -1881,31 +1828,25 @@ __global__ __launch_bounds__(kBlock) void k_combine_win(Ctl ctl, Vecs vs, double
   const double *w0src = norm0 ? wk[0] : f;
 
   const int lane_off = threadIdx.x * VEC;                  // piece q of a tile starts q*512 elements further
-#if NKA_DEAD_SLOT_TILE0
-#define DEAD_OFF(live, off) ((live) ? (off) : (int64_t)lane_off)      // (dead ring slots: see NKA_DEAD_SLOT_TILE0)
-#else
-#define DEAD_OFF(live, off) (off)
-#endif
+  // A launch wider than the list (the host's bound is one too high in the update that takes a dependence drop, and too high
+  // by more for a caller that never synchronises) has DEAD ring slots.  They re-read f's first tile (4 KiB that stay in the
+  // caches) rather than the tile at hand, half of which came from HBM again (PMC: 19.55 words per element where the list
+  // needs 19; PB -2.5 % with the first tile, neutral without dead slots).
+#define DEAD_OFF(live, off) ((live) ? (off) : (int64_t)lane_off)
   V finv[T], w0v[T], rw[COMPACT ? 1 : W][T], rv[W][T];
-  // logical tile t -> the elements it covers (kPbReverse: counted from the end; elementwise pass, same bits either way)
-  const bool rev = (flags & kPbReverse) != 0;
-  const int64_t tlast = ntile - 1;
-#define TILE_ELEM(t) (((rev) ? tlast - (t) : (t)) * TILE + lane_off)
-  // pair 0 is the pending pair, whose raw w PA has just read (NKA_F_TEMPORAL): the other ring loads stream
-#define LD_W(j, p) ((j) == 0 ? ld_keep<VEC, 2>(p) : ld<VEC>(p))
   int64_t t = tail_block ? ntile : (int64_t)blockIdx.x;
   if (t < ntile) {
-    const int64_t e = TILE_ELEM(t);
+    const int64_t e = t * TILE + lane_off;
 #pragma unroll
     for (int q = 0; q < T; q++) {
-      finv[q] = ld_keep<VEC, 2>(f + e + q * (kBlock * VEC));
-      if (COMPACT) w0v[q] = ld_keep<VEC, 2>(w0src + e + q * (kBlock * VEC));
+      finv[q] = ld<VEC>(f + e + q * (kBlock * VEC));
+      if (COMPACT) w0v[q] = ld<VEC>(w0src + e + q * (kBlock * VEC));
     }
 #pragma unroll
     for (int j = 0; j < W; j++)
 #pragma unroll
       for (int q = 0; q < T; q++) {
-        if (!COMPACT) rw[j][q] = LD_W(j, wk[j] + DEAD_OFF(j < ncomb, e) + q * (kBlock * VEC));
+        if (!COMPACT) rw[j][q] = ld<VEC>(wk[j] + DEAD_OFF(j < ncomb, e) + q * (kBlock * VEC));
         rv[j][q] = ld<VEC>(vk[j] + DEAD_OFF(j < ncomb, e) + q * (kBlock * VEC));
       }
   }
@@ -1917,12 +1858,12 @@ __global__ __launch_bounds__(kBlock) void k_combine_win(Ctl ctl, Vecs vs, double
   int64_t tnext = t + G;
   unsigned par = 0;
   while (t < ntile) {
-    const int64_t e = TILE_ELEM(t);
+    const int64_t e = t * TILE + lane_off;
     const bool more = tnext < ntile;
     unsigned claimed = kNoTicket;
     if (tickets && more && threadIdx.x == 0) claimed = ticket_request(my_ticket, ticket_base, (unsigned)ng, grp);
     const int64_t tn = more ? tnext : t;                 // the last iteration prefetches its own tile again
-    const int64_t en = TILE_ELEM(tn);
+    const int64_t en = tn * TILE + lane_off;
     V fin[T], w0[T], x[T];
 #pragma unroll
     for (int q = 0; q < T; q++) {
@@ -1934,8 +1875,8 @@ __global__ __launch_bounds__(kBlock) void k_combine_win(Ctl ctl, Vecs vs, double
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < T; q++) {
-      finv[q] = ld_keep<VEC, 2>(f + en + q * (kBlock * VEC));
-      if (COMPACT) w0v[q] = ld_keep<VEC, 2>(w0src + en + q * (kBlock * VEC));
+      finv[q] = ld<VEC>(f + en + q * (kBlock * VEC));
+      if (COMPACT) w0v[q] = ld<VEC>(w0src + en + q * (kBlock * VEC));
     }
 #pragma unroll
     for (int j = 0; j < MAXK; j++) {
@@ -1949,10 +1890,10 @@ __global__ __launch_bounds__(kBlock) void k_combine_win(Ctl ctl, Vecs vs, double
 #pragma unroll
       for (int q = 0; q < T; q++) {
         if (j + W < MAXK) {
-          if (!COMPACT) rw[COMPACT ? 0 : j % W][q] = LD_W(j + W, wk[j + W] + DEAD_OFF(j + W < ncomb, e) + q * (kBlock * VEC));
+          if (!COMPACT) rw[COMPACT ? 0 : j % W][q] = ld<VEC>(wk[j + W] + DEAD_OFF(j + W < ncomb, e) + q * (kBlock * VEC));
           rv[j % W][q] = ld<VEC>(vk[j + W] + DEAD_OFF(j + W < ncomb, e) + q * (kBlock * VEC));
         } else {
-          if (!COMPACT) rw[COMPACT ? 0 : j % W][q] = LD_W(j + W - MAXK, wk[j + W - MAXK] + DEAD_OFF(j + W - MAXK < ncomb, en) + q * (kBlock * VEC));
+          if (!COMPACT) rw[COMPACT ? 0 : j % W][q] = ld<VEC>(wk[j + W - MAXK] + DEAD_OFF(j + W - MAXK < ncomb, en) + q * (kBlock * VEC));
           rv[j % W][q] = ld<VEC>(vk[j + W - MAXK] + DEAD_OFF(j + W - MAXK < ncomb, en) + q * (kBlock * VEC));
         }
       }
@@ -2021,8 +1962,6 @@ __global__ __launch_bounds__(kBlock) void k_combine_win(Ctl ctl, Vecs vs, double
     }
   }
 #undef DEAD_OFF
-#undef TILE_ELEM
-#undef LD_W
 }
 
 // ---- scalar kernels: list surgery + Cholesky + substitutions on one wavefront ----

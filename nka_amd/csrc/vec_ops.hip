@@ -8,14 +8,7 @@
 // blocks, fixed-order two-stage reductions (bitwise reproducible).  Compiled
 // with -ffp-contract=off so  a*x + b*y + z  rounds as the Fortran expression
 // ((a*x) + (b*y)) + z  does.
-#include "../../include/nka_hip.h"
-#include "../../include/nka_hip_ext.h"
-#include "../../include/nka_hip_vec.h"
-#include "nka_kernels.hpp"
-#include "host_logic.hpp"
-#include "rccl_dl.hpp"
-
-#include <hip/hip_runtime.h>
+#include "handles.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -27,52 +20,7 @@
 
 using namespace nka;
 
-extern "C" const char *nka_hip_last_error(void);
-namespace nka_detail {
-int set_error(int code, const std::string &msg);
-std::string last_error();
-bool &span_check_failed();   // (thread-local) set by a failing check_device_span
-int check_device_span(const void *p, int64_t n, const char *what);
-void invalidate_span_cache();
-void register_allocation(const void *p, size_t bytes, const void *owner);
-void unregister_owner(const void *owner);
-void unregister_allocation(const void *p);
-}
-
-struct nka_hip_vec_ws {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int num_cu = 256;
-  double *partials = nullptr;  // kMaxGrid
-  unsigned *tickets = nullptr; // tile-ticket counters of k_update_many_keep_win (kTicketWords, zero between launches)
-  int ticket_groups = -1;      // -1 automatic, 0 static tile mapping, 1/2/4/8 counters (nka_hip_vec_set_tuning "tickets")
-  double *host_results = nullptr; // pinned, 2*kManyMax+2 doubles
-  double *host_results_dev = nullptr;  // its device-side address: the final-sum kernel writes straight into host
-                                       // memory (no copy kernel, no staging)
-  // parallel-aware reductions ("the vector base class reduction methods will necessarily be
-  // parallel-aware", src-F08-vector/README.md:16-22): every sum a reduction returns to the host is first
-  // summed over the ranks -- on the device by `allreduce` (stream-ordered; built-in: RCCL), and/or on the
-  // host by `host_allreduce` after the stream has been synchronised
-  nka_hip_allreduce_fn allreduce = nullptr;
-  void *allreduce_ctx = nullptr;
-  nka_hip_host_allreduce_fn host_allreduce = nullptr;
-  void *host_allreduce_ctx = nullptr;
-  ncclComm_t comm = nullptr;
-  double *red_dev = nullptr;      // 2*kManyMax+2 doubles: the sums of one reduction in canonical layout
-  int sum_order = 0;              // nka_hip_vec_set_sum_order: 1 = dot() sums element after element, unfused (k_dot_ordered)
-};
-
 namespace {
-
-#define HIP_TRYV(expr)                                                                   \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      (void)hipGetLastError(); /* reported here: not left for a later hipGetLastError() */ \
-      return nka_detail::set_error(e_ == hipErrorOutOfMemory ? NKA_HIP_ENOMEM : NKA_HIP_EHIP, \
-                                   std::string(#expr) + ": " + hipGetErrorString(e_));  \
-    }                                                                                    \
-  } while (0)
 
 // OP: 0 setval  z = a
 //     1 scale   z = a*z                         (grid_vector_type.F90:117)
@@ -841,7 +789,7 @@ int run_elementwise(nka_hip_vec_ws *ws, int64_t n, double *z, const double *x, c
   if (!ws) return nka_detail::set_error(NKA_HIP_EINVAL, "null workspace");
   if (n < 0) return nka_detail::set_error(NKA_HIP_EINVAL, "negative length");
   if (n == 0) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (int rc = nka_detail::check_device_span(z, n, "vector hook: z")) return rc;
   if (OP >= 2) if (int rc = nka_detail::check_device_span(x, n, "vector hook: x")) return rc;
   if (OP >= 4) if (int rc = nka_detail::check_device_span(y, n, "vector hook: y")) return rc;
@@ -851,7 +799,7 @@ int run_elementwise(nka_hip_vec_ws *ws, int64_t n, double *z, const double *x, c
     hipLaunchKernelGGL((k_elementwise<OP, 2>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, y, a, b, c);
   else
     hipLaunchKernelGGL((k_elementwise<OP, 1>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, y, a, b, c);
-  HIP_TRYV(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -867,7 +815,7 @@ int update_many_keep(nka_hip_vec_ws_t ws, int64_t n, double *z, const double *a,
   if ((pend.flags & 1) && (count < 1 || (!PAIRS && !pend.w)))
     return nka_detail::set_error(NKA_HIP_EINVAL, "pending pair: entry 0 of the lists (and its w) must be given");
   if (n == 0) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if ((pend.flags & 1) && !PAIRS) if (int rc = nka_detail::check_device_span(pend.w, n, who)) return rc;
   if (int rc = nka_detail::check_device_span(z, n, who)) return rc;
   if (keep_in) if (int rc = nka_detail::check_device_span(keep_in, n, who)) return rc;
@@ -910,7 +858,7 @@ int update_many_keep(nka_hip_vec_ws_t ws, int64_t n, double *z, const double *a,
     if (win) { NKA_DISPATCH_EXACT(nv, LAUNCHW) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }   // (unaligned operands: 8-byte path)
 #undef LAUNCHW
 #undef LAUNCH1
-    HIP_TRYV(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     base += m.count;
   }
   return 0;
@@ -988,8 +936,8 @@ int fetch_sums(nka_hip_vec_ws_t ws, int g, int rows, int nv, int count, int extr
       // single rank (or host-side hook only): straight into pinned host memory, no copy in between
       hipLaunchKernelGGL(k_finalize_rows, dim3(ncols), dim3(kBlock), 0, ws->stream, ws->partials, g, rows, nv, count,
                          ws->host_results_dev);
-      HIP_TRYV(hipGetLastError());
-      HIP_TRYV(hipStreamSynchronize(ws->stream));
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(ws->stream));
     } else {
       for (int i = 0; i < total; i++) ws->host_results[i] = 0.0;
     }
@@ -997,14 +945,14 @@ int fetch_sums(nka_hip_vec_ws_t ws, int g, int rows, int nv, int count, int extr
   }
   if (have) {
     hipLaunchKernelGGL(k_finalize_rows, dim3(ncols), dim3(kBlock), 0, ws->stream, ws->partials, g, rows, nv, count, ws->red_dev);
-    HIP_TRYV(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   } else {
-    HIP_TRYV(hipMemsetAsync(ws->red_dev, 0, sizeof(double) * (size_t)total, ws->stream));
+    HIP_TRY(hipMemsetAsync(ws->red_dev, 0, sizeof(double) * (size_t)total, ws->stream));
   }
   if (int rc = ws->allreduce(ws->allreduce_ctx, ws->red_dev, total, ws->stream))
     return rc < 0 ? rc : nka_detail::set_error(NKA_HIP_ECOMM, "vector reduction: the all-reduce hook failed");
-  HIP_TRYV(hipMemcpyAsync(ws->host_results, ws->red_dev, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ws->stream));
-  HIP_TRYV(hipStreamSynchronize(ws->stream));
+  HIP_TRY(hipMemcpyAsync(ws->host_results, ws->red_dev, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ws->stream));
+  HIP_TRY(hipStreamSynchronize(ws->stream));
   return run_host_hook(ws, ws->host_results, total);
 }
 
@@ -1023,9 +971,9 @@ int nka_hip_vec_workspace_create(nka_hip_vec_ws_t *out, int32_t device, void *st
   if (!out) return nka_detail::set_error(NKA_HIP_EINVAL, "out is NULL");
   *out = nullptr;
   int ndev = 0;
-  HIP_TRYV(hipGetDeviceCount(&ndev));
+  HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return nka_detail::set_error(NKA_HIP_EINVAL, "no such HIP device");
-  HIP_TRYV(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   auto *ws = new nka_hip_vec_ws();
   ws->device = device;
   ws->stream = (hipStream_t)stream;  // NULL = HIP's default stream
@@ -1063,44 +1011,31 @@ int nka_hip_vec_workspace_destroy(nka_hip_vec_ws_t ws) {
   return 0;
 }
 
-#ifdef NKA_DIAGNOSTIC      // only in libnka_hip_diag.so (include/nka_hip_diag.h)
-int nka_hip_vec_set_tuning(nka_hip_vec_ws_t ws, const char *key, int32_t value) {
-  if (!ws || !key) return nka_detail::set_error(NKA_HIP_EINVAL, "null argument");
-  if (std::string(key) == "tickets") {
-    if (value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
-      return nka_detail::set_error(NKA_HIP_EINVAL, "tickets: -1 (auto), 0 (static tile mapping), 1, 2, 4, 8 (ticket counters)");
-    ws->ticket_groups = value;
-    return 0;
-  }
-  return nka_detail::set_error(NKA_HIP_EINVAL, std::string("unknown tuning key: ") + key);
-}
-#endif  // NKA_DIAGNOSTIC
-
 int nka_hip_vec_alloc(nka_hip_vec_ws_t ws, int64_t n, double **out_dev) {
   if (!ws || !out_dev || n < 0) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
-  HIP_TRYV(hipSetDevice(ws->device));
-  HIP_TRYV(hipMalloc((void **)out_dev, sizeof(double) * (size_t)std::max<int64_t>(n, 1)));
+  HIP_TRY(hipSetDevice(ws->device));
+  HIP_TRY(hipMalloc((void **)out_dev, sizeof(double) * (size_t)std::max<int64_t>(n, 1)));
   nka_detail::register_allocation(*out_dev, sizeof(double) * (size_t)std::max<int64_t>(n, 1), ws);   // exact pointer checks, no HIP call
   return 0;
 }
 
 int nka_hip_vec_free(nka_hip_vec_ws_t ws, double *dev) {
   if (!ws) return nka_detail::set_error(NKA_HIP_EINVAL, "null workspace");
-  HIP_TRYV(hipSetDevice(ws->device));
-  HIP_TRYV(hipStreamSynchronize(ws->stream));
+  HIP_TRY(hipSetDevice(ws->device));
+  HIP_TRY(hipStreamSynchronize(ws->stream));
   nka_detail::invalidate_span_cache();
   nka_detail::unregister_allocation(dev);
-  HIP_TRYV(hipFree(dev));
+  HIP_TRY(hipFree(dev));
   return 0;
 }
 
 int nka_hip_vec_copy(nka_hip_vec_ws_t ws, int64_t n, double *dst, const double *src) {
   if (!ws || n < 0) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   if (n == 0 || dst == src) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (int rc = nka_detail::check_device_span(dst, n, "vec_copy: dst")) return rc;
   if (int rc = nka_detail::check_device_span(src, n, "vec_copy: src")) return rc;
-  HIP_TRYV(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ws->stream));
+  HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ws->stream));
   return 0;
 }
 
@@ -1129,7 +1064,7 @@ static int nka_hip_vec_dot_entry(nka_hip_vec_ws_t ws, int64_t n, const double *x
   if (!ws || !host_result || n < 0) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   *host_result = 0.0;
   if (n == 0 && !ws_parallel(ws)) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   int g = 1;
   if (n > 0) {
     if (int rc = nka_detail::check_device_span(x, n, "vec_dot: x")) return rc;
@@ -1167,7 +1102,7 @@ static int nka_hip_vec_dot_many_entry(nka_hip_vec_ws_t ws, int64_t n, const doub
   if (!ws || n < 0 || count < 0 || (count > 0 && (!ys || !host_vals))) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   for (int j = 0; j < count; j++) host_vals[j] = 0.0;
   if (count == 0 || (n == 0 && !ws_parallel(ws))) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (n > 0) {
     if (int rc = nka_detail::check_device_span(x, n, "vec_dot_many: x")) return rc;
     for (int j = 0; j < count; j++)
@@ -1193,7 +1128,7 @@ static int nka_hip_vec_dot_many_entry(nka_hip_vec_ws_t ws, int64_t n, const doub
     if (v2) { NKA_DISPATCH_NV(nv, LAUNCH2) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }
 #undef LAUNCH2
 #undef LAUNCH1
-    HIP_TRYV(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (int rc = fetch_sums(ws, g, 1, nv, m.count, 0, true)) return rc;
     for (int j = 0; j < m.count; j++) host_vals[base + j] = ws->host_results[j];
   }
@@ -1217,7 +1152,7 @@ static int nka_hip_vec_dot_pair_many_entry(nka_hip_vec_ws_t ws, int64_t n, const
   *host_cross = 0.0;
   for (int j = 0; j < count; j++) host_vals0[j] = host_vals1[j] = 0.0;
   if (n == 0 && !ws_parallel(ws)) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (n > 0) {
     if (int rc = nka_detail::check_device_span(x0, n, "vec_dot_pair_many: x0")) return rc;
     if (int rc = nka_detail::check_device_span(x1, n, "vec_dot_pair_many: x1")) return rc;
@@ -1250,7 +1185,7 @@ static int nka_hip_vec_dot_pair_many_entry(nka_hip_vec_ws_t ws, int64_t n, const
     if (v2) { NKA_DISPATCH_NV(nv, LAUNCH2) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }
 #undef LAUNCH2
 #undef LAUNCH1
-    HIP_TRYV(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (int rc = fetch_sums(ws, g, 2, nv, m.count, 1, true)) return rc;
     for (int j = 0; j < m.count; j++) {
       host_vals0[base + j] = ws->host_results[j];
@@ -1273,7 +1208,7 @@ int nka_hip_vec_update_many(nka_hip_vec_ws_t ws, int64_t n, double *z, const dou
                             const double *b, const double *const *ys, int32_t count) {
   if (!ws || n < 0 || count < 0 || (count > 0 && (!a || !b || !xs || !ys))) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   if (n == 0 || count == 0) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (int rc = nka_detail::check_device_span(z, n, "vec_update_many: z")) return rc;
   for (int j = 0; j < count; j++) {
     if (int rc = nka_detail::check_device_span(xs[j], n, "vec_update_many: xs[j]")) return rc;
@@ -1297,7 +1232,7 @@ int nka_hip_vec_update_many(nka_hip_vec_ws_t ws, int64_t n, double *z, const dou
     if (v2) { NKA_DISPATCH_NV(nv, LAUNCH2) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }
 #undef LAUNCH2
 #undef LAUNCH1
-    HIP_TRYV(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   return 0;
 }
@@ -1308,7 +1243,7 @@ int nka_hip_vec_axpy_many(nka_hip_vec_ws_t ws, int64_t n, double *z, const doubl
                           int32_t count) {
   if (!ws || n < 0 || count < 0 || (count > 0 && (!a || !xs))) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   if (n == 0 || count == 0) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (int rc = nka_detail::check_device_span(z, n, "vec_axpy_many: z")) return rc;
   for (int j = 0; j < count; j++)
     if (int rc = nka_detail::check_device_span(xs[j], n, "vec_axpy_many: xs[j]")) return rc;
@@ -1328,7 +1263,7 @@ int nka_hip_vec_axpy_many(nka_hip_vec_ws_t ws, int64_t n, double *z, const doubl
     if (v2) { NKA_DISPATCH_NV(nv, LAUNCH2) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }
 #undef LAUNCH2
 #undef LAUNCH1
-    HIP_TRYV(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   return 0;
 }
@@ -1346,7 +1281,7 @@ static int nka_hip_vec_update_norm2_entry(nka_hip_vec_ws_t ws, int64_t n, double
   if (!ws || !host_norm || n < 0) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   *host_norm = 0.0;
   if (n == 0 && !ws_parallel(ws)) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (n == 0) {                        // empty slice: zero, but the collective is still joined
     if (int rc = fetch_sums(ws, 1, 1, 1, 1, 0, false)) return rc;
     *host_norm = std::sqrt(ws->host_results[0]);
@@ -1364,7 +1299,7 @@ static int nka_hip_vec_update_norm2_entry(nka_hip_vec_ws_t ws, int64_t n, double
     hipLaunchKernelGGL((k_update_norm2<1, true>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
   else
     hipLaunchKernelGGL((k_update_norm2<1, false>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
-  HIP_TRYV(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   if (int rc = fetch_sums(ws, g, 1, 1, 1, 0, true)) return rc;
   *host_norm = std::sqrt(ws->host_results[0]);     // the square root of the GLOBAL sum
   return 0;
@@ -1469,7 +1404,7 @@ static int scale_dot_pair_many_impl(nka_hip_vec_ws_t ws, int64_t n, double *w, d
   *host_cross = 0.0;
   for (int j = 0; j < count; j++) host_vals_w[j] = host_vals_f[j] = 0.0;
   if (n == 0 && !ws_parallel(ws)) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (n == 0) {                        // empty slice: zeros, but every collective is still joined
     const int c0 = std::min(kManyMax, count);
     if (int rc = fetch_sums(ws, 1, 2, std::max(c0, 1), c0, extra, false)) return rc;
@@ -1539,7 +1474,7 @@ static int scale_dot_pair_many_impl(nka_hip_vec_ws_t ws, int64_t n, double *w, d
 #undef NKA_SDPMW
 #undef LWDD
 #undef L1DD
-    HIP_TRYV(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (int rc = fetch_sums(ws, g, 2, nv, m.count, extra, true)) return rc;
     for (int j = 0; j < m.count; j++) {
       host_vals_w[j] = ws->host_results[j];
@@ -1631,7 +1566,7 @@ int nka_hip_vec_comm_init_rank(nka_hip_vec_ws_t ws, const void *id128, int32_t n
   if (nranks < 1 || rank < 0 || rank >= nranks) return nka_detail::set_error(NKA_HIP_EINVAL, "bad rank / nranks");
   const auto &R = nka_detail::rccl();
   if (!R.ok()) return nka_detail::set_error(NKA_HIP_ECOMM, R.err);
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (int rc = nka_hip_vec_comm_destroy(ws)) return rc;
   ncclUniqueId id;
   static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is expected to be 128 bytes");
@@ -1649,8 +1584,8 @@ int nka_hip_vec_comm_init_rank(nka_hip_vec_ws_t ws, const void *id128, int32_t n
 int nka_hip_vec_comm_destroy(nka_hip_vec_ws_t ws) {
   if (!ws) return nka_detail::set_error(NKA_HIP_EINVAL, "null workspace");
   if (ws->comm) {
-    HIP_TRYV(hipSetDevice(ws->device));
-    HIP_TRYV(hipStreamSynchronize(ws->stream));
+    HIP_TRY(hipSetDevice(ws->device));
+    HIP_TRY(hipStreamSynchronize(ws->stream));
     nka_detail::rccl().CommDestroy(ws->comm);
     ws->comm = nullptr;
   }
@@ -1665,13 +1600,13 @@ int nka_hip_vec_allreduce_now(nka_hip_vec_ws_t ws, double *host_vals, int32_t co
   if (!ws || count < 0 || count > 2 * kManyMax + 2 || (count > 0 && !host_vals))
     return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   if (count == 0) return 0;
-  HIP_TRYV(hipSetDevice(ws->device));
+  HIP_TRY(hipSetDevice(ws->device));
   if (ws->allreduce) {
-    HIP_TRYV(hipMemcpyAsync(ws->red_dev, host_vals, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ws->stream));
+    HIP_TRY(hipMemcpyAsync(ws->red_dev, host_vals, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ws->stream));
     if (int rc = ws->allreduce(ws->allreduce_ctx, ws->red_dev, count, ws->stream))
       return rc < 0 ? rc : nka_detail::set_error(NKA_HIP_ECOMM, "vector reduction: the all-reduce hook failed");
-    HIP_TRYV(hipMemcpyAsync(ws->host_results, ws->red_dev, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ws->stream));
-    HIP_TRYV(hipStreamSynchronize(ws->stream));
+    HIP_TRY(hipMemcpyAsync(ws->host_results, ws->red_dev, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ws->stream));
+    HIP_TRY(hipStreamSynchronize(ws->stream));
     for (int i = 0; i < count; i++) host_vals[i] = ws->host_results[i];
   }
   return run_host_hook(ws, host_vals, count);
@@ -1679,17 +1614,17 @@ int nka_hip_vec_allreduce_now(nka_hip_vec_ws_t ws, double *host_vals, int32_t co
 
 int nka_hip_vec_h2d(nka_hip_vec_ws_t ws, int64_t n, double *dst_dev, const double *src_host) {
   if (!ws || n < 0) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
-  HIP_TRYV(hipSetDevice(ws->device));
-  HIP_TRYV(hipMemcpyAsync(dst_dev, src_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ws->stream));
-  HIP_TRYV(hipStreamSynchronize(ws->stream));
+  HIP_TRY(hipSetDevice(ws->device));
+  HIP_TRY(hipMemcpyAsync(dst_dev, src_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ws->stream));
+  HIP_TRY(hipStreamSynchronize(ws->stream));
   return 0;
 }
 
 int nka_hip_vec_d2h(nka_hip_vec_ws_t ws, int64_t n, double *dst_host, const double *src_dev) {
   if (!ws || n < 0) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
-  HIP_TRYV(hipSetDevice(ws->device));
-  HIP_TRYV(hipMemcpyAsync(dst_host, src_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ws->stream));
-  HIP_TRYV(hipStreamSynchronize(ws->stream));
+  HIP_TRY(hipSetDevice(ws->device));
+  HIP_TRY(hipMemcpyAsync(dst_host, src_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ws->stream));
+  HIP_TRY(hipStreamSynchronize(ws->stream));
   return 0;
 }
 

@@ -4,12 +4,11 @@
 One accelerator per build, all on the same device, fed from ONE pool of inputs; the variants are alternated in blocks
 of K updates for R rounds (order reversed every other round), per-phase device times from the library's HIP events.
 
-  tools/ab_libs.py --libs nka_amd/libnka_hip_diag.so nka_amd/libnka_hip_diag_ft.so \
-                   --combos pb_reverse=0 pb_reverse=1 --flavor c --vlen 1.25e7 --mvec 20
+  tools/ab_libs.py --libs nka_amd/libnka_hip_diag.so nka_amd/libnka_hip_diag_w4.so \
+                   --combos prime_pad=0 prime_pad=1 --flavor c --vlen 1.25e7 --mvec 20 --check-bits
 
-Every (build, combo) pair is one variant.  Round 5: do f and the pending pair's w, which PA and PB both read, come out of
-the Infinity Cache for PB when they are loaded with the default cache policy (libnka_hip_diag_ft.so:
--DNKA_F_TEMPORAL=1) and / or when PB walks its tiles in the reverse of PA's order (pb_reverse=1)?
+Every (build, combo) pair is one variant; a combo of "" sets no switch.  With --check-bits the builds also run the same
+inputs and must agree bit for bit, e.g. the WIDTH_STEP=4 build (`make -C nka_amd/csrc w4`) against the default one.
 """
 import argparse
 import os
@@ -23,7 +22,7 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--libs", nargs="+", required=True)
-    ap.add_argument("--combos", nargs="+", default=["pb_reverse=0"], help="key=value[,key=value...] per variant")
+    ap.add_argument("--combos", nargs="+", default=[""], help="key=value[,key=value...] per variant")
     ap.add_argument("--flavor", default="c", choices=["f08", "c", "f08vec"])
     ap.add_argument("--vlen", type=float, default=1.25e7)
     ap.add_argument("--mvec", type=int, default=20)
@@ -42,7 +41,7 @@ def main():
     work = torch.empty(n + (n % 2), dtype=torch.float64, device="cuda")
 
     def apply(acc, combo):
-        for kv in combo.split(","):
+        for kv in filter(None, combo.split(",")):
             k_, v_ = kv.split("=")
             acc.set_tuning(k_, int(v_))
 
@@ -87,7 +86,7 @@ def main():
     base = statistics.mean(res[variants[0]]["all"])
     for v in variants:
         d = res[v]
-        print(f"  {os.path.basename(a.libs[v[0]]):28s} {v[1]:14s} PA {statistics.mean(d['PA']):.4f}  PB {statistics.mean(d['PB']):.4f} "
+        print(f"  {os.path.basename(a.libs[v[0]]):28s} {v[1] or '-':14s} PA {statistics.mean(d['PA']):.4f}  PB {statistics.mean(d['PB']):.4f} "
               f"(min {min(d['PB']):.4f} sd {statistics.pstdev(d['PB']):.4f})  update {statistics.mean(d['all']):.4f} ms "
               f"({100.0 * (statistics.mean(d['all']) / base - 1.0):+.2f} %)")
     return 1 if nbad else 0

@@ -16,7 +16,6 @@
 #   reforder                    whole GPU suite, cost table of the reference-order sums, soak over the three sum modes
 #   rank-rehearsal              bench.py --gpus 4 in the plain form, ranks sharing the GPU: staged asked / rccl asked
 #   scale                       one-GPU rehearsal of every shard size + sweep                   (tools/scale_rehearsal.sh, sweep.sh)
-#   mall                        round 5: Infinity-Cache reuse between the passes (needs `make -C nka_amd/csrc ftemporal`)
 #   p2p                         round 5: the peer-to-peer exchange, latency as far as one GPU can tell
 #   lib-ab ROUNDS "ARGS" LIBS   interleaved bench.py A/B of several builds of libnka_hip.so     (tools/ab_bench.sh)
 set -o pipefail
@@ -116,23 +115,6 @@ rank-rehearsal)
 scale)
   bash tools/scale_rehearsal.sh > /dev/null 2>&1; cat gpurun_out/scale_rehearsal.txt
   bash tools/sweep.sh c > gpurun_out/sweep_n_mvec.txt 2>&1; cat gpurun_out/sweep_n_mvec.txt ;;
-mall)
-  # (a) temporal loads for the vectors both passes read (libnka_hip_diag_ft<bits>.so: 1 = in PA, 2 = in PB, 3 = both),
-  # (b) PB in the reverse of PA's tile order (pb_reverse), (c) both: profiles/r05/ab_mall_reuse.txt
-  D=nka_amd/libnka_hip_diag
-  out=gpurun_out/r5_mall_ab.txt; : > $out
-  for spec in "c 1.25e7 20" "f08 1.25e7 20" "c 1e7 10" "f08 1e7 10" "c 5e6 20" "c 1e8 20"; do
-    set -- $spec
-    echo "=== flavor $1 n $2 m $3: base build against temporal loads in both passes, each with pb_reverse 0 / 1" | tee -a $out
-    python tools/ab_libs.py --libs $D.so ${D}_ft3.so --combos pb_reverse=0 pb_reverse=1 --flavor $1 --vlen $2 --mvec $3 \
-        --rounds 10 --steps 16 --check-bits 2>&1 | grep -v amdgpu.ids | tee -a $out; pass_on ${PIPESTATUS[0]}
-  done
-  for spec in "c 1.25e7 20" "c 1e7 10" "f08 1.25e7 20" "c 1e8 20"; do
-    set -- $spec
-    echo "=== flavor $1 n $2 m $3: which pass's policy matters (ft1 = PA only, ft2 = PB only, ft3 = both)" | tee -a $out
-    python tools/ab_libs.py --libs $D.so ${D}_ft1.so ${D}_ft2.so ${D}_ft3.so --combos pb_reverse=0 --flavor $1 --vlen $2 --mvec $3 \
-        --rounds 10 --steps 16 --check-bits 2>&1 | grep -v amdgpu.ids | tee -a $out; pass_on ${PIPESTATUS[0]}
-  done ;;
 p2p)
   out=gpurun_out/r5_p2p_latency.txt; : > $out
   python tools/p2p_latency.py 12500000 2>&1 | grep -E "one rank|hook " | tee -a $out
