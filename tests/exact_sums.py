@@ -1,0 +1,205 @@
+"""Exact inner products and the error bound of the device's blocked sums (host code, no GPU).
+
+exact_dot(x, y) is the reference every fast sum of the library is held to (tests/test_sums_exact_gpu.py);
+k_steps / device_k derive how many roundings a product can meet on its way through the kernels that form the sums
+(nka_amd/csrc/nka_kernels.hpp: k_norm_diff, k_dots, k_dots_win, block_reduce_store, k_norm_fin, k_finalize_dots) with the
+grids the library launches them on (nka_amd/csrc/nka_hip.hip: sums_rounded, launch_dots_win_1, launch_dots_1, grid_for);
+planted_input builds the inputs of the GPU tests: a small random background with sentinels at the indices where the
+kernels hand elements from one loop, block or launch to the next.  tests/test_exact_sums_cpu.py holds all of it to
+Fraction arithmetic and shows that losing or doubling any one sentinel breaks the bound.
+"""
+import math
+
+import numpy as np
+
+U = 2.0 ** -53                  # unit roundoff of binary64 (round to nearest)
+SPLIT = 2.0 ** 27 + 1.0         # Veltkamp: x = hi + lo, both halves of <= 26 significant bits
+
+# launch geometry of the sum kernels (nka_kernels.hpp)
+BLOCK = 256                     # kBlock: threads per block, 4 wavefronts of 64
+WAVE = 64
+WAVES = BLOCK // WAVE
+FIN_THREADS = 64                # kFinThreads (k_finalize_dots) and the one wavefront of k_norm_fin
+WAVE_LEVELS = 6                 # exchange-and-add steps of a 64-lane butterfly (wave_sum / block_reduce_store)
+DOTS_PER_CU_MAX = 4             # grid_for: (22 + nloads - 1) / nloads blocks per CU for k_dots<4, *> (6 loads per thread)
+
+# exact_dot is exact for |x_i|, |y_i| < 2**995 (the split SPLIT*x and the products stay finite) and nonzero products
+# |x_i*y_i| >= 2**-916 (the smallest partial product of the split, ~2**-106 |x_i*y_i|, stays a normal number)
+MAX_ABS = 2.0 ** 995
+MIN_PRODUCT = 2.0 ** -916
+
+
+def two_prod(x, y):
+    """Error-free products (Dekker / Veltkamp): x*y == p + e exactly, elementwise, inside the range above."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    p = x * y
+    c = SPLIT * x
+    xh = c - (c - x)
+    xl = x - xh
+    c = SPLIT * y
+    yh = c - (c - y)
+    yl = y - yh
+    e = ((xh * yh - p) + xh * yl + xl * yh) + xl * yl
+    return p, e
+
+
+def exact_dot(x, y):
+    """The correctly rounded value of sum x_i*y_i.
+
+    Finite inputs: every product becomes p + e exactly (two_prod) and math.fsum rounds the sum of all of them once.
+    Inputs outside the range where the split is exact (MAX_ABS, MIN_PRODUCT) raise ValueError.  Non-finite inputs follow
+    IEEE arithmetic in ANY order of summation: NaN where a product is NaN (NaN, Inf * 0) or where products of both
+    infinities meet, else the infinity of the products."""
+    x = np.asarray(x, dtype=np.float64).ravel()
+    y = np.asarray(y, dtype=np.float64).ravel()
+    if x.shape != y.shape:
+        raise ValueError("exact_dot: lengths differ")
+    if x.size == 0:
+        return 0.0
+    fin = np.isfinite(x) & np.isfinite(y)
+    if not fin.all():
+        with np.errstate(invalid="ignore", over="ignore"):
+            q = x * y
+        if np.isnan(q).any() or ((q == np.inf).any() and (q == -np.inf).any()):
+            return math.nan
+        if np.isinf(q[fin]).any():
+            raise ValueError("exact_dot: a product of finite elements overflows")
+        return math.inf if (q == np.inf).any() else -math.inf
+    if max(float(np.abs(x).max()), float(np.abs(y).max())) >= MAX_ABS:
+        raise ValueError("exact_dot: an element beyond the range of the exact split")
+    p, e = two_prod(x, y)
+    ap = np.abs(p)
+    if ((ap > 0) & (ap < MIN_PRODUCT)).any():
+        raise ValueError("exact_dot: a product below the range of the exact split")
+    return math.fsum(np.concatenate([p, e]))
+
+
+def abs_dot(x, y):
+    """sum |x_i*y_i|, rounded upwards far enough to be an upper bound (the scale of the error bound)."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.size == 0:
+        return 0.0
+    return float(np.abs(x * y).sum()) * (1.0 + (x.size + 2) * U)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def k_steps(n, G, width):
+    """Roundings a product can meet in a blocked fma sum of n elements over G blocks, `width` elements per thread and
+    tile (2: the 16-byte path, tiles of 512; 1: the scalar path of an unaligned f, tiles of 256).
+
+      per-thread chain   width * ceil(ntile / G) fma on full tiles (block b takes tiles b, b + G, ...; k_norm_diff's
+                         8-tiles-ahead loop visits them in the same order), ntile = n // (BLOCK * width);
+      ragged tail        ceil(tail / BLOCK) more fma in the last block (tail < BLOCK * width elements, stride BLOCK);
+                         the unaligned k_norm_diff's grid-stride over elements, ceil(n / (G * BLOCK)) fma, is no longer;
+      block_reduce_store a 64-lane butterfly of WAVE_LEVELS additions, then waves 1..3 added to wave 0 in turn (3);
+      final sum          ceil(G / FIN_THREADS) additions per lane of k_finalize_dots / k_norm_fin, then a butterfly.
+
+    A fma rounds once (the product enters exactly), so a product picks up at most this many factors (1 + delta)."""
+    tile = BLOCK * width
+    ntile = n // tile
+    chain = width * _cdiv(ntile, G) + _cdiv(n - ntile * tile, BLOCK)
+    block = WAVE_LEVELS + (WAVES - 1)
+    fin = _cdiv(G, FIN_THREADS) + WAVE_LEVELS
+    return chain + block + fin
+
+
+def pass_grids(n, ncu, aligned):
+    """(G, width) of every launch that can form a sum of one single-rank update on a device of `ncu` compute units.
+
+    16-byte aligned f: k_norm_diff and k_dots_win run one block per CU, at most one per 512-element tile (sums_rounded,
+    launch_dots_win_1); k_dots<4, 2> -- the update whose only stored vector is the pending pair -- takes up to
+    DOTS_PER_CU_MAX blocks per CU as its occupancy allows (launch_dots_1, grid_for).  Unaligned f: k_norm_diff's
+    grid-stride over elements on the same grid, and k_dots<4, 1> on tiles of 256."""
+    t2 = max(n // (BLOCK * 2), 1)
+    if aligned:
+        return [(min(ncu, t2), 2)] + [(min(ncu * q, t2), 2) for q in range(1, DOTS_PER_CU_MAX + 1)]
+    t1 = max(n // BLOCK, 1)
+    return [(min(ncu, t2), 1)] + [(min(ncu * q, t1), 1) for q in range(1, DOTS_PER_CU_MAX + 1)]
+
+
+def device_k(n, ncu, aligned=True):
+    """K for every sum of one update: the largest k_steps over the launches that may form it."""
+    return max(k_steps(n, G, w) for G, w in pass_grids(n, ncu, aligned))
+
+
+def sum_bound(n, G, width):
+    """Relative error bound of the device's blocked fma sum against the ROUNDED exact sum, per unit of sum |x_i*y_i|:
+    gamma(K + 1) = (K + 1) u / (1 - (K + 1) u), K = k_steps(n, G, width); the + 1 is the rounding of exact_dot itself
+    (|fl(S) - S| <= u |S| <= u sum |x_i*y_i|)."""
+    k = k_steps(n, G, width) + 1
+    return k * U / (1.0 - k * U)
+
+
+def gamma(k):
+    """gamma(K + 1) for a K from device_k (see sum_bound)."""
+    return (k + 1) * U / (1.0 - (k + 1) * U)
+
+
+# ---- planted inputs -------------------------------------------------------------------------------------------------------
+
+def sentinel_indices(n, G):
+    """Indices where the aligned sum kernels hand elements over, for a grid of G blocks (one per CU) and tiles of 512,
+    by name.  Empty arrays where a shape has no such place."""
+    tile = BLOCK * 2
+    ntile = n // tile
+    out = {"ends": np.unique(np.array([0, n - 1] if n else [], dtype=np.int64))}
+    out["tile_last"] = np.arange(1, ntile + 1, dtype=np.int64) * tile - 1          # last element of every full tile
+    out["tail_first"] = np.array([ntile * tile] if ntile * tile < n else [], dtype=np.int64)
+    blocks = np.arange(min(G, ntile), dtype=np.int64)
+    last_tile = blocks + G * ((ntile - 1 - blocks) // G)
+    out["block_first"] = blocks * tile                                            # first element of each block's first tile
+    out["block_last"] = last_tile * tile                                          # ... and of its last tile
+    # k_norm_diff's ahead loop serves tiles t, t + G, ..., t + 7G while t + 7G < ntile, stepping 8G; the first tile the
+    # plain loop serves after it, where there is one
+    ahead = np.where(ntile - 7 * G - blocks - 1 >= 0, (ntile - 7 * G - blocks - 1) // (8 * G) + 1, 0)
+    plain = blocks + 8 * G * ahead
+    out["plain_first"] = plain[(ahead > 0) & (plain < ntile)] * tile
+    return out
+
+
+def all_sentinels(n, G):
+    s = sentinel_indices(n, G)
+    return np.unique(np.concatenate([v for v in s.values()] + [np.zeros(0, np.int64)]))
+
+
+def planted_input(n, G, rng, prev=None, background=0.125):
+    """One input f: N(0, background^2) everywhere, +-2^e (e in 0..3, random sign) at every sentinel.  A sentinel never
+    repeats the value it had in `prev` (the previous input), so that d = w1 - f is at least 1 in magnitude there: every
+    product at a sentinel -- of f, d, the normalised w1' and the stored w -- is far above the error bound."""
+    x = rng.standard_normal(n) * background
+    idx = all_sentinels(n, G)
+    if idx.size == 0:
+        return x
+    val = np.ldexp(1.0, rng.integers(0, 4, idx.size)) * rng.choice([-1.0, 1.0], idx.size)
+    if prev is not None:
+        same = val == prev[idx]
+        val[same] = -val[same]
+    x[idx] = val
+    return x
+
+
+def boundary_shapes(G):
+    """The vector lengths where the kernels change hands, for G compute units: tiny vectors around one wavefront and one
+    tile, every block owning exactly one tile (G * 512 +- 1), and the hand-over of k_norm_diff's 8-tiles-ahead loop to
+    its plain loop (8 G * 512 ...)."""
+    t = BLOCK * 2
+    return [1, 2, 7, 63, 64, 65, 511, 512, 513,
+            G * t - 1, G * t, G * t + 1,
+            8 * G * t - 1, 8 * G * t, 8 * G * t + 1, 8 * G * t + 511, 9 * G * t + 77]
+
+
+def pb_ticket_shape(G):
+    """A length at which PB hands its tiles out by tickets (pb_tickets_apply: n / 512 >= 64 G), not a multiple of 512."""
+    return 64 * G * BLOCK * 2 + 1031
+
+
+def detectable(term, bound, total_abs):
+    """A sum that lost (or doubled) the product `term` is off the exact sum by |term| minus its own error: the check
+    |red - exact| <= bound * total_abs cannot pass if |term| > 2 bound total_abs + u total_abs (the last: rounding of the
+    exact sum)."""
+    return abs(term) > (2.0 * bound + U) * total_abs

@@ -19,8 +19,26 @@ from launch_util import run_ranks  # noqa: E402
 
 import parity_util as P
 import scenarios as S
+from nka_amd import SUMS_BLOCKED, SUMS_BLOCKED_ROUNDED
 
 pytestmark = pytest.mark.gpu
+
+# The fixture-held tests run in both fast sum modes: SUMS_BLOCKED_ROUNDED -- what SUMS_AUTO resolves to beyond 64 elements
+# and on every sharded handle -- first, then the opt-in SUMS_BLOCKED
+SUMS_NAME = {SUMS_BLOCKED_ROUNDED: "rounded", SUMS_BLOCKED: "blocked"}
+
+
+def both_sums(values):
+    """Parameters of the outermost parametrisation of a fixture-held test, each value once per fast sum mode: SUMS_BLOCKED_ROUNDED
+    (id suffix "-rounded") first, then SUMS_BLOCKED under the id the test had before it ran in two modes.  `values`: the
+    former parameter values (tuples for several names)."""
+    out = []
+    for v in values:
+        t = v if isinstance(v, tuple) else (v,)
+        vid = "-".join(str(x) for x in t)
+        out += [pytest.param(*t, SUMS_BLOCKED_ROUNDED, id=f"{vid}-rounded"), pytest.param(*t, SUMS_BLOCKED, id=vid)]
+    return out
+
 
 TOL_SMALL = 1e-12   # n <= 1e5, well-conditioned subspace
 FLAVORS = {0: "f_out_f08", 2: "f_out_c", 1: "f_out_f08vec"}
@@ -41,9 +59,11 @@ def torch_cuda():
 
 
 def make_acc(n, m, flavor=0, sums=None):
-    """This file holds the FAST passes to their bars at every n (blocked, fused sums; raw-sum Gram row), also up to 64
-    elements, where a single-rank accelerator would sum in the reference's order by itself (nka_hip_set_sum_order; a
-    sharded one keeps the fast passes there).  Reference-order sums have their own file: tests/test_hip_reference_order.py."""
+    """This file holds the FAST passes to their bars at every n, also up to 64 elements, where a single-rank accelerator would
+    sum in the reference's order by itself (nka_hip_set_sum_order; a sharded one keeps the fast passes there).  `sums` names
+    the fast mode, always set explicitly: SUMS_BLOCKED_ROUNDED (the default beyond 64 elements: the norm in a pass of its own,
+    the Gram row on the rounded w1') in the runs both_sums adds, else SUMS_BLOCKED (one fused pass, raw-sum Gram
+    row).  Reference-order sums have their own file: tests/test_hip_reference_order.py."""
     import nka_amd
     return nka_amd.nka().init(n, m, flavor=flavor).set_sum_order(nka_amd.SUMS_BLOCKED if sums is None else sums)
 
@@ -56,15 +76,15 @@ def dev_update(torch):
     return update
 
 
-@pytest.mark.parametrize("name", S.scenario_names())
+@pytest.mark.parametrize("name,sums", both_sums(S.scenario_names()))
 @pytest.mark.parametrize("flavor", [0, 1, 2])
-def test_scenarios_decisions_exact_values_within_tolerance(torch_cuda, oracle, name, flavor):
+def test_scenarios_decisions_exact_values_within_tolerance(torch_cuda, oracle, name, flavor, sums):
     g = S.load(name)
     key = FLAVORS[flavor]
     if key not in g.files:
         pytest.skip("fixture has no output for this flavour")
     n, m = int(g["n"]), int(g["mvec"])
-    acc = make_acc(n, m, flavor)
+    acc = make_acc(n, m, flavor, sums)          # (n = 64: set explicitly, SUMS_AUTO would sum in the reference's order)
     states = []
     outs, trace = S.replay(acc, g, update=dev_update(torch_cuda), after_update=lambda u, a: states.append(a.state()))
     assert acc.defined()
@@ -76,12 +96,13 @@ def test_scenarios_decisions_exact_values_within_tolerance(torch_cuda, oracle, n
     exact, err_ref = P.fixture_truth(g, oracle)
     for u in range(len(outs)):
         truth = (S.rel_err(outs[u], exact[u], inputs[u]), err_ref[u], n, m)
-        P.check(S.rel_err(outs[u], g[key][u], inputs[u]), states[u], f"scenario {name} flavor {flavor} vs own reference",
-                where=u, spread=spreads[u], truth=truth)
+        P.check(S.rel_err(outs[u], g[key][u], inputs[u]), states[u],
+                f"scenario {name} flavor {flavor} vs own reference [{SUMS_NAME[sums]}]", where=u, spread=spreads[u], truth=truth)
         # every flavour -- the front ends' default C/compact one included -- against the
         # reference FORTRAN path (src-F08) on the same inputs, same rule
         P.check(S.rel_err(outs[u], g["f_out_f08"][u], inputs[u]), states[u],
-                f"scenario {name} flavor {flavor} vs src-F08 reference", where=u, spread=spreads[u], truth=truth)
+                f"scenario {name} flavor {flavor} vs src-F08 reference [{SUMS_NAME[sums]}]", where=u, spread=spreads[u],
+                truth=truth)
     if "first" in g.files:                                           # list state of the C reference
         for u, st in enumerate(states):
             assert (st.first, st.last, st.free) == (g["first"][u], g["last"][u], g["free"][u]), (name, u)
@@ -224,11 +245,11 @@ def test_dot_products_within_tolerance(torch_cuda):
                 assert red[2 + m + p] == pytest.approx(float(f_in @ W[k]), abs=1e-13 * nf)
 
 
-def test_medium_case_against_f08_reference_fixture(torch_cuda):
+def test_medium_case_against_f08_reference_fixture(torch_cuda, sums=SUMS_BLOCKED):
     g = np.load(os.path.join(S.GOLD, "medium_n100000_m10.npz"))
     n, m, calls = int(g["n"]), int(g["mvec"]), int(g["calls"])
     rng = np.random.Generator(np.random.PCG64(int(g["seed"])))
-    acc = make_acc(n, m)
+    acc = make_acc(n, m, sums=sums)
     probe = np.cos(np.arange(n) * 0.001)
     for t in range(calls):
         f = rng.random(n) * 2.0 - 1.0
@@ -243,13 +264,18 @@ def test_medium_case_against_f08_reference_fixture(torch_cuda):
         assert abs(float(out @ probe) - g["out_probe"][t]) <= TOL_SMALL * fin_norm * np.linalg.norm(probe)
 
 
-@pytest.mark.parametrize("flavor", [0, 1, 2])
+def test_medium_case_against_f08_reference_fixture_rounded_sums(torch_cuda):
+    """The same in the default fast mode, SUMS_BLOCKED_ROUNDED (the test above keeps SUMS_BLOCKED)."""
+    test_medium_case_against_f08_reference_fixture(torch_cuda, sums=SUMS_BLOCKED_ROUNDED)
+
+
+@pytest.mark.parametrize("flavor,sums", both_sums([0, 1, 2]))
 @pytest.mark.parametrize("n,m", [(0, 2), (1, 1), (7, 8), (1000, 1), (777, 40), (2048, 33), (5000, 64)])
-def test_edge_shapes_against_oracle(torch_cuda, oracle, n, m, flavor):
+def test_edge_shapes_against_oracle(torch_cuda, oracle, n, m, flavor, sums):
     """Empty and tiny vectors, mvec = 1, and mvec beyond one unrolled pass (the
     PA/PB kernels then run several passes of 32)."""
     rng = np.random.default_rng(n * 131 + m)
-    acc, ora = make_acc(n, m, flavor), oracle.OracleNKA(n, m, flavor)
+    acc, ora = make_acc(n, m, flavor, sums), oracle.OracleNKA(n, m, flavor)
     spread = P.Spread(oracle, n, m)
     ncall = min(m + 4, 45)
     basis = rng.standard_normal((3, n))
@@ -265,15 +291,16 @@ def test_edge_shapes_against_oracle(torch_cuda, oracle, n, m, flavor):
         assert acc.state().list_order() == ora.state().list_order()
         assert acc.state().free_order() == ora.state().free_order()
         if n:
-            P.check(S.rel_err(out, f, x), acc.state(), f"edge shape n={n} m={m} flavor {flavor}", where=t, spread=spread.value,
+            P.check(S.rel_err(out, f, x), acc.state(), f"edge shape n={n} m={m} flavor {flavor} [{SUMS_NAME[sums]}]", where=t,
+                    spread=spread.value,
                 truth=spread.truth(out, x))
     assert acc.defined()
 
 
-def test_unaligned_device_pointer_takes_scalar_path(torch_cuda, oracle):
+def test_unaligned_device_pointer_takes_scalar_path(torch_cuda, oracle, sums=SUMS_BLOCKED):
     n, m = 3001, 5
     rng = np.random.default_rng(9)
-    acc, ora = make_acc(n, m), oracle.OracleNKA(n, m)
+    acc, ora = make_acc(n, m, sums=sums), oracle.OracleNKA(n, m)
     buf = torch_cuda.zeros(n + 1, dtype=torch_cuda.float64, device="cuda")
     view = buf[1:]                                   # 8-byte but not 16-byte aligned
     assert view.data_ptr() % 16 == 8
@@ -284,21 +311,31 @@ def test_unaligned_device_pointer_takes_scalar_path(torch_cuda, oracle):
         view.copy_(torch_cuda.from_numpy(x))
         acc.accel_update(view)
         assert acc.num_vec() == ora.num_vec()
-        P.record(S.rel_err(view.cpu().numpy(), f, x), TOL_SMALL, "unaligned pointer n=3001 m=5")
+        P.record(S.rel_err(view.cpu().numpy(), f, x), TOL_SMALL, f"unaligned pointer n=3001 m=5 [{SUMS_NAME[sums]}]")
 
 
-def test_host_array_compat_entry_and_config1_example(torch_cuda, oracle):
+def test_unaligned_device_pointer_takes_scalar_path_rounded_sums(torch_cuda, oracle):
+    """The same in the default fast mode, SUMS_BLOCKED_ROUNDED (the test above keeps SUMS_BLOCKED)."""
+    test_unaligned_device_pointer_takes_scalar_path(torch_cuda, oracle, sums=SUMS_BLOCKED_ROUNDED)
+
+
+def test_host_array_compat_entry_and_config1_example(torch_cuda, oracle, sums=SUMS_BLOCKED):
     """BASELINE config 1: the 50x50 example driven through the HIP path (host
     array entry point, like the reference signature) reproduces reference_output."""
     import json
     with open(os.path.join(S.GOLD, "example_tables.json")) as fh:
         tables = json.load(fh)
     for mvec, nsweep, key in ((5, 2, "f08 --nka-vec 5"), (5, 4, "f08 --sweeps 4 --nka-vec 5")):
-        acc = make_acc(2500, mvec)
+        acc = make_acc(2500, mvec, sums=sums)
         rn, _ = oracle.example_solve(nsweep=nsweep, accel=acc)
         lines = [f"{0:3d}:{rn[0]:14.6E}"] + [oracle.format_example_line(i, rn[i], rn[0]) for i in range(1, len(rn))]
         assert lines[-1] == tables[key][-1]
         assert lines == tables[key][1:]
+
+
+def test_host_array_compat_entry_and_config1_example_rounded_sums(torch_cuda, oracle):
+    """The same in the default fast mode, SUMS_BLOCKED_ROUNDED (the test above keeps SUMS_BLOCKED)."""
+    test_host_array_compat_entry_and_config1_example(torch_cuda, oracle, sums=SUMS_BLOCKED_ROUNDED)
 
 
 def test_api_surface_defaults_and_errors(torch_cuda):
@@ -432,14 +469,14 @@ def test_bench_multi_gpu_plumbing_rehearsal_single_rank(torch_cuda, hook):
     assert d["value"] > 0
 
 
-@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
-def test_non_finite_input_takes_the_same_decisions_as_the_oracle(torch_cuda, oracle, bad):
+@pytest.mark.parametrize("bad,sums", both_sums([float("nan"), float("inf")]))
+def test_non_finite_input_takes_the_same_decisions_as_the_oracle(torch_cuda, oracle, bad, sums):
     """A NaN / Inf in f: the reference has no guard (s == 0 is false for NaN,
     hkk > vtol**2 is false for NaN -> the entry is dropped); the device takes the
     same branches, and restart() recovers a clean object."""
     n, m = 257, 3
     rng = np.random.default_rng(17)
-    acc, ora = make_acc(n, m), oracle.OracleNKA(n, m)
+    acc, ora = make_acc(n, m, sums=sums), oracle.OracleNKA(n, m)
     for t in range(7):
         x = rng.standard_normal(n)
         if t == 3:
@@ -465,9 +502,9 @@ def test_non_finite_input_takes_the_same_decisions_as_the_oracle(torch_cuda, ora
 
 @pytest.mark.skipif(not __import__("oracle.oracle_py", fromlist=["x"]).have_ref(),
                     reason="compiled reference (oracle/_ref) did not travel to this box")
-@pytest.mark.parametrize("seed", [1, 2, 3])
+@pytest.mark.parametrize("seed,sums", both_sums([1, 2, 3]))
 @pytest.mark.parametrize("flavor", [0, 1, 2])
-def test_against_the_live_compiled_reference(torch_cuda, oracle, seed, flavor):
+def test_against_the_live_compiled_reference(torch_cuda, oracle, seed, flavor, sums):
     """The reference's own src-F08 module (compiled from /root/reference into
     oracle/_ref and shipped with the repo) and the HIP path, side by side, on
     fresh random streams with dependent vectors, relax and restart mixed in.
@@ -477,7 +514,7 @@ def test_against_the_live_compiled_reference(torch_cuda, oracle, seed, flavor):
     n, m = 20011, 8
     rng = np.random.default_rng(seed)
     ref = oracle.RefF08(n, m)
-    acc = make_acc(n, m, flavor)
+    acc = make_acc(n, m, flavor, sums)
     spread = P.Spread(oracle, n, m)
     basis = rng.standard_normal((4, n))
     worst = 0.0
@@ -493,7 +530,8 @@ def test_against_the_live_compiled_reference(torch_cuda, oracle, seed, flavor):
         acc.accel_update(ft)
         assert acc.num_vec() == ref.num_vec(), (seed, flavor, t)
         err = P.check(S.rel_err(ft.cpu().numpy(), f, x), acc.state(),
-                      f"live src-F08 reference n={n} m={m} flavor {flavor}", where=(seed, t), spread=spread.value,
+                      f"live src-F08 reference n={n} m={m} flavor {flavor} [{SUMS_NAME[sums]}]", where=(seed, t),
+                      spread=spread.value,
                 truth=spread.truth(ft.cpu().numpy(), x))
         worst = max(worst, err)
         if t == 20:
@@ -612,8 +650,8 @@ def test_steady_state_update_is_hipgraph_capturable(torch_cuda, n, tickets):
     assert not acc.capture_safe()
 
 
-@pytest.mark.parametrize("m,seed", [(2, 0), (5, 1), (9, 2), (5, 3), (33, 4)])
-def test_randomised_call_sequences_against_oracle(torch_cuda, oracle, m, seed):
+@pytest.mark.parametrize("m,seed,sums", both_sums([(2, 0), (5, 1), (9, 2), (5, 3), (33, 4)]))
+def test_randomised_call_sequences_against_oracle(torch_cuda, oracle, m, seed, sums):
     """Long random sequences of every public operation -- updates with fresh,
     dependent, repeated and zero inputs, relax, restart, set_vec_tol -- must keep
     the device state machine (and the host's bounds that size the kernels) in
@@ -621,7 +659,7 @@ def test_randomised_call_sequences_against_oracle(torch_cuda, oracle, m, seed):
     call, values within the conditioning-aware tolerance."""
     n = 257
     rng = np.random.default_rng(1000 + seed)
-    acc = make_acc(n, m)
+    acc = make_acc(n, m, sums=sums)
     ora = oracle.OracleNKA(n, m, acc.flavor())
     spread = P.Spread(oracle, n, m)
     basis = rng.standard_normal((3, n))
@@ -649,7 +687,7 @@ def test_randomised_call_sequences_against_oracle(torch_cuda, oracle, m, seed):
             st = acc.state()
             nx = np.linalg.norm(x)
             if nx > 0:
-                P.check(S.rel_err(ft.cpu().numpy(), f, x), st, f"random call sequence m={m} seed={seed}",
+                P.check(S.rel_err(ft.cpu().numpy(), f, x), st, f"random call sequence m={m} seed={seed} [{SUMS_NAME[sums]}]",
                         where=(step, nupd), spread=spread.value,
                 truth=spread.truth(ft.cpu().numpy(), x))
         elif r < 0.88:
