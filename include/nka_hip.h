@@ -133,7 +133,8 @@ int nka_hip_set_vec_tol(nka_hip_t a, double vtol);
  *   NKA_HIP_SUMS_BLOCKED          opt-in FAST mode: ONE pure-read pass forms every sum of an update, the Gram row of the
  *                                 normalised difference is taken from raw sums, fl(<d,w_k>/s): 2 words per element and one
  *                                 exchange less (5-9 % faster), the same typical distance from the truth, a heavier tail
- * A user dot product (nka_hip_set_host_dot) overrides them all.  Can be changed between updates.  The environment variable
+ * A user dot product (nka_hip_set_host_dot) overrides them all; diagonal weights (nka_hip_set_dot_weights) take the fast
+ * passes only.  Can be changed between updates.  The environment variable
  * NKA_HIP_SUMS = auto | rounded | blocked | reference sets what a new handle starts with (for callers that cannot call
  * this function: the reference's own programs relinked against the front ends). */
 enum { NKA_HIP_SUMS_AUTO = 0, NKA_HIP_SUMS_REFERENCE_ORDER = 1, NKA_HIP_SUMS_BLOCKED = 2, NKA_HIP_SUMS_BLOCKED_ROUNDED = 3 };
@@ -163,6 +164,36 @@ int nka_hip_device_info(nka_hip_t a, char *name64, int32_t *num_cu);
  * 2+L vectors cross PCIe per update and the call synchronises: a compatibility path.  fn = NULL restores the device sums. */
 typedef double (*nka_hip_host_dot_fn)(void *ctx, int64_t n, const double *x, const double *y);
 int nka_hip_set_host_dot(nka_hip_t a, nka_hip_host_dot_fn fn, void *ctx);
+
+/* DIAGONAL WEIGHTS: the dp  <x,y>_w = sum_i w_i x_i y_i  on the DEVICE, in the fast passes (no host copies, no
+ * synchronisation in accel_update).  For unknowns of different scale, ghost / overlap entries of a slice (w_i = 0: each
+ * entry then counts once in the global sums through the installed all-reduce, whatever the slices hold), masks.
+ *   nka_hip_set_dot_weights       w_dev: vlen_local doubles in device memory (checked like f); NULL = plain sums again
+ *   nka_hip_set_dot_weights_host  the same from host memory
+ *   nka_hip_dot_weighted          (nka_hip_ext.h) 1 = weighted, 0 = plain; < 0 on error
+ * The values are COPIED into a buffer of the handle (allocated at the first set, freed by nka_hip_destroy only) and checked
+ * there on the device; the call synchronises, and the caller's buffer is free again when it returns.  Every weight must be
+ * finite and >= 0: otherwise NKA_HIP_EINVAL and the previous weighting stays in force.  With vlen_local == 0 a non-NULL
+ * pointer is never read.  Refused (nothing changes): while the handle's stream is capturing (NKA_HIP_ESTATE); together with
+ * NKA_HIP_SUMS_REFERENCE_ORDER (NKA_HIP_EINVAL, whichever is set first, the NKA_HIP_SUMS=reference start value included:
+ * those kernels form plain sums only); together with nka_hip_set_host_dot (NKA_HIP_ESTATE, whichever is set first).  With
+ * weights NKA_HIP_SUMS_AUTO resolves to _BLOCKED_ROUNDED at every n.  nka_hip_clone copies them.  Like a new dp in the
+ * reference, a change applies from the next update on; the subspace then mixes two metrics -- call nka_hip_restart() to start
+ * it in the new one.  A captured update keeps whether it was weighted; it reads the values of the handle's buffer at replay,
+ * so new values set between replays apply to the next replay.
+ * What the fast passes then sum (a_w = fl(w_i * a_i) is the FIRST operand of every product, fma(a_w, b_i, acc); the blocked
+ * order, the grid rules and the per-thread accumulation order are those of the plain passes; d = fl(w1 - f), w1' = fl(d/s),
+ * or fl(fl(1/s)*d) in the F08-vector flavour):
+ *               NKA_HIP_SUMS_BLOCKED_ROUNDED (default)    NKA_HIP_SUMS_BLOCKED
+ *   red[0]      sum fl(w d) d                              sum fl(w d) d
+ *   red[1]      sum fl(w f) w1'                            sum fl(w f) d
+ *   red[2+p]    sum fl(w w1') w_p                          sum fl(w d) w_p
+ *   red[2+m+p]  sum fl(w f) w_p                            sum fl(w f) w_p
+ * Exact consequences (tests/test_dot_weights_gpu.py): w == 1 returns the bits of a plain handle; w_i = 4^k_i (integers k_i,
+ * nothing over- or underflowing) returns 2^-k o (a plain run on 2^k o f), bit for bit, with the same decisions; w_i = 0 makes
+ * entry i contribute nothing to any sum while every value stays finite (0 * Inf is NaN, as in the reference's dp). */
+int nka_hip_set_dot_weights(nka_hip_t a, const double *w_dev);
+int nka_hip_set_dot_weights_host(nka_hip_t a, const double *w_host);
 
 /* ---- distribution (contiguous n-slices, one handle per rank; F08:58-64) --- */
 

@@ -16,6 +16,9 @@
  *   BLOCKED (opt-in fast mode)    yes    yes (1 exchange)     yes (1 exchange)        yes (opt-in; fused into the final sums)
  *   REFERENCE_ORDER               yes    validation only: 2N exchanges per update through any hook that sums; mvec <= 250
  *   user dot product (core)       yes    the user's dp IS the global reduction: hooks are not applied on top
+ *   diagonal weights (core)       yes    with AUTO / BLOCKED_ROUNDED / BLOCKED: the partial sums keep their layout, so every
+ *                                        transport of that row applies (not yet held by a test beyond "none"); refused with
+ *                                        REFERENCE_ORDER and with the user dot product
  *   out-of-place entry            every row above except the user dot product; not capturable into a graph
  * F08 = /root/reference/src-F08/nka_type.F90, C = /root/reference/src-C/nonlinear_krylov_accelerator.{h,c}.
  */
@@ -121,6 +124,8 @@ int nka_hip_accel_update_swap(nka_hip_t a, double **f_io, const double **f_acc);
  * (nka_hip_set_allreduce: a host callback a replay would not call again; the built-in
  * RCCL hook only enqueues on the stream and can be captured). */
 int nka_hip_capture_safe(nka_hip_t a);
+/* 1 while the handle has diagonal dot-product weights (nka_hip_set_dot_weights, core header), 0 without; < 0 on error. */
+int nka_hip_dot_weighted(nka_hip_t a);
 
 /* Upper bound on the list length (pending pair included) at the entry of the next update, as the HOST knows it
  * without synchronising: its own count (+1 per update up to mvec+1, -1 per relax, 0 after restart) tightened by the

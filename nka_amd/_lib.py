@@ -52,6 +52,9 @@ SIGNATURES = {
     "nka_hip_p2p_attach_local": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32]),
     "nka_hip_state_digest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "nka_hip_set_host_dot": (C.c_int, [C.c_void_p, HOST_DOT_FN, C.c_void_p]),
+    "nka_hip_set_dot_weights": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nka_hip_set_dot_weights_host": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nka_hip_dot_weighted": (C.c_int, [C.c_void_p]),
     "nka_hip_set_timing": (C.c_int, [C.c_void_p, C.c_int32]),
     "nka_hip_get_timing": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_float)]),
     "nka_hip_set_timing_stride": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -138,6 +138,10 @@ struct nka_hip_state {
                               // communicator belongs to the original, and rank-local sums would be silently wrong
   nka_hip_host_dot_fn host_dot = nullptr;   // user dot product on host copies (compatibility path)
   void *host_dot_ctx = nullptr;
+  double *wgt = nullptr;      // diagonal dot-product weights (nka_hip_set_dot_weights): n doubles, allocated at the first set,
+                              // freed at destroy only (a captured update holds the address)
+  unsigned long long *wgt_chk = nullptr;   // two words for the set-time check of the weights (k_check_weights), freed at destroy
+  bool weighted = false;      // the passes that form sums run their WGT = true instantiations (k_norm_diff, k_dots, k_dots_win)
   // instrumentation
   // kTimingEvents events per update, in a ring of timing_cap updates
   int timing_cap = 0;

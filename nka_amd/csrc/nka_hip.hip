@@ -212,11 +212,17 @@ int p2p_allreduce(void *ctx, double *buf, int32_t count, void *stream) {
 }
 
 // ---- kernel dispatch by unroll width ------------------------------------------
+// (a weighted handle, nka_hip_set_dot_weights: the WGT = true twin of each pass, same grid rules -- the grid follows the
+//  occupancy of the UNWEIGHTED kernel, so that the blocked sums have the same order whether the weights are set or not)
 template <int MAXL, int VEC>
 int launch_dots_1(const nka_hip_state *a, const double *f, int pass, int npass) {
   static const int occ = occupancy_of(k_dots<MAXL, VEC>);
   const int g = grid_for(a, 0, VEC, occ, MAXL + 2);
-  hipLaunchKernelGGL((k_dots<MAXL, VEC>), dim3(g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, pass, a->pa_normed);
+  if (a->weighted)
+    hipLaunchKernelGGL((k_dots<MAXL, VEC, true>), dim3(g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, pass,
+                       a->pa_normed);
+  else
+    hipLaunchKernelGGL((k_dots<MAXL, VEC>), dim3(g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, pass, a->pa_normed);
   hipLaunchKernelGGL((k_finalize_dots<MAXL>), dim3(2 * MAXL + 2), dim3(kFinThreads), 0, a->stream, a->ctl,
                      a->partials, g, pass, npass * MAXL, pass * MAXL, a->p2p_fused ? a->p2p : P2P{}, a->pa_normed ? 1 : 0);
   return g;
@@ -229,7 +235,11 @@ int launch_dots_win_1(const nka_hip_state *a, const double *f, int bpc, int base
   const int64_t ntile = a->n / (kBlock * 2);
   int64_t g = (int64_t)a->num_cu * std::min(occ, std::max(1, bpc));
   g = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(g, std::max<int64_t>(ntile, 1)), kMaxGrid));
-  hipLaunchKernelGGL((k_dots_win<MAXL, W>), dim3((int)g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base, a->pa_normed);
+  if (a->weighted)
+    hipLaunchKernelGGL((k_dots_win<MAXL, W, true>), dim3((int)g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base,
+                       a->pa_normed);
+  else
+    hipLaunchKernelGGL((k_dots_win<MAXL, W>), dim3((int)g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base, a->pa_normed);
   // (Round 3 measured forming these sums -- and the scalar step -- in the tail of the PA launch, by the block that
   //  finishes last: 2-4 us SLOWER per update than the launches it saves, profiles/r03/ab_small_pa_tail_not_kept.txt.)
   hipLaunchKernelGGL((k_finalize_dots<MAXL>), dim3(2 * MAXL + 2), dim3(kFinThreads), 0, a->stream, a->ctl,
@@ -685,6 +695,8 @@ int nka_hip_destroy(nka_hip_t a) {
   if (a->list_word) hipHostFree(a->list_word);
   hipFree(a->f_stage);
   hipFree(a->hd_scratch);
+  hipFree(a->wgt);
+  hipFree(a->wgt_chk);
   for (auto &e : a->ev)
     if (e) hipEventDestroy(e);
   a->ev.clear();
@@ -788,6 +800,19 @@ int nka_hip_clone(nka_hip_t src, nka_hip_t *out) {
   }
   b->host_dot = src->host_dot;
   b->host_dot_ctx = src->host_dot_ctx;
+  if (src->weighted && src->n > 0) {      // the diagonal weights are part of the object, like the dp (a buffer of its own)
+    e = hipMalloc((void **)&b->wgt, sizeof(double) * (size_t)src->n);
+    const long long off = e == hipSuccess ? buffer_offset(b, b->wgt) : 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(b->wgt, src->wgt, sizeof(double) * (size_t)src->n, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->ctl.pc + PC_WGT, &off, sizeof off, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      nka_hip_destroy(b);
+      return fail(e == hipErrorOutOfMemory ? NKA_HIP_ENOMEM : NKA_HIP_EHIP, std::string("nka_hip_clone: ") + hipGetErrorString(e));
+    }
+  }
+  b->weighted = src->weighted;
   *out = b;
   return 0;
 }
@@ -1102,8 +1127,9 @@ static int host_dot_update_scalars(nka_hip_t a, const double *f, int mode) {
 }
 
 // Reference-order sums: asked for, or free -- a vector of at most kOrdAutoMax elements on a single rank.
+// (never with diagonal weights: the reference-order kernels form plain sums only, so AUTO takes the fast passes at every n)
 static bool ordered_sums(const nka_hip_state *a) {
-  if (a->allreduce || a->host_dot || a->mvec > kOrdMaxMvec) return false;
+  if (a->allreduce || a->host_dot || a->weighted || a->mvec > kOrdMaxMvec) return false;
   return a->sum_order == NKA_HIP_SUMS_REFERENCE_ORDER || (a->sum_order == NKA_HIP_SUMS_AUTO && a->n <= kOrdAutoMax);
 }
 
@@ -1306,7 +1332,10 @@ static SumsResult sums_rounded(nka_hip_t a, const double *f, int vec, int mode, 
   auto hip = [&](hipError_t e) { if (e != hipSuccess && !r.rc) r.rc = fail(NKA_HIP_EHIP, std::string("accel_update: ") + hipGetErrorString(e)); return e == hipSuccess; };
   if (a->pending) {
     const int g = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)a->num_cu, std::max<int64_t>(a->n / (kBlock * 2), 1)));
-    hipLaunchKernelGGL(k_norm_diff, dim3(g), dim3(kBlock), 0, s, a->ctl, a->vs, f, a->partials);
+    if (a->weighted)
+      hipLaunchKernelGGL(k_norm_diff<true>, dim3(g), dim3(kBlock), 0, s, a->ctl, a->vs, f, a->partials);
+    else
+      hipLaunchKernelGGL(k_norm_diff<false>, dim3(g), dim3(kBlock), 0, s, a->ctl, a->vs, f, a->partials);
     hipLaunchKernelGGL(k_norm_fin, dim3(1), dim3(64), 0, s, a->ctl, a->partials, g);
     if (!hip(hipGetLastError())) return r;
     if (a->allreduce)
@@ -1862,9 +1891,92 @@ int nka_hip_set_shard(nka_hip_t a, int32_t rank, int32_t nranks) {
 
 int nka_hip_set_host_dot(nka_hip_t a, nka_hip_host_dot_fn fn, void *ctx) {
   if (!a) return fail(NKA_HIP_EINVAL, "null handle");
+  if (fn && a->weighted)
+    return fail(NKA_HIP_ESTATE, "set_host_dot: the handle has diagonal dot-product weights (nka_hip_set_dot_weights(a, NULL) first)");
   a->host_dot = fn;
   a->host_dot_ctx = fn ? ctx : nullptr;
   return 0;
+}
+
+// ---- diagonal dot-product weights (include/nka_hip.h: nka_hip_set_dot_weights) ----
+// `src` holds n doubles in device memory; they are checked where they lie, and only then copied into the handle's own buffer
+// (allocated at the first set, freed at destroy only: a captured update holds its address), so invalid weights leave the
+// previous weighting in force.  Synchronises.
+static int set_weights_from_device(nka_hip_t a, const double *src, const char *what) {
+  hipStream_t s = a->stream;
+  const int64_t n = a->n;
+  // the buffers live as long as the handle (nka_hip_destroy frees them): no free here, which would synchronise the DEVICE,
+  // not only this stream -- and wait forever for slices of one device that exchange their sums on the device
+  if (!a->wgt_chk) HIP_TRY(hipMalloc((void **)&a->wgt_chk, 2 * sizeof(unsigned long long)));
+  if (!a->wgt) HIP_TRY(hipMalloc((void **)&a->wgt, sizeof(double) * (size_t)n));
+  unsigned long long res[2] = {0ull, ~0ull};
+  HIP_TRY(hipMemcpyAsync(a->wgt_chk, res, sizeof res, hipMemcpyHostToDevice, s));
+  const int g = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)a->num_cu * 4, (n + kBlock - 1) / kBlock));
+  hipLaunchKernelGGL(k_check_weights, dim3(g), dim3(kBlock), 0, s, src, n, a->wgt_chk);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(res, a->wgt_chk, sizeof res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (res[0] != 0)
+    return fail(NKA_HIP_EINVAL, std::string(what) + ": " + std::to_string(res[0]) + " weight(s) negative or not finite, the first at index " +
+                                    std::to_string(res[1]) + " (the previous weighting stays in force)");
+  // the address word is written by every successful set (the weighted passes find the buffer through the address block)
+  const long long off = buffer_offset(a, a->wgt);
+  HIP_TRY(hipMemcpyAsync(a->ctl.pc + PC_WGT, &off, sizeof off, hipMemcpyHostToDevice, s));
+  if (src != a->wgt) HIP_TRY(hipMemcpyAsync(a->wgt, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  a->weighted = true;
+  return 0;
+}
+// what every setter checks first: the combinations that are refused, and no capture in progress
+static int weights_settable(nka_hip_t a, bool setting, const char *what) {
+  if (a->poisoned) return fail(NKA_HIP_ESTATE, std::string(what) + ": an earlier update failed after its scalar step had been enqueued: destroy the handle");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(a->stream, &cs) != hipSuccess) (void)hipGetLastError();
+  if (cs != hipStreamCaptureStatusNone) return fail(NKA_HIP_ESTATE, std::string(what) + ": the handle's stream is capturing");
+  if (!setting) return 0;
+  if (a->host_dot) return fail(NKA_HIP_ESTATE, std::string(what) + ": the handle has a user dot product on host copies (nka_hip_set_host_dot)");
+  if (a->sum_order == NKA_HIP_SUMS_REFERENCE_ORDER)
+    return fail(NKA_HIP_EINVAL, std::string(what) + ": not with NKA_HIP_SUMS_REFERENCE_ORDER (those kernels form plain sums only)");
+  return 0;
+}
+
+int nka_hip_set_dot_weights(nka_hip_t a, const double *w_dev) {
+  if (!a) return fail(NKA_HIP_EINVAL, "null handle");
+  HIP_TRY(hipSetDevice(a->device));
+  if (int rc = weights_settable(a, w_dev != nullptr, "set_dot_weights")) return rc;
+  if (!w_dev) {
+    a->weighted = false;      // (the buffer stays: a captured update may hold its address)
+    return 0;
+  }
+  if (a->n == 0) {            // nothing to read
+    a->weighted = true;
+    return 0;
+  }
+  if (int rc = nka_detail::check_device_span(w_dev, a->n, "set_dot_weights: w")) return rc;
+  return set_weights_from_device(a, w_dev, "set_dot_weights");
+}
+
+int nka_hip_set_dot_weights_host(nka_hip_t a, const double *w_host) {
+  if (!a) return fail(NKA_HIP_EINVAL, "null handle");
+  HIP_TRY(hipSetDevice(a->device));
+  if (int rc = weights_settable(a, w_host != nullptr, "set_dot_weights_host")) return rc;
+  if (!w_host) {
+    a->weighted = false;
+    return 0;
+  }
+  if (a->n == 0) {
+    a->weighted = true;
+    return 0;
+  }
+  // staged in the buffer of the host-array update (used only inside that synchronous call), checked there, then copied
+  if (!a->f_stage) HIP_TRY(hipMalloc((void **)&a->f_stage, sizeof(double) * (size_t)std::max<int64_t>(a->n, 1)));
+  HIP_TRY(hipMemcpyAsync(a->f_stage, w_host, sizeof(double) * (size_t)a->n, hipMemcpyHostToDevice, a->stream));
+  return set_weights_from_device(a, a->f_stage, "set_dot_weights_host");
+}
+
+int nka_hip_dot_weighted(nka_hip_t a) {
+  if (!a) return fail(NKA_HIP_EINVAL, "null handle");
+  return a->weighted ? 1 : 0;
 }
 
 int nka_hip_comm_unique_id(void *id128) {
@@ -2011,6 +2123,8 @@ int nka_hip_set_sum_order(nka_hip_t a, int32_t order) {
     return fail(NKA_HIP_EINVAL, "set_sum_order: NKA_HIP_SUMS_AUTO, _REFERENCE_ORDER, _BLOCKED or _BLOCKED_ROUNDED");
   if (order == NKA_HIP_SUMS_REFERENCE_ORDER && a->mvec > kOrdMaxMvec)
     return fail(NKA_HIP_EINVAL, "set_sum_order: reference-order sums are offered up to mvec = " + std::to_string(kOrdMaxMvec));
+  if (order == NKA_HIP_SUMS_REFERENCE_ORDER && a->weighted)
+    return fail(NKA_HIP_EINVAL, "set_sum_order: reference-order sums are not offered with diagonal dot-product weights");
   a->sum_order = order;
   return 0;
 }

@@ -75,6 +75,7 @@ enum {
   PC_NEW_V = 2,
   PC_OLD_W = 3,    // what an out-of-place update displaced from that slot: handed to the caller /
   PC_OLD_V = 4,    //   kept as the library's next spare
+  PC_WGT = 5,      // the diagonal dot-product weights of nka_hip_set_dot_weights (read by the WGT = true passes only)
   PC_HEADER = 8
 };
 
@@ -376,9 +377,26 @@ __device__ __forceinline__ double pa_operand(double d, int normed, double s, dou
   return (normed & 2) ? rs * d : d / s;
 }
 
-template <int MAXL, int VEC>
+// DIAGONAL WEIGHTS (nka_hip_set_dot_weights): every product of the weighted passes takes fl(w_i * a_i) as its FIRST operand
+// and the unweighted value as its second, fma(fl(w a), b, acc); the order of the sums is the unweighted kernels'.  The
+// passes that form sums (k_norm_diff, k_dots, k_dots_win) take `bool WGT = false`: with false these helpers return `a` and
+// no weight is loaded -- the instructions of the plain kernels -- with true the weights (n doubles, 256-byte aligned, found
+// through Ctl::pc[PC_WGT] like every other buffer) stream beside f and w1 in the same 16-byte non-temporal loads.
+template <bool WGT, class V>
+__device__ __forceinline__ double wgt_first(const V &om, int q, double a) {
+  if constexpr (WGT) return ex(om, q) * a;
+  else return a;
+}
+template <bool WGT>
+__device__ __forceinline__ double wgt_at(const double *__restrict__ wgt, int64_t i, double a) {
+  if constexpr (WGT) return wgt[i] * a;
+  else return a;
+}
+
+template <int MAXL, int VEC, bool WGT = false>
 __global__ __launch_bounds__(kBlock) void k_dots(Ctl ctl, Vecs vs, const double *__restrict__ f,
                                                  double *__restrict__ partials, int pass, int normed) {
+  const double *wgt = WGT ? vs.w + ctl.pc[PC_WGT] : nullptr;      // (WGT = false: never read)
   using V = typename VecT<VEC>::type;
   constexpr int NACC = 2 * MAXL + 2;
   const int G = gridDim.x;
@@ -404,6 +422,8 @@ __global__ __launch_bounds__(kBlock) void k_dots(Ctl ctl, Vecs vs, const double 
     const int64_t e = t * (kBlock * VEC) + threadIdx.x * VEC;
     const V fv = ld<VEC>(f + e);
     const V w1v = ld<VEC>(w1 + e);
+    V omv = {};
+    if constexpr (WGT) omv = ld<VEC>(wgt + e);
     V wkv[MAXL];
 #pragma unroll
     for (int j = 0; j < MAXL; j++) wkv[j] = ld<VEC>(wk[j] + e);
@@ -414,12 +434,13 @@ __global__ __launch_bounds__(kBlock) void k_dots(Ctl ctl, Vecs vs, const double 
     for (int q = 0; q < VEC; q++) {
       const double fq = ex(fv, q);
       const double d = pa_operand(ex(w1v, q) - fq, normed, s_n, rs_n);      // F08:266 ((-1)*f + w1 in F08V:237: same bits)
-      acc[0] = fma(d, d, acc[0]);
-      acc[1] = fma(fq, d, acc[1]);
+      const double dw = wgt_first<WGT>(omv, q, d), fw = wgt_first<WGT>(omv, q, fq);
+      acc[0] = fma(dw, d, acc[0]);
+      acc[1] = fma(fw, d, acc[1]);
 #pragma unroll
       for (int j = 0; j < MAXL; j++) {
-        acc[2 + j] = fma(d, ex(wkv[j], q), acc[2 + j]);
-        acc[2 + MAXL + j] = fma(fq, ex(wkv[j], q), acc[2 + MAXL + j]);
+        acc[2 + j] = fma(dw, ex(wkv[j], q), acc[2 + j]);
+        acc[2 + MAXL + j] = fma(fw, ex(wkv[j], q), acc[2 + MAXL + j]);
       }
     }
   }
@@ -427,13 +448,14 @@ __global__ __launch_bounds__(kBlock) void k_dots(Ctl ctl, Vecs vs, const double 
     for (int64_t i = ntile * (kBlock * VEC) + threadIdx.x; i < vs.n; i += kBlock) {
       const double fq = f[i];
       const double d = pa_operand(w1[i] - fq, normed, s_n, rs_n);
-      acc[0] = fma(d, d, acc[0]);
-      acc[1] = fma(fq, d, acc[1]);
+      const double dw = wgt_at<WGT>(wgt, i, d), fw = wgt_at<WGT>(wgt, i, fq);
+      acc[0] = fma(dw, d, acc[0]);
+      acc[1] = fma(fw, d, acc[1]);
 #pragma unroll
       for (int j = 0; j < MAXL; j++) {
         const double x = wk[j][i];
-        acc[2 + j] = fma(d, x, acc[2 + j]);
-        acc[2 + MAXL + j] = fma(fq, x, acc[2 + MAXL + j]);
+        acc[2 + j] = fma(dw, x, acc[2 + j]);
+        acc[2 + MAXL + j] = fma(fw, x, acc[2 + MAXL + j]);
       }
     }
   }
@@ -441,9 +463,11 @@ __global__ __launch_bounds__(kBlock) void k_dots(Ctl ctl, Vecs vs, const double 
 }
 
 // The norm pass of NKA_HIP_SUMS_BLOCKED_ROUNDED: sum d^2 with d = w1 - f (F08:266-267) over this rank's slice, two streams,
-// per-block partial sums in column 0 of `partials` (k_norm_fin adds them in a fixed order).
+// per-block partial sums in column 0 of `partials` (k_norm_fin adds them in a fixed order).  WGT: sum fl(w d)*d, three streams.
+template <bool WGT = false>
 static __global__ __launch_bounds__(kBlock) __attribute__((unused)) void k_norm_diff(Ctl ctl, Vecs vs, const double *__restrict__ f,
                                                                                          double *__restrict__ partials) {
+  const double *wgt = WGT ? vs.w + ctl.pc[PC_WGT] : nullptr;
   const int G = gridDim.x;
   const double *w1 = vs.w + ctl.pc[PC_FIRST_W];
   const bool v2 = (reinterpret_cast<uintptr_t>(f) % 16) == 0;      // (slot bases are 256-byte aligned)
@@ -457,12 +481,13 @@ static __global__ __launch_bounds__(kBlock) __attribute__((unused)) void k_norm_
     // tiles in the same order as the plain loop below, so the partial sums carry the same bits
     constexpr int kNormAhead = 8;
     for (; t + (int64_t)(kNormAhead - 1) * G < ntile; t += (int64_t)kNormAhead * G) {
-      d2 fv[kNormAhead], wv[kNormAhead];
+      d2 fv[kNormAhead], wv[kNormAhead], om[kNormAhead] = {};   // (om: WGT only)
 #pragma unroll
       for (int u = 0; u < kNormAhead; u++) {
         const int64_t e = (t + (int64_t)u * G) * (kBlock * 2) + threadIdx.x * 2;
         fv[u] = ld<2>(f + e);
         wv[u] = ld<2>(w1 + e);
+        if constexpr (WGT) om[u] = ld<2>(wgt + e);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -470,16 +495,18 @@ static __global__ __launch_bounds__(kBlock) __attribute__((unused)) void k_norm_
 #pragma unroll
         for (int q = 0; q < 2; q++) {
           const double d = wv[u][q] - fv[u][q];
-          acc = fma(d, d, acc);
+          acc = fma(wgt_first<WGT>(om[u], q, d), d, acc);
         }
     }
     for (; t < ntile; t += G) {
       const int64_t e = t * (kBlock * 2) + threadIdx.x * 2;
       const d2 fv = ld<2>(f + e), wv = ld<2>(w1 + e);
+      d2 om = {};
+      if constexpr (WGT) om = ld<2>(wgt + e);
 #pragma unroll
       for (int q = 0; q < 2; q++) {
         const double d = wv[q] - fv[q];
-        acc = fma(d, d, acc);
+        acc = fma(wgt_first<WGT>(om, q, d), d, acc);
       }
     }
     done = ntile * (kBlock * 2);
@@ -489,12 +516,12 @@ static __global__ __launch_bounds__(kBlock) __attribute__((unused)) void k_norm_
     if ((int)blockIdx.x == G - 1)
       for (int64_t i = done + threadIdx.x; i < vs.n; i += kBlock) {
         const double d = w1[i] - f[i];
-        acc = fma(d, d, acc);
+        acc = fma(wgt_at<WGT>(wgt, i, d), d, acc);
       }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < vs.n; i += (int64_t)G * kBlock) {
       const double d = w1[i] - f[i];
-      acc = fma(d, d, acc);
+      acc = fma(wgt_at<WGT>(wgt, i, d), d, acc);
     }
   }
   const double one[1] = {acc};
@@ -521,7 +548,7 @@ static __global__ __launch_bounds__(64) __attribute__((unused)) void k_norm_fin(
 // `base` (round 5): the first plan entry of this launch.  A list longer than kMaxPerPass is served by several launches of
 // BALANCED exact widths (33 = 17 + 16: enqueue_pa), each on its own part of the plan; only the launch with base == 0 has its
 // first two sums (d^2, <f,d>) used (k_finalize_dots).
-template <int MAXL, int W>
+template <int MAXL, int W, bool WGT = false>
 __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const double *__restrict__ f,
                                                      double *__restrict__ partials, int base, int normed) {
   constexpr int VEC = 2;
@@ -536,6 +563,7 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
   const long long *pw = ctl.plan_w() + base;
   const double *w1p = vs.w + ctl.pc[PC_FIRST_W];           // (read whether pending or not: no branch around a load)
   const double *w1 = pending ? w1p : f;
+  const double *wgt = WGT ? vs.w + ctl.pc[PC_WGT] : nullptr;      // (WGT = false: never read)
   // every plan slot is requested at once, whether the list reaches it or not (the plan array is longer than any
   // width): written as `j < nolder ? slots[j] ...` each slot became a branch around its own s_load + s_waitcnt --
   // twenty serial scalar round trips, 4.2 k cycles of prologue at m = 20 against 2 k at m = 5
@@ -555,12 +583,13 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
   //  +2...5 % of PA with NO dead slot, which is every launch of a caller that synchronises once per iteration, since PA
   //  then runs at exactly the list length; profiles/r04/ab_dead_slot.txt)
 #define DEAD_OFF(live, off) (off)
-  V fv, w1v, ring[W];
+  V fv, w1v, omv = {}, ring[W];      // (omv: WGT only)
   int64_t t = blockIdx.x;
   if (t < ntile) {
     const int64_t e = t * (kBlock * VEC) + threadIdx.x * VEC;
     fv = ld<VEC>(f + e);
     w1v = ld<VEC>(w1 + e);
+    if constexpr (WGT) omv = ld<VEC>(wgt + e);
 #pragma unroll
     for (int j = 0; j < W; j++) ring[j] = ld<VEC>(wk[j] + (DEAD_OFF(j < nolder, e)));
   }
@@ -569,17 +598,20 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
     const int64_t e = t * (kBlock * VEC) + threadIdx.x * VEC;
     const int64_t tn = (t + G < ntile) ? t + G : t;     // the last iteration prefetches its own tile again
     const int64_t en = tn * (kBlock * VEC) + threadIdx.x * VEC;
-    double dq[VEC], fq[VEC];
+    double dq[VEC], fq[VEC];      // (weighted: the first operands fl(w d), fl(w f); the second ones are not kept)
 #pragma unroll
     for (int q = 0; q < VEC; q++) {
-      fq[q] = ex(fv, q);
-      dq[q] = pa_operand(ex(w1v, q) - fq[q], normed, s_n, rs_n);      // F08:266 (and F08:283 when the norm is known)
-      acc[0] = fma(dq[q], dq[q], acc[0]);
-      acc[1] = fma(fq[q], dq[q], acc[1]);
+      const double fx = ex(fv, q);
+      const double dx = pa_operand(ex(w1v, q) - fx, normed, s_n, rs_n);      // F08:266 (and F08:283 when the norm is known)
+      dq[q] = wgt_first<WGT>(omv, q, dx);
+      fq[q] = wgt_first<WGT>(omv, q, fx);
+      acc[0] = fma(dq[q], dx, acc[0]);
+      acc[1] = fma(fq[q], dx, acc[1]);
     }
     __builtin_amdgcn_sched_barrier(0);
     fv = ld<VEC>(f + en);
     w1v = ld<VEC>(w1 + en);
+    if constexpr (WGT) omv = ld<VEC>(wgt + en);
 #pragma unroll
     for (int j = 0; j < MAXL; j++) {
       const V x = ring[j % W];
@@ -596,15 +628,16 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
   }
   if ((int)blockIdx.x == G - 1) {  // ragged tail, scalar
     for (int64_t i = ntile * (kBlock * VEC) + threadIdx.x; i < vs.n; i += kBlock) {
-      const double fq = f[i];
-      const double d = pa_operand(w1[i] - fq, normed, s_n, rs_n);
-      acc[0] = fma(d, d, acc[0]);
-      acc[1] = fma(fq, d, acc[1]);
+      const double fx = f[i];
+      const double d = pa_operand(w1[i] - fx, normed, s_n, rs_n);
+      const double dw = wgt_at<WGT>(wgt, i, d), fw = wgt_at<WGT>(wgt, i, fx);
+      acc[0] = fma(dw, d, acc[0]);
+      acc[1] = fma(fw, d, acc[1]);
 #pragma unroll
       for (int j = 0; j < MAXL; j++) {
         const double x = wk[j][i];
-        acc[2 + j] = fma(d, x, acc[2 + j]);
-        acc[2 + MAXL + j] = fma(fq, x, acc[2 + MAXL + j]);
+        acc[2 + j] = fma(dw, x, acc[2 + j]);
+        acc[2 + MAXL + j] = fma(fw, x, acc[2 + MAXL + j]);
       }
     }
   }
@@ -612,6 +645,24 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
   block_reduce_store<NACC>(acc, partials, G);
   NKA_STAMP0(ctl, 13);
 #undef DEAD_OFF
+}
+
+// Set-time check of a weight vector (nka_hip_set_dot_weights): out[0] += entries that are not finite or below zero,
+// out[1] = min over their indices (starts at ~0).  Grid-stride; runs once per set, not in an update.
+static __global__ __launch_bounds__(kBlock) __attribute__((unused)) void k_check_weights(const double *__restrict__ w, int64_t n,
+                                                                                             unsigned long long *out) {
+  unsigned long long bad = 0, first = ~0ull;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const double x = w[i];
+    if (!(x >= 0.0 && x <= __DBL_MAX__)) {      // NaN, -Inf, +Inf, negative (-0.0 is >= 0)
+      bad++;
+      if ((unsigned long long)i < first) first = (unsigned long long)i;
+    }
+  }
+  if (bad) {
+    atomicAdd(out, bad);
+    atomicMin(out + 1, first);
+  }
 }
 
 // Final sums of one PA pass scattered into red[] (layout above).  One wavefront

@@ -65,6 +65,11 @@ module nka_type
     procedure :: init
     procedure :: set_vec_tol
     procedure :: set_dot_prod
+    procedure :: set_dot_weights
+    procedure :: set_dot_weights_dev
+    procedure :: clear_dot_weights
+    procedure :: dot_weighted
+    procedure :: state_digest
     procedure :: set_allreduce
     procedure :: use_rccl
     procedure :: p2p_export
@@ -152,6 +157,43 @@ contains
     call nka_hip_check(nka_hip_set_host_dot(this%handle, c_funloc(host_dot_trampoline), c_loc(this%user_dp)), &
                        'nka%set_dot_prod')
   end subroutine
+
+  !! Diagonal dot-product weights: every inner product of an update becomes sum w_i x_i y_i, formed by the device passes
+  !! (nka_hip_set_dot_weights, include/nka_hip.h) -- what a diagonal dot_prod computes, without the host copies of
+  !! set_dot_prod.  The weights are copied (the caller's array is free again on return), must be finite and >= 0, apply
+  !! from the next update on (call a%restart() to start the subspace in the new metric) and travel with b = a.
+  !! Not with reference-order sums nor with set_dot_prod (the library refuses both combinations).
+  subroutine set_dot_weights(this, w)
+    class(nka), intent(inout) :: this
+    real(r8), intent(in), target :: w(:)
+    if (size(w, kind=c_int64_t) /= nka_hip_vec_len(this%handle)) error stop 'nka%set_dot_weights: size(w) /= vec_len()'
+    call nka_hip_check(nka_hip_set_dot_weights_host(this%handle, w), 'nka%set_dot_weights')
+  end subroutine
+  !! ... from device memory (vec_len() doubles on the accelerator's device)
+  subroutine set_dot_weights_dev(this, w_dev)
+    class(nka), intent(inout) :: this
+    type(c_ptr), intent(in) :: w_dev
+    if (.not. c_associated(w_dev)) error stop 'nka%set_dot_weights_dev: null pointer (clear_dot_weights restores plain sums)'
+    call nka_hip_check(nka_hip_set_dot_weights(this%handle, w_dev), 'nka%set_dot_weights_dev')
+  end subroutine
+  !! plain sums again
+  subroutine clear_dot_weights(this)
+    class(nka), intent(inout) :: this
+    call nka_hip_check(nka_hip_set_dot_weights(this%handle, c_null_ptr), 'nka%clear_dot_weights')
+  end subroutine
+  logical function dot_weighted(this)
+    class(nka), intent(in) :: this
+    integer(c_int) :: r
+    r = nka_hip_dot_weighted(this%handle)
+    if (r < 0) call nka_hip_check(r, 'nka%dot_weighted')
+    dot_weighted = r == 1
+  end function
+  !! 64-bit digest of the device-resident scalar state (nka_hip_state_digest): flags, lists, h, c, the last sums
+  function state_digest(this) result(d)
+    class(nka), intent(in) :: this
+    integer(c_int64_t) :: d
+    call nka_hip_check(nka_hip_state_digest(this%handle, d), 'nka%state_digest')
+  end function
 
   !! nka_hip_host_dot_fn: C calls this with host copies of the operands.
   function host_dot_trampoline(ctx, n, x, y) bind(C) result(d)

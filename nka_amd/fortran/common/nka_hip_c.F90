@@ -117,6 +117,20 @@ module nka_hip_c
       type(c_ptr), value :: handle, ctx
       type(c_funptr), value :: fn
     end function
+    !! diagonal dot-product weights (include/nka_hip.h): w_dev / w_host = vlen_local doubles, copied; NULL = plain sums again
+    integer(c_int) function nka_hip_set_dot_weights(handle, w_dev) bind(C)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, w_dev
+    end function
+    integer(c_int) function nka_hip_set_dot_weights_host(handle, w_host) bind(C)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle
+      real(c_double), intent(in) :: w_host(*)
+    end function
+    integer(c_int) function nka_hip_dot_weighted(handle) bind(C)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+    end function
     integer(c_int) function nka_hip_state_digest(handle, digest) bind(C)
       import :: c_int, c_ptr, c_int64_t
       type(c_ptr), value :: handle

@@ -182,6 +182,39 @@ class nka:  # noqa: N801  (the reference's type name)
         self._hd = _lib.HOST_DOT_FN(tramp)
         _check(self._L.nka_hip_set_host_dot(self._handle(), self._hd, None), "set_host_dot", self._L)
 
+    def set_dot_weights(self, w):
+        """Diagonal dot-product weights on the device (nka_hip_set_dot_weights): every inner product of an update becomes
+        sum_i w_i x_i y_i, in the fast passes.  `w`: a contiguous float64 CUDA tensor of vec_len() elements on this object's
+        device, or a float64 numpy array (host entry); both are copied, so the caller's buffer is free again on return.  None
+        restores the plain sums.  Weights must be finite and >= 0.  A change applies from the next update; restart() starts
+        the subspace in the new metric.  Returns self."""
+        h = self._handle()
+        if w is None:
+            _check(self._L.nka_hip_set_dot_weights(h, None), "set_dot_weights", self._L)
+            return self
+        if isinstance(w, np.ndarray):
+            if w.dtype != np.float64 or w.ndim != 1 or not w.flags["C_CONTIGUOUS"] or w.size != self._vlen:
+                raise NKAError("set_dot_weights: need a contiguous 1-d float64 array of vec_len() elements")
+            _check(self._L.nka_hip_set_dot_weights_host(h, C.c_void_p(w.ctypes.data)), "set_dot_weights_host", self._L)
+            return self
+        import torch
+        if not (isinstance(w, torch.Tensor) and w.is_cuda and w.dtype == torch.float64 and w.is_contiguous()
+                and w.numel() == self._vlen and w.device.index == self._device):
+            raise NKAError("set_dot_weights: need a contiguous float64 CUDA tensor of vec_len() elements on the accelerator's "
+                           "device, a float64 numpy array, or None")
+        if self._follow_torch_stream:      # the copy is ordered after the work that produced w on torch's current stream
+            cur = int(torch.cuda.current_stream(self._device).cuda_stream)
+            if cur != self._stream:
+                self.set_stream(cur)
+        _check(self._L.nka_hip_set_dot_weights(h, C.c_void_p(w.data_ptr())), "set_dot_weights", self._L)
+        return self
+
+    def dot_weighted(self) -> bool:
+        """True while diagonal dot-product weights are set (nka_hip_dot_weighted)."""
+        r = self._L.nka_hip_dot_weighted(self._handle())
+        _check(min(r, 0), "dot_weighted", self._L)
+        return r == 1
+
     def use_rccl(self, unique_id: bytes, nranks: int, rank: int):
         """Built-in hook: the RCCL all-reduces of an update on the object's stream (two small ones with the default sums -- the norm,
         then the rows --, one in the fast mode SUMS_BLOCKED)."""
