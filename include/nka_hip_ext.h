@@ -17,8 +17,10 @@
  *   REFERENCE_ORDER               yes    validation only: 2N exchanges per update through any hook that sums; mvec <= 250
  *   user dot product (core)       yes    the user's dp IS the global reduction: hooks are not applied on top
  *   diagonal weights (core)       yes    with AUTO / BLOCKED_ROUNDED / BLOCKED: the partial sums keep their layout, so every
- *                                        transport of that row applies (not yet held by a test beyond "none"); refused with
- *                                        REFERENCE_ORDER and with the user dot product
+ *                                        transport of that row applies (held by tests/test_dot_weights_sharded_gpu.py on slices
+ *                                        with ghost entries: the hook and the mailboxes with 2 ... 9 ranks, RCCL with one rank,
+ *                                        N ranks gated on a multi-GPU box); refused with REFERENCE_ORDER and with the user dot
+ *                                        product
  *   out-of-place entry            every row above except the user dot product; not capturable into a graph
  * F08 = /root/reference/src-F08/nka_type.F90, C = /root/reference/src-C/nonlinear_krylov_accelerator.{h,c}.
  */

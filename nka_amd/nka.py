@@ -192,10 +192,14 @@ class nka:  # noqa: N801  (the reference's type name)
         if w is None:
             _check(self._L.nka_hip_set_dot_weights(h, None), "set_dot_weights", self._L)
             return self
+        # an empty slice (vec_len() == 0: a rank of a sharded run that holds nothing): an empty tensor's address is 0, which
+        # the library reads as "plain sums again" -- hand it a non-NULL address instead (never read: include/nka_hip.h)
+        nothing = C.c_double()
         if isinstance(w, np.ndarray):
             if w.dtype != np.float64 or w.ndim != 1 or not w.flags["C_CONTIGUOUS"] or w.size != self._vlen:
                 raise NKAError("set_dot_weights: need a contiguous 1-d float64 array of vec_len() elements")
-            _check(self._L.nka_hip_set_dot_weights_host(h, C.c_void_p(w.ctypes.data)), "set_dot_weights_host", self._L)
+            _check(self._L.nka_hip_set_dot_weights_host(h, C.c_void_p(w.ctypes.data or C.addressof(nothing))),
+                   "set_dot_weights_host", self._L)
             return self
         import torch
         if not (isinstance(w, torch.Tensor) and w.is_cuda and w.dtype == torch.float64 and w.is_contiguous()
@@ -206,7 +210,7 @@ class nka:  # noqa: N801  (the reference's type name)
             cur = int(torch.cuda.current_stream(self._device).cuda_stream)
             if cur != self._stream:
                 self.set_stream(cur)
-        _check(self._L.nka_hip_set_dot_weights(h, C.c_void_p(w.data_ptr())), "set_dot_weights", self._L)
+        _check(self._L.nka_hip_set_dot_weights(h, C.c_void_p(w.data_ptr() or C.addressof(nothing))), "set_dot_weights", self._L)
         return self
 
     def dot_weighted(self) -> bool:
