@@ -1,0 +1,99 @@
+/*
+ * nka_hip_batch.h -- OPTIONAL: a BATCHED accelerator, many small independent systems advanced by one kernel launch
+ * (libnka_hip.so; the core of include/nka_hip.h and its entries do not change, and nothing here changes what they return).
+ *
+ * A lone handle (nka_hip_create) spends a small update on kernel boundaries and on a scalar step that runs on one wavefront
+ * while the rest of the device idles.  A caller with MANY independent small systems of equal shape -- an ensemble or
+ * parameter sweep, one nonlinear solve per mesh column or subdomain, the stages of an implicit integrator per cell -- creates
+ * one batch instead: `nsys` independent NKA states (own subspace, own drop decisions, own history), and
+ * nka_hip_batch_accel_update advances all of them in ONE launch with ONE workgroup per system (nka_amd/csrc/nka_batch.hip:
+ * skip / norm / other sums / scalar step / combine, separated by workgroup barriers instead of kernel boundaries).  A lone
+ * system is what lone handles are for: a batch of one is supported and correct, but it runs on one compute unit.
+ *
+ *   LAYOUT   f_dev is nsys rows of ld doubles (ld >= vlen), row `sys` holds system `sys`.  Its span -- (nsys-1)*ld + vlen
+ *            doubles -- and the mask's are checked against their allocations before any launch, like every pointer that
+ *            crosses this ABI.  Rows that are 16-byte aligned are read with 16-byte loads, others element by element: the
+ *            same bits.
+ *   MASKS    active_dev: nsys int32 in DEVICE memory (0 = the system sits this call out), or NULL for all systems.  The mask
+ *            stays on the device, so a caller's per-system convergence test never reaches the host.  For a system that sits
+ *            out, its row of f and every byte of its state are left exactly as they were.
+ *   ASYNC    accel_update, restart, relax and set_vec_tol only enqueue on the batch's stream: no allocation, no
+ *            synchronisation.  The queries synchronise it.  Not thread-safe per batch; distinct batches are independent.
+ *   GRAPHS   The list length is read on the device, per system: no kernel width depends on what the host knows.  An update
+ *            can therefore be captured into a hipGraph FROM THE FIRST UPDATE ON and replayed through drops, relax and
+ *            restart (a lone handle: only once its list is full, nka_hip_capture_safe).
+ *   BITS     Results are bitwise reproducible and do not depend on nsys, on a system's position in the batch, on ld or the
+ *            alignment of its row, or on which other systems are active: no workgroup reads what another writes, there are
+ *            no atomics, flags or cooperative launches.
+ *   ERRORS   Status codes, nka_hip_last_error() and the resolution of NKA_HIP_FLAVOR_DEFAULT / NKA_HIP_FLAVOR are the core's.
+ *            Storage is the lone handle's for the flavour: nka_hip_batch_get_w / _get_v return what nka_hip_get_w / _get_v
+ *            return (compact storage in the C flavour: v holds fl(v' - w') of a normalised pair).
+ *   SUMS     NKA_HIP_SUMS_AUTO = reference order for vlen <= 64, else _BLOCKED_ROUNDED; NKA_HIP_SUMS_REFERENCE_ORDER (every
+ *            sum element after element, one rounding per product and per addition, the norm first, then the rows on the
+ *            rounded w1': a system then carries the BITS of the reference flavour it runs; validation speed, at every vlen)
+ *            and NKA_HIP_SUMS_BLOCKED_ROUNDED (products by fma, per-thread strided accumulation, fixed-order reduction over
+ *            the workgroup; held to the numerical contract of nka_hip.h, items 1 and 3) are accepted.  NKA_HIP_SUMS_BLOCKED is
+ *            refused with NKA_HIP_EINVAL: a batch has no exchange to save.
+ *   LIMITS   1 <= vlen <= NKA_HIP_BATCH_MAX_VLEN, 1 <= mvec <= NKA_HIP_BATCH_MAX_MVEC, nsys >= 1, vtol > 0: NKA_HIP_EINVAL
+ *            outside; device memory that does not suffice: NKA_HIP_ENOMEM.  NKA_HIP_BATCH_MAX_VLEN = 16 384 is MEASURED
+ *            (profiles/r08/batch_throughput.txt, 1 x MI355X): the largest power of two at which the batch beats a loop over
+ *            lone handles at every grid point from 16 systems on.  At the cap, mvec = 20: 1.52 x with 16 systems, 17 x with
+ *            256, 23 x with 4096 (0.55 of 8 TB/s); at vlen = 1024, mvec = 10: 9.2 x / 151 x / 444 x.  Beyond it a 16-system
+ *            batch -- 16 of 256 compute units -- loses (0.99 x at 32 768, mvec = 20): longer systems are for lone handles.  A
+ *            batch of ONE is slower than a lone handle at most shapes (0.10 ... 1.76 x, recorded without a bar).
+ *   OUT OF SCOPE  sharding and all-reduce hooks, the user dot product, diagonal weights, the out-of-place entry, the
+ *            abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs any
+ *            of these uses lone handles.
+ */
+#ifndef NKA_HIP_BATCH_H
+#define NKA_HIP_BATCH_H
+
+#include <stdint.h>
+
+#include "nka_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct nka_hip_batch_state *nka_hip_batch_t;
+
+enum { NKA_HIP_BATCH_MAX_VLEN = 16384, NKA_HIP_BATCH_MAX_MVEC = 32 };
+
+/* nsys accelerators of vlen elements and at most mvec vectors each, all restarted (F08:185-200 per system); `device` and
+ * `stream` as in nka_hip_create.  Allocates 2*nsys*(mvec+1) slot vectors (slot stride: vlen rounded up to 32 doubles). */
+int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                         int32_t flavor, int32_t device, void *stream);
+int nka_hip_batch_destroy(nka_hip_batch_t b);
+
+/* call a%accel_update(f) for every active system, one launch.  Rows of inactive systems are not touched. */
+int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, const int32_t *active_dev);
+/* call a%restart() / a%relax() for every active system (F08:422-457). */
+int nka_hip_batch_restart(nka_hip_batch_t b, const int32_t *active_dev);
+int nka_hip_batch_relax(nka_hip_batch_t b, const int32_t *active_dev);
+/* call a%set_vec_tol(vtol) for ALL systems (F08:202-207); stream-ordered like the updates around it. */
+int nka_hip_batch_set_vec_tol(nka_hip_batch_t b, double vtol);
+int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order);
+/* Rebind to another hipStream_t; work already enqueued stays ordered before. */
+int nka_hip_batch_set_stream(nka_hip_batch_t b, void *stream);
+
+/* ---- queries (synchronise the stream) ---- */
+int nka_hip_batch_num_vec(nka_hip_batch_t b, int32_t *num_vec_host /* nsys */);
+int nka_hip_batch_flavor(nka_hip_batch_t b);   /* NKA_HIP_FLAVOR_* the batch runs (DEFAULT resolved); < 0 on error */
+/* System `sys` (0-based) as nka_hip_get_state / _get_reductions / _get_w / _get_v / nka_hip_state_digest report a lone
+ * handle (nka_hip_ext.h), with ONE DIFFERENCE in the reductions: a batched update REWRITES ALL 2 + 2*mvec entries of red[],
+ * with zero wherever it formed no sum (no pending pair: red[0]; s == 0 or no pending pair: red[1], red[2+p]; beyond the
+ * list: red[2+p], red[2+mvec+p]), whereas a lone handle leaves such entries as an earlier update wrote them.  The entries an
+ * update does form carry the lone handle's bits with reference-order sums.  red[1] and red[2+p] are the sums on the
+ * NORMALISED difference, <f,w1'> and <w1',w_p>, in both sum orders. */
+int nka_hip_batch_get_state(nka_hip_batch_t b, int32_t sys, int32_t *subspace, int32_t *pending, int32_t *first,
+                            int32_t *last, int32_t *free_, int32_t *next, int32_t *prev, double *h, double *c);
+int nka_hip_batch_get_reductions(nka_hip_batch_t b, int32_t sys, double *red_out);
+int nka_hip_batch_get_w(nka_hip_batch_t b, int32_t sys, int32_t slot, double *host_out);
+int nka_hip_batch_get_v(nka_hip_batch_t b, int32_t sys, int32_t slot, double *host_out);
+int nka_hip_batch_state_digest(nka_hip_batch_t b, int32_t sys, uint64_t *digest);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* NKA_HIP_BATCH_H */

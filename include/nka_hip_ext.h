@@ -22,6 +22,10 @@
  *                                        N ranks gated on a multi-GPU box); refused with REFERENCE_ORDER and with the user dot
  *                                        product
  *   out-of-place entry            every row above except the user dot product; not capturable into a graph
+ *   batched (nka_hip_batch.h)     none of the transports: single device, no hooks.  AUTO (reference order up to 64 elements, else
+ *                                 BLOCKED_ROUNDED), BLOCKED_ROUNDED and REFERENCE_ORDER (any vlen up to the cap, mvec <= 32); BLOCKED, the
+ *                                 user dot product, diagonal weights and the out-of-place entry are refused or absent; capturable
+ *                                 into a graph from the first update on (tests/test_batch_gpu.py)
  * F08 = /root/reference/src-F08/nka_type.F90, C = /root/reference/src-C/nonlinear_krylov_accelerator.{h,c}.
  */
 #ifndef NKA_HIP_EXT_H

@@ -123,6 +123,28 @@ SIGNATURES.update({
 })
 
 
+# include/nka_hip_batch.h (the batched accelerator: many small systems in one launch, nka_amd/batch.py): an optional header
+# of its own, so a table of its own -- every library that holds the product's objects exports these too
+BATCH_SIGNATURES = {
+    "nka_hip_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                       C.c_void_p]),
+    "nka_hip_batch_destroy": (C.c_int, [C.c_void_p]),
+    "nka_hip_batch_accel_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "nka_hip_batch_restart": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nka_hip_batch_relax": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nka_hip_batch_set_vec_tol": (C.c_int, [C.c_void_p, C.c_double]),
+    "nka_hip_batch_set_sum_order": (C.c_int, [C.c_void_p, C.c_int32]),
+    "nka_hip_batch_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nka_hip_batch_num_vec": (C.c_int, [C.c_void_p, _i32p]),
+    "nka_hip_batch_flavor": (C.c_int, [C.c_void_p]),
+    "nka_hip_batch_get_state": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _dp, _dp]),
+    "nka_hip_batch_get_reductions": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "nka_hip_batch_get_w": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp]),
+    "nka_hip_batch_get_v": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp]),
+    "nka_hip_batch_state_digest": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]),
+}
+
+
 # include/nka_hip_diag.h: only in the diagnostic build libnka_hip_diag.so (the product's objects + nka_amd/csrc/lab.hip)
 DIAG_SIGNATURES = {
     "nka_hip_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
@@ -150,7 +172,7 @@ def load_diag() -> C.CDLL:
         if not os.path.exists(path):
             raise RuntimeError(f"{path} not found: `make -C nka_amd/csrc diag` (or __graft_entry__.build())")
         L = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(DIAG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(DIAG_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -169,7 +191,7 @@ def load_diag_at(path: str) -> C.CDLL:
         if not os.path.exists(path):
             raise RuntimeError(f"{path} not found")
         L = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(DIAG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()) + list(DIAG_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -201,7 +223,7 @@ def load() -> C.CDLL:
                 f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(nka_amd has no CPU fallback)")
         L = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(BATCH_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the ABI lost a symbol
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,175 @@
+"""Python mirror of the batched accelerator (include/nka_hip_batch.h): `nsys` independent NKA states of equal shape,
+advanced by ONE kernel launch per call, one workgroup per system.  Method names are those of `nka_amd.nka`; the
+per-system queries take the system's index first.  All arithmetic happens in libnka_hip.so on the GPU; this file is
+plumbing (ctypes + torch for device memory and streams)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .nka import FLAVOR_DEFAULT, NKAError, State, _check
+
+BATCH_MAX_VLEN, BATCH_MAX_MVEC = 16384, 32      # NKA_HIP_BATCH_MAX_VLEN / _MVEC (include/nka_hip_batch.h)
+
+
+class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
+    """A batch of MI355X accelerator objects; see the module docstring."""
+
+    def __init__(self):
+        self._h = None
+        self._L = _lib.load()          # raises if the HIP library is missing: no CPU path
+
+    def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
+             stream: int | None = None):
+        """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
+        hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`)."""
+        import torch
+
+        self.delete()
+        if not torch.cuda.is_available():
+            raise NKAError("no HIP device visible: nka_amd has no CPU path")
+        if device is None:
+            device = torch.cuda.current_device()
+        explicit_stream = stream
+        if stream is None:
+            stream = torch.cuda.current_stream(device).cuda_stream
+        h = C.c_void_p()
+        _check(self._L.nka_hip_batch_create(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                            C.c_void_p(stream)), "nka_hip_batch_create", self._L)
+        self._h, self._device, self._nsys, self._vlen, self._mvec = h, device, int(nsys), int(vlen), int(mvec)
+        self._stream, self._follow_torch_stream = int(stream), explicit_stream is None
+        return self
+
+    def delete(self):
+        if self._h is not None:
+            self._L.nka_hip_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.delete()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if self._h is None:
+            raise NKAError("nka_batch object used before init")
+        return self._h
+
+    def _follow(self):
+        if self._follow_torch_stream:      # stay on torch's CURRENT stream (e.g. inside `with torch.cuda.stream(s)`)
+            import torch
+            cur = int(torch.cuda.current_stream(self._device).cuda_stream)
+            if cur != self._stream:
+                self.set_stream(cur)
+
+    def _mask(self, active, what):
+        """-> device address of the int32 mask, or None for all systems."""
+        if active is None:
+            return None
+        import torch
+        if not (isinstance(active, torch.Tensor) and active.is_cuda and active.dtype == torch.int32 and active.is_contiguous()
+                and active.dim() == 1 and active.device.index == self._device):
+            raise NKAError(f"{what}: the mask must be a contiguous 1-d int32 CUDA tensor on the batch's device, or None")
+        if active.numel() != self._nsys:
+            raise NKAError(f"{what}: the mask must have one entry per system ({self._nsys}), got {active.numel()}")
+        return C.c_void_p(active.data_ptr())
+
+    def set_stream(self, stream: int):
+        _check(self._L.nka_hip_batch_set_stream(self._handle(), C.c_void_p(int(stream))), "batch_set_stream", self._L)
+        self._stream = int(stream)
+
+    def accel_update(self, F, active=None):
+        """F: 2-d float64 CUDA tensor, one row per system (nsys x vlen; rows contiguous, the row stride is `ld`), updated in
+        place, asynchronously on the batch's stream.  active: optional int32 CUDA tensor of nsys entries, 0 = the system sits
+        this call out (its row and its state are not touched)."""
+        import torch
+        h = self._handle()
+        if not (isinstance(F, torch.Tensor) and F.is_cuda and F.dtype == torch.float64 and F.dim() == 2):
+            raise NKAError("batch accel_update: need a 2-d float64 CUDA tensor, one row per system")
+        if F.shape[0] != self._nsys or F.shape[1] != self._vlen:
+            raise NKAError(f"batch accel_update: need {self._nsys} rows of {self._vlen} elements, got {tuple(F.shape)}")
+        if (self._vlen > 1 and F.stride(1) != 1) or (self._nsys > 1 and F.stride(0) < self._vlen):
+            raise NKAError("batch accel_update: the rows must be contiguous (element stride 1) and must not overlap")
+        if F.device.index != self._device:
+            raise NKAError("batch accel_update: tensor lives on another device than the batch")
+        ld = int(F.stride(0)) if self._nsys > 1 else max(int(F.stride(0)), self._vlen)
+        mask = self._mask(active, "batch accel_update")
+        self._follow()
+        _check(self._L.nka_hip_batch_accel_update(h, C.c_void_p(F.data_ptr()), ld, mask), "batch_accel_update", self._L)
+        return F
+
+    def restart(self, active=None):
+        mask = self._mask(active, "batch restart")
+        self._follow()
+        _check(self._L.nka_hip_batch_restart(self._handle(), mask), "batch_restart", self._L)
+
+    def relax(self, active=None):
+        mask = self._mask(active, "batch relax")
+        self._follow()
+        _check(self._L.nka_hip_batch_relax(self._handle(), mask), "batch_relax", self._L)
+
+    def set_vec_tol(self, vtol: float):
+        """For ALL systems; ordered on the stream like the updates around it."""
+        self._follow()
+        _check(self._L.nka_hip_batch_set_vec_tol(self._handle(), float(vtol)), "batch_set_vec_tol", self._L)
+
+    def set_sum_order(self, order: int):
+        """SUMS_AUTO (reference order up to 64 elements, else SUMS_BLOCKED_ROUNDED), SUMS_REFERENCE_ORDER or
+        SUMS_BLOCKED_ROUNDED; SUMS_BLOCKED is refused.  Returns self."""
+        _check(self._L.nka_hip_batch_set_sum_order(self._handle(), int(order)), "batch_set_sum_order", self._L)
+        return self
+
+    # -- queries (synchronise) ---------------------------------------------
+    def num_sys(self) -> int:
+        return self._nsys
+
+    def vec_len(self) -> int:
+        return self._vlen
+
+    def max_vec(self) -> int:
+        return self._mvec
+
+    def flavor(self) -> int:
+        return self._L.nka_hip_batch_flavor(self._handle())
+
+    def num_vec(self) -> np.ndarray:
+        out = np.zeros(self._nsys, np.int32)
+        _check(self._L.nka_hip_batch_num_vec(self._handle(), out.ctypes.data_as(_lib._i32p)), "batch_num_vec", self._L)
+        return out
+
+    def state(self, sys: int) -> State:
+        n = self._mvec + 1
+        ints = [C.c_int32() for _ in range(5)]
+        nxt = np.zeros(n, np.int32)
+        prv = np.zeros(n, np.int32)
+        h = np.zeros((n, n), np.float64)
+        c = np.zeros(n, np.float64)
+        _check(self._L.nka_hip_batch_get_state(self._handle(), int(sys), *[C.byref(i) for i in ints],
+                                               nxt.ctypes.data_as(_lib._i32p), prv.ctypes.data_as(_lib._i32p),
+                                               h.ctypes.data_as(_lib._dp), c.ctypes.data_as(_lib._dp)), "batch_get_state", self._L)
+        return State(ints[0].value, ints[1].value, ints[2].value, ints[3].value, ints[4].value, nxt, prv, h.T.copy(), c)
+
+    def reductions(self, sys: int) -> np.ndarray:
+        """[<d,d>, <f,w1'>, <w1',w_p>..., <f,w_p>...] of the system's most recent update (zeros where it formed no sum)."""
+        out = np.zeros(2 + 2 * self._mvec)
+        _check(self._L.nka_hip_batch_get_reductions(self._handle(), int(sys), out.ctypes.data_as(_lib._dp)),
+               "batch_get_reductions", self._L)
+        return out
+
+    def w(self, sys: int, slot: int) -> np.ndarray:
+        out = np.zeros(self._vlen)
+        _check(self._L.nka_hip_batch_get_w(self._handle(), int(sys), int(slot), out.ctypes.data_as(_lib._dp)), "batch_get_w", self._L)
+        return out
+
+    def v(self, sys: int, slot: int) -> np.ndarray:
+        out = np.zeros(self._vlen)
+        _check(self._L.nka_hip_batch_get_v(self._handle(), int(sys), int(slot), out.ctypes.data_as(_lib._dp)), "batch_get_v", self._L)
+        return out
+
+    def state_digest(self, sys: int) -> int:
+        d = C.c_uint64()
+        _check(self._L.nka_hip_batch_state_digest(self._handle(), int(sys), C.byref(d)), "batch_state_digest", self._L)
+        return int(d.value)

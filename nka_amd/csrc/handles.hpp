@@ -23,10 +23,12 @@ int set_error(int code, const std::string &msg);
 std::string last_error();
 bool &span_check_failed();   // (thread-local) set by a failing check_device_span
 int check_device_span(const void *p, int64_t n, const char *what);
+int check_device_span_i32(const void *p, int64_t n, const char *what);
 void invalidate_span_cache();
 void register_allocation(const void *p, size_t bytes, const void *owner);
 void unregister_owner(const void *owner);
 void unregister_allocation(const void *p);
+int resolve_flavor(int32_t *flavor_io, const char *who);   // NKA_HIP_FLAVOR_DEFAULT / NKA_HIP_FLAVOR (include/nka_hip.h)
 
 // pieces of an update, for the lab (lab.hip)
 void enqueue_pa(nka_hip_t a, const double *f, int vec, int older_ub);

@@ -89,4 +89,56 @@ struct BufferBook {
   }
 };
 
+// THE BATCHED ACCELERATOR (include/nka_hip_batch.h, nka_batch.hip): where the pieces of system `sys` lie.  Host and kernel
+// compile this text; tests/c/batch_layout_check.cpp holds it against a brute-force model (no two pieces overlap, every
+// stride a multiple of 32 doubles, the LDS budget).
+#if defined(__HIPCC__)
+#define NKA_HOST_DEVICE __host__ __device__
+#else
+#define NKA_HOST_DEVICE
+#endif
+constexpr int kBatchWaves = 4;                   // wavefronts of a workgroup (256 threads)
+constexpr int kBatchGroup = 4;                   // older vectors per sweep of the sums
+constexpr int kBatchAcc = 2 * kBatchGroup + 1;   // their two sums each, and <f,w1'>
+// control block of one system in the layout of Ctl (nka_kernels.hpp): int32 header (16), next, prev [m1+1], plan_slots,
+// comb_slots [m1+32]; double header (2), h [(m1+1)^2], c [m1+1], comb_c [m1+32], red [2+2 mvec], stamps [16]
+NKA_HOST_DEVICE constexpr int batch_ic_count(int mvec) { return 16 + 2 * (mvec + 2) + 2 * (mvec + 1 + kMaxPerPass); }
+NKA_HOST_DEVICE constexpr int batch_dc_count(int mvec) {
+  return 2 + (mvec + 2) * (mvec + 2) + (mvec + 2) + (mvec + 1 + kMaxPerPass) + (2 + 2 * mvec) + 16;
+}
+struct BatchLayout {
+  int64_t stride;        // doubles between the slots of a system: vlen rounded up to 32 (256 bytes)
+  int64_t sys_stride;    // doubles between systems in the w and the v allocation: (mvec + 1) slots
+  int32_t ic_stride;     // int32 between the control blocks (a multiple of 32: 128 bytes)
+  int32_t dc_stride;     // doubles between them (a multiple of 32: 256 bytes)
+};
+NKA_HOST_DEVICE constexpr BatchLayout batch_layout(int64_t vlen, int mvec) {
+  const int64_t stride = ((vlen < 1 ? 1 : vlen) + 31) / 32 * 32;
+  return BatchLayout{stride, stride * (mvec + 1), (batch_ic_count(mvec) + 31) / 32 * 32, (batch_dc_count(mvec) + 31) / 32 * 32};
+}
+// LDS of one workgroup: doubles first (offsets in doubles), then int32 (offsets in int32 from the end of the doubles)
+struct BatchLds {
+  int h, c, red, cc, sm, res, ndouble;      // h [(m1+1)^2], c [m1+1], red [2+2 mvec], cc [m1], sm [waves][kBatchAcc], res [kBatchAcc+1]
+  int next, prev, ps, cs, hdr, nint;        // next, prev [m1+1], ps, cs [m1], hdr [8]
+  NKA_HOST_DEVICE constexpr size_t bytes() const { return sizeof(double) * (size_t)ndouble + sizeof(int32_t) * (size_t)nint; }
+};
+NKA_HOST_DEVICE constexpr BatchLds batch_lds(int mvec) {
+  const int m1 = mvec + 1;
+  BatchLds l{};
+  l.h = 0;
+  l.c = l.h + (m1 + 1) * (m1 + 1);
+  l.red = l.c + (m1 + 1);
+  l.cc = l.red + (2 + 2 * mvec);
+  l.sm = l.cc + m1;
+  l.res = l.sm + kBatchWaves * kBatchAcc;
+  l.ndouble = l.res + kBatchAcc + 1;
+  l.next = 0;
+  l.prev = l.next + (m1 + 1);
+  l.ps = l.prev + (m1 + 1);
+  l.cs = l.ps + m1;
+  l.hdr = l.cs + m1;
+  l.nint = l.hdr + 8;
+  return l;
+}
+
 }  // namespace nka_host

@@ -1,0 +1,733 @@
+// nka_batch.hip -- the batched accelerator of include/nka_hip_batch.h: nsys independent NKA states of equal shape, one
+// kernel launch per update of the whole batch, ONE WORKGROUP PER SYSTEM (blockIdx.x = system).
+//
+// Inside a workgroup the phases of an update (nka_kernels.hpp: PA / scalar step / PB of a lone handle, three to six
+// kernels) are separated by __syncthreads():
+//   0 skip      active[sys] == 0: return before any memory of the system is touched
+//   1 load      h, c and the links into LDS; thread 0 lists the older entries (the list length is read HERE, on the device)
+//   2 norm      sum d^2, d = fl(w1 - f), per-thread strided fma, fixed-order reduction; s = sqrt
+//   3 sums      on the ROUNDED w1' = fl(d/s) (fl(fl(1/s)*d) in the F08-vector flavour): <f,w1'>, <w1',w_p>, <f,w_p> while the
+//               older w stream past once, kBatchGroup of them per sweep (f and w1 are re-read from cache per sweep)
+//   4 scalar    thread 0, on the working copy in LDS: the lst_* functions of nka_kernels.hpp, i.e. the statements of k_solve:
+//               decisions given the sums are the reference's by construction
+//   5 store     the working copy back to the system's control block
+//   6 combine   normalise the pending pair, combine in list order with the flavour's association, w_new = f_in,
+//               v_new = f_out, f
+// No workgroup waits for another one: no flags, no spinning, no cooperative launch, no atomics.  The element -> thread
+// mapping (pairs 2t, 2t+1 of every 512) and every accumulation order are the same whether a row of f is 16-byte aligned
+// (16-byte loads) or not (two 8-byte loads), so results do not depend on ld, on nsys, or on a system's position.
+// ORDERED = true is the reference-order sibling: every sum element after element, unfused, one thread per sum.
+// (handles.hpp brings in all of nka_kernels.hpp -- Ctl, Lst and the lst_* functions, comb1, wave_sum are needed -- and with it
+//  this object file carries unused copies of the core's non-template kernels, as vec_ops.o does: about 10 s of build time and
+//  dead code objects in the library, accepted rather than splitting the header the core's kernels are frozen in.)
+#include "handles.hpp"
+#include "../../include/nka_hip_batch.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+using namespace nka;
+
+namespace {
+
+using nka_host::kBatchAcc;
+using nka_host::kBatchGroup;
+using nka_host::kBatchWaves;
+constexpr int kBatchThreads = 64 * kBatchWaves;
+constexpr int kBatchTile = 2 * kBatchThreads;   // elements per sweep step: thread t owns 2t, 2t+1
+
+struct BatchArgs {
+  double *w, *v;        // system sys, slot k (1-based) at base + sys*sys_stride + (k-1)*stride
+  int32_t *ic;          // control blocks in the layout of Ctl (nka_kernels.hpp), ic_stride / dc_stride apart
+  double *dc;
+  int64_t stride, sys_stride, n;
+  int32_t ic_stride, dc_stride, mvec, nsys;
+};
+
+__host__ __device__ inline Ctl batch_ctl(const BatchArgs &a, int sys) {
+  Ctl c{};
+  c.ic = a.ic + (size_t)sys * a.ic_stride;
+  c.dc = a.dc + (size_t)sys * a.dc_stride;
+  c.mvec = a.mvec;
+  return c;
+}
+
+// (where the pieces of a system lie, and the LDS of a workgroup -- 5.3 KB at mvec = 20, 11.2 KB at 32: host_logic.hpp)
+static_assert(nka_host::batch_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 40 * 1024, "four workgroups of a batch must fit the LDS of a CU");
+
+// pair (i, i+1) of a vector of n elements, i even; beyond n: zeros (never accumulated, never stored)
+__device__ __forceinline__ d2 ld_pair(const double *__restrict__ p, int64_t i, int64_t n, bool vec) {
+  if (vec && i + 1 < n) return *reinterpret_cast<const d2 *>(p + i);
+  d2 r;
+  r[0] = i < n ? p[i] : 0.0;
+  r[1] = i + 1 < n ? p[i + 1] : 0.0;
+  return r;
+}
+__device__ __forceinline__ void st_pair(double *__restrict__ p, int64_t i, int64_t n, bool vec, d2 x) {
+  if (vec && i + 1 < n) {
+    *reinterpret_cast<d2 *>(p + i) = x;
+    return;
+  }
+  if (i < n) p[i] = x[0];
+  if (i + 1 < n) p[i + 1] = x[1];
+}
+
+// The same inside a FULL tile (no element beyond n): straight-line code, so that every load of a tile is in flight before
+// the first is waited for; VEC = false (a row of f that is not 16-byte aligned): two 8-byte loads, the same values.
+template <bool FULL, bool VEC>
+__device__ __forceinline__ d2 ld_tile(const double *__restrict__ p, int64_t i, int64_t n) {
+  if (!FULL) return ld_pair(p, i, n, VEC);
+  if (VEC) return *reinterpret_cast<const d2 *>(p + i);
+  d2 r;
+  r[0] = p[i];
+  r[1] = p[i + 1];
+  return r;
+}
+template <bool FULL, bool VEC>
+__device__ __forceinline__ void st_tile(double *__restrict__ p, int64_t i, int64_t n, d2 x) {
+  if (!FULL) { st_pair(p, i, n, VEC, x); return; }
+  if (VEC) { *reinterpret_cast<d2 *>(p + i) = x; return; }
+  p[i] = x[0];
+  p[i + 1] = x[1];
+}
+// One sweep over a system's elements: body(FULL, FVEC, i) for this thread's pair i = 2t, 2t + 512, ... -- the full tiles
+// first, then the ragged one with guards.  The order in which a thread meets its elements is the same on every path.
+template <class Body>
+__device__ __forceinline__ void batch_sweep(int64_t n, bool fvec, Body body) {
+  using T = std::true_type;
+  using F = std::false_type;
+  int64_t base = 0;
+  if (fvec) for (; base + kBatchTile <= n; base += kBatchTile) body(T{}, T{}, base + 2 * threadIdx.x);
+  else for (; base + kBatchTile <= n; base += kBatchTile) body(T{}, F{}, base + 2 * threadIdx.x);
+  if (base < n) {
+    if (fvec) body(F{}, T{}, base + 2 * threadIdx.x); else body(F{}, F{}, base + 2 * threadIdx.x);
+  }
+}
+
+// the value PB stores as w1' (nka_kernels.hpp: pa_operand with `normed`)
+template <bool RCP> __device__ __forceinline__ double batch_nrm(double x, double s, double rs) { return RCP ? rs * x : x / s; }
+
+// Sums of NACC per-thread accumulators over the workgroup in a fixed order: lanes by the butterfly of wave_sum, then
+// wavefronts 0, 1, 2, 3.  Result a in res[a] (LDS), valid after the trailing barrier.
+template <int NACC>
+__device__ __forceinline__ void batch_block_sum(const double (&acc)[NACC], double *sm, double *res) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int a = 0; a < NACC; a++) {
+    const double x = wave_sum(acc[a]);
+    if (lane == 0) sm[wv * NACC + a] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < NACC) {
+    double r = sm[threadIdx.x];
+#pragma unroll
+    for (int q = 1; q < kBatchWaves; q++) r += sm[q * NACC + threadIdx.x];
+    res[threadIdx.x] = r;
+  }
+  __syncthreads();
+}
+
+enum { HDR_PENDING = 0, HDR_FIRST = 1, HDR_NOLDER = 2, HDR_NCOMB = 3, HDR_NEW = 4, HDR_NORMED = 5 };
+
+template <int COMB, bool ORDERED>
+__global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, double *__restrict__ f_all, int64_t ld,
+                                                                const int32_t *__restrict__ active) {
+#pragma clang fp contract(off)      // elementwise statements and the reference-order sums round like the reference; fma is explicit
+  constexpr bool RCP = (COMB == 1);
+  constexpr bool COMPACT = (COMB == 2);
+  const int sys = blockIdx.x;
+  if (active != nullptr && active[sys] == 0) return;      // phase 0: nothing of this system is read or written
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int mvec = a.mvec, m1 = mvec + 1, nh = (m1 + 1) * (m1 + 1);
+  const int64_t n = a.n;
+  const Ctl ctl = batch_ctl(a, sys);
+  double *const f = f_all + (size_t)sys * ld;
+  double *const W = a.w + (size_t)sys * a.sys_stride, *const V = a.v + (size_t)sys * a.sys_stride;
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;      // (stored vectors: always 16-byte aligned)
+
+  const nka_host::BatchLds lds = nka_host::batch_lds(mvec);
+  double *const shd = reinterpret_cast<double *>(smem);
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  Lst L;
+  L.h = shd + lds.h;
+  L.c = shd + lds.c;
+  double *const red = shd + lds.red;
+  double *const cc = shd + lds.cc;           // combine plan: coefficients in list order (slots: cs)
+  double *const sm = shd + lds.sm;
+  double *const res = shd + lds.res;
+  L.next = shi + lds.next;
+  L.prev = shi + lds.prev;
+  int32_t *const ps = shi + lds.ps;          // older list entries at entry, in list order
+  int32_t *const cs = shi + lds.cs;
+  int32_t *const hdr = shi + lds.hdr;
+  L.m1 = m1;
+  L.mvec = mvec;
+
+  // ---- phase 1: the working copy ----
+  for (int i = t; i < nh; i += kBatchThreads) L.h[i] = ctl.h()[i];
+  for (int i = t; i < m1 + 1; i += kBatchThreads) {
+    L.c[i] = ctl.c()[i];
+    L.next[i] = ctl.next()[i];
+    L.prev[i] = ctl.prev()[i];
+  }
+  for (int i = t; i < 2 + 2 * mvec; i += kBatchThreads) red[i] = 0.0;      // an update rewrites every entry
+  L.subspace = L.pending = L.first = L.last = L.free_ = 0;
+  L.vtol = 0.0;
+  __syncthreads();
+  if (t == 0) {
+    L.subspace = ctl.ic[IC_SUBSPACE];
+    L.pending = ctl.ic[IC_PENDING];
+    L.first = ctl.ic[IC_FIRST];
+    L.last = ctl.ic[IC_LAST];
+    L.free_ = ctl.ic[IC_FREE];
+    L.vtol = ctl.dc[DC_VTOL];
+    int no = 0;
+    for (int k = L.pending ? L.next[L.first] : L.first; k != 0 && no < m1; k = L.next[k]) ps[no++] = k;
+    hdr[HDR_PENDING] = L.pending;
+    hdr[HDR_FIRST] = L.first;
+    hdr[HDR_NOLDER] = no;
+  }
+  __syncthreads();
+  const int pending = hdr[HDR_PENDING], nolder = hdr[HDR_NOLDER];
+  const double *const w1 = pending ? W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride : f;
+  const double *const w1s = pending ? w1 : W;      // always a stored (16-byte aligned) vector: for loads whose value may go unused
+
+  // ---- phase 2: the norm (F08:266-267) ----
+  double s = 0.0;
+  if (pending) {
+    if (ORDERED) {
+      if (t == 0) {
+        double dd = 0.0;
+        for (int64_t i = 0; i < n; i++) {
+          const double d = w1[i] - f[i];
+          dd = dd + d * d;
+        }
+        res[kBatchAcc] = dd;
+      }
+      __syncthreads();
+    } else {
+      double acc[1] = {0.0};
+      batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+        constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+        const d2 fv = ld_tile<FULL, FV>(f, i, n), wv = ld_tile<FULL, true>(w1, i, n);
+#pragma unroll
+        for (int q = 0; q < 2; q++)
+          if (FULL || i + q < n) {
+            const double d = wv[q] - fv[q];
+            acc[0] = fma(d, d, acc[0]);
+          }
+      });
+      batch_block_sum<1>(acc, sm, res + kBatchAcc);
+    }
+    s = sqrt(res[kBatchAcc]);
+    if (t == 0) red[0] = res[kBatchAcc];
+  }
+  const bool normed = pending && s != 0.0;      // (s == 0: the scalar step relaxes, F08:275; NaN: goes on, like the reference)
+  const double rs = 1.0 / s;
+
+  // ---- phase 3: every other sum, on the rounded w1' (F08:286-290, 371) ----
+  if (ORDERED) {
+    // thread r <= nolder: r = 0 <f,w1'>, else <w1',w_(r-1)> (only if normed); thread 64 + p: <f,w_p>
+    if (normed && t <= nolder) {
+      const double *y = t == 0 ? f : W + (size_t)(ps[t - 1] - 1) * a.stride;
+      double acc = 0.0;
+      for (int64_t i = 0; i < n; i++) {
+        const double wn = batch_nrm<RCP>(w1[i] - f[i], s, rs);
+        acc = acc + wn * y[i];
+      }
+      red[t == 0 ? 1 : 2 + (t - 1)] = acc;
+    } else if (t >= 64 && t - 64 < nolder) {
+      const double *y = W + (size_t)(ps[t - 64] - 1) * a.stride;
+      double acc = 0.0;
+      for (int64_t i = 0; i < n; i++) acc = acc + f[i] * y[i];
+      red[2 + mvec + (t - 64)] = acc;
+    }
+  } else {
+    const int ngroup = (nolder + kBatchGroup - 1) / kBatchGroup;
+    for (int g = 0; g < (ngroup > 0 ? ngroup : (normed ? 1 : 0)); g++) {
+      const double *wk[kBatchGroup];
+#pragma unroll
+      for (int j = 0; j < kBatchGroup; j++) {
+        const int p = g * kBatchGroup + j;
+        wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1s;   // (beyond the list: a re-read, discarded)
+      }
+      double acc[kBatchAcc];
+#pragma unroll
+      for (int q = 0; q < kBatchAcc; q++) acc[q] = 0.0;
+      batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+        constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+        const d2 fv = ld_tile<FULL, FV>(f, i, n);
+        const d2 dv = ld_tile<FULL, true>(w1s, i, n);     // (no pending pair: a stored vector whose value is not used)
+        d2 wv[kBatchGroup];
+#pragma unroll
+        for (int j = 0; j < kBatchGroup; j++) wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+#pragma unroll
+        for (int q = 0; q < 2; q++)
+          if (FULL || i + q < n) {
+            const double fq = fv[q];
+            if (normed) {
+              const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
+              if (g == 0) acc[2 * kBatchGroup] = fma(fq, wn, acc[2 * kBatchGroup]);
+#pragma unroll
+              for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wn, wv[j][q], acc[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fq, wv[j][q], acc[kBatchGroup + j]);
+          }
+      });
+      batch_block_sum<kBatchAcc>(acc, sm, res);
+      if (t < kBatchGroup && g * kBatchGroup + t < nolder) {
+        if (normed) red[2 + g * kBatchGroup + t] = res[t];
+        red[2 + mvec + g * kBatchGroup + t] = res[kBatchGroup + t];
+      }
+      if (t == 0 && g == 0 && normed) red[1] = res[2 * kBatchGroup];
+      // (res is rewritten only behind the two barriers of the next batch_block_sum)
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 4: the scalar step, the statements of k_solve on this system's working copy ----
+  if (t == 0) {
+    const int entry_first = L.first;
+    bool nrm = false;
+    int nrelax = ctl.ic[IC_NRELAX];
+    if (L.pending) {
+      ctl.dc[DC_S] = s;
+      if (s == 0.0) {                       // F08:275
+        lst_relax(L);
+        nrelax++;
+      }
+    }
+    if (L.pending) {
+      nrm = true;
+      for (int p = 0; p < nolder; p++) L.H(L.first, ps[p]) = red[2 + p];      // Gram row of w1' (F08:286-290)
+      lst_factor(L);
+    }
+    const int slot = L.free_;
+    L.free_ = L.next[slot];
+    int ncomb = 0;
+    if (L.subspace) {
+      if (nrm) L.c[entry_first] = red[1];
+      for (int p = 0; p < nolder; p++) L.c[ps[p]] = red[2 + mvec + p];
+      lst_solve(L);
+      for (int k = L.first; k != 0; k = L.next[k]) {
+        cs[ncomb] = k;
+        cc[ncomb] = L.c[k];
+        ncomb++;
+      }
+    }
+    lst_prepend(L, slot);
+    hdr[HDR_NCOMB] = ncomb;
+    hdr[HDR_NEW] = slot;
+    hdr[HDR_NORMED] = nrm ? 1 : 0;
+    ctl.ic[IC_SUBSPACE] = L.subspace;
+    ctl.ic[IC_PENDING] = L.pending;
+    ctl.ic[IC_FIRST] = L.first;
+    ctl.ic[IC_LAST] = L.last;
+    ctl.ic[IC_FREE] = L.free_;
+    ctl.ic[IC_NEW] = slot;
+    ctl.ic[IC_NCOMB] = ncomb;
+    ctl.ic[IC_NORMED] = nrm ? 1 : 0;
+    ctl.ic[IC_NRELAX] = nrelax;
+  }
+  __syncthreads();
+
+  // ---- phase 5: the working copy back ----
+  for (int i = t; i < nh; i += kBatchThreads) ctl.h()[i] = L.h[i];
+  for (int i = t; i < m1 + 1; i += kBatchThreads) {
+    ctl.c()[i] = L.c[i];
+    ctl.next()[i] = L.next[i];
+    ctl.prev()[i] = L.prev[i];
+  }
+  for (int i = t; i < 2 + 2 * mvec; i += kBatchThreads) ctl.red()[i] = red[i];
+
+  // ---- phase 6: normalise the pending pair, combine, ring stores (F08:282-283, 361, 395-404) ----
+  const int ncomb = hdr[HDR_NCOMB];
+  const bool norm0 = hdr[HDR_NORMED] != 0;      // pair 0 of the plan is the pending pair, still raw
+  double *const wnew = W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
+  batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+    constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+    if (!FULL && i >= n) return;
+    const d2 fin = ld_tile<FULL, FV>(f, i, n);
+    d2 x = fin;
+    int j0 = 0;
+    if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
+      double *const wk = W + (size_t)(cs[0] - 1) * a.stride, *const vk = V + (size_t)(cs[0] - 1) * a.stride;
+      d2 wv = ld_tile<FULL, true>(wk, i, n), vv = ld_tile<FULL, true>(vk, i, n);
+      const double c = cc[0];
+#pragma unroll
+      for (int q = 0; q < 2; q++) {
+        const double wn = batch_nrm<RCP>(wv[q] - fin[q], s, rs);
+        const double vn = batch_nrm<RCP>(vv[q], s, rs);
+        wv[q] = wn;
+        vv[q] = COMPACT ? vn - wn : vn;
+        x[q] = COMPACT ? x[q] + c * vv[q] : comb1<COMB>(x[q], c, wv[q], vv[q]);
+      }
+      st_tile<FULL, true>(wk, i, n, wv);
+      st_tile<FULL, true>(vk, i, n, vv);
+      j0 = 1;
+    }
+    constexpr int U = 4;      // pairs whose loads are in flight together (beyond the plan: the last pair again, not applied)
+    for (int j = j0; j < ncomb; j += U) {
+      d2 wv[U], vv[U];
+      double c[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int jj = j + u < ncomb ? j + u : ncomb - 1;
+        const size_t off = (size_t)(cs[jj] - 1) * a.stride;
+        c[u] = cc[jj];
+        vv[u] = ld_tile<FULL, true>(V + off, i, n);
+        if (!COMPACT) wv[u] = ld_tile<FULL, true>(W + off, i, n); else wv[u] = vv[u];
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (j + u < ncomb) {
+#pragma unroll
+          for (int q = 0; q < 2; q++) x[q] = COMPACT ? x[q] + c[u] * vv[u][q] : comb1<COMB>(x[q], c[u], wv[u][q], vv[u][q]);
+        }
+    }
+    st_tile<FULL, true>(wnew, i, n, fin);
+    st_tile<FULL, true>(vnew, i, n, x);
+    if (ncomb > 0) st_tile<FULL, FV>(f, i, n, x);      // (nothing to combine: f stays as it is)
+  });
+}
+
+// restart / relax (F08:422-457) of the active systems, one thread per system, on the control block in global memory
+enum { kBatchOpRestart = 0, kBatchOpRelax = 1 };
+__global__ __launch_bounds__(64) void k_batch_list_op(BatchArgs a, int op, const int32_t *__restrict__ active) {
+  const int sys = blockIdx.x * 64 + threadIdx.x;
+  if (sys >= a.nsys) return;
+  if (active != nullptr && active[sys] == 0) return;
+  const Ctl ctl = batch_ctl(a, sys);
+  Lst L;
+  L.h = ctl.h();
+  L.c = ctl.c();
+  L.next = ctl.next();
+  L.prev = ctl.prev();
+  L.m1 = a.mvec + 1;
+  L.mvec = a.mvec;
+  L.vtol = ctl.dc[DC_VTOL];
+  L.subspace = ctl.ic[IC_SUBSPACE];
+  L.pending = ctl.ic[IC_PENDING];
+  L.first = ctl.ic[IC_FIRST];
+  L.last = ctl.ic[IC_LAST];
+  L.free_ = ctl.ic[IC_FREE];
+  if (op == kBatchOpRestart) lst_restart(L); else lst_relax(L);
+  ctl.ic[IC_SUBSPACE] = L.subspace;
+  ctl.ic[IC_PENDING] = L.pending;
+  ctl.ic[IC_FIRST] = L.first;
+  ctl.ic[IC_LAST] = L.last;
+  ctl.ic[IC_FREE] = L.free_;
+}
+
+__global__ __launch_bounds__(64) void k_batch_set_vtol(BatchArgs a, double vtol) {
+  const int sys = blockIdx.x * 64 + threadIdx.x;
+  if (sys < a.nsys) batch_ctl(a, sys).dc[DC_VTOL] = vtol;
+}
+
+}  // namespace
+
+struct nka_hip_batch_state {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int flavor = NKA_HIP_FLAVOR_C;
+  int sum_order = NKA_HIP_SUMS_AUTO;
+  double vtol = 0.01;
+  BatchArgs k{};
+};
+
+namespace {
+
+bool batch_ordered(const nka_hip_batch_state *b) {
+  return b->sum_order == NKA_HIP_SUMS_REFERENCE_ORDER || (b->sum_order == NKA_HIP_SUMS_AUTO && b->k.n <= kOrdAutoMax);
+}
+
+int check_mask(const nka_hip_batch_state *b, const int32_t *active, const char *what) {
+  if (!active) return 0;
+  return nka_detail::check_device_span_i32(active, b->k.nsys, what);
+}
+
+int check_sys(const nka_hip_batch_state *b, int32_t sys, const char *who) {
+  if (!b) return fail(NKA_HIP_EINVAL, std::string(who) + ": null handle");
+  if (sys < 0 || sys >= b->k.nsys) return fail(NKA_HIP_EINVAL, std::string(who) + ": system out of range");
+  return 0;
+}
+
+// control block of one system as it stands on the device (synchronises)
+int fetch_sys(nka_hip_batch_t b, int32_t sys, std::vector<int32_t> &ic, std::vector<double> &dc) {
+  HIP_TRY(hipSetDevice(b->device));
+  const Ctl c = batch_ctl(b->k, sys);
+  ic.resize((size_t)c.ic_count());
+  dc.resize((size_t)c.dc_count());
+  HIP_TRY(hipMemcpyAsync(ic.data(), c.ic, sizeof(int32_t) * ic.size(), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(dc.data(), c.dc, sizeof(double) * dc.size(), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int list_op(nka_hip_batch_t b, int op, const int32_t *active, const char *who) {
+  if (!b) return fail(NKA_HIP_EINVAL, std::string(who) + ": null handle");
+  HIP_TRY(hipSetDevice(b->device));
+  if (int rc = check_mask(b, active, who)) return rc;
+  hipLaunchKernelGGL(k_batch_list_op, dim3((unsigned)((b->k.nsys + 63) / 64)), dim3(64), 0, b->stream, b->k, op, active);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+template <int COMB>
+void launch_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active) {
+  const size_t lds = nka_host::batch_lds(b->k.mvec).bytes();
+  if (batch_ordered(b))
+    hipLaunchKernelGGL((k_batch_update<COMB, true>), dim3((unsigned)b->k.nsys), dim3(kBatchThreads), lds, b->stream, b->k, f, ld, active);
+  else
+    hipLaunchKernelGGL((k_batch_update<COMB, false>), dim3((unsigned)b->k.nsys), dim3(kBatchThreads), lds, b->stream, b->k, f, ld, active);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                         int32_t device, void *stream) {
+  if (!out) return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: out is NULL");
+  *out = nullptr;
+  if (nsys < 1) return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: nsys must be >= 1");
+  if (vlen < 1 || vlen > NKA_HIP_BATCH_MAX_VLEN)
+    return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: vlen must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_VLEN) +
+                                    " (longer systems: lone handles, nka_hip_create)");
+  if (mvec < 1 || mvec > NKA_HIP_BATCH_MAX_MVEC)
+    return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: mvec must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_MVEC));
+  if (!(vtol > 0.0)) return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: vtol must be > 0");
+  if (int rc = nka_detail::resolve_flavor(&flavor, "nka_hip_batch_create")) return rc;
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+
+  auto *b = new nka_hip_batch_state();
+  b->device = device;
+  b->stream = (hipStream_t)stream;
+  b->flavor = flavor;
+  b->vtol = vtol;
+  BatchArgs &k = b->k;
+  k.n = vlen;
+  k.mvec = mvec;
+  k.nsys = nsys;
+  const nka_host::BatchLayout lay = nka_host::batch_layout(vlen, mvec);
+  k.stride = lay.stride;
+  k.sys_stride = lay.sys_stride;
+  k.ic_stride = lay.ic_stride;
+  k.dc_stride = lay.dc_stride;
+  {
+    Ctl c{};
+    c.mvec = mvec;
+    if (c.ic_count() != nka_host::batch_ic_count(mvec) || c.dc_count() != nka_host::batch_dc_count(mvec)) {
+      delete b;
+      return fail(NKA_HIP_ESTATE, "nka_hip_batch_create: host_logic.hpp and nka_kernels.hpp disagree on the control block");
+    }
+  }
+  const double slot_bytes = (double)k.sys_stride * 8.0 * (double)nsys;
+  if (slot_bytes > 1.0e13) {      // (beyond any device: also keeps the size arithmetic below inside 64 bits)
+    delete b;
+    return fail(NKA_HIP_ENOMEM, "nka_hip_batch_create: the batch needs more device memory than any device has");
+  }
+  int rc = 0;
+  auto alloc = [&](void **p, size_t bytes) {
+    if (rc) return;
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(NKA_HIP_ENOMEM, std::string("hipMalloc(") + std::to_string(bytes) + " B): " + hipGetErrorString(e));
+    }
+  };
+  alloc((void **)&k.w, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys);
+  alloc((void **)&k.v, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys);
+  alloc((void **)&k.ic, sizeof(int32_t) * (size_t)k.ic_stride * (size_t)nsys);
+  alloc((void **)&k.dc, sizeof(double) * (size_t)k.dc_stride * (size_t)nsys);
+  if (!rc && (hipMemsetAsync(k.ic, 0, sizeof(int32_t) * (size_t)k.ic_stride * (size_t)nsys, b->stream) != hipSuccess ||
+              hipMemsetAsync(k.dc, 0, sizeof(double) * (size_t)k.dc_stride * (size_t)nsys, b->stream) != hipSuccess ||
+              hipMemsetAsync(k.w, 0, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys, b->stream) != hipSuccess ||
+              hipMemsetAsync(k.v, 0, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys, b->stream) != hipSuccess)) {
+    (void)hipGetLastError();
+    rc = fail(NKA_HIP_EHIP, "nka_hip_batch_create: initialising the batch failed");
+  }
+  if (!rc) {
+    hipLaunchKernelGGL(k_batch_set_vtol, dim3((unsigned)((nsys + 63) / 64)), dim3(64), 0, b->stream, k, vtol);
+    hipLaunchKernelGGL(k_batch_list_op, dim3((unsigned)((nsys + 63) / 64)), dim3(64), 0, b->stream, k, (int)kBatchOpRestart,
+                       (const int32_t *)nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) rc = fail(NKA_HIP_EHIP, std::string("nka_hip_batch_create: ") + hipGetErrorString(e));
+  }
+  if (rc) {
+    nka_hip_batch_destroy(b);
+    return rc;
+  }
+  *out = b;
+  return 0;
+}
+
+int nka_hip_batch_destroy(nka_hip_batch_t b) {
+  if (!b) return 0;
+  nka_detail::invalidate_span_cache();
+  hipSetDevice(b->device);
+  hipStreamSynchronize(b->stream);
+  hipFree(b->k.w);
+  hipFree(b->k.v);
+  hipFree(b->k.ic);
+  hipFree(b->k.dc);
+  delete b;
+  return 0;
+}
+
+int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, const int32_t *active_dev) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_accel_update: null handle");
+  if (!f_dev) return fail(NKA_HIP_EINVAL, "batch_accel_update: f is NULL");
+  if (ld < b->k.n) return fail(NKA_HIP_EINVAL, "batch_accel_update: ld must be >= vlen");
+  if (ld > (INT64_MAX / (int64_t)sizeof(double) - b->k.n) / (int64_t)b->k.nsys)      // (the span below, in bytes, stays inside 64 bits)
+    return fail(NKA_HIP_EINVAL, "batch_accel_update: ld is larger than any allocation");
+  HIP_TRY(hipSetDevice(b->device));
+  if (int rc = nka_detail::check_device_span(f_dev, (int64_t)(b->k.nsys - 1) * ld + b->k.n, "batch_accel_update: f")) return rc;
+  if (int rc = check_mask(b, active_dev, "batch_accel_update: active")) return rc;
+  switch (b->flavor) {
+    case NKA_HIP_FLAVOR_F08_VECTOR: launch_update<1>(b, f_dev, ld, active_dev); break;
+    case NKA_HIP_FLAVOR_C: launch_update<2>(b, f_dev, ld, active_dev); break;
+    default: launch_update<0>(b, f_dev, ld, active_dev);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int nka_hip_batch_restart(nka_hip_batch_t b, const int32_t *active_dev) { return list_op(b, kBatchOpRestart, active_dev, "batch_restart"); }
+int nka_hip_batch_relax(nka_hip_batch_t b, const int32_t *active_dev) { return list_op(b, kBatchOpRelax, active_dev, "batch_relax"); }
+
+int nka_hip_batch_set_vec_tol(nka_hip_batch_t b, double vtol) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_set_vec_tol: null handle");
+  if (!(vtol > 0.0)) return fail(NKA_HIP_EINVAL, "batch_set_vec_tol: vtol must be > 0");      // F08:205
+  HIP_TRY(hipSetDevice(b->device));
+  b->vtol = vtol;
+  hipLaunchKernelGGL(k_batch_set_vtol, dim3((unsigned)((b->k.nsys + 63) / 64)), dim3(64), 0, b->stream, b->k, vtol);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_set_sum_order: null handle");
+  if (order == NKA_HIP_SUMS_BLOCKED)
+    return fail(NKA_HIP_EINVAL, "batch_set_sum_order: NKA_HIP_SUMS_BLOCKED is not offered by a batch (it has no exchange to save): "
+                                "NKA_HIP_SUMS_BLOCKED_ROUNDED, _REFERENCE_ORDER or _AUTO");
+  if (order != NKA_HIP_SUMS_AUTO && order != NKA_HIP_SUMS_REFERENCE_ORDER && order != NKA_HIP_SUMS_BLOCKED_ROUNDED)
+    return fail(NKA_HIP_EINVAL, "batch_set_sum_order: unknown sum order");
+  b->sum_order = order;
+  return 0;
+}
+
+int nka_hip_batch_set_stream(nka_hip_batch_t b, void *stream) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_set_stream: null handle");
+  hipStream_t ns = (hipStream_t)stream;
+  if (ns == b->stream) return 0;
+  HIP_TRY(hipSetDevice(b->device));
+  hipEvent_t ev;
+  HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e1 = hipEventRecord(ev, b->stream);
+  hipError_t e2 = (e1 == hipSuccess) ? hipStreamWaitEvent(ns, ev, 0) : e1;
+  hipEventDestroy(ev);
+  if (e2 != hipSuccess) return fail(NKA_HIP_EHIP, std::string("batch_set_stream: ") + hipGetErrorString(e2));
+  b->stream = ns;
+  return 0;
+}
+
+int nka_hip_batch_flavor(nka_hip_batch_t b) { return b ? b->flavor : fail(NKA_HIP_EINVAL, "batch_flavor: null handle"); }
+
+int nka_hip_batch_num_vec(nka_hip_batch_t b, int32_t *num_vec_host) {
+  if (!b || !num_vec_host) return fail(NKA_HIP_EINVAL, "batch_num_vec: null argument");
+  HIP_TRY(hipSetDevice(b->device));
+  std::vector<int32_t> ic((size_t)b->k.ic_stride * (size_t)b->k.nsys);
+  HIP_TRY(hipMemcpyAsync(ic.data(), b->k.ic, sizeof(int32_t) * ic.size(), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  for (int sys = 0; sys < b->k.nsys; sys++) {
+    const int32_t *c = ic.data() + (size_t)sys * b->k.ic_stride, *next = c + IC_HEADER;
+    int n = 0;
+    for (int k = c[IC_FIRST]; k != 0 && n <= b->k.mvec + 1; k = next[k]) n++;      // F08:224-229
+    num_vec_host[sys] = c[IC_PENDING] ? n - 1 : n;                                    // F08:230
+  }
+  return 0;
+}
+
+int nka_hip_batch_get_state(nka_hip_batch_t b, int32_t sys, int32_t *subspace, int32_t *pending, int32_t *first, int32_t *last,
+                            int32_t *free_, int32_t *next, int32_t *prev, double *h, double *c) {
+  if (int rc = check_sys(b, sys, "batch_get_state")) return rc;
+  std::vector<int32_t> ic;
+  std::vector<double> dc;
+  if (int rc = fetch_sys(b, sys, ic, dc)) return rc;
+  const int m1 = b->k.mvec + 1;
+  if (subspace) *subspace = ic[IC_SUBSPACE];
+  if (pending) *pending = ic[IC_PENDING];
+  if (first) *first = ic[IC_FIRST];
+  if (last) *last = ic[IC_LAST];
+  if (free_) *free_ = ic[IC_FREE];
+  const int32_t *nx = ic.data() + IC_HEADER, *pv = nx + (m1 + 1);
+  const double *hh = dc.data() + DC_HEADER, *cc = hh + (m1 + 1) * (m1 + 1);
+  for (int k = 1; k <= m1; k++) {
+    if (next) next[k - 1] = nx[k];
+    if (prev) prev[k - 1] = pv[k];
+    if (c) c[k - 1] = cc[k];
+  }
+  if (h)
+    for (int j = 1; j <= m1; j++)
+      for (int i = 1; i <= m1; i++) h[(i - 1) + (size_t)(j - 1) * m1] = hh[i * (m1 + 1) + j];
+  return 0;
+}
+
+int nka_hip_batch_get_reductions(nka_hip_batch_t b, int32_t sys, double *red_out) {
+  if (int rc = check_sys(b, sys, "batch_get_reductions")) return rc;
+  if (!red_out) return fail(NKA_HIP_EINVAL, "batch_get_reductions: null argument");
+  HIP_TRY(hipSetDevice(b->device));
+  const Ctl c = batch_ctl(b->k, sys);
+  HIP_TRY(hipMemcpyAsync(red_out, c.red(), sizeof(double) * (size_t)c.red_count(), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+static int batch_get_slot(nka_hip_batch_t b, bool v, int32_t sys, int32_t slot, double *host_out) {
+  if (int rc = check_sys(b, sys, v ? "batch_get_v" : "batch_get_w")) return rc;
+  if (slot < 1 || slot > b->k.mvec + 1) return fail(NKA_HIP_EINVAL, "batch_get_w/v: slot out of range");
+  if (!host_out) return fail(NKA_HIP_EINVAL, "batch_get_w/v: null argument");
+  HIP_TRY(hipSetDevice(b->device));
+  const double *src = (v ? b->k.v : b->k.w) + (size_t)sys * b->k.sys_stride + (size_t)(slot - 1) * b->k.stride;
+  HIP_TRY(hipMemcpyAsync(host_out, src, sizeof(double) * (size_t)b->k.n, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+int nka_hip_batch_get_w(nka_hip_batch_t b, int32_t sys, int32_t slot, double *host_out) { return batch_get_slot(b, false, sys, slot, host_out); }
+int nka_hip_batch_get_v(nka_hip_batch_t b, int32_t sys, int32_t slot, double *host_out) { return batch_get_slot(b, true, sys, slot, host_out); }
+
+// FNV-1a over the system's two control blocks, as nka_hip_state_digest
+int nka_hip_batch_state_digest(nka_hip_batch_t b, int32_t sys, uint64_t *digest) {
+  if (int rc = check_sys(b, sys, "batch_state_digest")) return rc;
+  if (!digest) return fail(NKA_HIP_EINVAL, "batch_state_digest: null argument");
+  std::vector<int32_t> ic;
+  std::vector<double> dc;
+  if (int rc = fetch_sys(b, sys, ic, dc)) return rc;
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&h](const void *p, size_t nbytes) {
+    const unsigned char *q = static_cast<const unsigned char *>(p);
+    for (size_t i = 0; i < nbytes; i++) {
+      h ^= q[i];
+      h *= 1099511628211ull;
+    }
+  };
+  mix(ic.data(), ic.size() * sizeof(int32_t));
+  mix(dc.data(), dc.size() * sizeof(double));
+  *digest = h;
+  return 0;
+}
+
+}  // extern "C"

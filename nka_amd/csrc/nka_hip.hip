@@ -83,13 +83,19 @@ void unregister_owner(const void *owner) {
   for (auto it = g_reg.begin(); it != g_reg.end();) it = (it->second.owner == owner) ? g_reg.erase(it) : std::next(it);
 }
 
-static int check_device_span_impl(const void *p, int64_t n, const char *what);
+static int check_device_span_impl(const void *p, int64_t n, const char *what, size_t elem = sizeof(double));
 int check_device_span(const void *p, int64_t n, const char *what) {
   const int rc = check_device_span_impl(p, n, what);
   if (rc) span_check_failed() = true;
   return rc;
 }
-static int check_device_span_impl(const void *p, int64_t n, const char *what) {
+// the same for n int32 (the device-resident masks of the batched accelerator, nka_batch.hip)
+int check_device_span_i32(const void *p, int64_t n, const char *what) {
+  const int rc = check_device_span_impl(p, n, what, sizeof(int32_t));
+  if (rc) span_check_failed() = true;
+  return rc;
+}
+static int check_device_span_impl(const void *p, int64_t n, const char *what, size_t elem) {
   static const int mode = [] {      // 0 off, 1 strict (default), 2 cached
     const char *e = getenv("NKA_HIP_CHECK_POINTERS");
     if (e && e[0] == '0') return 0;
@@ -98,7 +104,7 @@ static int check_device_span_impl(const void *p, int64_t n, const char *what) {
   }();
   if (mode == 0 || n <= 0) return 0;
   if (!p) return fail(NKA_HIP_EINVAL, std::string(what) + ": NULL device pointer");
-  const size_t need = (size_t)n * sizeof(double);
+  const size_t need = (size_t)n * elem;
   const uintptr_t addr = reinterpret_cast<uintptr_t>(p);
   bool hit_in_registry = false;
   {
@@ -139,6 +145,24 @@ static int check_device_span_impl(const void *p, int64_t n, const char *what) {
   if (lo < static_cast<const char *>(base) || lo + need > end)
     return fail(NKA_HIP_EINVAL, std::string(what) + ": device buffer shorter than the vector length");
   if (e) *e = Entry{p, (size_t)(end - lo), gen, now};
+  return 0;
+}
+// NKA_HIP_FLAVOR_DEFAULT -> what the process runs; one rule for every front end and for the batched accelerator
+// (nka_batch.hip): NKA_HIP_FLAVOR, else compact storage (include/nka_hip.h)
+int resolve_flavor(int32_t *flavor_io, const char *who) {
+  int32_t flavor = *flavor_io;
+  if (flavor == NKA_HIP_FLAVOR_DEFAULT) {
+    flavor = NKA_HIP_FLAVOR_C;
+    if (const char *e = getenv("NKA_HIP_FLAVOR")) {
+      const std::string v(e);
+      if (v == "f08" || v == "F08" || v == "0") flavor = NKA_HIP_FLAVOR_F08;
+      else if (v == "f08vec" || v == "F08VEC" || v == "f08_vector" || v == "1") flavor = NKA_HIP_FLAVOR_F08_VECTOR;
+      else if (v == "c" || v == "C" || v == "compact" || v == "2") flavor = NKA_HIP_FLAVOR_C;
+      else if (!v.empty()) return fail(NKA_HIP_EINVAL, "NKA_HIP_FLAVOR: expected f08, f08vec or c, got '" + v + "'");
+    }
+  }
+  if (flavor < 0 || flavor > 2) return fail(NKA_HIP_EINVAL, std::string(who) + ": unknown flavor");
+  *flavor_io = flavor;
   return 0;
 }
 }  // namespace nka_detail
@@ -477,18 +501,7 @@ int nka_hip_create(nka_hip_t *out, int64_t vlen_local, int32_t mvec, double vtol
   if (mvec <= 0) return fail(NKA_HIP_EINVAL, "nka_hip_create: mvec must be > 0");
   if (vlen_local < 0) return fail(NKA_HIP_EINVAL, "nka_hip_create: vlen must be >= 0");
   if (!(vtol > 0.0)) return fail(NKA_HIP_EINVAL, "nka_hip_create: vtol must be > 0");
-  if (flavor == NKA_HIP_FLAVOR_DEFAULT) {
-    // one rule for every front end: NKA_HIP_FLAVOR, else compact storage (include/nka_hip.h)
-    flavor = NKA_HIP_FLAVOR_C;
-    if (const char *e = getenv("NKA_HIP_FLAVOR")) {
-      const std::string v(e);
-      if (v == "f08" || v == "F08" || v == "0") flavor = NKA_HIP_FLAVOR_F08;
-      else if (v == "f08vec" || v == "F08VEC" || v == "f08_vector" || v == "1") flavor = NKA_HIP_FLAVOR_F08_VECTOR;
-      else if (v == "c" || v == "C" || v == "compact" || v == "2") flavor = NKA_HIP_FLAVOR_C;
-      else if (!v.empty()) return fail(NKA_HIP_EINVAL, "NKA_HIP_FLAVOR: expected f08, f08vec or c, got '" + v + "'");
-    }
-  }
-  if (flavor < 0 || flavor > 2) return fail(NKA_HIP_EINVAL, "nka_hip_create: unknown flavor");
+  if (int rc = nka_detail::resolve_flavor(&flavor, "nka_hip_create")) return rc;
   if (mvec > (1 << 20) / 8) return fail(NKA_HIP_EINVAL, "nka_hip_create: mvec is absurdly large");   // (mvec+2)^2 doubles of h
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));

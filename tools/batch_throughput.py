@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""Throughput of the batched accelerator (include/nka_hip_batch.h) against the same systems as lone handles.
+
+Two contenders on the same inputs, alternated in ONE process, profiler off, device events around windows of at least
+--window seconds, every shape warmed, median of --repeats windows:
+  (a) nka_hip_batch_accel_update: the whole batch in one launch;
+  (b) nsys lone nka_hip_accel_update handles, one after another on one stream, called straight through the C ABI (no
+      Python wrapper between two updates).
+Steady state, full list, default flavour and default sums.  Before every update both contenders copy the next of
+mvec + 3 random input sets into their f (device to device; the same cost on both sides, so the ratio (b)/(a) is, if
+anything, understated): inputs must not repeat while their difference is still in the subspace, or it collapses.
+
+Per grid point: updates/s of the whole batch (a), bytes moved 8*nsys*vlen*(11+L+k) (compact storage, L = mvec - 1 older
+vectors in the sums, k = mvec combined) over time as a share of 8 TB/s, and the ratio time(b)/time(a); the bar for
+nsys >= 16 is 1.06.  --probe-vlens / --probe-nsys add points beyond the grid (to find the length at which the loop over
+lone handles catches up: the cap NKA_HIP_BATCH_MAX_VLEN).  Every line is flushed as it is measured."""
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK = 8.0e12
+BAR = 1.06
+
+
+def measure(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
+    npool = mvec + 3
+    need = 8.0 * nsys * vlen * (2 * 2 * (mvec + 1) + npool + 2)          # both contenders' slots, the pool, two f
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    Fa = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+    Fb = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+    batch = nka_amd.nka_batch().init(nsys, vlen, mvec)
+    lones = [nka_amd.nka().init(vlen, mvec) for _ in range(nsys)]
+    hb = batch._handle()
+    hl = [a._handle() for a in lones]
+    pl = [C.c_void_p(Fb[k].data_ptr()) for k in range(nsys)]
+    pa, ld = C.c_void_p(Fa.data_ptr()), int(Fa.stride(0)) if nsys > 1 else vlen
+    upd_a, upd_b = L.nka_hip_batch_accel_update, L.nka_hip_accel_update
+    step = [0]
+
+    def run_a(reps):
+        for _ in range(reps):
+            Fa.copy_(pool[step[0] % npool])
+            step[0] += 1
+            assert upd_a(hb, pa, ld, None) == 0
+
+    def run_b(reps):
+        for _ in range(reps):
+            Fb.copy_(pool[step[0] % npool])
+            step[0] += 1
+            for k in range(nsys):
+                if upd_b(hl[k], pl[k]) != 0:
+                    raise RuntimeError(L.nka_hip_last_error())
+
+    def timed(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn(reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    for fn in (run_a, run_b):                      # warm: fill the lists (steady state), settle clocks and caches
+        step[0] = 0
+        fn(mvec + 4)
+    torch.cuda.synchronize()
+    assert (batch.num_vec() == mvec).all() and lones[0].num_vec() == mvec and lones[-1].num_vec() == mvec
+    reps = {}
+    for name, fn in (("a", run_a), ("b", run_b)):
+        t = timed(fn, 3)
+        reps[name] = max(3, int(window / t) + 1)
+    ta, tb = [], []
+    for _ in range(repeats):                       # alternate the contenders
+        ta.append(timed(run_a, reps["a"]))
+        tb.append(timed(run_b, reps["b"]))
+    assert (batch.num_vec() == mvec).all() and lones[0].num_vec() == mvec
+    a, b = statistics.median(ta), statistics.median(tb)
+    nbytes = 8.0 * nsys * vlen * (11 + (mvec - 1) + mvec)
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec, t_batch_us=a * 1e6, t_lone_us=b * 1e6, updates_per_s=1.0 / a,
+               system_updates_per_s=nsys / a, share_of_peak=nbytes / a / PEAK, ratio=b / a, reps_a=reps["a"], reps_b=reps["b"],
+               spread_a=(max(ta) - min(ta)) / a, spread_b=(max(tb) - min(tb)) / b)
+    for x in lones:
+        x.delete()
+    batch.delete()
+    del pool, Fa, Fb
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--nsys", default="1,16,256,1024,4096")
+    ap.add_argument("--vlens", default="64,1024,16384,cap")
+    ap.add_argument("--mvecs", default="5,10,20")
+    ap.add_argument("--probe-vlens", default="", help="extra lengths, measured at --probe-nsys only")
+    ap.add_argument("--probe-nsys", default="16")
+    ap.add_argument("--window", type=float, default=0.5)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--mem-gb", type=float, default=200.0, help="skip (and say so) a point that needs more device memory")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import nka_amd
+    assert torch.cuda.is_available(), "needs the MI355X"
+    torch.cuda.set_device(0)
+    L = nka_amd.load()
+    cap = nka_amd.BATCH_MAX_VLEN
+    vl = lambda s: list(dict.fromkeys(cap if v == "cap" else int(v) for v in s.split(",") if v))      # noqa: E731  (cap may be in the list already)
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    grid = [(n, v, m) for v in vl(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    # the probes first: they decide the cap
+    points = [(n, v, m) for v in vl(args.probe_vlens) for m in ints(args.mvecs) for n in ints(args.probe_nsys) if (n, v, m) not in grid]
+    points += grid
+    out = open(args.out, "w") if args.out else None
+
+    def emit(line):
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    emit(f"# batched update (a) against nsys lone handles in a loop on one stream (b); {torch.cuda.get_device_name(0)}; "
+         f"windows >= {args.window} s, median of {args.repeats}, contenders alternated; cap = {cap}; default flavour and sums, "
+         f"full list")
+    emit("# bytes = 8*nsys*vlen*(11 + L + k), L = mvec - 1, k = mvec; share = bytes / time(a) / 8 TB/s; bar for nsys >= 16: "
+         f"ratio >= {BAR}")
+    emit(f"{'nsys':>5} {'vlen':>6} {'mvec':>4} {'batch us':>10} {'lone-loop us':>12} {'batch upd/s':>12} {'system upd/s':>13} "
+         f"{'share of 8 TB/s':>15} {'ratio b/a':>9}  bar")
+    t0 = time.time()
+    missed = []
+    for n, v, m in points:
+        r = measure(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9)
+        if r is None:
+            emit(f"{n:5d} {v:6d} {m:4d}   EXCLUDED: both contenders' stored vectors and the input pool, resident together so that "
+                 f"the two can alternate, need more than {args.mem_gb:g} GB of device memory")
+            continue
+        bar = "-" if n < 16 else ("ok" if r["ratio"] >= BAR else "MISSED")
+        if bar == "MISSED":
+            missed.append((n, v, m, r["ratio"]))
+        emit(f"{n:5d} {v:6d} {m:4d} {r['t_batch_us']:10.1f} {r['t_lone_us']:12.1f} {r['updates_per_s']:12.1f} "
+             f"{r['system_updates_per_s']:13.0f} {r['share_of_peak']:15.3f} {r['ratio']:9.2f}  {bar}   "
+             f"(spread a {100 * r['spread_a']:.1f} % b {100 * r['spread_b']:.1f} %)")
+    emit(f"# {len(points)} points in {time.time() - t0:.0f} s; missed the bar: {missed if missed else 'none'}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
