@@ -7,6 +7,10 @@ grids the library launches them on (nka_amd/csrc/nka_hip.hip: sums_rounded, laun
 planted_input builds the inputs of the GPU tests: a small random background with sentinels at the indices where the
 kernels hand elements from one loop, block or launch to the next.  tests/test_exact_sums_cpu.py holds all of it to
 Fraction arithmetic and shows that losing or doubling any one sentinel breaks the bound.
+
+The batched accelerator (nka_amd/csrc/nka_batch.hip) forms its sums in one workgroup per system: batch_k,
+batch_sentinel_indices and batch_planted_input, at the end of this file, are its counterparts of device_k, sentinel_indices
+and planted_input (tests/test_batch_sums_exact_gpu.py).
 """
 import math
 
@@ -203,3 +207,74 @@ def detectable(term, bound, total_abs):
     |red - exact| <= bound * total_abs cannot pass if |term| > 2 bound total_abs + u total_abs (the last: rounding of the
     exact sum)."""
     return abs(term) > (2.0 * bound + U) * total_abs
+
+
+# ---- the batched accelerator (nka_amd/csrc/nka_batch.hip: k_batch_update<*, false>) ---------------------------------------
+# One workgroup per system forms every sum of that system: there is no grid and no cross-block stage.
+
+BATCH_THREADS = 256             # kBatchThreads: 4 wavefronts of 64
+BATCH_TILE = 2 * BATCH_THREADS  # kBatchTile: thread t owns the pair 2t, 2t + 1 of every 512 elements
+BATCH_GROUP = 4                 # kBatchGroup: older vectors per sweep of phase 3
+BATCH_MAX_VLEN = 16384          # NKA_HIP_BATCH_MAX_VLEN
+# offsets inside a tile of the first and the last pair of each wavefront (lanes 0 and 63 of wavefronts 0..3)
+BATCH_WAVE_EDGES = tuple(2 * (64 * w + lane) + q for w in range(WAVES) for lane in (0, 63) for q in (0, 1))
+
+
+def batch_k(n):
+    """Roundings a product can meet in a sum of k_batch_update<*, false> over n elements, read off the kernel:
+
+      per-thread chain   batch_sweep gives thread t the pair (2t, 2t + 1) of every tile of 512 elements, the full tiles
+                         first, then the ragged one; each element is ONE fma into ONE accumulator per sum (phase 2:
+                         acc[0]; phase 3: acc[j], acc[4 + j], acc[8]), so a thread's chain is at most two fma per tile:
+                         2 * ceil(n / 512).  (The first fma adds to 0.0 and so rounds the product only: still one.)
+      batch_block_sum    wave_sum, a 64-lane butterfly of WAVE_LEVELS = 6 additions (offsets 32, 16, 8, 4, 2, 1), then
+                         sm[0] + sm[1] + sm[2] + sm[3]: wavefronts 1..3 added to wavefront 0 in turn, 3 additions.
+      nothing else       res[] is copied to red[]; one workgroup owns the whole system.
+
+    A fma rounds once (the product enters it exactly): 2 * ceil(n / 512) + 9 factors (1 + delta) at most; 11 up to one
+    tile, 73 at the cap of 16 384 elements.  The bound applied is gamma(batch_k(n)) * abs_dot (gamma adds the rounding
+    of exact_dot itself)."""
+    return 2 * _cdiv(n, BATCH_TILE) + WAVE_LEVELS + (WAVES - 1)
+
+
+def batch_sentinel_indices(n):
+    """Indices where the batch kernel changes hands in a system of n elements, by name (empty where there is none):
+
+      ends          0, n - 1 and n - 2;
+      wave_edges    in every tile, the full ones and the ragged one, the first and the last pair of each wavefront
+                    (BATCH_WAVE_EDGES): where the butterfly of one wavefront ends and sm[] takes over;
+      ragged_first  the first element of the ragged tile (batch_sweep leaves the straight-line full tiles for the
+                    guarded body);
+      odd_last      n - 1 for odd n: the first element of a pair whose second lies beyond n (ld_pair falls back from the
+                    16-byte load to guarded 8-byte loads and returns a zero that must not be accumulated)."""
+    ntile = n // BATCH_TILE
+    i = (np.arange(_cdiv(n, BATCH_TILE), dtype=np.int64)[:, None] * BATCH_TILE +
+         np.array(BATCH_WAVE_EDGES, dtype=np.int64)[None, :]).ravel()
+    return {"ends": np.unique(np.array([k for k in (0, n - 2, n - 1) if k >= 0], dtype=np.int64)),
+            "wave_edges": i[i < n],
+            "ragged_first": np.array([ntile * BATCH_TILE] if ntile * BATCH_TILE < n else [], dtype=np.int64),
+            "odd_last": np.array([n - 1] if n % 2 else [], dtype=np.int64)}
+
+
+def batch_all_sentinels(n):
+    return np.unique(np.concatenate(list(batch_sentinel_indices(n).values())))
+
+
+def batch_planted_input(n, rng, prev=None, background=0.125):
+    """planted_input for one system of a batch: N(0, background^2) everywhere, +-2^e (e in 0..3, random sign) at every
+    batch sentinel, never the value `prev` has there."""
+    x = rng.standard_normal(n) * background
+    idx = batch_all_sentinels(n)
+    val = np.ldexp(1.0, rng.integers(0, 4, idx.size)) * rng.choice([-1.0, 1.0], idx.size)
+    if prev is not None:
+        same = val == prev[idx]
+        val[same] = -val[same]
+    x[idx] = val
+    return x
+
+
+# shapes of tests/test_batch_sums_exact_gpu.py: around one wavefront's pairs (127 .. 129), two (255 .. 257), one tile
+# (511 .. 514: the ragged tile of one element, and of one full pair), two tiles, three tiles + 1, eight tiles + 3
+BATCH_SHAPES = [1, 2, 3, 7, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 514, 1023, 1024, 1025, 1537, 4099]
+BATCH_WIDTH_SHAPE = 700         # every older count up to NKA_HIP_BATCH_MAX_MVEC = 32
+BATCH_CAP_SHAPES = [BATCH_MAX_VLEN - 1, BATCH_MAX_VLEN]
