@@ -1,13 +1,14 @@
 // handles.hpp -- the two handle types of the C ABI and the host functions the library's translation units share.
-// Private to nka_amd/csrc: nka_hip.hip (the accelerator), vec_ops.hip (the abstract-vector hooks) and lab.hip (the
-// entry points of include/nka_hip_diag.h, linked into libnka_hip_diag.so only) include it.  Declarations only: every
-// function below is defined in nka_hip.hip.
+// Private to nka_amd/csrc: nka_hip.hip (the accelerator), vec_ops.hip (the abstract-vector hooks), nka_batch.hip (the batched
+// accelerator) and lab.hip (the entry points of include/nka_hip_diag.h, linked into libnka_hip_diag.so only) include it.
+// Declarations only: every function below is defined in nka_hip.hip.  Of the device side only the layout of the control block
+// (nka_ctl.hpp) comes with it: a unit that launches kernels includes nka_device.hpp / nka_chain.hpp / nka_kernels.hpp itself.
 #pragma once
 
 #include "../../include/nka_hip.h"
 #include "../../include/nka_hip_ext.h"
 #include "../../include/nka_hip_vec.h"
-#include "nka_kernels.hpp"
+#include "nka_ctl.hpp"
 #include "host_logic.hpp"
 #include "rccl_dl.hpp"
 
@@ -67,7 +68,7 @@ struct nka_hip_state {
   // what the host knows without reading the device back
   bool pending = false;
   int list_ub = 0;            // upper bound on the list length
-  // ... and what the device tells it without being asked: the list word (Ctl::hw, nka_kernels.hpp), one 64-bit word
+  // ... and what the device tells it without being asked: the list word (Ctl::hw, nka_ctl.hpp), one 64-bit word
   // in pinned host memory that PB of update number u overwrites with (u, list length at its exit).
   unsigned long long *list_word = nullptr;
   int64_t seq = 0;            // updates enqueued so far; the next one is number seq + 1
@@ -126,7 +127,7 @@ struct nka_hip_state {
   nka_hip_allreduce_fn allreduce = nullptr;
   void *allreduce_ctx = nullptr;
   ncclComm_t comm = nullptr;
-  // peer-to-peer exchange (nka_hip_p2p_export / _attach; nka_kernels.hpp: struct P2P)
+  // peer-to-peer exchange (nka_hip_p2p_export / _attach; nka_ctl.hpp: struct P2P)
   nka::P2P p2p{};                          // base == nullptr: none
   void *p2p_mail = nullptr;           // this rank's mailbox (fine-grained device memory, exported through hipIpc)
   std::vector<void *> p2p_opened;     // the peers' mailboxes as mapped here (hipIpcCloseMemHandle at detach)

@@ -1,5 +1,5 @@
-// host_logic.hpp -- the PURE host-side arithmetic of libnka_hip.so: pass widths, the decoding of the list word, who holds
-// which buffer, launch groups of the abstract-vector hooks.  No HIP, no device state: nka_hip.hip / vec_ops.hip include it,
+// host_logic.hpp -- the PURE host-side arithmetic of libnka_hip.so: pass widths, the decoding of the list word and of a control-
+// block snapshot, who holds which buffer, launch groups of the vector hooks.  No HIP, no device state: the .hip files include it,
 // and tests/c/host_logic_check.cpp compiles the same text with g++ -fsanitize=address,undefined and checks every function
 // against a brute-force model on the CPU (`make -C nka_amd/csrc hostcheck`, tests/test_sanitizers_cpu.py) -- the part of the
 // host code a sanitizer can see without a GPU (the reference's stand-in is its `defined` invariant check,
@@ -11,10 +11,12 @@
 #include <set>
 #include <vector>
 
+#include "nka_ctl.hpp"
+
 namespace nka_host {
 
-constexpr int kMaxPerPass = 32;        // largest list width one launch of the streaming kernels takes (= nka_kernels.hpp)
-constexpr int kListWordLenBits = 20;   // list word = update number << 20 | list length at its exit (= nka_kernels.hpp)
+using nka::kMaxPerPass;        // largest list width one launch of the streaming kernels takes
+using nka::kListWordLenBits;   // list word = update number << 20 | list length at its exit
 constexpr int kManyMax = 24;           // vectors per launch of the batched vector hooks (= vec_ops.hip)
 
 inline int round_up4(int x) { return ((std::max(x, 1) + 3) / 4) * 4; }
@@ -89,23 +91,62 @@ struct BufferBook {
   }
 };
 
+// A SNAPSHOT OF THE CONTROL BLOCK on the host (`ic`, `dc`: the two arrays of a Ctl of `mvec`, copied from the device): what the
+// accessors of both handle types (nka_hip_num_vec / _get_state / _state_digest and their nka_hip_batch_ siblings) report.
+// Vectors in the subspace: the list length (F08:224-229; the walk ends after mvec + 1 steps whatever the links say) less the
+// pending pair (F08:230).
+inline int snapshot_num_vec(const int32_t *ic, int mvec) {
+  const int32_t *next = ic + nka::IC_HEADER;
+  int n = 0;
+  for (int k = ic[nka::IC_FIRST]; k != 0 && n <= mvec + 1; k = next[k]) n++;
+  return ic[nka::IC_PENDING] ? n - 1 : n;
+}
+// The state as the reference's get-state hands it out (every output optional): slots 1-based on the device, arrays 0-based
+// here; h column-major m1 x m1 with h[(i-1) + (j-1) m1] = the reference's h(i,j).
+inline void snapshot_unpack(const int32_t *ic, const double *dc, int mvec, int32_t *subspace, int32_t *pending, int32_t *first,
+                            int32_t *last, int32_t *free_, int32_t *next, int32_t *prev, double *h, double *c) {
+  const int m1 = mvec + 1;
+  if (subspace) *subspace = ic[nka::IC_SUBSPACE];
+  if (pending) *pending = ic[nka::IC_PENDING];
+  if (first) *first = ic[nka::IC_FIRST];
+  if (last) *last = ic[nka::IC_LAST];
+  if (free_) *free_ = ic[nka::IC_FREE];
+  const int32_t *nx = ic + nka::IC_HEADER, *pv = nx + (m1 + 1);
+  const double *hh = dc + nka::DC_HEADER, *cc = hh + (m1 + 1) * (m1 + 1);
+  for (int k = 1; k <= m1; k++) {
+    if (next) next[k - 1] = nx[k];
+    if (prev) prev[k - 1] = pv[k];
+    if (c) c[k - 1] = cc[k];
+  }
+  if (h)
+    for (int j = 1; j <= m1; j++)
+      for (int i = 1; i <= m1; i++) h[(i - 1) + (size_t)(j - 1) * m1] = hh[i * (m1 + 1) + j];
+}
+// FNV-1a, 64 bits.  The digest of a snapshot mixes the bytes of ic, then those of dc, from the seed the library has always used
+// (the published offset basis less its last decimal digit): digests are compared between ranks, runs and versions, so it stays.
+constexpr uint64_t kFnvOffsetBasis = 14695981039346656037ull, kFnvPrime = 1099511628211ull;
+constexpr uint64_t kDigestSeed = 1469598103934665603ull;
+inline uint64_t fnv1a(const void *p, size_t nbytes, uint64_t h = kFnvOffsetBasis) {
+  const unsigned char *b = static_cast<const unsigned char *>(p);
+  for (size_t i = 0; i < nbytes; i++) {
+    h ^= b[i];
+    h *= kFnvPrime;
+  }
+  return h;
+}
+inline uint64_t snapshot_digest(const std::vector<int32_t> &ic, const std::vector<double> &dc) {
+  return fnv1a(dc.data(), dc.size() * sizeof(double), fnv1a(ic.data(), ic.size() * sizeof(int32_t), kDigestSeed));
+}
+
 // THE BATCHED ACCELERATOR (include/nka_hip_batch.h, nka_batch.hip): where the pieces of system `sys` lie.  Host and kernel
 // compile this text; tests/c/batch_layout_check.cpp holds it against a brute-force model (no two pieces overlap, every
 // stride a multiple of 32 doubles, the LDS budget).
-#if defined(__HIPCC__)
-#define NKA_HOST_DEVICE __host__ __device__
-#else
-#define NKA_HOST_DEVICE
-#endif
 constexpr int kBatchWaves = 4;                   // wavefronts of a workgroup (256 threads)
 constexpr int kBatchGroup = 4;                   // older vectors per sweep of the sums
 constexpr int kBatchAcc = 2 * kBatchGroup + 1;   // their two sums each, and <f,w1'>
-// control block of one system in the layout of Ctl (nka_kernels.hpp): int32 header (16), next, prev [m1+1], plan_slots,
-// comb_slots [m1+32]; double header (2), h [(m1+1)^2], c [m1+1], comb_c [m1+32], red [2+2 mvec], stamps [16]
-NKA_HOST_DEVICE constexpr int batch_ic_count(int mvec) { return 16 + 2 * (mvec + 2) + 2 * (mvec + 1 + kMaxPerPass); }
-NKA_HOST_DEVICE constexpr int batch_dc_count(int mvec) {
-  return 2 + (mvec + 2) * (mvec + 2) + (mvec + 2) + (mvec + 1 + kMaxPerPass) + (2 + 2 * mvec) + 16;
-}
+// control block of one system: the counts of a Ctl (nka_ctl.hpp) of that mvec, asked of one with no arrays behind it
+NKA_HOST_DEVICE constexpr int batch_ic_count(int mvec) { nka::Ctl c{}; c.mvec = mvec; return c.ic_count(); }
+NKA_HOST_DEVICE constexpr int batch_dc_count(int mvec) { nka::Ctl c{}; c.mvec = mvec; return c.dc_count(); }
 struct BatchLayout {
   int64_t stride;        // doubles between the slots of a system: vlen rounded up to 32 (256 bytes)
   int64_t sys_stride;    // doubles between systems in the w and the v allocation: (mvec + 1) slots

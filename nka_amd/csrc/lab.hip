@@ -2,6 +2,7 @@
 // product's own objects (nka_amd/csrc/Makefile).  Host code only: it defines and launches no kernel; what it enqueues goes
 // through the product's functions (handles.hpp), so the lab library runs the product's kernels and nothing else.
 #include "handles.hpp"
+#include "nka_chain.hpp"
 #include "../../include/nka_hip_diag.h"
 
 #include <algorithm>

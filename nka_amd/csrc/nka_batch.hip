@@ -8,7 +8,7 @@
 //   2 norm      sum d^2, d = fl(w1 - f), per-thread strided fma, fixed-order reduction; s = sqrt
 //   3 sums      on the ROUNDED w1' = fl(d/s) (fl(fl(1/s)*d) in the F08-vector flavour): <f,w1'>, <w1',w_p>, <f,w_p> while the
 //               older w stream past once, kBatchGroup of them per sweep (f and w1 are re-read from cache per sweep)
-//   4 scalar    thread 0, on the working copy in LDS: the lst_* functions of nka_kernels.hpp, i.e. the statements of k_solve:
+//   4 scalar    thread 0, on the working copy in LDS: the lst_* functions of nka_device.hpp, i.e. the statements of k_solve:
 //               decisions given the sums are the reference's by construction
 //   5 store     the working copy back to the system's control block
 //   6 combine   normalise the pending pair, combine in list order with the flavour's association, w_new = f_in,
@@ -17,10 +17,8 @@
 // mapping (pairs 2t, 2t+1 of every 512) and every accumulation order are the same whether a row of f is 16-byte aligned
 // (16-byte loads) or not (two 8-byte loads), so results do not depend on ld, on nsys, or on a system's position.
 // ORDERED = true is the reference-order sibling: every sum element after element, unfused, one thread per sum.
-// (handles.hpp brings in all of nka_kernels.hpp -- Ctl, Lst and the lst_* functions, comb1, wave_sum are needed -- and with it
-//  this object file carries unused copies of the core's non-template kernels, as vec_ops.o does: about 10 s of build time and
-//  dead code objects in the library, accepted rather than splitting the header the core's kernels are frozen in.)
 #include "handles.hpp"
+#include "nka_device.hpp"
 #include "../../include/nka_hip_batch.h"
 
 #include <algorithm>
@@ -43,7 +41,7 @@ constexpr int kBatchTile = 2 * kBatchThreads;   // elements per sweep step: thre
 
 struct BatchArgs {
   double *w, *v;        // system sys, slot k (1-based) at base + sys*sys_stride + (k-1)*stride
-  int32_t *ic;          // control blocks in the layout of Ctl (nka_kernels.hpp), ic_stride / dc_stride apart
+  int32_t *ic;          // control blocks in the layout of Ctl (nka_ctl.hpp), ic_stride / dc_stride apart
   double *dc;
   int64_t stride, sys_stride, n;
   int32_t ic_stride, dc_stride, mvec, nsys;
@@ -109,7 +107,7 @@ __device__ __forceinline__ void batch_sweep(int64_t n, bool fvec, Body body) {
   }
 }
 
-// the value PB stores as w1' (nka_kernels.hpp: pa_operand with `normed`)
+// the value PB stores as w1' (nka_device.hpp: pa_operand with `normed`)
 template <bool RCP> __device__ __forceinline__ double batch_nrm(double x, double s, double rs) { return RCP ? rs * x : x / s; }
 
 // Sums of NACC per-thread accumulators over the workgroup in a fixed order: lanes by the butterfly of wave_sum, then
@@ -182,11 +180,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
   L.vtol = 0.0;
   __syncthreads();
   if (t == 0) {
-    L.subspace = ctl.ic[IC_SUBSPACE];
-    L.pending = ctl.ic[IC_PENDING];
-    L.first = ctl.ic[IC_FIRST];
-    L.last = ctl.ic[IC_LAST];
-    L.free_ = ctl.ic[IC_FREE];
+    lst_load_scalars(L, ctl);
     L.vtol = ctl.dc[DC_VTOL];
     int no = 0;
     for (int k = L.pending ? L.next[L.first] : L.first; k != 0 && no < m1; k = L.next[k]) ps[no++] = k;
@@ -327,11 +321,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
     hdr[HDR_NCOMB] = ncomb;
     hdr[HDR_NEW] = slot;
     hdr[HDR_NORMED] = nrm ? 1 : 0;
-    ctl.ic[IC_SUBSPACE] = L.subspace;
-    ctl.ic[IC_PENDING] = L.pending;
-    ctl.ic[IC_FIRST] = L.first;
-    ctl.ic[IC_LAST] = L.last;
-    ctl.ic[IC_FREE] = L.free_;
+    lst_store_scalars(L, ctl);
     ctl.ic[IC_NEW] = slot;
     ctl.ic[IC_NCOMB] = ncomb;
     ctl.ic[IC_NORMED] = nrm ? 1 : 0;
@@ -407,24 +397,10 @@ __global__ __launch_bounds__(64) void k_batch_list_op(BatchArgs a, int op, const
   if (active != nullptr && active[sys] == 0) return;
   const Ctl ctl = batch_ctl(a, sys);
   Lst L;
-  L.h = ctl.h();
-  L.c = ctl.c();
-  L.next = ctl.next();
-  L.prev = ctl.prev();
-  L.m1 = a.mvec + 1;
-  L.mvec = a.mvec;
-  L.vtol = ctl.dc[DC_VTOL];
-  L.subspace = ctl.ic[IC_SUBSPACE];
-  L.pending = ctl.ic[IC_PENDING];
-  L.first = ctl.ic[IC_FIRST];
-  L.last = ctl.ic[IC_LAST];
-  L.free_ = ctl.ic[IC_FREE];
+  lst_on_ctl(L, ctl);
+  lst_load_scalars(L, ctl);      // (neither operation reads vtol)
   if (op == kBatchOpRestart) lst_restart(L); else lst_relax(L);
-  ctl.ic[IC_SUBSPACE] = L.subspace;
-  ctl.ic[IC_PENDING] = L.pending;
-  ctl.ic[IC_FIRST] = L.first;
-  ctl.ic[IC_LAST] = L.last;
-  ctl.ic[IC_FREE] = L.free_;
+  lst_store_scalars(L, ctl);
 }
 
 __global__ __launch_bounds__(64) void k_batch_set_vtol(BatchArgs a, double vtol) {
@@ -525,14 +501,6 @@ int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32
   k.sys_stride = lay.sys_stride;
   k.ic_stride = lay.ic_stride;
   k.dc_stride = lay.dc_stride;
-  {
-    Ctl c{};
-    c.mvec = mvec;
-    if (c.ic_count() != nka_host::batch_ic_count(mvec) || c.dc_count() != nka_host::batch_dc_count(mvec)) {
-      delete b;
-      return fail(NKA_HIP_ESTATE, "nka_hip_batch_create: host_logic.hpp and nka_kernels.hpp disagree on the control block");
-    }
-  }
   const double slot_bytes = (double)k.sys_stride * 8.0 * (double)nsys;
   if (slot_bytes > 1.0e13) {      // (beyond any device: also keeps the size arithmetic below inside 64 bits)
     delete b;
@@ -652,12 +620,8 @@ int nka_hip_batch_num_vec(nka_hip_batch_t b, int32_t *num_vec_host) {
   std::vector<int32_t> ic((size_t)b->k.ic_stride * (size_t)b->k.nsys);
   HIP_TRY(hipMemcpyAsync(ic.data(), b->k.ic, sizeof(int32_t) * ic.size(), hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
-  for (int sys = 0; sys < b->k.nsys; sys++) {
-    const int32_t *c = ic.data() + (size_t)sys * b->k.ic_stride, *next = c + IC_HEADER;
-    int n = 0;
-    for (int k = c[IC_FIRST]; k != 0 && n <= b->k.mvec + 1; k = next[k]) n++;      // F08:224-229
-    num_vec_host[sys] = c[IC_PENDING] ? n - 1 : n;                                    // F08:230
-  }
+  for (int sys = 0; sys < b->k.nsys; sys++)
+    num_vec_host[sys] = nka_host::snapshot_num_vec(ic.data() + (size_t)sys * b->k.ic_stride, b->k.mvec);
   return 0;
 }
 
@@ -667,22 +631,7 @@ int nka_hip_batch_get_state(nka_hip_batch_t b, int32_t sys, int32_t *subspace, i
   std::vector<int32_t> ic;
   std::vector<double> dc;
   if (int rc = fetch_sys(b, sys, ic, dc)) return rc;
-  const int m1 = b->k.mvec + 1;
-  if (subspace) *subspace = ic[IC_SUBSPACE];
-  if (pending) *pending = ic[IC_PENDING];
-  if (first) *first = ic[IC_FIRST];
-  if (last) *last = ic[IC_LAST];
-  if (free_) *free_ = ic[IC_FREE];
-  const int32_t *nx = ic.data() + IC_HEADER, *pv = nx + (m1 + 1);
-  const double *hh = dc.data() + DC_HEADER, *cc = hh + (m1 + 1) * (m1 + 1);
-  for (int k = 1; k <= m1; k++) {
-    if (next) next[k - 1] = nx[k];
-    if (prev) prev[k - 1] = pv[k];
-    if (c) c[k - 1] = cc[k];
-  }
-  if (h)
-    for (int j = 1; j <= m1; j++)
-      for (int i = 1; i <= m1; i++) h[(i - 1) + (size_t)(j - 1) * m1] = hh[i * (m1 + 1) + j];
+  nka_host::snapshot_unpack(ic.data(), dc.data(), b->k.mvec, subspace, pending, first, last, free_, next, prev, h, c);
   return 0;
 }
 
@@ -716,17 +665,7 @@ int nka_hip_batch_state_digest(nka_hip_batch_t b, int32_t sys, uint64_t *digest)
   std::vector<int32_t> ic;
   std::vector<double> dc;
   if (int rc = fetch_sys(b, sys, ic, dc)) return rc;
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&h](const void *p, size_t nbytes) {
-    const unsigned char *q = static_cast<const unsigned char *>(p);
-    for (size_t i = 0; i < nbytes; i++) {
-      h ^= q[i];
-      h *= 1099511628211ull;
-    }
-  };
-  mix(ic.data(), ic.size() * sizeof(int32_t));
-  mix(dc.data(), dc.size() * sizeof(double));
-  *digest = h;
+  *digest = nka_host::snapshot_digest(ic, dc);
   return 0;
 }
 

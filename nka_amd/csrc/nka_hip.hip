@@ -11,6 +11,7 @@
 // it can know without looking: whether a pair is pending, and an upper bound on
 // the list length (used to pick the unroll width of PA/PB).
 #include "handles.hpp"
+#include "nka_kernels.hpp"
 
 #include <dlfcn.h>
 
@@ -181,7 +182,7 @@ using nka_detail::enqueue_pa;
 
 }  // namespace
 
-// Entries of the address block (Ctl::pc) are offsets in doubles from vs.w (nka_kernels.hpp).
+// Entries of the address block (Ctl::pc) are offsets in doubles from vs.w (nka_ctl.hpp).
 static inline long long buffer_offset(const nka_hip_state *a, const double *p) {
   return (long long)((reinterpret_cast<intptr_t>(p) - reinterpret_cast<intptr_t>(a->vs.w)) / (intptr_t)sizeof(double));
 }
@@ -424,7 +425,6 @@ using nka_host::balanced_passes;
 using nka_host::balanced_widths;
 using nka_host::heavy_prime;
 using nka_host::round_up4;
-static_assert(nka_host::kMaxPerPass == kMaxPerPass && nka_host::kListWordLenBits == kListWordLenBits, "host_logic.hpp out of step with nka_kernels.hpp");
 
 // Optional ROCTx ranges around the phases of an update (NKA_HIP_ROCTX=1), for
 // rocprofv3 --marker-trace timelines.  The library is looked up at run time so
@@ -1371,7 +1371,7 @@ static SumsResult sums_blocked(nka_hip_t a, const double *f, int vec, int older_
   if (!(a->pending || older_ub > 0)) return r;
   RoctxRange range("nka:PA dots + all-reduce");
   // peer-to-peer exchange: the final sums go straight into every rank's mailbox and the scalar step gathers them -- no
-  // kernel in between (nka_kernels.hpp: struct P2P)
+  // kernel in between (nka_ctl.hpp: struct P2P)
   r.gather = a->allreduce == p2p_allreduce && a->p2p.base != nullptr;
   a->p2p_fused = r.gather;
   enqueue_pa(a, f, vec, older_ub);
@@ -1642,10 +1642,7 @@ int nka_hip_num_vec(nka_hip_t a) {
   std::vector<int32_t> ic;
   std::vector<double> dc;
   if (int rc = fetch_state(a, ic, dc)) return rc;
-  const int32_t *next = ic.data() + IC_HEADER;
-  int n = 0;
-  for (int k = ic[IC_FIRST]; k != 0 && n <= a->mvec + 1; k = next[k]) n++;  // F08:224-229
-  return ic[IC_PENDING] ? n - 1 : n;                                          // F08:230
+  return nka_host::snapshot_num_vec(ic.data(), a->mvec);
 }
 
 int nka_hip_max_vec(nka_hip_t a) { return a ? a->mvec : fail(NKA_HIP_EINVAL, "null handle"); }
@@ -1663,22 +1660,7 @@ int nka_hip_get_state(nka_hip_t a, int32_t *subspace, int32_t *pending, int32_t 
   std::vector<int32_t> ic;
   std::vector<double> dc;
   if (int rc = fetch_state(a, ic, dc)) return rc;
-  const int m1 = a->mvec + 1;
-  if (subspace) *subspace = ic[IC_SUBSPACE];
-  if (pending) *pending = ic[IC_PENDING];
-  if (first) *first = ic[IC_FIRST];
-  if (last) *last = ic[IC_LAST];
-  if (free_) *free_ = ic[IC_FREE];
-  const int32_t *nx = ic.data() + IC_HEADER, *pv = nx + (m1 + 1);
-  const double *hh = dc.data() + DC_HEADER, *cc = hh + (m1 + 1) * (m1 + 1);
-  for (int k = 1; k <= m1; k++) {
-    if (next) next[k - 1] = nx[k];
-    if (prev) prev[k - 1] = pv[k];
-    if (c) c[k - 1] = cc[k];
-  }
-  if (h)
-    for (int j = 1; j <= m1; j++)
-      for (int i = 1; i <= m1; i++) h[(i - 1) + (size_t)(j - 1) * m1] = hh[i * (m1 + 1) + j];
+  nka_host::snapshot_unpack(ic.data(), dc.data(), a->mvec, subspace, pending, first, last, free_, next, prev, h, c);
   return 0;
 }
 
@@ -2081,17 +2063,7 @@ int nka_hip_state_digest(nka_hip_t a, uint64_t *digest) {
   std::vector<int32_t> ic;
   std::vector<double> dc;
   if (int rc = fetch_state(a, ic, dc)) return rc;
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&h](const void *p, size_t nbytes) {
-    const unsigned char *b = static_cast<const unsigned char *>(p);
-    for (size_t i = 0; i < nbytes; i++) {
-      h ^= b[i];
-      h *= 1099511628211ull;
-    }
-  };
-  mix(ic.data(), ic.size() * sizeof(int32_t));
-  mix(dc.data(), dc.size() * sizeof(double));
-  *digest = h;
+  *digest = nka_host::snapshot_digest(ic, dc);
   return 0;
 }
 

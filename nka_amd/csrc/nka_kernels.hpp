@@ -36,363 +36,27 @@
 // F08 = /root/reference/src-F08/nka_type.F90.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "nka_kernels.hpp is written for gfx950 (CDNA4) only: v_permlane32_swap / v_permlane16_swap reductions, 160 KiB LDS, tile shapes measured on MI355X.  Build with --offload-arch=gfx950."
-#endif
+#include "nka_chain.hpp"
 
 namespace nka {
 
-constexpr int kBlock = 256;  // 4 wavefronts of 64
-constexpr int kWavesPerBlock = kBlock / 64;
-constexpr int kMaxGrid = 4096;  // upper bound on persistent grid size (partials buffer)
+// ONE includer only (nka_hip.hip): the non-template kernels below are plain definitions with external linkage, so a second
+// translation unit that included this header would define them again and the library would not link.
 
-// ---- indices into the small device-resident control arrays -----------------
-// int32 control block
-enum {
-  IC_SUBSPACE = 0,
-  IC_PENDING = 1,
-  IC_FIRST = 2,
-  IC_LAST = 3,
-  IC_FREE = 4,
-  IC_NEW = 5,          // slot that receives (f_in, f_out) in the current update
-  IC_NCOMB = 6,        // number of (slot, coefficient) pairs in the combine plan
-  IC_PLAN_PENDING = 7, // plan for PA of the NEXT update: `pending` at its entry
-  IC_PLAN_FIRST = 8,   //   slot holding the pending pair
-  IC_PLAN_NOLDER = 9,  //   number of list entries to dot against
-  IC_NRELAX = 10,      // count of s == 0 events (diagnostic)
-  IC_NORMED = 11,      // this update normalises the pending pair (pending && s != 0)
-  IC_HEADER = 16
-};
-// double control block
-enum { DC_VTOL = 0, DC_S = 1, DC_HEADER = 2 };
-// pointer control block (Ctl::pc)
-enum {
-  PC_FIRST_W = 0,  // w of the pending pair at the entry of the NEXT update (PA)
-  PC_NEW_W = 1,    // w, v buffers of the slot that receives (f_in, f_out) in the current update (PB)
-  PC_NEW_V = 2,
-  PC_OLD_W = 3,    // what an out-of-place update displaced from that slot: handed to the caller /
-  PC_OLD_V = 4,    //   kept as the library's next spare
-  PC_WGT = 5,      // the diagonal dot-product weights of nka_hip_set_dot_weights (read by the WGT = true passes only)
-  PC_HEADER = 8
-};
-
-constexpr int kMaxPerPass = 32;  // largest MAXL / MAXK instantiated
-
-constexpr int kStamps = 16;      // s_memtime stamps of the scalar step, written only when NKA_SOLVE_STAMPS is defined
-#ifdef NKA_SOLVE_STAMPS
-#define NKA_STAMP(ctl, i) do { if (threadIdx.x == 0) (ctl).stamps()[i] = (double)__builtin_amdgcn_s_memtime(); } while (0)
-#define NKA_STAMP0(ctl, i) do { if (blockIdx.x == 0 && threadIdx.x == 0) (ctl).stamps()[i] = (double)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define NKA_STAMP(ctl, i) do { } while (0)
-#define NKA_STAMP0(ctl, i) do { } while (0)
-#endif
-
-struct Ctl {
-  int32_t *ic;         // header, then next[M1+1], prev[M1+1], plan_slots[M1+pad], comb_slots[M1+pad]
-  double *dc;          // header, then h[(M1+1)^2], c[M1+1], comb_c[M1+pad], red[2+2*mvec]
-  int32_t mvec;
-  // LIST WORD: one 64-bit word in pinned host memory (nullptr: none) that block 0 of PB overwrites with
-  // (number of this update << kListWordLenBits | list length at its exit), see list_word_publish; `seq` = the
-  // number the host gave this update.  The host reads it WITHOUT synchronising to learn that dependence drops
-  // (F08:326-345) have made the list shorter than its own bookkeeping says (nka_hip.hip: list_bound_now).
-  unsigned long long *hw;
-  unsigned long long seq;
-  // ADDRESS CONTROL BLOCK.  The streaming passes take the ADDRESSES of the stored vectors from here, not slot numbers:
-  // wtab / vtab map slot -> buffer (at creation slot k -> (k-1)*stride of the two slot-major allocations; the out-of-place
-  // entry nka_hip_accel_update_swap exchanges entries with buffers of the caller), and the scalar kernels, which alone know
-  // the slots, resolve them when they write the plans.  Every entry is an OFFSET IN DOUBLES FROM Vecs::w (any buffer of the
-  // device, the caller's included, is some 64-bit offset from it): a pointer read from memory carries no address space and
-  // the compiler would reach it with FLAT loads -- one counter for LDS and memory, every wait a wait for everything (the
-  // first version of this block did: PB -13 %) -- while vs.w + offset is a global address like any kernel argument.
-  long long *pc;
-  __host__ __device__ long long *plan_w() const { return pc + PC_HEADER; }          // w of PA's older entries [m1p]
-  __host__ __device__ long long *comb_w() const { return plan_w() + m1p(); }        // w of PB's pairs [m1p]
-  __host__ __device__ long long *comb_v() const { return comb_w() + m1p(); }        // v of PB's pairs [m1p]
-  __host__ __device__ long long *wtab() const { return comb_v() + m1p(); }          // slot -> w buffer [m1+1], 1-based
-  __host__ __device__ long long *vtab() const { return wtab() + (m1() + 1); }       // slot -> v buffer [m1+1]
-  __host__ __device__ int pc_count() const { return PC_HEADER + 3 * m1p() + 2 * (m1() + 1); }
-  // plan_slots / comb_slots / comb_c are padded by one pass width: the unrolled
-  // kernels read (and ignore) entries up to the end of their last pass.
-  __host__ __device__ int m1() const { return mvec + 1; }
-  __host__ __device__ int m1p() const { return mvec + 1 + kMaxPerPass; }
-  __host__ __device__ int32_t *next() const { return ic + IC_HEADER; }
-  __host__ __device__ int32_t *prev() const { return next() + (m1() + 1); }
-  __host__ __device__ int32_t *plan_slots() const { return prev() + (m1() + 1); }
-  __host__ __device__ int32_t *comb_slots() const { return plan_slots() + m1p(); }
-  __host__ __device__ int ic_count() const { return IC_HEADER + 2 * (m1() + 1) + 2 * m1p(); }
-  __host__ __device__ double *h() const { return dc + DC_HEADER; }
-  __host__ __device__ double *c() const { return h() + (m1() + 1) * (m1() + 1); }
-  __host__ __device__ double *comb_c() const { return c() + (m1() + 1); }
-  __host__ __device__ double *red() const { return comb_c() + m1p(); }
-  __host__ __device__ int red_count() const { return 2 + 2 * mvec; }
-  __host__ __device__ double *stamps() const { return red() + red_count(); }   // kStamps cycle stamps (diagnostic builds)
-  __host__ __device__ int dc_count() const {
-    return DC_HEADER + (m1() + 1) * (m1() + 1) + (m1() + 1) + m1p() + red_count() + kStamps;
-  }
-};
-constexpr long long kNoBuffer = (long long)0x8000000000000000ull;      // "no buffer" among the offsets of Ctl::pc
-constexpr int kListWordLenBits = 20;        // mvec + 1 <= 2^17 + 1 (nka_hip_create)
-// PB, first thread of block 0, before its first tile: the store is posted while the pass streams, so it costs the
-// update nothing and has landed long before the pass ends (a caller that synchronises once per iteration -- every
-// solver reads a residual norm -- sees the word of the update it has just waited for).  ncomb + 1 = the combined
-// entries plus the new pending pair = the list length at the exit of this update.
-// Words 1..3 of the record belong to the out-of-place updates: the buffers the update displaced (PC_OLD_W / PC_OLD_V),
-// written BEFORE the number of that update, which is stored with release semantics; other updates leave them alone.
-__device__ __forceinline__ void list_word_publish(const Ctl &ctl, int ncomb, int swapping) {
-  if (ctl.hw != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-    if (swapping) {      // an out-of-place update: what it displaced (words 1, 2), then its number (word 3)
-      ctl.hw[1] = (unsigned long long)ctl.pc[PC_OLD_W];       // (offsets from Vecs::w, like everything in the block)
-      ctl.hw[2] = (unsigned long long)ctl.pc[PC_OLD_V];
-      __hip_atomic_store(ctl.hw + 3, ctl.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    __hip_atomic_store(ctl.hw, (ctl.seq << kListWordLenBits) | (unsigned long long)(ncomb + 1), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-// red[] layout (raw sums of PA, d = w1 - f NOT yet divided by s):
-//   [0] sum d^2, [1] <f,d>, [2+p] <d,w_older(p)>, [2+mvec+p] <f,w_older(p)>
-
-struct Vecs {
-  double *v, *w;       // slot k (1-based) at base + (k-1)*stride
-  int64_t stride;      // in doubles, multiple of 32 (256 B)
-  int64_t n;           // local vector length
-};
-
-// ---- PEER-TO-PEER EXCHANGE of the 2 + 2 mvec sums (round 5, opt-in: nka_hip_p2p_attach) -----------------------------------
-// The one exchange of a sharded update is an all-reduce of 336 bytes: latency, not bandwidth.  Through RCCL it is a kernel of
-// its own between the final sums and the scalar step.  Here every rank owns a MAILBOX in fine-grained device memory that its
-// peers map through hipIpc: the final-sums kernel of rank p writes each sum it forms straight into row p of EVERY rank's
-// mailbox (value, then -- released at system scope -- the number of the exchange as that entry's flag), and the scalar step of
-// rank q starts by waiting, entry by entry, for the N flags and adding the N rows IN RANK ORDER: the same additions in the same
-// order on every rank, hence the same bits -- no communication kernel, two kernel boundaries fewer.
-//   mailbox of one rank: val[2][N][cap] doubles, then flag[2][N][cap] 64-bit words; slot = exchange number & 1.  Two slots
-//   suffice: a rank can start exchange x+2 only after its scalar step of x+1 has seen EVERY peer's row of x+1, and a peer sends
-//   x+1 only after its own scalar step has consumed x (stream order).
-//   `xseq` (device memory of this rank): number of the NEXT exchange, advanced by whoever gathers; device-resident so that a
-//   captured update replays correctly.  Peers' mailboxes are reached as BYTE OFFSETS from this rank's own (`off[q]`): a pointer
-//   read from memory has no address space and would be accessed with FLAT instructions (see Ctl::pc).
-//   A wait is bounded (`timeout_ticks` of the 100 MHz wall clock): a peer that never sends makes the gather store NaNs, raise
-//   `status` and go on, so that the grid always drains; the host reports NKA_HIP_ECOMM at its next synchronising call.
-struct P2P {
-  char *base;                    // this rank's mailbox (nullptr: no peer-to-peer exchange)
-  const long long *off;          // [n] byte offset of rank q's mailbox from `base` (device memory)
-  unsigned long long *xseq;      // number of the next exchange (device memory, starts at 1)
-  int *status;                   // != 0: a wait timed out
-  int n, me, cap;
-  long long timeout_ticks;
-  __device__ double *val(int q, int slot, int src, int e) const {
-    return reinterpret_cast<double *>(base + off[q]) + ((size_t)slot * n + src) * cap + e;
-  }
-  __device__ unsigned long long *flag(int q, int slot, int src, int e) const {
-    return reinterpret_cast<unsigned long long *>(base + off[q]) + (size_t)2 * n * cap + ((size_t)slot * n + src) * cap + e;
-  }
-};
-__host__ __device__ inline size_t p2p_mailbox_bytes(int n, int cap) { return (size_t)2 * n * cap * 16; }
-
-// One lane sends entry e of exchange `seq` to rank q: the value, then the flag released at system scope.
-__device__ __forceinline__ void p2p_send_one(const P2P &x, int q, unsigned long long seq, int e, double v) {
-  const int slot = (int)(seq & 1ull);
-  __hip_atomic_store(x.val(q, slot, x.me, e), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(x.flag(q, slot, x.me, e), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// A whole wavefront sends entry e (lanes q = lane, lane + 64, ... < n each serve one peer); v is uniform.
-__device__ __forceinline__ void p2p_send_wave(const P2P &x, unsigned long long seq, int e, double v) {
-  for (int q = threadIdx.x & 63; q < x.n; q += 64) p2p_send_one(x, q, seq, e, v);
-}
-// Entry e of exchange `seq`, summed over the ranks in rank order (one lane).  Bounded wait.
-__device__ __forceinline__ double p2p_gather_one(const P2P &x, unsigned long long seq, int e) {
-  const int slot = (int)(seq & 1ull);
-  double acc = 0.0;
-  bool late = false;
-  const long long t0 = wall_clock64();
-  for (int r = 0; r < x.n; r++) {
-    unsigned long long *fl = x.flag(x.me, slot, r, e);
-    while (!late && __hip_atomic_load(fl, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) != seq) {
-      __builtin_amdgcn_s_sleep(2);
-      if (wall_clock64() - t0 > x.timeout_ticks) late = true;
-    }
-    const double v = __hip_atomic_load(x.val(x.me, slot, r, e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    acc = (r == 0) ? v : acc + v;
-  }
-  if (late) {
-    *x.status = 1;
-    acc = __builtin_nan("");
-  }
-  return acc;
-}
-// The gather at the head of the scalar step: red[e] <- sum over ranks, e < count, by the threads of ONE workgroup; then the
-// exchange number moves on.  (Each thread reads back only entries it wrote itself or after the barrier.)
-__device__ __forceinline__ void p2p_gather_block(const P2P &x, double *red, int count) {
-  const unsigned long long seq = *x.xseq;
-  for (int e = threadIdx.x; e < count; e += blockDim.x) red[e] = p2p_gather_one(x, seq, e);
-  __syncthreads();
-  if (threadIdx.x == 0) *x.xseq = seq + 1;
-}
-// The generic form (the hook behind nka_hip_allreduce_now, the self-test and the reference-order chain): one workgroup sends
-// its `count` values to every rank, then gathers.
-static __global__ __launch_bounds__(128) __attribute__((unused)) void k_p2p_allreduce(P2P x, double *buf, int count) {
+// The peer-to-peer exchange (P2P) in its generic form (the hook behind nka_hip_allreduce_now, the self-test and the
+// reference-order chain): one workgroup sends its `count` values to every rank, then gathers.
+__global__ __launch_bounds__(128) void k_p2p_allreduce(P2P x, double *buf, int count) {
   const unsigned long long seq = *x.xseq;
   for (int i = threadIdx.x; i < count * x.n; i += blockDim.x) p2p_send_one(x, i % x.n, seq, i / x.n, buf[i / x.n]);
   __syncthreads();
   p2p_gather_block(x, buf, count);
 }
 
-__device__ __forceinline__ double readlane_f64(double x, int src_lane_uniform) {
-  union { double d; int i[2]; } u;
-  u.d = x;
-  u.i[0] = __builtin_amdgcn_readlane(u.i[0], src_lane_uniform);
-  u.i[1] = __builtin_amdgcn_readlane(u.i[1], src_lane_uniform);
-  return u.d;
-}
-
-// ---- reductions ---------------------------------------------------------------
-// Sum over the wavefront, valid in LANE 0: the butterfly x += x[lane + off], off = 32, 16, 8, 4, 2, 1 -- the tree
-// __shfl_down builds, hence the same bits -- but through REGISTERS: gfx950's v_permlane32_swap / v_permlane16_swap
-// for the two steps that cross a row of 16 lanes, DPP row_shl for the four inside row 0 (after the step with
-// offset 16 only lanes 0..15 carry partial sums that reach lane 0).  __shfl_down is two ds_bpermute_b32 and an
-// LDS wait per step: the 42 sums of a PA block took 22 k cycles (~9.5 us of a 15 us launch at n = 1e5) that way.
-__device__ __forceinline__ double swap_sum32(double A, double B);
-__device__ __forceinline__ double swap_sum16(double A, double B);
-template <int N> __device__ __forceinline__ double row_shl_sum(double x);
-__device__ __forceinline__ double wave_sum(double x) {
-  x = swap_sum32(x, x);
-  x = swap_sum16(x, x);
-  x = row_shl_sum<8>(x);
-  x = row_shl_sum<4>(x);
-  x = row_shl_sum<2>(x);
-  return row_shl_sum<1>(x);
-}
-
-// The first two butterfly steps for TWO sums at once.  swap_sum32(A, B): lanes 0..31 get A[i] + A[i+32], lanes
-// 32..63 get B[i-32] + B[i]; swap_sum16(A, B), row by row of 16 lanes: (A.r0 + A.r1, B.r0 + B.r1, A.r2 + A.r3,
-// B.r2 + B.r3).  The same pairs the butterfly of wave_sum adds, parked in the half / row that the butterfly
-// leaves idle.
-__device__ __forceinline__ double swap_sum32(double A, double B) {
-  union U { double d; unsigned u[2]; } a, b;
-  a.d = A;
-  b.d = B;
-#pragma unroll
-  for (int w = 0; w < 2; w++) {
-    const auto r = __builtin_amdgcn_permlane32_swap(a.u[w], b.u[w], false, false);
-    a.u[w] = r[0];
-    b.u[w] = r[1];
-  }
-  return a.d + b.d;
-}
-__device__ __forceinline__ double swap_sum16(double A, double B) {
-  union U { double d; unsigned u[2]; } a, b;
-  a.d = A;
-  b.d = B;
-#pragma unroll
-  for (int w = 0; w < 2; w++) {
-    const auto r = __builtin_amdgcn_permlane16_swap(a.u[w], b.u[w], false, false);
-    a.u[w] = r[0];
-    b.u[w] = r[1];
-  }
-  return a.d + b.d;
-}
-// x[i] + x[i+N] inside every row of 16 lanes (lanes whose partner is outside the row keep x + x: never used)
-template <int N> __device__ __forceinline__ double row_shl_sum(double x) {
-  union U { double d; unsigned u[2]; } a, b;
-  a.d = x;
-  b.u[0] = __builtin_amdgcn_update_dpp(a.u[0], a.u[0], 0x100 + N, 0xf, 0xf, false);
-  b.u[1] = __builtin_amdgcn_update_dpp(a.u[1], a.u[1], 0x100 + N, 0xf, 0xf, false);
-  return a.d + b.d;
-}
-
-// Sum NACC per-thread accumulators over the block (fixed order: lanes by butterfly, then waves 0..3) and store
-// column a at partials[a*G + block].  Every sum is the tree of wave_sum -- the same bits -- but the NACC
-// butterflies share their steps: the step with offset 32 folds accumulators k and k + H1 into one register
-// (lower / upper half of the wavefront), the step with offset 16 folds registers k and k + H2 (even / odd rows),
-// the four steps inside a row then serve four accumulators each.  ~NACC/4 x 6 exchange-and-add groups instead of
-// NACC x 6 (42 sums of PA at m = 20: 9.9 k -> ~3 k cycles; with __shfl_down 22 k).
-template <int NACC>
-__device__ __forceinline__ void block_reduce_store(const double (&acc)[NACC], double *partials, int G) {
-  __shared__ double sm[kWavesPerBlock][NACC];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  constexpr int H1 = (NACC + 1) / 2, H2 = (H1 + 1) / 2;
-  double r1[H1], r2[H2];
-#pragma unroll
-  for (int k = 0; k < H1; k++) r1[k] = swap_sum32(acc[k], acc[k + H1 < NACC ? k + H1 : k]);
-#pragma unroll
-  for (int k = 0; k < H2; k++) r2[k] = swap_sum16(r1[k], r1[k + H2 < H1 ? k + H2 : k]);
-  const int row = lane >> 4;
-#pragma unroll
-  for (int k = 0; k < H2; k++) {
-    double x = r2[k];
-    x = row_shl_sum<8>(x);
-    x = row_shl_sum<4>(x);
-    x = row_shl_sum<2>(x);
-    x = row_shl_sum<1>(x);
-    // row 0: accumulator k; row 1: k + H2 (a register of the second half); rows 2, 3: the same + H1
-    const int reg = k + (row & 1) * H2;
-    const int a = reg + (row >> 1) * H1;
-    if ((lane & 15) == 0 && reg < H1 && a < NACC) sm[wv][a] = x;
-  }
-  __syncthreads();
-  for (int a = threadIdx.x; a < NACC; a += kBlock) {
-    double r = sm[0][a];
-#pragma unroll
-    for (int q = 1; q < kWavesPerBlock; q++) r += sm[q][a];
-    partials[(size_t)a * G + blockIdx.x] = r;
-  }
-}
-
-// ---- 8-B / 16-B per lane streaming accesses ---------------------------------------
-// Non-temporal (nt) loads and stores (nt stores: +2-3 % on the mixed pass against plain ones).
-typedef double d2 __attribute__((ext_vector_type(2)));
-template <int VEC> struct VecT;
-template <> struct VecT<1> { using type = double; };
-template <> struct VecT<2> { using type = d2; };
-
-template <int VEC> __device__ __forceinline__ typename VecT<VEC>::type ld(const double *p);
-template <> __device__ __forceinline__ double ld<1>(const double *p) { return __builtin_nontemporal_load(p); }
-template <> __device__ __forceinline__ d2 ld<2>(const double *p) {
-  return __builtin_nontemporal_load(reinterpret_cast<const d2 *>(p));
-}
-__device__ __forceinline__ void st(double *p, double x) { __builtin_nontemporal_store(x, p); }
-__device__ __forceinline__ void st(double *p, d2 x) { __builtin_nontemporal_store(x, reinterpret_cast<d2 *>(p)); }
-
-__device__ __forceinline__ double ex(double x, int) { return x; }
-__device__ __forceinline__ double ex(d2 x, int i) { return x[i]; }
-__device__ __forceinline__ void setc(double &x, int, double val) { x = val; }
-__device__ __forceinline__ void setc(d2 &x, int i, double val) { x[i] = val; }
-
 // ---- PA: every inner product of the update in one pure-read pass --------------------
 // MAXL stored vectors per pass; entries beyond the actual count re-read f (cache
 // hit) into accumulators that are discarded, which keeps every load of a tile
 // unconditional so that all MAXL+2 of them are in flight together.
-// acc: [0] sum d^2, [1] <f,d>, [2+j] <d,w_j>, [2+MAXL+j] <f,w_j>.
-// `normed` (round 5, NKA_HIP_SUMS_BLOCKED_ROUNDED): the norm is already known -- red[0] holds the GLOBAL sum d^2 of a pass of
-// its own (k_norm_diff) -- and the sums are formed on the ROUNDED w1' = fl(d/s) (bit 1 of `normed`: fl((1/s)*d), the
-// F08-vector flavour), the value PB stores: acc[1] = <f,w1'>, acc[2+j] = <w1',w_j> as the reference defines them (F08:286-290,
-// 371), in blocks and with fma.  The scalar step then takes them as they are (kSolvePrenorm).
-__device__ __forceinline__ double pa_operand(double d, int normed, double s, double rs) {
-  if (normed == 0) return d;
-  if (s == 0.0) return 0.0;                       // (the scalar step relaxes, F08:275: these sums are dead)
-  return (normed & 2) ? rs * d : d / s;
-}
-
-// DIAGONAL WEIGHTS (nka_hip_set_dot_weights): every product of the weighted passes takes fl(w_i * a_i) as its FIRST operand
-// and the unweighted value as its second, fma(fl(w a), b, acc); the order of the sums is the unweighted kernels'.  The
-// passes that form sums (k_norm_diff, k_dots, k_dots_win) take `bool WGT = false`: with false these helpers return `a` and
-// no weight is loaded -- the instructions of the plain kernels -- with true the weights (n doubles, 256-byte aligned, found
-// through Ctl::pc[PC_WGT] like every other buffer) stream beside f and w1 in the same 16-byte non-temporal loads.
-template <bool WGT, class V>
-__device__ __forceinline__ double wgt_first(const V &om, int q, double a) {
-  if constexpr (WGT) return ex(om, q) * a;
-  else return a;
-}
-template <bool WGT>
-__device__ __forceinline__ double wgt_at(const double *__restrict__ wgt, int64_t i, double a) {
-  if constexpr (WGT) return wgt[i] * a;
-  else return a;
-}
-
+// acc: [0] sum d^2, [1] <f,d>, [2+j] <d,w_j>, [2+MAXL+j] <f,w_j>.  (`normed`, WGT: pa_operand, wgt_first in nka_device.hpp)
 template <int MAXL, int VEC, bool WGT = false>
 __global__ __launch_bounds__(kBlock) void k_dots(Ctl ctl, Vecs vs, const double *__restrict__ f,
                                                  double *__restrict__ partials, int pass, int normed) {
@@ -465,8 +129,8 @@ __global__ __launch_bounds__(kBlock) void k_dots(Ctl ctl, Vecs vs, const double 
 // The norm pass of NKA_HIP_SUMS_BLOCKED_ROUNDED: sum d^2 with d = w1 - f (F08:266-267) over this rank's slice, two streams,
 // per-block partial sums in column 0 of `partials` (k_norm_fin adds them in a fixed order).  WGT: sum fl(w d)*d, three streams.
 template <bool WGT = false>
-static __global__ __launch_bounds__(kBlock) __attribute__((unused)) void k_norm_diff(Ctl ctl, Vecs vs, const double *__restrict__ f,
-                                                                                         double *__restrict__ partials) {
+__global__ __launch_bounds__(kBlock) void k_norm_diff(Ctl ctl, Vecs vs, const double *__restrict__ f,
+                                                      double *__restrict__ partials) {
   const double *wgt = WGT ? vs.w + ctl.pc[PC_WGT] : nullptr;
   const int G = gridDim.x;
   const double *w1 = vs.w + ctl.pc[PC_FIRST_W];
@@ -528,7 +192,7 @@ static __global__ __launch_bounds__(kBlock) __attribute__((unused)) void k_norm_
   block_reduce_store<1>(one, partials, G);
 }
 // ... and its final sum, one wavefront, into red[0] (zero without a pending pair: nothing stale reaches the exchange)
-static __global__ __launch_bounds__(64) __attribute__((unused)) void k_norm_fin(Ctl ctl, const double *__restrict__ partials, int G) {
+__global__ __launch_bounds__(64) void k_norm_fin(Ctl ctl, const double *__restrict__ partials, int G) {
   double r = 0.0;
   for (int b = threadIdx.x; b < G; b += 64) r += partials[b];
   r = wave_sum(r);
@@ -649,8 +313,8 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
 
 // Set-time check of a weight vector (nka_hip_set_dot_weights): out[0] += entries that are not finite or below zero,
 // out[1] = min over their indices (starts at ~0).  Grid-stride; runs once per set, not in an update.
-static __global__ __launch_bounds__(kBlock) __attribute__((unused)) void k_check_weights(const double *__restrict__ w, int64_t n,
-                                                                                             unsigned long long *out) {
+__global__ __launch_bounds__(kBlock) void k_check_weights(const double *__restrict__ w, int64_t n,
+                                                          unsigned long long *out) {
   unsigned long long bad = 0, first = ~0ull;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
     const double x = w[i];
@@ -735,78 +399,14 @@ __global__ __launch_bounds__(kFinThreads) void k_finalize_dots(Ctl ctl, const do
 // MI355X (tools/sum_order_cost.py, profiles/r04/sum_order_cost.txt): on par with the blocked PA and its final sums up to
 // n = 64 (the default there), +12-18 us per update at n = 512, 40 ms per update at n = 1e6.  Single rank only: the Gram row needs the GLOBAL norm
 // first, i.e. a second exchange (nka_hip_set_sum_order).
-constexpr int kOrdThreads = 256;
-constexpr int kOrdChunkMax = 512;
-constexpr int kOrdMaxMvec = 250;                     // two sums per thread and eight elements per LDS row at least
-constexpr int kOrdAutoMax = 64;                      // NKA_HIP_SUMS_AUTO sums in the reference's order up to this length (where it costs nothing)
-constexpr int kOrdLdsDoubles = 16000;                // 125 KiB of dynamic LDS (one workgroup; 160 KiB per CU on gfx950) ...
-constexpr int kOrdLdsPad = 16;                       // ... plus what ord_sum may read past the last row
-__host__ __device__ inline int ord_chunk(int rows) {
-  int c = kOrdLdsDoubles / (rows < 1 ? 1 : rows) - 1;
-  return c > kOrdChunkMax ? kOrdChunkMax : (c < 8 ? 8 : c);
-}
-__host__ __device__ inline size_t ord_lds_bytes(int rows) {
-  return sizeof(double) * ((size_t)rows * (ord_chunk(rows) + 1) + kOrdLdsPad);
-}
-// a + x[0]*y[0] + x[1]*y[1] + ... in THAT order, one rounding per product and per addition; the LDS reads of the next eight
-// elements are in flight while the eight additions of this batch wait for one another (rows are padded: reading up to
-// seven elements past `len` stays inside the allocation; those products are not added).
-__device__ __forceinline__ double ord_sum(double a, const double *x, const double *y, int len) {
-#pragma clang fp contract(off)      // products and additions stay separate roundings whatever the build's flags
-  double xb[8], yb[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) { xb[u] = x[u]; yb[u] = y[u]; }
-  for (int i0 = 0; i0 < len; i0 += 8) {
-    double xn[8], yn[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) { xn[u] = x[i0 + 8 + u]; yn[u] = y[i0 + 8 + u]; }
-    if (i0 + 8 <= len) {
-#pragma unroll
-      for (int u = 0; u < 8; u++) a = a + xb[u] * yb[u];
-    } else {
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-        if (i0 + u < len) a = a + xb[u] * yb[u];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) { xb[u] = xn[u]; yb[u] = yn[u]; }
-  }
-  return a;
-}
-// Chunk [c0, c0+len) of the older w's into LDS rows 2..: eight rows at a time, two elements of each row per thread (a chunk
-// has at most 512 elements): sixteen loads in flight per thread, the row addresses uniform (scalar loads of the plan).
-__device__ __forceinline__ void ord_load_older(double *sh, int S, const Vecs &vs, const long long *pw, int nolder, int64_t c0, int len) {
-  const int i0 = threadIdx.x, i1 = threadIdx.x + kOrdThreads;
-  static_assert(kOrdChunkMax <= 2 * kOrdThreads, "two elements of a row per thread cover a chunk");
-  for (int p0 = 0; p0 < nolder; p0 += 8) {
-    double v0[8], v1[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int p = p0 + u < nolder ? p0 + u : nolder - 1;      // (the last group repeats a row: the loads stay unconditional)
-      const double *wp = vs.w + pw[p] + c0;
-      v0[u] = i0 < len ? wp[i0] : 0.0;
-      v1[u] = i1 < len ? wp[i1] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      if (p0 + u >= nolder) continue;
-      double *dst = sh + (size_t)(2 + p0 + u) * S;
-      if (i0 < len) dst[i0] = v0[u];
-      if (i1 < len) dst[i1] = v1[u];
-    }
-  }
-}
-
 // SHARDED (round 5): the reference's sum over the GLOBAL vector is one chain of additions through the slices in rank
 // order, so rank r CONTINUES the running sums of rank r-1: `carry` != 0 starts every accumulator from the value red[]
 // holds (the prefix over the ranks before this one) instead of 0, and the update is made in two kinds of rounds (nka_hip.hip,
 // ordered_chain): phase 1 = the norm only (red[0]); phase 2 = with s from the GLOBAL red[0], the sums on the rounded w1'
 // and on f (red[1..]).  phase 0 = both in one launch, the single-rank form described above.
 enum { kOrdAll = 0, kOrdNorm = 1, kOrdRows = 2 };
-static __global__ __launch_bounds__(kOrdThreads) __attribute__((unused)) void k_dots_ordered(Ctl ctl, Vecs vs,
-                                                                                              const double *__restrict__ f,
-                                                                                              int rcp, int chunk, int phase,
-                                                                                              int carry) {
+__global__ __launch_bounds__(kOrdThreads) void k_dots_ordered(Ctl ctl, Vecs vs, const double *__restrict__ f, int rcp,
+                                                              int chunk, int phase, int carry) {
   extern __shared__ double ord_sh[];
   __shared__ double sum_dd;
   const int t = threadIdx.x;
@@ -918,498 +518,9 @@ static __global__ __launch_bounds__(kOrdThreads) __attribute__((unused)) void k_
     if (dst[q] >= 0 && (normed || !on_w1)) red[dst[q]] = acc[q];
 }
 
-// ---- The same sums, ONE WORKGROUP PER SUM (round 5, long vectors) ----------------------------------
-// k_dots_ordered walks every sum on one compute unit and waits for each chunk's loads before it adds: 40 ns per element.
-// A sequential sum is a chain of n dependent roundings whatever is done, but (1) the 2 + 2L sums of an update are
-// independent chains once the norm is known, (2) the products are not part of any chain and (3) -- see chain_block_summary --
-// while the running sum stays inside one binade its roundings are roundings to a FIXED grid, which is integer
-// arithmetic and therefore associative.  Here sum c has workgroup c to itself: its eight wavefronts load the next group of
-// 8 192 elements, round the products into LDS and summarise one block of 1 024 each, and wavefront 0 takes the group
-// through the chain.  Two launches per update: set kChainNorm = the norm (block 0) and, with `with_f`, the sums on f alone (blocks
-// 1..ub); set kChainRows = with s from red[0], <f,w1'> (block 0), the Gram row on the ROUNDED w1' (blocks 1..ub) and,
-// with `with_f`, the sums on f alone (blocks ub+1..2ub) -- the sharded rounds of ordered_chain take the second form (their
-// norm rounds hold red[0] only).  EVERY chain starts from the value red[] holds: the host zeroes red[] where no prefix of
-// other ranks is to be continued (0 + p == p: the same bits as starting at 0).
-constexpr int kChainWaves = 8;
-constexpr int kChainThreads = 64 * kChainWaves;
-constexpr int kChainLaneElems = 16;                               // consecutive elements of a block per lane
-constexpr int kChainBlock = 64 * kChainLaneElems;                 // elements per step of the chain
-constexpr int kChainGroupBlocks = kChainWaves;                    // one block of a group per wavefront
-constexpr int kChainGroup = kChainGroupBlocks * kChainBlock;      // elements whose products are in LDS at a time
-constexpr int kChainPerThread = kChainGroup / kChainThreads;
-constexpr int kChainRow = 2 * 64 + 4;                             // doubles between the PAIR rows of a block in LDS: row k holds
-                                                                  // elements 2k, 2k+1 of every lane, lane after lane -- the
-                                                                  // lanes of a wavefront read 16 bytes each, side by side
-constexpr int kChainBlockLds = (kChainLaneElems / 2) * kChainRow;
-constexpr int kChainGroupLds = kChainGroupBlocks * kChainBlockLds;
-constexpr size_t kChainLdsBytes = sizeof(double) * kChainGroupLds;   // (dynamic: beyond the 64 KiB of static LDS)
-enum { kChainNorm = 0, kChainRows = 1, kChainProbe = 2 };   // (probe: <f, probe> from red[2 + mvec], diagnostic entry)
-enum { kChainKindNorm = 0, kChainKindFW1 = 1, kChainKindW1W = 2, kChainKindFW = 3 };
-// where element i of a group lies in LDS
-__device__ __forceinline__ int chain_idx(int i) {
-  const int blk = i / kChainBlock, ib = i % kChainBlock;
-  const int lane = ib / kChainLaneElems, j = ib % kChainLaneElems;
-  return blk * kChainBlockLds + (j / 2) * kChainRow + 2 * lane + (j & 1);
-}
-// the 16 products of lane `lane` of a block, in order
-__device__ __forceinline__ void chain_lane_read(double (&p)[kChainLaneElems], const double *blk, int lane) {
-  using V2 = typename VecT<2>::type;
-#pragma unroll
-  for (int k = 0; k < kChainLaneElems / 2; k++) {
-    const V2 v = *reinterpret_cast<const V2 *>(blk + k * kChainRow + 2 * lane);
-    p[2 * k] = v.x;
-    p[2 * k + 1] = v.y;
-  }
-}
-
-// a + p[0] + p[1] + ... + p[len-1] in THAT order, one rounding per addition: the chain as it stands (every lane does the
-// same additions on the same LDS words: no divergence, the sum stays wave-uniform).  One lane's worth (16 products) per
-// step, read while the additions of the step before wait for one another, two steps per trip (no register copies): the
-// loop is the chain of dependent v_add_f64 and little else (2.3 ns each, tools/micro/dep_add.hip).
-__device__ __forceinline__ double chain_block_serial(double a, const double *blk, int len, int g = 0) {   // (from lane g on)
-#pragma clang fp contract(off)
-  const int ng = len / kChainLaneElems;                 // whole lanes
-  if (g < ng) {
-    double A[kChainLaneElems], B[kChainLaneElems];
-    chain_lane_read(A, blk, g);
-    for (; g + 2 <= ng; g += 2) {
-      chain_lane_read(B, blk, g + 1);
-      __builtin_amdgcn_sched_barrier(0);                 // (the reads of the NEXT lane go out before this lane's additions)
-#pragma unroll
-      for (int j = 0; j < kChainLaneElems; j++) a = a + A[j];
-      __builtin_amdgcn_sched_barrier(0);
-      chain_lane_read(A, blk, g + 3 <= ng ? g + 2 : g);   // (the last trip re-reads: the loads stay unconditional)
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < kChainLaneElems; j++) a = a + B[j];
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (g < ng) {                                        // (A holds lane g whenever a whole lane remains)
-#pragma unroll
-      for (int j = 0; j < kChainLaneElems; j++) a = a + A[j];
-      g++;
-    }
-  }
-  for (int i = g * kChainLaneElems; i < len; i++) a = a + blk[chain_idx(i)];
-  return a;
-}
-
-// reductions and one scan over the 64 lanes through DPP (row shifts, then the row broadcasts of gfx9)
-template <int CTRL, int RM> __device__ __forceinline__ float dpp_f32(float x, float old) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), CTRL, RM, 0xf, false));
-}
-template <int CTRL, int RM> __device__ __forceinline__ int dpp_i32(int x, int old) {
-  return __builtin_amdgcn_update_dpp(old, x, CTRL, RM, 0xf, false);
-}
-template <int CTRL, int RM> __device__ __forceinline__ double dpp_f64(double x, double old) {
-  union { double d; int u[2]; } a, o, r;
-  a.d = x; o.d = old;
-  r.u[0] = __builtin_amdgcn_update_dpp(o.u[0], a.u[0], CTRL, RM, 0xf, false);
-  r.u[1] = __builtin_amdgcn_update_dpp(o.u[1], a.u[1], CTRL, RM, 0xf, false);
-  return r.d;
-}
-// lane l: the operation over lanes 0..l  (OP 0: +, 1: min, 2: max; `idn` the operation's identity: what lanes without a
-// source take)
-#define NKA_WAVE_SCAN(T, DPP)                                                                        \
-  x = op(x, DPP<0x111, 0xf>(x, idn)); x = op(x, DPP<0x112, 0xf>(x, idn)); x = op(x, DPP<0x114, 0xf>(x, idn)); \
-  x = op(x, DPP<0x118, 0xf>(x, idn)); x = op(x, DPP<0x142, 0xa>(x, idn)); x = op(x, DPP<0x143, 0xc>(x, idn)); \
-  return x;
-template <int OP> __device__ __forceinline__ float wave_scan_f32(float x, const float idn) {
-  auto op = [](float a, float b) { return OP == 0 ? a + b : OP == 1 ? fminf(a, b) : fmaxf(a, b); };
-  NKA_WAVE_SCAN(float, dpp_f32)
-}
-__device__ __forceinline__ int wave_scan_add_i32(int x) {
-  auto op = [](int a, int b) { return a + b; };
-  const int idn = 0;
-  NKA_WAVE_SCAN(int, dpp_i32)
-}
-__device__ __forceinline__ double wave_scan_add_f64(double x) {
-  auto op = [](double a, double b) { return a + b; };
-  const double idn = 0.0;
-  NKA_WAVE_SCAN(double, dpp_f64)
-}
-#undef NKA_WAVE_SCAN
-
-// One step of a chain over a FULL block of products without walking it element after element.
-// While  2^e <= |a| < 2^(e+1)  every representable neighbour of the running sum is a multiple of u = 2^(e-52), so
-// fl(a + p) = u * (S + R(p/u)) with S = |a|/u an integer in [2^52, 2^53) and R the rounding of t = p/u to an integer,
-// halves going to whichever neighbour makes S + R EVEN (round-to-nearest-even acts on the sum's significand).  The
-// additions of integers are exact and associative; the only thing a step inherits from its predecessors is the PARITY of
-// S, and only a halfway case reads it (after which the sum is even whatever it was).  So each lane takes 16 consecutive
-// products: r = rne(t) (t + 1.5*2^52 - 1.5*2^52), the halfway flag |t - r| == 0.5, the plain sum of the r's, its own
-// parity map and the corrections (+-1) a halfway case owes under either incoming parity; ballots carry the parity from
-// lane to lane and one prefix sum places every lane's excursion.  That SUMMARY of a block depends on the running sum only
-// through its sign and exponent (chain_block_summary), so the wavefronts of the workgroup take one block each under the
-// exponent the group starts with; wavefront 0 then walks the summaries (chain_block_apply): a block is accepted iff it
-// was summarised under the sum's present sign and exponent, every prefix provably stays inside the binade and every
-// lane's sum of |r| < 2^51 (r exact, lane sums exact; NaN and Inf fail the comparison).  The prefix bounds are kept in SINGLE precision,
-// rounded to nearest: they are off by < 2^33 units, and the acceptance window leaves 2^34 units (2^-18 of the binade)
-// at either end -- which also covers the corrections (<= 1024) and the one inexact case (sums beyond 2^53 are only ever
-// formed in blocks that leave the window by far more than their error).  Otherwise the block is summarised again under
-// the present exponent or, failing that, walked (chain_block_serial).  Same bits as the walk by construction;
-// tests/test_chain_sums_gpu.py holds the two to each other and to numpy's sequential accumulate on adversarial inputs
-// (halfway cases under both parities, binade crossings, cancellation, zeros, subnormals, overflow, NaN).
-// what one lane makes of its 16 consecutive products under the scale of the sum's binade
-struct ChainLane {
-  double base, absl;         // sum of the r's; sum of their magnitudes (< 2^51: every r and every partial sum exact)
-  double pmin, pmax;         // least / greatest prefix sum inside the lane, the empty one (0) included
-  int par, differ;           // parity of the lane's sum if it starts even; whether starting odd still flips it (no halfway case met)
-  int adj0, adj1;            // corrections the halfway cases owe if the lane starts even / odd
-};
-__device__ __forceinline__ ChainLane chain_lane_pass(const double (&pl)[kChainLaneElems], double scale) {
-#pragma clang fp contract(off)
-  constexpr double M = 6755399441055744.0;                         // 1.5 * 2^52
-  ChainLane ln;
-  ln.base = ln.absl = ln.pmin = ln.pmax = 0.0;
-  ln.differ = 1; ln.adj0 = ln.adj1 = 0;
-  int parw = 0;
-  bool halfway = false;
-#pragma unroll
-  for (int j = 0; j < kChainLaneElems; j++) {
-    const double t = pl[j] * scale;                                // exact (a power of two), |t| tiny if it underflows
-    const double tm = t + M;                                       // rounds t to an integer, halves to even
-    const double r = tm - M;
-    const double diff = t - r;                                     // exact
-    halfway |= fabs(diff) == 0.5;
-    parw ^= __double2loint(tm);
-    ln.base = ln.base + r;
-    ln.absl = ln.absl + fabs(r);
-    ln.pmin = fmin(ln.pmin, ln.base);
-    ln.pmax = fmax(ln.pmax, ln.base);
-  }
-  if (__any(halfway)) {                                            // the parity bookkeeping in its own pass
-    parw = 0;
-#pragma unroll
-    for (int j = 0; j < kChainLaneElems; j++) {
-      const double t = pl[j] * scale;
-      const double tm = t + M;
-      const double diff = t - (tm - M);
-      if (fabs(diff) == 0.5) {                                     // halfway: r is the EVEN neighbour of t, r + 2 diff the odd one
-        const int tau = diff > 0.0 ? 1 : -1;
-        // r being even, S + r has the parity of S: an odd S takes the other neighbour, and the sum is even either way
-        if (parw & 1) ln.adj0 += tau;
-        if ((parw ^ ln.differ) & 1) ln.adj1 += tau;
-        parw = 0; ln.differ = 0;
-      } else {
-        parw ^= __double2loint(tm);
-      }
-    }
-  }
-  ln.par = parw & 1;
-  return ln;
-}
-// the parity each lane starts from if the block starts EVEN (q), and whether a block starting odd flips it (no halfway
-// case in any lane before this one)
-__device__ __forceinline__ void chain_lane_parity(const ChainLane &ln, int lane, int &q, bool &flips) {
-  const unsigned long long T = __ballot(ln.differ == 0), A = __ballot(ln.par);
-  const unsigned long long lt = (1ull << lane) - 1ull, Tl = T & lt;
-  flips = Tl == 0;
-  if (flips) q = __popcll(A & lt) & 1;
-  else {
-    const int h = 63 - __clzll(Tl);                                // the last lane before this one that met a halfway case
-    q = __popcll(A & lt & ~((1ull << h) - 1ull)) & 1;
-  }
-}
-
-struct ChainSummary {
-  double total;              // sum of the r's
-  float gmin, gmax;          // least / greatest prefix bound
-  int adj;                   // corrections if S starts even (low half) / odd (high half), each biased by kChainAdjBias
-  int hi;                    // sign and exponent word the summary assumed; 0: none, or a product out of range
-};
-constexpr int kChainAdjBias = 64 * kChainLaneElems;
-__device__ __forceinline__ bool chain_scalable(double a) {
-  const int ef = (__double2hiint(a) >> 20) & 0x7ff;
-  return ef >= 1023 - 900 && ef <= 1023 + 900;                    // not zero, subnormal, Inf, NaN; scale factors in range
-}
-__device__ __forceinline__ ChainSummary chain_block_summary(double a, const double *blk) {
-#pragma clang fp contract(off)
-  ChainSummary sm;
-  sm.hi = 0; sm.total = 0.0; sm.gmin = sm.gmax = 0.f; sm.adj = 0;
-  if (!chain_scalable(a)) return sm;
-  const int lane = threadIdx.x & 63;
-  const int hi = __double2hiint(a);
-  const int e = ((hi >> 20) & 0x7ff) - 1023;
-  const double scale = __hiloint2double((hi & (int)0x80000000) | ((1023 + 52 - e) << 20), 0);    // +-2^(52-e): S > 0
-  double pl[kChainLaneElems];
-  chain_lane_read(pl, blk, lane);
-  const ChainLane ln = chain_lane_pass(pl, scale);
-  const bool bad = !(ln.absl < 0x1p51);                            // some |t| >= 2^51 / Inf / NaN: r = rne(t) and the lane's sums are exact below that
-  // where the lane's excursion lies: the prefix before it + its own least / greatest prefix, in single precision
-  const float basef = (float)ln.base;
-  const float exclf = wave_scan_f32<0>(basef, 0.f) - basef;
-  const float lo = wave_scan_f32<1>(exclf + (float)ln.pmin, __builtin_inff());
-  const float up = wave_scan_f32<2>(exclf + (float)ln.pmax, -__builtin_inff());
-  int q;
-  bool flips;
-  chain_lane_parity(ln, lane, q, flips);
-  const int qo = flips ? q ^ 1 : q;
-  const int packed = ((q ? ln.adj1 : ln.adj0) + kChainLaneElems) | (((qo ? ln.adj1 : ln.adj0) + kChainLaneElems) << 16);
-  const int adjs = wave_scan_add_i32(packed);
-  const double tot = wave_scan_add_f64(ln.base);
-  sm.total = readlane_f64(tot, 63);
-  sm.gmin = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lo), 63));
-  sm.gmax = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(up), 63));
-  sm.adj = __builtin_amdgcn_readlane(adjs, 63);
-  sm.hi = __any(bad) ? 0 : (hi & (int)0xfff00000);
-  return sm;
-}
-// The running sum through summarised blocks.  S = |a| / u as long as blocks are accepted (ChainRun); leaving that form
-// gives the double back.
-struct ChainRun {
-  double S, unscale;
-  int hi;                    // sign and exponent word of the sum S stands for; 0: none (a is authoritative)
-};
-__device__ __forceinline__ void chain_run_enter(ChainRun &run, double a) {
-  run.hi = 0;
-  if (!chain_scalable(a)) return;
-  const int hi = __double2hiint(a);
-  const int e = ((hi >> 20) & 0x7ff) - 1023;
-  const double scale = __hiloint2double((hi & (int)0x80000000) | ((1023 + 52 - e) << 20), 0);
-  run.unscale = __hiloint2double((hi & (int)0x80000000) | ((1023 - 52 + e) << 20), 0);
-  run.S = a * scale;                                               // exact, an integer in [2^52, 2^53)
-  run.hi = hi & (int)0xfff00000;
-}
-__device__ __forceinline__ bool chain_block_apply(ChainRun &run, const ChainSummary &sm) {
-#pragma clang fp contract(off)
-  if (sm.hi == 0 || run.hi != sm.hi) return false;
-  constexpr double kEdge = 0x1p34;
-  if (!(run.S + (double)sm.gmin >= 0x1p52 + kEdge) || !(run.S + (double)sm.gmax <= 0x1p53 - kEdge)) return false;
-  const int odd = __double2loint(run.S) & 1;                       // the parity of S: the last bit of the significand
-  const int adj = ((odd ? sm.adj >> 16 : sm.adj) & 0xffff) - kChainAdjBias;
-  run.S = run.S + (sm.total + (double)adj);
-  return true;
-}
-
-// The loop of one sum: `load(g0)` brings the operands of the group that starts at element g0 into the caller's registers
-// (wavefront w: block w of the group), `store()` rounds their products into the wavefront's block of `prod`.  Returns the
-// sum (valid in thread 0).  The whole workgroup calls it.
-struct ChainStamps {
-#ifdef NKA_CHAIN_STAMPS
-  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // 10 ns ticks of wavefront 0: load issue, summary, wait, apply, wait, store
-  unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // blocks: in a run / on their own / summarised again / walked
-#endif
-};
-template <class Load, class Store>
-__device__ __forceinline__ double chain_drive(double a, int64_t n, double *prod, ChainSummary *summ, double *sh_a_p, int walk,
-                                              ChainStamps &stamps, Load load, Store store) {
-#pragma clang fp contract(off)
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-  double *myblk = prod + wave * kChainBlockLds;
-  if (t == 0) *sh_a_p = a;
-  if (n > 0) { load(0); store(); }
-  __syncthreads();
-#ifdef NKA_CHAIN_STAMPS
-  unsigned long long tk = wall_clock64(), tn;
-#define NKA_CHAIN_STAMP(i) tn = wall_clock64(); stamps.st[i] += tn - tk; tk = tn;
-#define NKA_CHAIN_COUNT(i, v) stamps.cnt[i] += (v);
-#else
-#define NKA_CHAIN_STAMP(i)
-#define NKA_CHAIN_COUNT(i, v)
-#endif
-  for (int64_t g0 = 0; g0 < n; g0 += kChainGroup) {
-    const bool more = g0 + kChainGroup < n;
-    if (more) load(g0 + kChainGroup);                  // in flight while this group goes through the chain
-    NKA_CHAIN_STAMP(0)
-    const int glen = (int)(n - g0 < kChainGroup ? n - g0 : kChainGroup);
-    const int nfull = glen / kChainBlock, nblk = (glen + kChainBlock - 1) / kChainBlock;
-    // every wavefront summarises its block under the sign and exponent the group starts with ...
-    const double a0 = *sh_a_p;
-    if (wave < nfull && !walk) {
-      const ChainSummary sm = chain_block_summary(a0, myblk);
-      if (lane == 0) summ[wave] = sm;
-    }
-    NKA_CHAIN_STAMP(1)
-    __syncthreads();
-    NKA_CHAIN_STAMP(2)
-    // ... and wavefront 0 takes the running sum through them: lane k holds the summary of block k
-    if (wave == 0) {
-      a = a0;
-      ChainRun run;
-      chain_run_enter(run, a);
-      ChainSummary mine = summ[lane < kChainGroupBlocks ? lane : 0];
-      int k = 0;
-      while (k < nblk) {
-        if (run.hi != 0 && !walk && k < nfull) {
-          // every block from k on that applies whatever the parity of the sum: their totals as one prefix sum, each
-          // checked against the sum it would start from; the longest run of acceptable blocks goes in at once
-          const bool cand = lane >= k && lane < nfull;
-          const int ae = (mine.adj & 0xffff) - kChainAdjBias, ao = ((mine.adj >> 16) & 0xffff) - kChainAdjBias;
-          const bool usable = cand && mine.hi == run.hi;
-          // the parity each block starts from, if every block before it goes in: block i flips it by the parity of its
-          // total plus the correction it takes under the parity it meets (a short scalar chain over two bit masks)
-          const int tpar = __double2loint(fabs(mine.total) + 0x1p52) & 1;     // (|total| < 2^52 in any block that goes in)
-          const unsigned pe = (unsigned)__ballot(usable && ((tpar ^ ae) & 1)), po = (unsigned)__ballot(usable && ((tpar ^ ao) & 1));
-          unsigned odd = 0;
-          {
-            unsigned p = (unsigned)__builtin_amdgcn_readfirstlane(__double2loint(run.S)) & 1u;   // (scalar: the chain runs on the SALU)
-            for (int i = k; i < nfull; i++) {
-              odd |= p << i;
-              p ^= ((p ? po : pe) >> i) & 1u;
-            }
-          }
-          const double tk_ = usable ? mine.total + (double)(((odd >> lane) & 1u) ? ao : ae) : 0.0;
-          double incl = tk_;
-          incl = incl + dpp_f64<0x111, 0xf>(incl, 0.0);
-          incl = incl + dpp_f64<0x112, 0xf>(incl, 0.0);
-          incl = incl + dpp_f64<0x114, 0xf>(incl, 0.0);
-          const double Sk = run.S + (incl - tk_);
-          constexpr double kEdge = 0x1p34;
-          const bool ok = usable && (Sk + (double)mine.gmin >= 0x1p52 + kEdge) && (Sk + (double)mine.gmax <= 0x1p53 - kEdge);
-          const unsigned long long need = ((1ull << nfull) - 1ull) & ~((1ull << k) - 1ull);
-          const unsigned long long failm = need & ~__ballot(ok);
-          const int F = failm ? __ffsll((long long)failm) - 1 : nfull;
-          if (F > k) {
-            run.S = run.S + readlane_f64(incl, F - 1);
-            NKA_CHAIN_COUNT(0, F - k)
-            k = F;
-            continue;
-          }
-        }
-        // block k on its own: under the parity of the sum, or summarised again under its present exponent, or walked
-        const double *bk = prod + k * kChainBlockLds;
-        const int len = glen - k * kChainBlock < kChainBlock ? glen - k * kChainBlock : kChainBlock;
-        bool done = false;
-        if (len == kChainBlock && !walk) {
-          ChainSummary sm = summ[k];
-          done = chain_block_apply(run, sm);
-          if (done) { NKA_CHAIN_COUNT(1, 1) }
-          if (!done && run.hi != 0 && run.hi != sm.hi) {           // another binade by now: summarise under the present one
-            sm = chain_block_summary(run.S * run.unscale, bk);
-            done = chain_block_apply(run, sm);
-            if (done) { NKA_CHAIN_COUNT(2, 1) }
-          }
-        }
-        if (!done) {
-          if (run.hi != 0) a = run.S * run.unscale;
-          if (len == kChainBlock && !walk) { NKA_CHAIN_COUNT(3, 1) }
-          // (walked whole: accepting its first lanes and taking the rest again under the next exponent was measured -- a
-          //  sum that meets an end of its binade hovers there, a round costs what walking 14 lanes costs and gained 5: a loss)
-          a = chain_block_serial(a, bk, len);
-          chain_run_enter(run, a);
-        }
-        k++;
-      }
-      if (run.hi != 0) a = run.S * run.unscale;
-      if (t == 0) *sh_a_p = a;
-    }
-    NKA_CHAIN_STAMP(3)
-    __syncthreads();
-    NKA_CHAIN_STAMP(4)
-    if (more) store();                                 // (each wavefront into its own block, which it alone summarises)
-    NKA_CHAIN_STAMP(5)
-  }
-  return a;
-#undef NKA_CHAIN_STAMP
-#undef NKA_CHAIN_COUNT
-}
-
-// One sum of an update as the chain kernels see it: which vectors, which rounding of their product, where the sum goes.
-struct ChainSum {
-  int kind, dst;             // kChainKind...; index into red[].  kind < 0: this sum does not exist in this update
-  const double *f, *w1, *wk; // f; the pending w (d = w1 - f); the older w of the sum (kinds W1W, FW)
-  double s, rs;              // the norm of d and its reciprocal (kinds FW1, W1W)
-  int rcp;                   // w1' = (1/s) * d (vector flavour) instead of d / s
-  int64_t n;
-  bool vec16;                // every base address allows 16-byte loads
-};
-// sum number b of a launch: set kChainNorm = the norm (b = 0) and, with `with_f`, the sums on f alone (b = 1..ub);
-// set kChainRows = <f,w1'> (b = 0), the Gram row on the rounded w1' (b = 1..ub) and, with `with_f`, the sums on f alone
-// (b = ub+1..2ub), s from red[0]; set kChainProbe = <f, probe> into red[2 + mvec] (diagnostic entry)
-__device__ __forceinline__ ChainSum chain_decode(const Ctl &ctl, const Vecs &vs, const double *f, int rcp, int set, int with_f,
-                                                 int ub, int b, const double *probe) {
-  ChainSum cs;
-  const int pending = ctl.ic[IC_PLAN_PENDING];
-  const int nolder = ctl.ic[IC_PLAN_NOLDER];
-  const int mvec = ctl.mvec;
-  const long long *pw = ctl.plan_w();
-  cs.kind = -1; cs.dst = 0;
-  cs.f = f; cs.w1 = pending ? vs.w + ctl.pc[PC_FIRST_W] : f; cs.wk = f;
-  cs.s = 0.0; cs.rcp = rcp; cs.n = vs.n;
-  if (set == kChainProbe) {
-    cs.kind = kChainKindFW; cs.dst = 2 + mvec; cs.wk = probe;
-  } else if (set == kChainNorm) {
-    if (b == 0) {
-      if (pending) { cs.kind = kChainKindNorm; cs.dst = 0; }
-    } else {
-      const int p = b - 1;
-      if (with_f && p < nolder) { cs.kind = kChainKindFW; cs.dst = 2 + mvec + p; cs.wk = vs.w + pw[p]; }
-    }
-  } else {
-    if (pending) cs.s = sqrt(ctl.red()[0]);           // the GLOBAL sum d^2 (F08:267)
-    const bool normed = pending && cs.s != 0.0;       // (s == 0: the scalar step relaxes, F08:268-275; the w1' sums are dead)
-    if (b == 0) {
-      if (normed) { cs.kind = kChainKindFW1; cs.dst = 1; }
-    } else if (b <= ub) {
-      const int k = b - 1;
-      if (normed && k < nolder) { cs.kind = kChainKindW1W; cs.dst = 2 + k; cs.wk = vs.w + pw[k]; }
-    } else {
-      const int p = b - 1 - ub;
-      if (with_f && p < nolder) { cs.kind = kChainKindFW; cs.dst = 2 + mvec + p; cs.wk = vs.w + pw[p]; }
-    }
-  }
-  cs.rs = 1.0 / cs.s;
-  cs.vec16 = ((reinterpret_cast<uintptr_t>(cs.f) | reinterpret_cast<uintptr_t>(cs.w1) | reinterpret_cast<uintptr_t>(cs.wk)) & 15) == 0;
-  return cs;
-}
-// The operands of one block (1024 elements from e0 on) in a wavefront's registers: pair j*64 + lane of the block per load,
-// i.e. 1 KiB per wave instruction ...
-constexpr int kChainPairs = kChainLaneElems / 2;       // 16-byte loads per thread and vector
-static_assert(kChainPairs == 8, "the pair mapping of chain_load_block / chain_store_block assumes 16 elements per lane");
-// xf = f; xb = the SECOND operand of the kind -- the older w (kind FW) or the pending w1 (every other kind); xc = the older w
-// of kind W1W.  (Round 6: three arrays named after the vectors, each written under its own branch, made the compiler sink the
-// stores of two branches into one store through a pointer phi -- the arrays then lived partly in scratch, 48-80 bytes per
-// lane in k_chain_sums / k_chain_blocks / k_chain_apply.  One destination per load, the ADDRESS selected instead.)
-struct ChainBlockRegs {
-  typename VecT<2>::type xf[kChainPairs], xb[kChainPairs], xc[kChainPairs];
-};
-__device__ __forceinline__ void chain_load_block(const ChainSum &cs, ChainBlockRegs &r, int64_t e0, int lane, bool full) {
-  using V2 = typename VecT<2>::type;
-  const int64_t n = cs.n;
-  const bool vec16 = cs.vec16;
-  auto ldpair = [&](const double *p, int64_t i) -> V2 {
-    V2 v;
-    if (full && vec16) v = *reinterpret_cast<const V2 *>(p + i);
-    else if (full) { v.x = p[i]; v.y = p[i + 1]; }
-    else { v.x = i < n ? p[i] : 0.0; v.y = i + 1 < n ? p[i + 1] : 0.0; }
-    return v;
-  };
-  const int64_t i0 = e0 + 2 * lane;
-  const double *const second = cs.kind == kChainKindFW ? cs.wk : cs.w1;
-#pragma unroll
-  for (int j = 0; j < kChainPairs; j++) { r.xf[j] = ldpair(cs.f, i0 + j * 128); r.xb[j] = ldpair(second, i0 + j * 128); }
-  if (cs.kind == kChainKindW1W) {
-#pragma unroll
-    for (int j = 0; j < kChainPairs; j++) r.xc[j] = ldpair(cs.wk, i0 + j * 128);
-  }
-}
-// ... and their rounded products where the lane that owns them reads them (blk: the block's kChainBlockLds doubles of LDS)
-__device__ __forceinline__ void chain_store_block(const ChainSum &cs, const ChainBlockRegs &r, double *blk, int lane) {
-#pragma clang fp contract(off)      // products and additions stay separate roundings whatever the build's flags
-  using V2 = typename VecT<2>::type;
-  const double s = cs.s, rs = cs.rs;
-#pragma unroll
-  for (int j = 0; j < kChainPairs; j++) {
-    V2 p;
-    if (cs.kind == kChainKindFW) { p.x = r.xf[j].x * r.xb[j].x; p.y = r.xf[j].y * r.xb[j].y; }
-    else {
-      const double d0 = r.xb[j].x - r.xf[j].x, d1 = r.xb[j].y - r.xf[j].y;   // F08:266 ((-1)*f + w1 in F08V:237: same bits)
-      if (cs.kind == kChainKindNorm) { p.x = d0 * d0; p.y = d1 * d1; }
-      else {
-        const double n0 = cs.rcp ? rs * d0 : d0 / s, n1 = cs.rcp ? rs * d1 : d1 / s;   // the value PB stores as w1' (F08:283; F08V:256)
-        if (cs.kind == kChainKindFW1) { p.x = r.xf[j].x * n0; p.y = r.xf[j].y * n1; }
-        else { p.x = n0 * r.xc[j].x; p.y = n1 * r.xc[j].y; }
-      }
-    }
-    // pair j*64 + lane of the block = elements 2 (j*64 + lane), +1: lane (j*64 + lane) / 8 of the chain, pair row lane % 8
-    *reinterpret_cast<V2 *>(blk + (lane % kChainPairs) * kChainRow + 2 * (j * (64 / kChainPairs) + lane / kChainPairs)) = p;
-  }
-}
-
-static __global__ __launch_bounds__(kChainThreads) __attribute__((unused)) void k_chain_sums(Ctl ctl, Vecs vs,
-                                                                                              const double *__restrict__ f,
-                                                                                              int rcp, int set, int with_f, int ub,
-                                                                                              int walk, const double *probe) {
+// ---- The same sums, ONE WORKGROUP PER SUM (long vectors): the chain of nka_chain.hpp ----
+__global__ __launch_bounds__(kChainThreads) void k_chain_sums(Ctl ctl, Vecs vs, const double *__restrict__ f, int rcp,
+                                                              int set, int with_f, int ub, int walk, const double *probe) {
   extern __shared__ __attribute__((aligned(16))) double prod[];   // kChainLdsBytes
   __shared__ ChainSummary summ[kChainGroupBlocks];
   __shared__ double sh_a;
@@ -1446,13 +557,10 @@ static __global__ __launch_bounds__(kChainThreads) __attribute__((unused)) void 
 //                            mispredicted, else walked (chain_block_serial), and the run goes on behind it.
 // Same functions, same acceptance rule, same bits as k_chain_sums; what remains sequential is ~10 ns per accepted block and
 // the walk of the blocks that meet an end of their binade.
-static __global__ __launch_bounds__(kChainThreads) __attribute__((unused)) void k_chain_blocks(Ctl ctl, Vecs vs,
-                                                                                                const double *__restrict__ f,
-                                                                                                int rcp, int set, int with_f, int ub,
-                                                                                                int nsum, long long nfull,
-                                                                                                double *__restrict__ pred,
-                                                                                                ChainSummary *__restrict__ summ,
-                                                                                                int mode, const double *probe) {
+__global__ __launch_bounds__(kChainThreads) void k_chain_blocks(Ctl ctl, Vecs vs, const double *__restrict__ f, int rcp,
+                                                                int set, int with_f, int ub, int nsum, long long nfull,
+                                                                double *__restrict__ pred, ChainSummary *__restrict__ summ,
+                                                                int mode, const double *probe) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) double prod[];   // kChainLdsBytes: one block per wavefront
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
@@ -1481,12 +589,9 @@ static __global__ __launch_bounds__(kChainThreads) __attribute__((unused)) void 
 }
 
 constexpr int kChainPredictThreads = 256;
-static __global__ __launch_bounds__(kChainPredictThreads) __attribute__((unused)) void k_chain_predict(Ctl ctl, Vecs vs,
-                                                                                                        const double *f, int rcp,
-                                                                                                        int set, int with_f, int ub,
-                                                                                                        long long nfull,
-                                                                                                        double *__restrict__ pred,
-                                                                                                        const double *probe) {
+__global__ __launch_bounds__(kChainPredictThreads) void k_chain_predict(Ctl ctl, Vecs vs, const double *f, int rcp, int set,
+                                                                        int with_f, int ub, long long nfull,
+                                                                        double *__restrict__ pred, const double *probe) {
   __shared__ double seg_sum[kChainPredictThreads];
   const int t = threadIdx.x, b = blockIdx.x;
   const ChainSum cs = chain_decode(ctl, vs, f, rcp, set, with_f, ub, b, probe);
@@ -1507,11 +612,9 @@ static __global__ __launch_bounds__(kChainPredictThreads) __attribute__((unused)
   for (long long i = lo; i < hi; i++) { const double v = p[i]; p[i] = run; run += v; }
 }
 
-static __global__ __launch_bounds__(64) __attribute__((unused)) void k_chain_apply(Ctl ctl, Vecs vs, const double *__restrict__ f,
-                                                                                  int rcp, int set, int with_f, int ub,
-                                                                                  long long nfull,
-                                                                                  const ChainSummary *__restrict__ summ, int walk,
-                                                                                  const double *probe) {
+__global__ __launch_bounds__(64) void k_chain_apply(Ctl ctl, Vecs vs, const double *__restrict__ f, int rcp, int set,
+                                                    int with_f, int ub, long long nfull,
+                                                    const ChainSummary *__restrict__ summ, int walk, const double *probe) {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) double blk_lds[kChainBlockLds];
   const int lane = threadIdx.x, b = blockIdx.x;
@@ -1657,13 +760,6 @@ enum { kPbNoStoreW = 1, kPbNoStoreF = 2,     // `flags` of PB in an out-of-place
        kPbNotFirst = 8, kPbNotLast = 16 };    // rolling-window PB over a list longer than kMaxPerPass: not the first / not the
                                               // last of its passes (enqueue_pb; in place only)
 
-template <int COMB>
-__device__ __forceinline__ double comb1(double x, double c, double w, double v) {
-  if (COMB == 0) return (x - c * w) + c * v;
-  if (COMB == 1) return ((-c) * w + c * v) + x;
-  return x + c * (v - w);
-}
-
 template <int MAXK, int VEC, int COMB>
 __global__ __launch_bounds__(kBlock) void k_combine(Ctl ctl, Vecs vs, double *f, int pass, int last_pass, int flags) {
   using V = typename VecT<VEC>::type;
@@ -1774,53 +870,6 @@ __global__ __launch_bounds__(kBlock) void k_combine(Ctl ctl, Vecs vs, double *f,
 // and, with compact storage, the raw w of the pending pair are requested one tile ahead.
 // Same arithmetic in the same order => same bits as k_combine.  Single pass, VEC = 2.
 //
-// TILE TICKETS (`tickets` != nullptr).  With the static mapping (tile t -> block t mod G) the
-// blocks of a mixed read/write pass drift apart -- by 5 % of the launch, i.e. ~40 tiles, at
-// n = 1e8 -- and the chip then works on a ~40 MB window of each of the 27 streams at once.
-// tools/hbm_probe (modes d, e, g; profiles/r02/hbm_probe_tile_tickets.txt) shows the same
-// streams moving 8-14 % faster when every block takes its next tile from ONE global counter:
-// the blocks then advance as a compact front (all end within 5 us of each other) and the DRAMs
-// see one narrow window per stream.  A block's first two tiles are static (b, b + G); thread 0
-// requests the tile after next with a returning atomic at the top of an iteration and publishes it
-// in LDS at the end (one workgroup barrier per tile): the OTHER three waves never wait for the
-// atomic, wave 0 does (see ticket_request).  `ng` counters (128 B apart), counter g serving the blocks with b % ng == g and
-// the tiles = g (mod ng): a single counter saturates near 60-75 tickets/us, which short lists
-// exceed.  The last block to finish resets the counters (a second counter, `done`), so a launch
-// always finds them zero.  Elementwise pass: which block handles a tile changes no bit.
-constexpr int kTicketStride = 32;                 // uint32 words between counters (128 B)
-constexpr int kTicketGroupsMax = 8;
-constexpr int kTicketWords = kTicketStride * (kTicketGroupsMax + 1);   // ng counters + `done`
-constexpr unsigned kNoTicket = 0xffffffffu;
-
-// thread 0: the tile after next of this block's group (returning atomic; the value is used a tile later).
-// hipcc's atomic optimiser broadcasts the result with v_readfirstlane right behind the instruction, so
-// wave 0 does wait for the atomic here (s_waitcnt vmcnt(0)); measured against an inline-asm request
-// whose result is only read at the end of the tile, that costs 0-2 % of PB -- and the asm form needs a
-// hand-counted s_waitcnt that turned out NOT to be safe: stores retire out of order with respect to the
-// atomic, a short tile read its ticket too early (tests caught it).  The plain form stays.
-__device__ __forceinline__ unsigned ticket_request(unsigned *group_counter, unsigned base, unsigned ng, unsigned grp) {
-  return (atomicAdd(group_counter, 1u) + base) * ng + grp;
-}
-// end of a tile: thread 0 publishes what it was given, every thread learns the block's tile after next
-// (two LDS words used alternately: a word is rewritten only after another barrier)
-__device__ __forceinline__ int64_t ticket_publish(unsigned *s_next, unsigned &par, unsigned claimed, int64_t ntile) {
-  if (threadIdx.x == 0) s_next[par] = claimed;
-  __syncthreads();
-  const unsigned nx = s_next[par];
-  par ^= 1u;
-  return nx == kNoTicket ? ntile : (int64_t)nx;
-}
-// end of the kernel: every ticket request of this block has returned; the block that arrives last
-// resets the counters, so the next launch finds them zero
-__device__ __forceinline__ void ticket_finish(unsigned *tickets, int ng, int G) {
-  if (threadIdx.x != 0) return;
-  unsigned *const done = tickets + kTicketGroupsMax * kTicketStride;
-  if (atomicAdd(done, 1u) == (unsigned)G - 1u) {
-    for (int g = 0; g < ng; g++) atomicExch(tickets + g * kTicketStride, 0u);
-    atomicExch(done, 0u);
-  }
-}
-
 // PASSES (round 5).  A list longer than kMaxPerPass pairs is combined by several launches of balanced exact widths, each on
 // the pairs [base, base + MAXK) of the plan, f carrying the running value in between (the k loop of F08:395-399 cut into
 // consecutive pieces: same statements in the same order, same bits).  The FIRST pass (no kPbNotFirst) normalises the pending
@@ -2015,193 +1064,7 @@ __global__ __launch_bounds__(kBlock) void k_combine_win(Ctl ctl, Vecs vs, double
 #undef DEAD_OFF
 }
 
-// ---- scalar kernels: list surgery + Cholesky + substitutions on one wavefront ----
-// Working copy of the control arrays in LDS (indices as in the Fortran: slots
-// 1..M1, 0 = end of list).
-struct Lst {
-  int32_t *next, *prev;
-  double *h;   // h[i*(M1+1)+j] == reference h(i,j)
-  double *c;
-  int first, last, free_, subspace, pending, m1, mvec;
-  double vtol;
-  __device__ double &H(int i, int j) { return h[i * (m1 + 1) + j]; }
-};
-
-// F08:439-457
-__device__ inline void lst_relax(Lst &L) {
-  if (!L.pending) return;
-  const int dropped = L.first;
-  L.first = L.next[dropped];
-  if (L.first == 0) L.last = 0; else L.prev[L.first] = 0;
-  L.next[dropped] = L.free_;
-  L.free_ = dropped;
-  L.pending = 0;
-}
-
-// F08:422-436
-__device__ inline void lst_restart(Lst &L) {
-  L.subspace = 0;
-  L.pending = 0;
-  L.first = 0;
-  L.last = 0;
-  L.free_ = 1;
-  for (int k = 1; k < L.m1; k++) L.next[k] = k + 1;
-  L.next[L.m1] = 0;
-}
-
-// F08:295-351.  Row-by-row Cholesky of the Gram matrix in list order; capacity
-// drop of the last entry; dependence drop when the pivot hkk <= vtol^2.  The
-// subtraction order of the inner loop (i ascending in list order) is preserved:
-// with equal dot products the decisions equal the reference's bit for bit.
-__device__ inline void lst_factor(Lst &L) {
-  L.H(L.first, L.first) = 1.0;
-  int k = L.next[L.first];
-  int nvec = 1;
-  while (k != 0) {
-    nvec++;
-    if (nvec > L.mvec) {
-      L.next[L.last] = L.free_;
-      L.free_ = k;
-      L.last = L.prev[k];
-      L.next[L.last] = 0;
-      break;
-    }
-    double hkk = 1.0;
-    for (int j = L.first; j != k; j = L.next[j]) {
-      double hkj = L.H(j, k);
-      for (int i = L.first; i != j; i = L.next[i]) hkj = hkj - L.H(k, i) * L.H(j, i);
-      hkj = hkj / L.H(j, j);
-      hkk = hkk - hkj * hkj;
-      L.H(k, j) = hkj;
-    }
-    if (hkk > L.vtol * L.vtol) {
-      L.H(k, k) = sqrt(hkk);
-    } else {
-      const int p = L.prev[k], nx = L.next[k];
-      L.next[p] = nx;
-      if (nx == 0) L.last = p; else L.prev[nx] = p;
-      L.next[k] = L.free_;
-      L.free_ = k;
-      k = p;
-      nvec--;
-    }
-    k = L.next[k];
-  }
-  L.subspace = 1;
-  L.pending = 0;
-}
-
-// F08:369-392 (c holds the right-hand side on entry)
-__device__ inline void lst_solve(Lst &L) {
-  for (int j = L.first; j != 0; j = L.next[j]) {
-    double cj = L.c[j];
-    for (int i = L.first; i != j; i = L.next[i]) cj = cj - L.H(j, i) * L.c[i];
-    L.c[j] = cj / L.H(j, j);
-  }
-  for (int j = L.last; j != 0; j = L.prev[j]) {
-    double cj = L.c[j];
-    for (int i = L.last; i != j; i = L.prev[i]) cj = cj - L.H(i, j) * L.c[i];
-    L.c[j] = cj / L.H(j, j);
-  }
-}
-
-// F08:406-417
-__device__ inline void lst_prepend(Lst &L, int slot) {
-  L.prev[slot] = 0;
-  L.next[slot] = L.first;
-  if (L.first == 0) L.last = slot; else L.prev[L.first] = slot;
-  L.first = slot;
-  L.pending = 1;
-}
-
-constexpr int kSolveThreads = 64;  // ONE wavefront
-
-// dynamic LDS: next[M1+1], prev[M1+1] (int32) then h[(M1+1)^2], c[M1+1] (double).
-// in_global != 0 (mvec > 140: the (mvec+2)^2 matrix no longer fits the 160 KiB of LDS): the working
-// arrays ARE the control block in global memory -- no copy in, none back; slow (every step of the
-// list-ordered loops is a dependent global access), but the reference has no limit on mvec
-// (F08:185-200) and neither has this build.
-__device__ inline void lst_load(Lst &L, const Ctl &ctl, unsigned char *smem, int in_global = 0) {
-  const int m1 = ctl.m1(), nh = (m1 + 1) * (m1 + 1);
-  L.m1 = m1;
-  L.mvec = ctl.mvec;
-  if (in_global) {
-    L.h = ctl.h();
-    L.c = ctl.c();
-    L.next = ctl.next();
-    L.prev = ctl.prev();
-  } else {
-    L.h = reinterpret_cast<double *>(smem);
-    L.c = L.h + nh;
-    L.next = reinterpret_cast<int32_t *>(L.c + (m1 + 1));
-    L.prev = L.next + (m1 + 1);
-    for (int i = threadIdx.x; i < nh; i += kSolveThreads) L.h[i] = ctl.h()[i];
-    for (int i = threadIdx.x; i < m1 + 1; i += kSolveThreads) {
-      L.c[i] = ctl.c()[i];
-      L.next[i] = ctl.next()[i];
-      L.prev[i] = ctl.prev()[i];
-    }
-  }
-  L.subspace = ctl.ic[IC_SUBSPACE];
-  L.pending = ctl.ic[IC_PENDING];
-  L.first = ctl.ic[IC_FIRST];
-  L.last = ctl.ic[IC_LAST];
-  L.free_ = ctl.ic[IC_FREE];
-  L.vtol = ctl.dc[DC_VTOL];
-  __syncthreads();
-}
-
-__host__ __device__ constexpr size_t lst_smem_bytes(int mvec) {
-  const int m1 = mvec + 1;
-  return (size_t)((m1 + 1) * (m1 + 1) + (m1 + 1)) * sizeof(double) + 2 * (size_t)(m1 + 1) * sizeof(int32_t);
-}
-
-// Lane 0 writes the scalars and the plan for the next update; all lanes copy
-// the arrays back.
-__device__ inline void lst_store(Lst &L, const Ctl &ctl, int in_global = 0) {
-  __syncthreads();
-  const int m1 = L.m1, nh = (m1 + 1) * (m1 + 1);
-  if (!in_global) {
-    for (int i = threadIdx.x; i < nh; i += kSolveThreads) ctl.h()[i] = L.h[i];
-    for (int i = threadIdx.x; i < m1 + 1; i += kSolveThreads) {
-      ctl.c()[i] = L.c[i];
-      ctl.next()[i] = L.next[i];
-      ctl.prev()[i] = L.prev[i];
-    }
-  }
-  if (threadIdx.x == 0) {
-    ctl.ic[IC_SUBSPACE] = L.subspace;
-    ctl.ic[IC_PENDING] = L.pending;
-    ctl.ic[IC_FIRST] = L.first;
-    ctl.ic[IC_LAST] = L.last;
-    ctl.ic[IC_FREE] = L.free_;
-    // plan for the next update's PA
-    ctl.ic[IC_PLAN_PENDING] = L.pending;
-    ctl.ic[IC_PLAN_FIRST] = L.first;
-    int n = 0;
-    int32_t *ps = ctl.plan_slots();
-    const long long *wt = ctl.wtab();
-    for (int k = L.pending ? L.next[L.first] : L.first; k != 0; k = L.next[k]) {
-      ctl.plan_w()[n] = wt[k];       // the streaming passes get addresses, not slots (Ctl::pc)
-      ps[n++] = k;
-    }
-    ctl.ic[IC_PLAN_NOLDER] = n;
-    ctl.pc[PC_FIRST_W] = wt[L.first];      // (entry 0 of the table is a valid dummy: first == 0 without a list)
-  }
-}
-
-// The slot that receives the new pair gets its buffers here.  An out-of-place update (swap_w / swap_v != kNoBuffer,
-// nka_hip_accel_update_swap) EXCHANGES them: the caller's buffer, which holds f_in, becomes the slot's w -- no copy --
-// and a spare buffer of the library becomes its v; what the slot held before is reported in PC_OLD_W / PC_OLD_V.
-__device__ inline void assign_new_buffers(const Ctl &ctl, int slot, long long swap_w, long long swap_v) {
-  long long *wt = ctl.wtab(), *vt = ctl.vtab();
-  if (swap_w != kNoBuffer) { ctl.pc[PC_OLD_W] = wt[slot]; wt[slot] = swap_w; }      // (other updates leave PC_OLD_* alone:
-  if (swap_v != kNoBuffer) { ctl.pc[PC_OLD_V] = vt[slot]; vt[slot] = swap_v; }      //  the host may collect them later)
-  ctl.pc[PC_NEW_W] = wt[slot];
-  ctl.pc[PC_NEW_V] = vt[slot];
-}
-
-static __global__ __launch_bounds__(kSolveThreads) __attribute__((unused)) void k_restart(Ctl ctl, int in_global) {
+__global__ __launch_bounds__(kSolveThreads) void k_restart(Ctl ctl, int in_global) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Lst L;
   lst_load(L, ctl, smem, in_global);
@@ -2209,7 +1072,7 @@ static __global__ __launch_bounds__(kSolveThreads) __attribute__((unused)) void 
   lst_store(L, ctl, in_global);
 }
 
-static __global__ __launch_bounds__(kSolveThreads) __attribute__((unused)) void k_relax(Ctl ctl, int in_global) {
+__global__ __launch_bounds__(kSolveThreads) void k_relax(Ctl ctl, int in_global) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Lst L;
   lst_load(L, ctl, smem, in_global);
@@ -2217,23 +1080,13 @@ static __global__ __launch_bounds__(kSolveThreads) __attribute__((unused)) void 
   lst_store(L, ctl, in_global);
 }
 
-// `mode` of the scalar step.  kSolveRcp: the F08-vector flavour, whose
-// normalisation is a multiplication by 1/s.  kSolvePrenorm: red[1] and the Gram
-// row red[2..] were already evaluated on the NORMALISED w1' (the host
-// dot-product path, nka_hip_set_host_dot) and are taken as they are.
-enum { kSolveRcp = 1, kSolvePrenorm = 2 };
-__device__ __forceinline__ double solve_nrm(double x, double s, double rs, int mode) {
-  return (mode & kSolvePrenorm) ? x : ((mode & kSolveRcp) ? rs * x : x / s);
-}
-
 // The scalar part of accel_update between PA and PB, reference loops verbatim on one lane.
 // `phase`: 0 = the whole step.  The user-dot-product path (nka_hip_set_host_dot) runs it in two halves so that
 // the host can ask the user's dp for the projection row AFTER the drop decisions, as the reference does (F08:371
 // comes behind F08:295-347): 1 = norm, s == 0 -> relax, Gram row, factorisation with drops; 2 = new slot, the
 // substitutions on the right-hand side the host has put into c[] BY SLOT, combine plan, prepend.
-static __global__ __launch_bounds__(kSolveThreads) __attribute__((unused)) void k_solve(Ctl ctl, int mode, int in_global,
-                                                                                       int phase, long long swap_w,
-                                                                                       long long swap_v, P2P x) {
+__global__ __launch_bounds__(kSolveThreads) void k_solve(Ctl ctl, int mode, int in_global, int phase, long long swap_w,
+                                                         long long swap_v, P2P x) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (x.base != nullptr) p2p_gather_block(x, ctl.red(), ctl.red_count());      // the sums of all ranks, in rank order
   Lst L;
@@ -2415,11 +1268,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
     if (lane < nolder) psL[lane] = psreg;
     for (int i = lane + kSolveThreads * kHB; i < nh; i += kSolveThreads) L.h[i] = gh[i];
   }
-  L.subspace = ctl.ic[IC_SUBSPACE];
-  L.pending = ctl.ic[IC_PENDING];
-  L.first = ctl.ic[IC_FIRST];
-  L.last = ctl.ic[IC_LAST];
-  L.free_ = ctl.ic[IC_FREE];
+  lst_load_scalars(L, ctl);
   L.vtol = ctl.dc[DC_VTOL];
   const int entry_pending = L.pending;
   __syncthreads();
@@ -2634,23 +1483,14 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
   // ---- state back to global memory (the plan was written above: without a subspace
   //      the list was empty before the prepend, so the next update has no older entry)
   __syncthreads();
-  for (int i = lane; i < nh; i += kSolveThreads) ctl.h()[i] = L.h[i];
-  for (int i = lane; i < m1 + 1; i += kSolveThreads) {
-    ctl.c()[i] = L.c[i];
-    ctl.next()[i] = L.next[i];
-    ctl.prev()[i] = L.prev[i];
-  }
+  lst_copy_out(L, ctl, kSolveThreads);
   if (lane == 0) {
     ctl.dc[DC_S] = s;
     if (entry_first != 0 && !normed && entry_pending) ctl.ic[IC_NRELAX] += 1;
     ctl.ic[IC_NEW] = slot;
     ctl.ic[IC_NCOMB] = nk;
     ctl.ic[IC_NORMED] = normed;
-    ctl.ic[IC_SUBSPACE] = L.subspace;
-    ctl.ic[IC_PENDING] = L.pending;
-    ctl.ic[IC_FIRST] = L.first;
-    ctl.ic[IC_LAST] = L.last;
-    ctl.ic[IC_FREE] = L.free_;
+    lst_store_scalars(L, ctl);
     ctl.ic[IC_PLAN_PENDING] = L.pending;
     ctl.ic[IC_PLAN_FIRST] = L.first;
     ctl.ic[IC_PLAN_NOLDER] = nk;

@@ -9,6 +9,7 @@
 // with -ffp-contract=off so  a*x + b*y + z  rounds as the Fortran expression
 // ((a*x) + (b*y)) + z  does.
 #include "handles.hpp"
+#include "nka_chain.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -103,7 +104,7 @@ static __global__ __launch_bounds__(kBlock) void k_dot_ordered(int64_t n, const 
   if (threadIdx.x == 0) partials[0] = acc;
 }
 
-// The same sum for LONG vectors (round 5): the per-sum machinery of the array flavour's reference-order pass (nka_kernels.hpp,
+// The same sum for LONG vectors (round 5): the per-sum machinery of the array flavour's reference-order pass (nka_chain.hpp,
 // chain_drive) -- the products of a group are rounded into LDS by eight wavefronts, whole blocks of 1024 go through the chain
 // in exact integer arithmetic wherever that is provably the walk's result, the walk elsewhere.  Same bits as k_dot_ordered
 // (tests/test_chain_sums_gpu.py holds the machinery to numpy's sequential sum), 10-20 x its speed from n ~ 1e5 on.

@@ -23,8 +23,8 @@ double nka_oracle_dot_fma(void *ctx, int64_t n, const double *x, const double *y
   return s;
 }
 
-/* The summation ORDER of the device's pass PA (nka_amd/csrc/nka_kernels.hpp: k_dots_win, block_reduce_store,
- * k_finalize_dots) on 256 compute units: tiles of 512 elements dealt round-robin to G = min(256, n / 512)
+/* The summation ORDER of the device's pass PA (nka_amd/csrc/nka_kernels.hpp: k_dots_win, k_finalize_dots;
+ * nka_device.hpp: block_reduce_store) on 256 compute units: tiles of 512 elements dealt round-robin to G = min(256, n / 512)
  * blocks (at least one) of 256 threads; a thread accumulates its two elements of each of its block's tiles in
  * order; the ragged tail (n mod 512) goes to the last block, one element per thread and round; then the
  * wavefront butterfly (x[i] += x[i + off], off = 32 ... 1), the four wavefronts of a block in order, and the

@@ -30,7 +30,7 @@ static void paint(std::vector<int> &map, long long off, long long len, int tag) 
 int main() {
   for (int mvec = 1; mvec <= 32; mvec++) {
     const int m1 = mvec + 1;
-    // the control block, piece by piece as Ctl lays it out (nka_kernels.hpp)
+    // the control block, piece by piece as Ctl lays it out (nka_ctl.hpp)
     int ic = 0, dc = 0;
     ic += 16; ic += m1 + 1; ic += m1 + 1; ic += m1 + kMaxPerPass; ic += m1 + kMaxPerPass;
     dc += 2; for (int i = 0; i <= m1; i++) for (int j = 0; j <= m1; j++) dc++;

@@ -157,15 +157,90 @@ static void check_buffer_book() {
   }
 }
 
+// The decoding of a control-block snapshot (num_vec, get_state, digest of both handle types) at the smallest shapes that can
+// go wrong.  Every block is an exact-size heap array: a read outside it is an AddressSanitizer report.
+static void check_snapshot() {
+  using namespace nka;
+  auto blocks = [](int mvec, std::vector<int32_t> &ic, std::vector<double> &dc) {
+    Ctl c{};
+    c.mvec = mvec;
+    ic.assign((size_t)c.ic_count(), 0);
+    dc.assign((size_t)c.dc_count(), 0.0);
+  };
+  std::vector<int32_t> ic;
+  std::vector<double> dc;
+  // mvec = 1 (two slots): empty list; one entry, pending or not; both entries
+  blocks(1, ic, dc);
+  int32_t *next = ic.data() + IC_HEADER, *prev = next + 3;
+  CHECK(snapshot_num_vec(ic.data(), 1) == 0, "mvec 1: empty list");
+  ic[IC_FIRST] = ic[IC_LAST] = 2;
+  CHECK(snapshot_num_vec(ic.data(), 1) == 1, "mvec 1: one entry");
+  ic[IC_PENDING] = 1;
+  CHECK(snapshot_num_vec(ic.data(), 1) == 0, "mvec 1: a one-entry list that is the pending pair");
+  next[2] = 1;
+  prev[1] = 2;
+  ic[IC_LAST] = 1;
+  CHECK(snapshot_num_vec(ic.data(), 1) == 1, "mvec 1: pending pair and one vector");
+  // mvec = 2 (three slots), list 3 -> 1 -> 2: not slot order; h and c distinct everywhere
+  blocks(2, ic, dc);
+  const int m1 = 3;
+  next = ic.data() + IC_HEADER;
+  prev = next + (m1 + 1);
+  ic[IC_SUBSPACE] = 1; ic[IC_PENDING] = 0; ic[IC_FIRST] = 3; ic[IC_LAST] = 2; ic[IC_FREE] = 0;
+  next[3] = 1; next[1] = 2; next[2] = 0;
+  prev[3] = 0; prev[1] = 3; prev[2] = 1;
+  next[0] = -7; prev[0] = -9;                   // entry 0 is not a slot: it must not reach the outputs
+  double *hh = dc.data() + DC_HEADER, *cc = hh + (m1 + 1) * (m1 + 1);
+  for (int i = 0; i <= m1; i++) {
+    for (int j = 0; j <= m1; j++) hh[i * (m1 + 1) + j] = 100.0 * i + j;      // the reference's h(i,j), 1-based; row / column 0 unused
+    cc[i] = 1000.0 + i;
+  }
+  CHECK(snapshot_num_vec(ic.data(), 2) == 3, "mvec 2: list 3 -> 1 -> 2");
+  ic[IC_PENDING] = 1;
+  CHECK(snapshot_num_vec(ic.data(), 2) == 2, "mvec 2: the same with a pending pair");
+  int32_t subspace = -1, pending = -1, first = -1, last = -1, free_ = -1;
+  std::vector<int32_t> onext((size_t)m1, -1), oprev((size_t)m1, -1);
+  std::vector<double> oh((size_t)m1 * m1, -1.0), oc((size_t)m1, -1.0);
+  snapshot_unpack(ic.data(), dc.data(), 2, &subspace, &pending, &first, &last, &free_, onext.data(), oprev.data(), oh.data(), oc.data());
+  CHECK(subspace == 1 && pending == 1 && first == 3 && last == 2 && free_ == 0, "scalars %d %d %d %d %d", subspace, pending, first, last, free_);
+  for (int k = 1; k <= m1; k++) {
+    CHECK(onext[(size_t)k - 1] == next[k] && oprev[(size_t)k - 1] == prev[k], "links of slot %d: %d %d", k, onext[(size_t)k - 1], oprev[(size_t)k - 1]);
+    CHECK(oc[(size_t)k - 1] == 1000.0 + k, "c of slot %d: %g", k, oc[(size_t)k - 1]);
+    for (int j = 1; j <= m1; j++)      // column-major m1 x m1, 0-based
+      CHECK(oh[(size_t)(k - 1) + (size_t)(j - 1) * m1] == 100.0 * k + j, "h(%d,%d): %g", k, j, oh[(size_t)(k - 1) + (size_t)(j - 1) * m1]);
+  }
+  snapshot_unpack(ic.data(), dc.data(), 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);      // every output is optional
+  // links that cycle (1 -> 2 -> 1 ...): the walk ends after mvec + 1 steps, inside the block
+  ic[IC_PENDING] = 0; ic[IC_FIRST] = 1;
+  next[1] = 2; next[2] = 1;
+  CHECK(snapshot_num_vec(ic.data(), 2) == 2 + 2, "cycling links: the walk stops one past the mvec + 1 slots");
+  next[1] = 1;
+  CHECK(snapshot_num_vec(ic.data(), 2) == 2 + 2, "a slot linked to itself");
+  // FNV-1a, the published vectors; the digest mixes ic first, then dc, from the library's own seed
+  CHECK(fnv1a(nullptr, 0) == 0xcbf29ce484222325ull, "FNV-1a of the empty input");
+  CHECK(fnv1a("a", 1) == 0xaf63dc4c8601ec8cull, "FNV-1a of \"a\"");
+  CHECK(snapshot_digest({}, {}) == kDigestSeed && kDigestSeed == 1469598103934665603ull, "digest of two empty blocks: the seed");
+  const std::vector<int32_t> i1 = {0x64636261};                                   // "abcd"
+  const std::vector<double> d1 = {1.5};
+  unsigned char bytes[12];
+  std::memcpy(bytes, i1.data(), 4);
+  std::memcpy(bytes + 4, d1.data(), 8);
+  CHECK(snapshot_digest(i1, d1) == fnv1a(bytes, 12, kDigestSeed), "digest: the bytes of ic, then those of dc");
+  std::memcpy(bytes, d1.data(), 8);
+  std::memcpy(bytes + 8, i1.data(), 4);
+  CHECK(snapshot_digest(i1, d1) != fnv1a(bytes, 12, kDigestSeed), "digest: dc first gives another value");
+}
+
 int main(int argc, char **argv) {
   check_pass_widths();
   check_list_word();
   check_buffer_book();
+  check_snapshot();
   if (failures) {
     std::fprintf(stderr, "host_logic_check: %d check(s) FAILED\n", failures);
     return 1;
   }
-  std::printf("host_logic_check: pass widths, launch groups, list word, buffer book: OK\n");
+  std::printf("host_logic_check: pass widths, launch groups, list word, buffer book, snapshot decoding: OK\n");
   if (argc > 1 && !std::strcmp(argv[1], "plant")) {
     // PLANTED: balanced_widths asked for one pass more than its array holds
     int *w = static_cast<int *>(std::malloc(sizeof(int) * 2));

@@ -2,7 +2,7 @@
 
 exact_dot(x, y) is the reference every fast sum of the library is held to (tests/test_sums_exact_gpu.py);
 k_steps / device_k derive how many roundings a product can meet on its way through the kernels that form the sums
-(nka_amd/csrc/nka_kernels.hpp: k_norm_diff, k_dots, k_dots_win, block_reduce_store, k_norm_fin, k_finalize_dots) with the
+(nka_amd/csrc/nka_kernels.hpp: k_norm_diff, k_dots, k_dots_win, k_norm_fin, k_finalize_dots; nka_device.hpp: block_reduce_store) with the
 grids the library launches them on (nka_amd/csrc/nka_hip.hip: sums_rounded, launch_dots_win_1, launch_dots_1, grid_for);
 planted_input builds the inputs of the GPU tests: a small random background with sentinels at the indices where the
 kernels hand elements from one loop, block or launch to the next.  tests/test_exact_sums_cpu.py holds all of it to
@@ -19,7 +19,7 @@ import numpy as np
 U = 2.0 ** -53                  # unit roundoff of binary64 (round to nearest)
 SPLIT = 2.0 ** 27 + 1.0         # Veltkamp: x = hi + lo, both halves of <= 26 significant bits
 
-# launch geometry of the sum kernels (nka_kernels.hpp)
+# launch geometry of the sum kernels (nka_device.hpp, nka_kernels.hpp)
 BLOCK = 256                     # kBlock: threads per block, 4 wavefronts of 64
 WAVE = 64
 WAVES = BLOCK // WAVE

@@ -8,7 +8,7 @@ from collections import namedtuple
 
 import numpy as np
 
-TILE = 512          # elements per tile of the aligned sum kernels (nka_amd/csrc/nka_kernels.hpp: kBlock * 2)
+TILE = 512          # elements per tile of the aligned sum kernels (nka_amd/csrc/nka_device.hpp: kBlock * 2)
 
 # src: int64 indices into the global vector; w: 0/1 float64; [lo, hi): the owned global range; first: the local index of
 # the first owned entry (the owned entries are local [first, first + hi - lo))

@@ -1,4 +1,4 @@
-"""The arithmetic behind the reference-order sums of long vectors (nka_amd/csrc/nka_kernels.hpp: chain_lane_pass,
+"""The arithmetic behind the reference-order sums of long vectors (nka_amd/csrc/nka_chain.hpp: chain_lane_pass,
 chain_block_summary, chain_block_apply), restated in numpy and held to numpy's strictly sequential `add.accumulate` ON THE
 BITS -- no GPU needed.  It is the executable form of the argument in docs/design/11_chain_sums.md:
 
