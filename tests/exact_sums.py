@@ -11,6 +11,10 @@ Fraction arithmetic and shows that losing or doubling any one sentinel breaks th
 The batched accelerator (nka_amd/csrc/nka_batch.hip) forms its sums in one workgroup per system: batch_k,
 batch_sentinel_indices and batch_planted_input, at the end of this file, are its counterparts of device_k, sentinel_indices
 and planted_input (tests/test_batch_sums_exact_gpu.py).
+
+The abstract-vector workspace (nka_amd/csrc/vec_ops.hip) sums on a persistent grid of its own: vec_grid, vec_k,
+vec_sentinel_indices, vec_planted_input and vec_boundary_shapes, behind the batch section, are read off its kernels
+(tests/test_vec_sums_exact_gpu.py).
 """
 import math
 
@@ -278,3 +282,175 @@ def batch_planted_input(n, rng, prev=None, background=0.125):
 BATCH_SHAPES = [1, 2, 3, 7, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 514, 1023, 1024, 1025, 1537, 4099]
 BATCH_WIDTH_SHAPE = 700         # every older count up to NKA_HIP_BATCH_MAX_MVEC = 32
 BATCH_CAP_SHAPES = [BATCH_MAX_VLEN - 1, BATCH_MAX_VLEN]
+
+
+# ---- the abstract-vector workspace (nka_amd/csrc/vec_ops.hip) --------------------------------------------------------------
+# k_dot, k_dot_many, k_dot_pair_many, k_update_norm2, k_scale_dot_pair_many and k_scale_dot_pair_many_win all sum the same
+# way: a persistent grid of G blocks, block b takes the tiles b, b + G, ... of 256 * VEC elements, the last block the
+# ragged tail, block_reduce_store leaves one partial per block and column, k_finalize_rows sums a column's partials.
+
+VEC_MAX_GRID = 4096             # kMaxGrid (nka_device.hpp:19)
+VEC_PER_CU_MAX = 8              # grid_for: at most 8 blocks per CU (vec_ops.hip:756)
+VEC_LOADS_PER_CU = 22           # grid_for: one block per CU once a thread keeps 22 loads in flight
+VEC_MANY_MAX = 24               # kManyMax (host_logic.hpp): vectors per launch
+VEC_FIN_THREADS = BLOCK         # k_finalize_rows runs kBlock threads (vec_ops.hip:877, 938)
+
+
+def vec_width(count):
+    """width_for (vec_ops.hip:762): the unroll width 4, 8, ..., 24 of a padded kernel for `count` vectors."""
+    return max(4, _cdiv(count, 4) * 4)
+
+
+def vec_groups(count):
+    """The widths of the balanced launch groups of a list of `count` vectors (host_logic.hpp: many_groups,
+    many_group_width; 25 = 13 + 12): what dot_pair_many_scaled and diff_norm_dot_pair_many run."""
+    ng = 1 if count <= VEC_MANY_MAX else _cdiv(count, VEC_MANY_MAX)
+    return [count // ng + (1 if p < count % ng else 0) for p in range(ng)]
+
+
+def vec_grid(n, ncu, vec, nloads):
+    """grid_for (vec_ops.hip:755-760): per_cu = max(1, min(8, (22 + nloads - 1) / nloads)) blocks per CU, at most one
+    block per tile of 256 * vec elements (at least one block), at most kMaxGrid.  `nloads` is what the entry passes: 2
+    (dot :1074, update_norm2 :1294), nv + 1 (dot_many :1126), nv + 2 (dot_pair_many :1183), 22 for the window kernels and
+    nv + 3 for the 8-byte k_scale_dot_pair_many (:1440); nv = vec_width(count) but for the window kernels, whose width
+    is max(count, 1) (:1439)."""
+    per_cu = max(1, min(VEC_PER_CU_MAX, _cdiv(VEC_LOADS_PER_CU, nloads)))
+    return min(ncu * per_cu, max(n // (BLOCK * vec), 1), VEC_MAX_GRID)
+
+
+def vec_k(n, G, vec):
+    """Roundings a product can meet in a sum of the workspace over n elements on a grid of G blocks, read off the kernels:
+
+      per-thread chain    block b serves the tiles b, b + G, ... < ntile = n // (256 * vec), one fma per element and sum
+                          into ONE accumulator (k_dot :72-78, k_dot_many :197-208, k_dot_pair_many :228-244,
+                          k_update_norm2 :336-347, k_scale_dot_pair_many :377-406, the window kernel :564-605 in the same
+                          order): vec * ceil(ntile / G) fma;
+      ragged tail         the last block walks the tail at stride 256 (:79-80, :209-212, :245-254, :348-353, :407-426,
+                          :606-625): ceil(tail / 256) more fma, tail < 256 * vec;
+      block_reduce_store  (nka_device.hpp:165) the 64-lane butterfly of WAVE_LEVELS = 6 additions, then the four wave
+                          sums in turn: 3 additions;
+      k_finalize_rows     (:877-901) thread t adds the partials t, t + 256, ... of its column -- ceil(G / 256) additions,
+                          256 threads, not the 64 of k_finalize_dots --, the butterfly (6) and the four wave sums (3).
+
+    A fma rounds once (the product enters it exactly), so a product meets at most this many factors (1 + delta).  The
+    bound applied is gamma(vec_k) * abs_dot (gamma adds the rounding of exact_dot itself)."""
+    tile = BLOCK * vec
+    ntile = n // tile
+    chain = vec * _cdiv(ntile, G) + _cdiv(n - ntile * tile, BLOCK)
+    block = WAVE_LEVELS + (WAVES - 1)
+    fin = _cdiv(G, VEC_FIN_THREADS) + WAVE_LEVELS + (WAVES - 1)
+    return chain + block + fin
+
+
+def _grids(G):
+    return (int(G),) if np.isscalar(G) else tuple(int(g) for g in G)
+
+
+def vec_sentinel_indices(n, G, vec):
+    """Indices where the workspace's sum kernels change hands in a vector of n elements, tiles of 256 * vec, on a grid of
+    G blocks (G may be several grids: the union), by name; empty arrays where a shape has no such place:
+
+      ends         0 and n - 1;
+      tile_last    the last element of every full tile (the tile loops :72, :197, :228, :336, :377, :564);
+      tail         the first element of the tail and the tail elements at offsets 255 and 256: the tail is walked at
+                   stride 256 (:80, :210, :246, :349, :408, :607), up to two elements per thread on the 16-byte path;
+      block_first  the first element of each block's first tile;
+      block_last   ... and of its last tile, where the window kernel prefetches its own tile again (tn == t, :566, :587);
+      wave_edges   the first and the last thread's elements of each wavefront in the first and in the last full tile
+                   (thread t owns elements vec * t ... of a tile): where a wavefront's butterfly ends and sm[] takes over."""
+    tile = BLOCK * vec
+    ntile = n // tile
+    tail0 = ntile * tile
+    out = {"ends": np.unique(np.array([0, n - 1] if n else [], dtype=np.int64)),
+           "tile_last": np.arange(1, ntile + 1, dtype=np.int64) * tile - 1,
+           "tail": np.array([i for i in (tail0, tail0 + BLOCK - 1, tail0 + BLOCK) if i < n], dtype=np.int64)}
+    first, last = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for g in _grids(G):
+        blocks = np.arange(min(g, ntile), dtype=np.int64)
+        first.append(blocks * tile)
+        last.append((blocks + g * ((ntile - 1 - blocks) // g)) * tile)
+    out["block_first"] = np.unique(np.concatenate(first))
+    out["block_last"] = np.unique(np.concatenate(last))
+    edges = np.array([vec * (WAVE * w + lane) + q for w in range(WAVES) for lane in (0, WAVE - 1) for q in range(vec)],
+                     dtype=np.int64)
+    tiles = np.unique(np.array([0, ntile - 1] if ntile else [], dtype=np.int64))
+    out["wave_edges"] = (tiles[:, None] * tile + edges[None, :]).ravel()
+    return out
+
+
+def vec_all_sentinels(n, G, vec):
+    return np.unique(np.concatenate(list(vec_sentinel_indices(n, G, vec).values()) + [np.zeros(0, np.int64)]))
+
+
+def vec_planted_input(n, G, vec, rng, background=0.125, prev=None):
+    """planted_input for the workspace: N(0, background^2) everywhere, +-2^e (e in 0..3, random sign) at every sentinel of
+    vec_sentinel_indices(n, G, vec), never the value `prev` has there."""
+    x = rng.standard_normal(n) * background
+    idx = vec_all_sentinels(n, G, vec)
+    if idx.size == 0:
+        return x
+    val = np.ldexp(1.0, rng.integers(0, 4, idx.size)) * rng.choice([-1.0, 1.0], idx.size)
+    if prev is not None:
+        same = val == prev[idx]
+        val[same] = -val[same]
+    x[idx] = val
+    return x
+
+
+def vec_boundary_shapes(G, vec):
+    """The lengths where the workspace's kernels change hands on a grid of up to G blocks (grid_for, vec_ops.hip:755-760:
+    one block per tile until G is reached), t = 256 * vec: the fixed small
+    ones around one wavefront's stride and one tile, every block's first tile being its last (G t +- 1), one block with a
+    second tile ((G + 1) t), and two tiles per block with and without a tail, the longest tail included."""
+    t = BLOCK * vec
+    return [1, 2, 255, 256, 257, 511, 512, 513,
+            G * t - 1, G * t, G * t + 1,
+            (G + 1) * t, 2 * G * t - 1, 2 * G * t + 1, 2 * G * t + t - 1]
+
+
+VEC_SHAPE_IDS = ["1", "2", "255", "256", "257", "511", "512", "513", "Gt-1", "Gt", "Gt+1", "(G+1)t", "2Gt-1", "2Gt+1", "2Gt+t-1"]
+
+# The scalars of the fused stages in the tests.  No power of two: with sentinels of +-2^e in both operands a*x + z and
+# pre_a*f + w never cancel at a sentinel (|0.7312 * 2^i +- 2^j| >= 0.2688, |0.75 * 2^i +- 2^j| >= 0.25), so every derived
+# operand keeps a sentinel of at least a quarter where its sources have one.
+VEC_A = 0.7312                  # r = a*x + z (update_norm2), d = a*x + z (diff_norm_dot_pair_many)
+VEC_PRE_A = -0.75               # w0 = pre_a*f + w
+VEC_SCALE = 0.3                 # wn = a*w0, vn = a*v
+
+
+def vec_operands(n, G, vec, rng, count):
+    """The host operands of tests/test_vec_sums_exact_gpu.py at one shape, all planted at the same sentinels: x, z, f, w, v
+    and `count` vectors ys, and the operands the fused stages derive from them, formed as the kernels form them (numpy:
+    IEEE, left to right, no fma):  r = a*x + z;  wn_pre = a*(pre_a*f + w), wn = a*w;  vn = a*v and vn - wn."""
+    o = {k: vec_planted_input(n, G, vec, rng) for k in ("x", "z", "f", "w", "v")}
+    o["ys"] = [vec_planted_input(n, G, vec, rng) for _ in range(count)]
+    o["r"] = VEC_A * o["x"] + o["z"]
+    o["wn0"] = VEC_SCALE * o["w"]
+    o["wn1"] = VEC_SCALE * (VEC_PRE_A * o["f"] + o["w"])
+    return o
+
+
+def vec_sum_pairs(o):
+    """(name, x, y) of every sum the workspace's entries form from vec_operands."""
+    pairs = [("<x,z>", o["x"], o["z"]), ("<x,x>", o["x"], o["x"]), ("<r,r>", o["r"], o["r"]), ("<x,r>", o["x"], o["r"]),
+             ("<f,wn0>", o["f"], o["wn0"]), ("<f,wn1>", o["f"], o["wn1"])]
+    for j, y in enumerate(o["ys"]):
+        pairs += [(f"<x,y{j}>", o["x"], y), (f"<z,y{j}>", o["z"], y), (f"<r,y{j}>", o["r"], y), (f"<f,y{j}>", o["f"], y),
+                  (f"<wn0,y{j}>", o["wn0"], y), (f"<wn1,y{j}>", o["wn1"], y)]
+    return pairs
+
+
+def vec_all_grids(n, ncu, vec):
+    """Every grid some entry of the workspace may launch at length n (nloads 2 ... kManyMax + 3): what operands shared by
+    several entries and counts are planted for."""
+    return sorted({vec_grid(n, ncu, vec, nl) for nl in range(2, VEC_MANY_MAX + 4)})
+
+
+def vec_widths_shape(ncu):
+    """Every count 1..24 runs here: three 512-tiles per block of the window kernels' grid (one block per CU) and a ragged
+    tail that gives some threads two elements."""
+    return 3 * ncu * 2 * BLOCK + 301
+
+
+VEC_LONG_SHAPE = 39 * 512 + 43          # counts 25, 37, 49: lists longer than one launch
+VEC_SMALL_SHAPES = [7 * 512 + 300, 3 * 512 + 77]     # the non-finite cases; the refusals in reference order

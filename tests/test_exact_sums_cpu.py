@@ -318,3 +318,205 @@ def test_near_threshold_generator_meets_both_outcomes(oracle):
     for _ in range(20):
         (xa, na), (xb, nb) = a.next(), b.next()
         assert na == nb and (xa == xb).all()
+
+
+# ---- the abstract-vector workspace: tests/test_vec_sums_exact_gpu.py --------------------------------------------------------
+
+# the grids of an MI355X (256 CUs): 1 block per CU (the window kernels), 2, 3, 4, 5 (the padded widths) and 8 (k_dot, k_update_norm2)
+VEC_GRIDS = (256, 512, 768, 1024, 1280, 2048)
+VEC_BIG = 1 << 19               # from here on the GPU tests run at most two vectors ys (the host's fsum is the cost)
+
+
+def test_vec_grid_and_vec_k_follow_the_kernels():
+    # grid_for: 8 blocks per CU for two loads, (22 + nloads - 1) / nloads beyond, one for the window kernels
+    assert [X.vec_grid(10 ** 8, 256, 2, nl) for nl in (2, 3, 5, 6, 9, 10, 11, 22, 27)] == [2048, 2048, 1280, 1024, 768, 768, 512, 256, 256]
+    assert X.vec_grid(10 ** 8, 1024, 2, 2) == 4096                        # kMaxGrid
+    assert X.vec_grid(1, 256, 2, 2) == 1 and X.vec_grid(1023, 256, 2, 2) == 1 and X.vec_grid(1024, 256, 2, 2) == 2
+    assert X.vec_grid(1023, 256, 1, 2) == 3
+    assert [X.vec_width(c) for c in (0, 1, 4, 5, 12, 13, 24)] == [4, 4, 4, 8, 12, 16, 24]
+    assert X.vec_groups(0) == [0] and X.vec_groups(24) == [24] and X.vec_groups(25) == [13, 12] and X.vec_groups(49) == [17, 16, 16]
+    # n = G * 512: one tile per block, two fma; block_reduce_store 9; k_finalize_rows one addition per thread + 9
+    assert X.vec_k(256 * 512, 256, 2) == 2 + 9 + 1 + 9
+    assert X.vec_k(256 * 512 + 1, 256, 2) == 2 + 1 + 9 + 10
+    assert X.vec_k(256 * 512 + 257, 256, 2) == 2 + 2 + 9 + 10
+    assert X.vec_k(2 * 2048 * 512 + 511, 2048, 2) == 4 + 2 + 9 + 8 + 9  # 8 partials per thread of k_finalize_rows
+    assert X.vec_k(7, 1, 2) == 1 + 9 + 1 + 9 and X.vec_k(3001, 11, 1) == 1 + 1 + 9 + 10
+
+
+def test_vec_sentinels_sit_where_the_kernels_change_hands():
+    G, t = 4, 512
+    s = X.vec_sentinel_indices(2 * G * t + t + 300, G, 2)                  # 9 tiles on 4 blocks and a tail of 300
+    assert list(s["ends"]) == [0, 9 * t + 299]
+    assert list(s["tile_last"]) == [k * t - 1 for k in range(1, 10)]
+    assert list(s["tail"]) == [9 * t, 9 * t + 255, 9 * t + 256]
+    assert list(s["block_first"]) == [0, t, 2 * t, 3 * t]
+    assert list(s["block_last"]) == [5 * t, 6 * t, 7 * t, 8 * t]          # sorted: blocks 1, 2, 3 and block 0 (tiles 0, 4, 8)
+    assert s["wave_edges"].size == 32 and {0, 1, 126, 127, 128, 129, 510, 511, 8 * t, 8 * t + 511} <= set(s["wave_edges"])
+    s = X.vec_sentinel_indices(3 * 256 + 7, 2, 1)                          # the 8-byte path: tiles of 256, one element each
+    assert list(s["tile_last"]) == [255, 511, 767] and list(s["tail"]) == [768]
+    assert list(s["block_first"]) == [0, 256] and list(s["block_last"]) == [256, 512]
+    assert s["wave_edges"].size == 16 and {0, 63, 64, 127, 255, 512, 767} <= set(s["wave_edges"])
+    s = X.vec_sentinel_indices(7, 1, 2)                                    # no full tile
+    assert list(s["ends"]) == [0, 6] and list(s["tail"]) == [0] and s["tile_last"].size == 0 and s["wave_edges"].size == 0
+    assert X.vec_sentinel_indices(0, 1, 2)["ends"].size == 0
+    both = X.vec_all_sentinels(9 * t, (4, 3), 2)                           # several grids: the union
+    assert set(X.vec_all_sentinels(9 * t, 4, 2)) | set(X.vec_all_sentinels(9 * t, 3, 2)) == set(both)
+    for vec in (1, 2):
+        for n in X.vec_boundary_shapes(5, vec):
+            idx = X.vec_all_sentinels(n, min(5, max(n // (256 * vec), 1)), vec)
+            assert idx.size >= min(n, 2) and idx.min() >= 0 and idx.max() < n and np.unique(idx).size == idx.size
+    rng = np.random.default_rng(0)
+    a = X.vec_planted_input(3000, 3, 2, rng)
+    b = X.vec_planted_input(3000, 3, 2, rng, prev=a)
+    idx = X.vec_all_sentinels(3000, 3, 2)
+    assert (np.abs(a[idx]) >= 1).all() and (a[idx] != b[idx]).all() and (np.abs(np.delete(a, idx)) < 1).all()
+
+
+def _fma(a, b, c):
+    """One fma: a*b + c rounded once (Fraction -> float rounds correctly)."""
+    return float(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
+
+
+def _block_sum(v):
+    """block_reduce_store / the end of k_finalize_rows: a butterfly over each wavefront of 64 (lane i + lane i + 32, 16,
+    8, 4, 2, 1), then the wave sums 0, 1, 2, 3 in turn."""
+    waves = []
+    for w in range(X.WAVES):
+        u = np.array(v[w * X.WAVE:(w + 1) * X.WAVE], dtype=np.float64)
+        while u.size > 1:
+            u = u[: u.size // 2] + u[u.size // 2:]
+        waves.append(u[0])
+    r = waves[0]
+    for w in waves[1:]:
+        r = r + w
+    return float(r)
+
+
+def _vec_model_sum(x, y, G, vec, tail_from=0, column_shift=None):
+    """The workspace's blocked sum restated on the host, every fma rounded once: block b of G takes the tiles b, b + G,
+    ..., thread t the elements vec * t ... vec * t + vec - 1 of a tile in turn; the last block walks the tail at stride
+    256; block_reduce_store; thread t of k_finalize_rows adds the partials t, t + 256, ... to 0.0; the block sum again.
+    `tail_from` = 1 is the MUTATION of a tail loop that starts one element late."""
+    n = x.size
+    tile = X.BLOCK * vec
+    ntile = n // tile
+    acc = [[0.0] * X.BLOCK for _ in range(G)]
+    for t in range(ntile):
+        a = acc[t % G]
+        for th in range(X.BLOCK):
+            for q in range(vec):
+                i = t * tile + th * vec + q
+                a[th] = _fma(x[i], y[i], a[th])
+    for i in range(ntile * tile + tail_from, n):
+        th = (i - ntile * tile - tail_from) % X.BLOCK
+        acc[G - 1][th] = _fma(x[i], y[i], acc[G - 1][th])
+    partials = [_block_sum(a) for a in acc]
+    lanes = np.zeros(X.BLOCK)
+    for b in range(G):
+        lanes[b % X.BLOCK] = lanes[b % X.BLOCK] + partials[b]
+    return _block_sum(lanes)
+
+
+def _vec_check_passes(got, x, y, k):
+    """The check of tests/test_vec_sums_exact_gpu.py: _hold."""
+    return abs(got - X.exact_dot(x, y)) <= X.gamma(k) * X.abs_dot(x, y)
+
+
+@pytest.mark.parametrize("vec", [1, 2])
+@pytest.mark.parametrize("G", [1, 3, 8])
+def test_the_vec_bound_holds_for_the_modelled_blocked_sum(G, vec):
+    """The model stays within gamma(vec_k) * abs_dot on planted inputs (three tiles per block and a tail that gives some
+    threads two elements; one tile per block and one element) and on adversarial exponents -- and a tail loop that starts
+    one element late does not (the first mutation of the issue, on the host-modelled part)."""
+    t = X.BLOCK * vec
+    rng = np.random.default_rng(10 * G + vec)
+    for n in (3 * G * t + 300, G * t + 1):
+        k = X.vec_k(n, G, vec)
+        o = X.vec_operands(n, G, vec, rng, 1)
+        for what, x, y in [p for p in X.vec_sum_pairs(o) if p[0] in ("<x,z>", "<r,r>", "<wn1,y0>")]:
+            got = _vec_model_sum(x, y, G, vec)
+            assert _vec_check_passes(got, x, y, k), (n, what, abs(got - X.exact_dot(x, y)) / (X.U * X.abs_dot(x, y)), k)
+            assert not _vec_check_passes(_vec_model_sum(x, y, G, vec, tail_from=1), x, y, k), (n, what, "late tail")
+    n = 2 * G * t + 77
+    x = rng.standard_normal(n) * np.ldexp(1.0, rng.integers(-30, 30, n))
+    y = rng.standard_normal(n)
+    assert _vec_check_passes(_vec_model_sum(x, y, G, vec), x, y, X.vec_k(n, G, vec))
+
+
+def _vec_shape_grid(n, G, vec):
+    """The grid grid_for launches at length n when G blocks are the most it may."""
+    return min(G, max(n // (X.BLOCK * vec), 1))
+
+
+@pytest.mark.parametrize("vec", [1, 2])
+@pytest.mark.parametrize("G", VEC_GRIDS)
+def test_every_planted_vec_sentinel_is_seen_by_the_bound(G, vec):
+    """The sensitivity argument of tests/test_vec_sums_exact_gpu.py without a GPU: at every shape of vec_boundary_shapes, for
+    every sum an entry forms from vec_operands, each sentinel's product exceeds twice the bound (plus the rounding of the
+    exact sum), so a device sum that dropped it or counted it twice fails the check."""
+    rng = np.random.default_rng(G + vec)
+    for n in X.vec_boundary_shapes(G, vec):
+        g = _vec_shape_grid(n, G, vec)
+        idx = X.vec_all_sentinels(n, g, vec)
+        sent = X.vec_sentinel_indices(n, g, vec)
+        assert idx.size >= min(n, 2) and idx.min() >= 0 and idx.max() < n
+        assert all(np.isin(v, idx).all() for v in sent.values())
+        if n >= G * X.BLOCK * vec:
+            assert sent["block_first"].size == G
+        bound = X.gamma(X.vec_k(n, g, vec))
+        for what, x, y in X.vec_sum_pairs(X.vec_operands(n, g, vec, rng, 2 if n >= VEC_BIG else 5)):
+            tot = X.abs_dot(x, y)
+            worst = float(np.abs(x[idx] * y[idx]).min())
+            assert X.detectable(worst, bound, tot), (n, what, worst / tot, bound)
+
+
+@pytest.mark.parametrize("G,vec", [(3, 1), (3, 2), (8, 2)])
+def test_dropping_or_doubling_a_vec_sentinel_fails_the_check_end_to_end(G, vec):
+    """The long way round on small grids: one sentinel zeroed or doubled, the sum taken exactly, held to the check of the
+    GPU test; the first and the last sentinel of every kind, at every boundary shape."""
+    rng = np.random.default_rng(17 * G + vec)
+    for n in X.vec_boundary_shapes(G, vec):
+        g = _vec_shape_grid(n, G, vec)
+        bound = X.gamma(X.vec_k(n, g, vec))
+        sent = X.vec_sentinel_indices(n, g, vec)
+        picks = sorted({int(v[0]) for v in sent.values() if v.size} | {int(v[-1]) for v in sent.values() if v.size})
+        for what, x, y in X.vec_sum_pairs(X.vec_operands(n, g, vec, rng, 1)):
+            if what in ("<x,x>", "<r,r>"):
+                continue                                                  # (one operand twice: a doubled element counts four times)
+            ex, tot = X.exact_dot(x, y), X.abs_dot(x, y)
+            for i in picks:
+                for factor in (0.0, 2.0):
+                    xp = x.copy()
+                    xp[i] *= factor
+                    assert abs(X.exact_dot(xp, y) - ex) > bound * tot, (n, what, i, factor)
+
+
+def test_a_wrong_column_of_partials_fails_the_check():
+    """The second mutation of the issue on the host model: k_finalize_rows reading column c + 1 returns the NEXT sum of
+    the launch; on planted operands no two sums of a launch agree within the bound."""
+    G, vec = 3, 2
+    n = 3 * G * 512 + 300
+    rng = np.random.default_rng(23)
+    o = X.vec_operands(n, G, vec, rng, 4)
+    k = X.vec_k(n, G, vec)
+    sums = [(x, y, _vec_model_sum(x, y, G, vec)) for x, y in [(o["x"], yj) for yj in o["ys"]] + [(o["x"], o["z"])]]
+    for c in range(len(sums) - 1):
+        x, y, own = sums[c]
+        assert _vec_check_passes(own, x, y, k) and not _vec_check_passes(sums[c + 1][2], x, y, k), c
+
+
+@pytest.mark.parametrize("vec", [1, 2])
+@pytest.mark.parametrize("ncu", [256, 80])
+def test_the_shared_vec_operands_are_seen_by_every_grid(ncu, vec):
+    """The shapes at which the GPU tests share one set of operands among entries and counts (every width 1..24, the long
+    lists, the small cases): planted for EVERY grid an entry may launch there, each sentinel detectable under the
+    largest bound among them."""
+    rng = np.random.default_rng(ncu + vec)
+    for n, count in [(X.vec_widths_shape(ncu), X.VEC_MANY_MAX), (X.VEC_LONG_SHAPE, 49)] + [(s, 5) for s in X.VEC_SMALL_SHAPES]:
+        grids = X.vec_all_grids(n, ncu, vec)
+        idx = X.vec_all_sentinels(n, grids, vec)
+        bound = max(X.gamma(X.vec_k(n, g, vec)) for g in grids)
+        for what, x, y in X.vec_sum_pairs(X.vec_operands(n, grids, vec, rng, count)):
+            tot = X.abs_dot(x, y)
+            worst = float(np.abs(x[idx] * y[idx]).min())
+            assert X.detectable(worst, bound, tot), (n, what, worst / tot, bound)
