@@ -31,6 +31,7 @@ import pytest
 import batch_seq as B
 import exact_sums as X
 import scenarios as S
+from split_update import _bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -65,12 +66,6 @@ def torch_cuda():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     torch.cuda.set_device(0)
     return torch
-
-
-def _bits_equal(a, b):
-    """Bit for bit, but NaN payloads (which the host and the device need not agree on) only as NaN."""
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
 
 
 def _hold(what, red, x, y, k, where):

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import exact_sums as X
+from split_update import _bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -65,12 +66,6 @@ def ncu(torch_cuda):
     acc.delete()
     assert g >= 1
     return g
-
-
-def _bits_equal(a, b):
-    """Bit for bit, but NaN payloads (which the host and the device need not agree on) only as NaN."""
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
 
 
 def _hold(mode, what, red, x, y, k, where):
