@@ -40,8 +40,17 @@ extern "C" {
  * "chain_many" = -1/0/1: reference-order sums of the longest vectors by the whole device (k_chain_blocks / _predict / _apply): -1 automatic
  * (from 2^19 elements on), 0 never (one compute unit per sum: k_chain_sums), 1 wherever a vector has a full block.  Same bits.
  * "chain_walk" = 0/1: reference-order sums of long vectors (k_chain_sums) walk every block element after element instead of
- * taking whole blocks through the chain in integer arithmetic (chain_block_summary / chain_block_apply).  Same bits. */
+ * taking whole blocks through the chain in integer arithmetic (chain_block_summary / chain_block_apply).  Same bits.
+ * "skip_last" = -1/0/1: with the list full, PA leaves out the vector that the update drops for capacity (one stream of
+ * mvec + 2) and three guarded launches behind the scalar step repair the rare update that needs its sums after all: -1
+ * automatic (from a vector length on, where the stream saved outweighs the launches), 0 never, 1 wherever the launch allows
+ * it (fast sums, one rank, the library's own dot product, 2 <= mvec <= 32, f 16-byte aligned) at any length.  Same outputs,
+ * lists, factor and stored vectors; nka_hip_get_reductions reads 0 in the two skipped entries (nka_hip_ext.h). */
 int nka_hip_set_tuning(nka_hip_t a, const char *key, int32_t value);
+
+/* The skip of the last vector ("skip_last") as the device holds it: out4 = { the plan of the next update may skip (0/1),
+ * updates still to run without the skip after a repair, a repair is pending (0 between updates), repairs so far }. */
+int nka_hip_get_skip_state(nka_hip_t a, int32_t out4[4]);
 
 /* Launch geometry knobs for tuning: blocks per CU of PA and PB (0 = automatic). */
 int nka_hip_set_grid(nka_hip_t a, int32_t pa_blocks_per_cu, int32_t pb_blocks_per_cu);

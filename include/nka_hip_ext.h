@@ -89,7 +89,14 @@ int nka_hip_get_state(nka_hip_t a, int32_t *subspace, int32_t *pending, int32_t 
  * for the p-th older list entry (2+2*mvec doubles).  The solve divides the d
  * rows by s = sqrt(red[0]).  With these a CPU restatement of the scalar step
  * can be checked bit for bit.  With reference-order sums (nka_hip_set_sum_order) red[1] and red[2+p] are the sums on the
- * NORMALISED difference, <f,w1'> and <w1',w_p>, and the solve takes them as they are. */
+ * NORMALISED difference, <f,w1'> and <w1',w_p>, and the solve takes them as they are.
+ * THE SKIPPED LAST VECTOR.  With the list full (a pending pair and mvec older entries) the update drops the oldest entry for
+ * capacity before its Gram entry or its projection is looked at (F08:301-309), and from a vector length on the fast sums of a
+ * single-rank handle no longer read that vector: its two entries, red[2+mvec-1] and red[2+2*mvec-1], then read 0.  The
+ * entries of h and c that belong to the freed slot are unspecified; nothing reads them, and a slot's rows are rewritten when
+ * it is reused (F08:288).  An update that does need those sums -- a dependence drop or s == 0 at a full list -- forms them
+ * in a repair pass on the device and red[] is complete.  Outputs, lists, the factor between listed slots, the coefficients
+ * and the stored vectors are the same bits either way. */
 int nka_hip_get_reductions(nka_hip_t a, double *red_out);
 /* Copy stored vector w(:,slot) / v(:,slot) (1-based slot) to host memory. */
 int nka_hip_get_w(nka_hip_t a, int32_t slot, double *host_out);

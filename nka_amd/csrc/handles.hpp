@@ -117,6 +117,9 @@ struct nka_hip_state {
                               // VGPRs and scratch in PA, every load of a tile in flight in PB) run the next width with ONE dead ring
                               // slot: -1 / 1 on (automatic), 0 off.  In-process A/B at n = 1e7 (profiles/r05/multipass.txt): update
                               // -12.7 % at m = 31, -3.4 % at 29, -0.3 % at 23 (compact); -11 / -4.4 / -2.9 % in the src-F08 rounding
+  int skip_last = -1;         // PA leaves out the vector a full list drops for capacity (nka_hip.hip, skip_last_applies): -1 automatic
+                              // (from a vector length on), 0 never, 1 wherever the launch allows it (diagnostic switch "skip_last")
+  int pa_skip = 0;            // the PA / final sums being enqueued: kSkipMay, kSkipRepair (nka_device.hpp) or 0
   bool state_in_global = false;  // mvec > 140: h, c and the links no longer fit the LDS of one CU; the one-lane
                                  // scalar kernels then work on the control block in global memory (slow, unlimited)
   bool serial_solve = false;  // NKA_HIP_SERIAL_SOLVE=1: reference loops verbatim on one lane

@@ -22,6 +22,15 @@ int nka_hip_get_stamps(nka_hip_t a, double *out16) {
   return 0;
 }
 
+// The skip of the last vector as the device sees it: plan flag, hysteresis countdown, pending repair, repairs so far.
+int nka_hip_get_skip_state(nka_hip_t a, int32_t out4[4]) {
+  if (!a || !out4) return fail(NKA_HIP_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(a->device));
+  HIP_TRY(hipMemcpyAsync(out4, a->ctl.ic + IC_PLAN_SKIP, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, a->stream));
+  HIP_TRY(hipStreamSynchronize(a->stream));
+  return 0;
+}
+
 int nka_hip_set_grid(nka_hip_t a, int32_t pa, int32_t pb) {
   if (!a) return fail(NKA_HIP_EINVAL, "null handle");
   const int32_t v[2] = {pa, pb};
@@ -122,6 +131,9 @@ int nka_hip_set_tuning(nka_hip_t a, const char *key, int32_t value) {
   } else if (k == "prime_pad") {      // -1 automatic = 1: list lengths 23 / 29 / 31 run the next width (one dead ring slot); 0: exact widths
     if (value < -1 || value > 1) return fail(NKA_HIP_EINVAL, "prime_pad: -1, 0, 1");
     a->prime_pad = value;
+  } else if (k == "skip_last") {      // -1 automatic (from a vector length on), 0 never, 1 wherever the launch allows it, at any n
+    if (value < -1 || value > 1) return fail(NKA_HIP_EINVAL, "skip_last: -1, 0, 1");
+    a->skip_last = value;
   } else if (k == "chain_many") {     // -1 automatic, 0: one compute unit per reference-order sum at every length, 1: many wherever blocks exist
     if (value < -1 || value > 1) return fail(NKA_HIP_EINVAL, "chain_many: -1, 0, 1");
     a->chain_many = value;

@@ -30,6 +30,12 @@ enum {
   IC_PLAN_NOLDER = 9,  //   number of list entries to dot against
   IC_NRELAX = 10,      // count of s == 0 events (diagnostic)
   IC_NORMED = 11,      // this update normalises the pending pair (pending && s != 0)
+  // SKIP OF THE LAST VECTOR (k_dots_win): with the list full, PA of the NEXT update may leave out the oldest w -- the capacity
+  // drop F08:301-309 ends the list before its sums are looked at -- when the launch allows it too (argument `skip`).
+  IC_PLAN_SKIP = 12,   //   plan for PA of the NEXT update: 1 = may skip (written by the scalar step: IC_SKIP_HOLD == 0)
+  IC_SKIP_HOLD = 13,   //   updates still to run WITHOUT the skip after a repair (hysteresis, counts down)
+  IC_REDO = 14,        //   the scalar step needed the skipped sums after all: the guarded repair launches behind it run
+  IC_NREDO = 15,       //   count of such repairs (diagnostic)
   IC_HEADER = 16
 };
 // double control block

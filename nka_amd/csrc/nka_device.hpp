@@ -223,6 +223,22 @@ __device__ __forceinline__ double pa_operand(double d, int normed, double s, dou
   return (normed & 2) ? rs * d : d / s;
 }
 
+// SKIP OF THE LAST VECTOR.  With the list full (pending pair + mvec older entries) the oldest entry is dropped for capacity
+// (F08:301-309) before its Gram entry or its projection is looked at -- unless an earlier entry is dropped as dependent
+// (F08:326-345) or s == 0 relaxes (F08:275), which is rare.  `skip` of k_dots_win / k_finalize_dots / k_solve_rows:
+//   kSkipMay     this launch may leave that vector out (the host's conditions hold: update_impl, skip_last_applies); it does
+//                when the device agrees -- the plan says so (IC_PLAN_SKIP), a pair is pending and the plan holds mvec entries.
+//                PA then treats the last plan entry as a dead ring slot, its two sums read 0, and a scalar step that finds
+//                it needs them after all raises IC_REDO and returns BEFORE any store of state;
+//   kSkipRepair  a guarded launch behind that scalar step: returns at once unless IC_REDO is set.  The three of them form
+//                the two missing sums (same grid, same per-thread tile sequence => the bits of the unskipped pass), store
+//                them, and run the scalar step again, which clears IC_REDO and holds the skip off for mvec updates.
+enum { kSkipMay = 1, kSkipRepair = 2 };
+__device__ __forceinline__ bool skip_last_planned(const Ctl &ctl, int skip, int pending, int nolder) {
+  return (skip & kSkipMay) && pending && nolder == ctl.mvec && ctl.ic[IC_PLAN_SKIP] != 0;
+}
+__device__ __forceinline__ bool skip_repair_idle(const Ctl &ctl, int skip) { return (skip & kSkipRepair) && ctl.ic[IC_REDO] == 0; }
+
 // DIAGONAL WEIGHTS (nka_hip_set_dot_weights): every product of the weighted passes takes fl(w_i * a_i) as its FIRST operand
 // and the unweighted value as its second, fma(fl(w a), b, acc); the order of the sums is the unweighted kernels'.  The
 // passes that form sums (k_norm_diff, k_dots, k_dots_win) take `bool WGT = false`: with false these helpers return `a` and

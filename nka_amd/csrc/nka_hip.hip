@@ -262,13 +262,15 @@ int launch_dots_win_1(const nka_hip_state *a, const double *f, int bpc, int base
   g = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(g, std::max<int64_t>(ntile, 1)), kMaxGrid));
   if (a->weighted)
     hipLaunchKernelGGL((k_dots_win<MAXL, W, true>), dim3((int)g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base,
-                       a->pa_normed);
+                       a->pa_normed, a->pa_skip);
   else
-    hipLaunchKernelGGL((k_dots_win<MAXL, W>), dim3((int)g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base, a->pa_normed);
+    hipLaunchKernelGGL((k_dots_win<MAXL, W>), dim3((int)g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base, a->pa_normed,
+                       a->pa_skip);
   // (Round 3 measured forming these sums -- and the scalar step -- in the tail of the PA launch, by the block that
   //  finishes last: 2-4 us SLOWER per update than the launches it saves, profiles/r03/ab_small_pa_tail_not_kept.txt.)
   hipLaunchKernelGGL((k_finalize_dots<MAXL>), dim3(2 * MAXL + 2), dim3(kFinThreads), 0, a->stream, a->ctl,
-                     a->partials, (int)g, pass, ncover < 0 ? MAXL : ncover, base, a->p2p_fused ? a->p2p : P2P{}, a->pa_normed ? 1 : 0);
+                     a->partials, (int)g, pass, ncover < 0 ? MAXL : ncover, base, a->p2p_fused ? a->p2p : P2P{}, a->pa_normed ? 1 : 0,
+                     a->pa_skip);
   return (int)g;
 }
 
@@ -792,6 +794,7 @@ int nka_hip_clone(nka_hip_t src, nka_hip_t *out) {
   b->pb_tile = src->pb_tile;
   b->pb_tickets = src->pb_tickets;
   b->prime_pad = src->prime_pad;
+  b->skip_last = src->skip_last;
   b->chain_walk = src->chain_walk;
   b->chain_many = src->chain_many;      // (the copy allocates its own block arrays when it needs them)
   b->chain_pred = nullptr; b->chain_summ = nullptr; b->chain_cap = 0;
@@ -873,7 +876,8 @@ int nka_hip_set_vec_tol(nka_hip_t a, double vtol) {
 }
 
 // ---- the three stages of an update, enqueued on the handle's stream -------------
-static int enqueue_solve(nka_hip_t a, int mode, long long swap_w = kNoBuffer, long long swap_v = kNoBuffer, bool gather = false) {
+static int enqueue_solve(nka_hip_t a, int mode, long long swap_w = kNoBuffer, long long swap_v = kNoBuffer, bool gather = false,
+                         int skip = 0) {
   hipStream_t s = a->stream;
   const P2P x = gather ? a->p2p : P2P{};      // the scalar step starts by gathering the sums of all ranks (peer-to-peer exchange)
   if (a->mvec + 1 <= kSolveWaveMax && !a->serial_solve) {
@@ -883,7 +887,8 @@ static int enqueue_solve(nka_hip_t a, int mode, long long swap_w = kNoBuffer, lo
     //  launch: a replay re-issues it with the arguments frozen at capture, a later out-of-place update would be invisible)
     const long long id_stride = (a->swapped || a->captured) ? 0 : (long long)a->vs.stride, id_vbase = buffer_offset(a, a->vs.v);
 #define ROWS(NL) \
-  hipLaunchKernelGGL((k_solve_rows<NL>), dim3(1), dim3(kSolveThreads), sm, s, a->ctl, mode, swap_w, swap_v, id_stride, id_vbase, x)
+  hipLaunchKernelGGL((k_solve_rows<NL>), dim3(1), dim3(kSolveThreads), sm, s, a->ctl, mode, swap_w, swap_v, id_stride, id_vbase, x, \
+                     skip)
     if (nl <= 6) ROWS(6);
     else if (nl <= 11) ROWS(11);
     else if (nl <= 21) ROWS(21);
@@ -1389,6 +1394,24 @@ static SumsResult sums_blocked(nka_hip_t a, const double *f, int vec, int older_
 static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_v);
 static int p2p_status_after_sync(nka_hip_t a);
 
+// SKIP OF THE LAST VECTOR (nka_device.hpp, kSkipMay): may PA of this update leave out the vector a full list drops for capacity?
+// The device decides whether it does (plan flag, pending pair, list really full); the host says whether the launch is one that
+// can: the fast sums on one rank (a repair behind an exchange would need a conditional exchange), the library's own dot
+// product, one rolling-window launch as wide as the list at one block per CU (the repair launch then has the same grid, hence
+// the same partial sums), the one-wavefront scalar step, and a bound that lets the list be full.  Every update that may is
+// followed by the three guarded repair launches (update_impl), ~5 us that a short vector does not earn back: automatic from
+// kSkipLastMinBytes per vector on: twice the smallest length at which the skip was not slower in the in-process A/B at m = 20
+// (n = 1e6: +3.4 us per update, 3e6: equal, 1e7: -4.6 us, 3e7: -25 us; profiles/skip_last/ab_inproc.txt).
+constexpr double kSkipLastMinBytes = 4.8e7;
+static bool skip_last_applies(const nka_hip_state *a, SumsStage stage, int vec, int older_ub) {
+  if (a->skip_last == 0) return false;
+  if (stage != SumsStage::Rounded && stage != SumsStage::Blocked) return false;
+  if (a->allreduce || a->host_dot || a->serial_solve) return false;
+  if (a->mvec < 2 || a->mvec > kMaxPerPass || vec != 2 || older_ub != a->mvec) return false;
+  if (a->pa_pipe != -1 && a->pa_pipe != 201) return false;
+  return a->skip_last > 0 || 8.0 * (double)a->n >= kSkipLastMinBytes;
+}
+
 int nka_hip_accel_update(nka_hip_t a, double *f) { return update_impl(a, f, kNoBuffer, kNoBuffer); }
 
 // One update.  swap_w / swap_v != kNoBuffer (offsets from vs.w): out of place (nka_hip_accel_update_swap) -- f (== swap_w)
@@ -1453,13 +1476,17 @@ static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_
   // step done -- and says what the scalar step must know.  Unaligned f (not 16-B aligned) takes scalar loads with the narrow
   // unroll.  A failure up to and including the all-reduce leaves the update NOT done (see above the stage functions).
   SumsResult sums{};
-  switch (pick_sums_stage(a)) {
+  const SumsStage stage = pick_sums_stage(a);
+  const bool skip = skip_last_applies(a, stage, vec, older_ub);
+  a->pa_skip = skip ? kSkipMay : 0;
+  switch (stage) {
     case SumsStage::HostDot:        sums = sums_host_dot(a, f, mode); break;
     case SumsStage::ReferenceChain: sums = sums_reference_chain(a, f, mode, older_ub); break;
     case SumsStage::ReferenceOrder: sums = sums_reference_order(a, f, mode, older_ub); break;
     case SumsStage::Rounded:        sums = sums_rounded(a, f, vec, mode, older_ub); break;
     case SumsStage::Blocked:        sums = sums_blocked(a, f, vec, older_ub); break;
   }
+  a->pa_skip = 0;
   if (sums.rc) return sums.rc;
   mode |= sums.mode_bits;
   const bool solved = sums.solved, gather = sums.gather;
@@ -1468,7 +1495,7 @@ static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_
   // ---- scalar part on one wavefront (F08:267-275, 295-358, 366-392, 406-417) ----
   RoctxRange range_tail("nka:solve + PB combine");
   if (!solved)
-    if (int rc = enqueue_solve(a, mode, swap_w, swap_v, gather)) return rc;
+    if (int rc = enqueue_solve(a, mode, swap_w, swap_v, gather, skip ? kSkipMay : 0)) return rc;
   // From here on the scalar step is in the stream: the lists, the factor and (out of place) the tables move on whatever
   // happens next.  What can still fail is a HIP call (an event record, a launch); the handle is then beyond repair.
   struct Poison {
@@ -1479,6 +1506,17 @@ static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_
   if (a->fail_after_solve) {      // (set only through the lab, lab.hip)
     a->fail_after_solve = 0;
     return fail(NKA_HIP_EHIP, "accel_update: injected failure behind the scalar step (lab switch fail_after_solve)");
+  }
+  if (skip) {
+    // the repair of a skip that did not hold (kSkipRepair): the balanced-pass form of PA on the last plan entry alone, its
+    // final sums, the scalar step again.  Each returns at once unless the scalar step above has raised IC_REDO -- no
+    // synchronisation, nothing read back, and a captured update carries them along.
+    a->pa_skip = kSkipRepair;
+    a->pa_normed = stage == SumsStage::Rounded ? ((mode & kSolveRcp) ? 3 : 1) : 0;
+    launch_dots_win(1, a, f, 1, a->mvec - 1, 1, a->mvec);
+    a->pa_skip = a->pa_normed = 0;
+    HIP_TRY(hipGetLastError());
+    if (int rc = enqueue_solve(a, mode, swap_w, swap_v, false, kSkipRepair)) return rc;
   }
   if (int rc = record(a, 2)) return rc;
 

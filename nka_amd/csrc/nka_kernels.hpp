@@ -20,7 +20,8 @@
 //                   list order (F08:395-399), and the two ring stores w_new = f_in
 //                   (F08:361), v_new = f_out (F08:404).  Reads (1+2k)n, writes 5n;
 //                   in the C flavour's compact storage (see k_combine) (2+k)n.
-// That moves 8n(8+L+2k) bytes per update -- 8n(9+L+k) compact -- against the
+// That moves 8n(8+L+2k) bytes per update -- 8n(9+L+k) compact; one stream less with the list full, whose last vector PA
+// does not read (kSkipMay, nka_device.hpp) -- against the
 // 8n(11+L+2k) of the three-pass schedule of SURVEY.md 8(d), with ONE
 // synchronisation point.
 // Round 5: lists longer than 32 run PA and PB as balanced passes of the same window kernels (`base` into the plans);
@@ -214,16 +215,24 @@ __global__ __launch_bounds__(64) void k_norm_fin(Ctl ctl, const double *__restri
 // first two sums (d^2, <f,d>) used (k_finalize_dots).
 template <int MAXL, int W, bool WGT = false>
 __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const double *__restrict__ f,
-                                                     double *__restrict__ partials, int base, int normed) {
+                                                     double *__restrict__ partials, int base, int normed, int skip) {
   constexpr int VEC = 2;
   using V = typename VecT<VEC>::type;
   constexpr int NACC = 2 * MAXL + 2;
   static_assert(MAXL % W == 0, "the ring must divide the stored vectors of a tile");
+  if (skip_repair_idle(ctl, skip)) return;                 // (a guarded repair launch with nothing to repair: nka_device.hpp)
   NKA_STAMP0(ctl, 10);
   const int G = gridDim.x;
   const int pending = ctl.ic[IC_PLAN_PENDING];
   const double s_n = normed ? sqrt(ctl.red()[0]) : 1.0, rs_n = 1.0 / s_n;      // (see k_dots: sums on the rounded w1')
-  const int nolder = ctl.ic[IC_PLAN_NOLDER] - base;        // entries of the plan from `base` on (<= 0: none, every slot dead)
+  // the list is full and its last vector is about to be dropped for capacity: that plan entry is a dead slot too
+  const int nplan = ctl.ic[IC_PLAN_NOLDER];
+  const bool skip_last = skip_last_planned(ctl, skip, pending, nplan);
+  const int nolder = nplan - (skip_last ? 1 : 0) - base;   // entries of the plan from `base` on (<= 0: none, every slot dead)
+  // ... and where it is this launch's last ring slot (a launch as wide as the list: the only one that pays), that ONE slot
+  // reads f's first tile instead of f at the tile at hand, as PB's dead slots do (half of such a re-read comes from HBM
+  // again, k_combine_win).  The tile number is uniform, so the choice is made on the scalar side of the address.
+  const bool last_far = skip_last && ctl.mvec - base == MAXL;
   const long long *pw = ctl.plan_w() + base;
   const double *w1p = vs.w + ctl.pc[PC_FIRST_W];           // (read whether pending or not: no branch around a load)
   const double *w1 = pending ? w1p : f;
@@ -245,23 +254,27 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
   // (dead ring slots -- a launch wider than the list -- re-read f at the tile at hand here.  Sending them to f's first
   //  tile, as PB does (k_combine_win), was measured in this pass too: 25 more VGPRs for the per-slot offsets and
   //  +2...5 % of PA with NO dead slot, which is every launch of a caller that synchronises once per iteration, since PA
-  //  then runs at exactly the list length; profiles/r04/ab_dead_slot.txt)
-#define DEAD_OFF(live, off) (off)
+  //  then runs at exactly the list length; profiles/r04/ab_dead_slot.txt.  The ONE slot of a skipped last vector does go
+  //  there -- `last_far` above: a scalar choice, no register per slot)
+#define DEAD_OFF(j, off, off_far) ((j) == MAXL - 1 ? (off_far) : (off))
   V fv, w1v, omv = {}, ring[W];      // (omv: WGT only)
   int64_t t = blockIdx.x;
   if (t < ntile) {
     const int64_t e = t * (kBlock * VEC) + threadIdx.x * VEC;
+    const int64_t ef = (last_far ? 0 : t) * (kBlock * VEC) + threadIdx.x * VEC;
     fv = ld<VEC>(f + e);
     w1v = ld<VEC>(w1 + e);
     if constexpr (WGT) omv = ld<VEC>(wgt + e);
 #pragma unroll
-    for (int j = 0; j < W; j++) ring[j] = ld<VEC>(wk[j] + (DEAD_OFF(j < nolder, e)));
+    for (int j = 0; j < W; j++) ring[j] = ld<VEC>(wk[j] + (DEAD_OFF(j, e, ef)));
   }
   NKA_STAMP0(ctl, 11);
   for (; t < ntile; t += G) {
     const int64_t e = t * (kBlock * VEC) + threadIdx.x * VEC;
     const int64_t tn = (t + G < ntile) ? t + G : t;     // the last iteration prefetches its own tile again
     const int64_t en = tn * (kBlock * VEC) + threadIdx.x * VEC;
+    const int64_t ef = (last_far ? 0 : t) * (kBlock * VEC) + threadIdx.x * VEC;        // (the skipped last slot: DEAD_OFF)
+    const int64_t enf = (last_far ? 0 : tn) * (kBlock * VEC) + threadIdx.x * VEC;
     double dq[VEC], fq[VEC];      // (weighted: the first operands fl(w d), fl(w f); the second ones are not kept)
 #pragma unroll
     for (int q = 0; q < VEC; q++) {
@@ -280,8 +293,8 @@ __global__ __launch_bounds__(kBlock) void k_dots_win(Ctl ctl, Vecs vs, const dou
     for (int j = 0; j < MAXL; j++) {
       const V x = ring[j % W];
       __builtin_amdgcn_sched_barrier(0);
-      if (j + W < MAXL) ring[j % W] = ld<VEC>(wk[j + W] + (DEAD_OFF(j + W < nolder, e)));
-      else ring[j % W] = ld<VEC>(wk[j + W - MAXL] + (DEAD_OFF(j + W - MAXL < nolder, en)));
+      if (j + W < MAXL) ring[j % W] = ld<VEC>(wk[j + W] + (DEAD_OFF(j + W, e, ef)));
+      else ring[j % W] = ld<VEC>(wk[j + W - MAXL] + (DEAD_OFF(j + W - MAXL, en, enf)));
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int q = 0; q < VEC; q++) {
@@ -339,7 +352,9 @@ constexpr int kFinThreads = 64;
 // scalar step gathers them; red[] is then written by that gather.
 template <int MAXL>
 __global__ __launch_bounds__(kFinThreads) void k_finalize_dots(Ctl ctl, const double *__restrict__ partials, int G,
-                                                               int pass, int ncover, int base, P2P x, int keep0 = 0) {
+                                                               int pass, int ncover, int base, P2P x, int keep0 = 0,
+                                                               int skip = 0) {
+  if (skip_repair_idle(ctl, skip)) return;
   const int lane = threadIdx.x;
   const int c = blockIdx.x;
   const bool p2p = x.base != nullptr;
@@ -349,8 +364,10 @@ __global__ __launch_bounds__(kFinThreads) void k_finalize_dots(Ctl ctl, const do
   double r = 0.0;
   for (int b = lane; b < G; b += kFinThreads) r += partials[(size_t)c * G + b];
   r = wave_sum(r);
-  const int nolder = ctl.ic[IC_PLAN_NOLDER];
   const int pending = ctl.ic[IC_PLAN_PENDING];
+  // (a skipped last vector, k_dots_win: its column is dead like the columns past the list, both rows read 0)
+  const int nplan = ctl.ic[IC_PLAN_NOLDER];
+  const int nolder = nplan - (skip_last_planned(ctl, skip, pending, nplan) ? 1 : 0);
   // (`base` = first plan entry of this pass: pass * MAXL for the passes of equal width, the running sum of the widths
   //  for the balanced passes of the window kernels)
   if (pass == 0 && c == 0)
@@ -1197,9 +1214,10 @@ __host__ __device__ inline size_t solve_wave_smem_bytes(int mvec) {
 // l_q = readlane(l, q) -- lanes p <= q update entries nobody reads.
 template <int NLMAX>
 __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode, long long swap_w, long long swap_v,
-                                                              long long id_stride, long long id_vbase, P2P x) {
+                                                              long long id_stride, long long id_vbase, P2P x, int skip) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x;
+  if (skip_repair_idle(ctl, skip)) return;     // (the second scalar step of an update that skipped: nothing to repair)
   // peer-to-peer exchange: wait for the rows of all ranks and add them in rank order (P2P above); red[] then holds the
   // global sums like after an all-reduce (lane e reads back below what it has just written itself)
   if (x.base != nullptr) p2p_gather_block(x, ctl.red(), ctl.red_count());
@@ -1225,6 +1243,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
   //      2 + 2 mvec <= 128, so the lists, sums and plan take one or two loads a lane; the Gram
   //      matrix kHB a lane (mvec <= 21), the rest of a larger one in the old loop.
   const int nolder = ctl.ic[IC_PLAN_NOLDER];
+  const int hold_in = ctl.ic[IC_SKIP_HOLD];
   {
     constexpr int kHB = 8;
     static_assert(kSolveWaveMax + 1 <= kSolveThreads, "lists: one load a lane");
@@ -1271,6 +1290,13 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
   lst_load_scalars(L, ctl);
   L.vtol = ctl.dc[DC_VTOL];
   const int entry_pending = L.pending;
+  // PA left out the last vector of a full list (nka_device.hpp, kSkipMay: the same three conditions as there): its two sums
+  // read 0.  The capacity drop normally ends the list before either is looked at; where this step is about to need them
+  // -- s == 0 keeps the whole older list, a dependence drop makes room for the last entry -- it raises IC_REDO and returns
+  // with NOTHING of the state stored (everything so far went to LDS and registers): the guarded launches behind it form
+  // the sums and run this step again (kSkipRepair), which then takes them as any other.
+  const bool skipped = !(skip & kSkipRepair) && skip_last_planned(ctl, skip, entry_pending, nolder);
+  bool redo = false;
   __syncthreads();
   NKA_STAMP(ctl, 1);
   const double vtol2 = L.vtol * L.vtol;
@@ -1283,6 +1309,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
     s = sqrt(redL[0]);                        // F08:267
     if (s == 0.0) lst_relax(L);               // F08:275
   }
+  if (skipped && s == 0.0) redo = true;       // (every older entry stays: the projection on the last one is needed)
   if (L.pending) normed = 1;
   {
     const double rs = 1.0 / s;
@@ -1291,6 +1318,13 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
       L.c[psL[p]] = redL[2 + M + p];                                                 // F08:371
     }
     if (normed && lane == 0) L.c[entry_first] = solve_nrm(redL[1], s, rs, mode);     // <f,w1'> = <f,d>/s
+  }
+  if (redo) {                                    // s == 0 with the last vector skipped (uniform; nothing stored yet)
+    if (lane == 0) {
+      ctl.ic[IC_REDO] = 1;
+      ctl.ic[IC_NREDO] += 1;
+    }
+    return;
   }
   __syncthreads();
   // list position -> slot WITHOUT walking the list: with a new pair this call the list is `first` followed
@@ -1334,6 +1368,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
           capdrop = i;                           // F08:301-308 capacity: i is the last entry
           open_ = false;
         } else {
+          if (skipped && i == nl - 1) redo = true;      // the last position is evaluated after all: its row was not summed
           const double hkk = readlane_f64(ddr, i);
           keep = hkk > vtol2;                    // F08:326
           if (keep) Lii = sqrt(hkk);
@@ -1353,6 +1388,13 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
       }
     }
     NKA_STAMP(ctl, 4);
+    if (redo) {                                  // (uniform; no global store has happened yet)
+      if (lane == 0) {
+        ctl.ic[IC_REDO] = 1;
+        ctl.ic[IC_NREDO] += 1;
+      }
+      return;
+    }
     // ---- phase 2: the factor back by slot, and into LDS for the back-substitution (which reads
     //      COLUMNS of it); replay the drops in list order
     // (branch-free: a lone wavefront pays ~20 cycles for every taken branch.  Rows are written whole --
@@ -1494,6 +1536,15 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
     ctl.ic[IC_PLAN_PENDING] = L.pending;
     ctl.ic[IC_PLAN_FIRST] = L.first;
     ctl.ic[IC_PLAN_NOLDER] = nk;
+    // the next update may skip unless a repair is recent: one that has just run holds the skip off for the following mvec
+    // updates, so that a solve which takes dependence drops at a full list in update after update pays one repair in mvec + 1
+    int hold = hold_in > 0 ? hold_in - 1 : 0;
+    if (skip & kSkipRepair) {
+      hold = M;
+      ctl.ic[IC_REDO] = 0;
+    }
+    ctl.ic[IC_SKIP_HOLD] = hold;
+    ctl.ic[IC_PLAN_SKIP] = hold == 0 ? 1 : 0;
   }
   NKA_STAMP(ctl, 9);
 }

@@ -482,6 +482,14 @@ class nka:  # noqa: N801  (the reference's type name)
         self._need_diag("set_tuning")
         _check(self._L.nka_hip_set_tuning(self._handle(), key.encode(), int(value)), "set_tuning", self._L)
 
+    def skip_state(self):
+        """The skip of the last vector as the device holds it (nka_hip_get_skip_state, include/nka_hip_diag.h):
+        (the next update may skip, updates still held off after a repair, a repair is pending, repairs so far)."""
+        self._need_diag("skip_state")
+        out = (C.c_int32 * 4)()
+        _check(self._L.nka_hip_get_skip_state(self._handle(), out), "get_skip_state", self._L)
+        return tuple(out)
+
     def debug_chain_sum(self, x, y, start: float = 0.0, walk: bool = False, many: bool = False):
         """start + x[0]*y[0] + x[1]*y[1] + ... formed by the reference-order kernel of long vectors over two device
         tensors (nka_hip_debug_chain_sum, include/nka_hip_diag.h); many: through the many-compute-unit kernels.  Returns

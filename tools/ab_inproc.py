@@ -3,7 +3,7 @@
 inputs, same thermal state), the variants alternated in blocks of K updates for
 R rounds; per-phase device times from the library's HIP events.
 
-  tools/ab_inproc.py --key pb_pipe --values 0 201 [--flavor f08] [--vlen 1e8] [--mvec 20] [--rounds 8] [--steps 10]
+  tools/ab_inproc.py --key pb_pipe --values 0 201 [--flavor f08] [--vlen 1e8] [--mvec 20] [--rounds 8] [--steps 10] [--sums blocked]
 """
 import argparse
 import os
@@ -25,6 +25,8 @@ def main():
     ap.add_argument("--mvec", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--sums", default="default", choices=["default", "rounded", "blocked"],
+                    help="the sum mode of the handle (nka_hip_set_sum_order)")
     ap.add_argument("--span-dim", type=int, default=0,
                     help="D > 0: every input in a D-dimensional span (a dependence drop per update, the subspace holds D "
                          "vectors) and one synchronisation per update, e.g. --key list_word --values 0 1")
@@ -35,6 +37,8 @@ def main():
     n, m = int(a.vlen), a.mvec
     fl = {"f08": nka_amd.FLAVOR_F08, "c": nka_amd.FLAVOR_C, "f08vec": nka_amd.FLAVOR_F08_VECTOR}[a.flavor]
     acc = nka_amd.nka(diagnostic=True).init(n, m, flavor=fl)      # libnka_hip_diag.so: the A/B switches
+    if a.sums != "default":
+        acc.set_sum_order({"rounded": nka_amd.SUMS_BLOCKED_ROUNDED, "blocked": nka_amd.SUMS_BLOCKED}[a.sums])
     P = min(m + 6, 30)
     pool = torch.empty((P, n + (n % 2)), dtype=torch.float64, device="cuda")
     D = a.span_dim
@@ -90,11 +94,17 @@ def main():
     assert acc.num_vec() == k_want
     if D > 0:
         print(f"inputs in a {D}-dimensional span: num_vec = {k_want} of mvec = {m}; host bound on the list: {acc.list_bound()}")
-    print(f"in-process A/B  key={a.key}  flavor={a.flavor} n={n} m={m}  {a.rounds} rounds x {a.steps} updates per variant")
+    print(f"in-process A/B  key={a.key}  flavor={a.flavor} sums={a.sums} n={n} m={m}  {a.rounds} rounds x {a.steps} updates per variant")
+
+    def spread(x):      # over the rounds of one variant
+        return f"{statistics.mean(x):.4f} (min {min(x):.4f}, max {max(x):.4f}, sd {statistics.pstdev(x):.4f})"
     for v in a.values:
         d = res[v]
-        print(f"  {a.key}={v}:  PB {statistics.mean(d['PB']):.3f} ms (min {min(d['PB']):.3f}, max {max(d['PB']):.3f}, "
-              f"sd {statistics.pstdev(d['PB']):.3f})   PA {statistics.mean(d['PA']):.3f}   update {statistics.mean(d['all']):.3f} ms")
+        print(f"  {a.key}={v}:  PB {spread(d['PB'])} ms   PA {spread(d['PA'])}   update {spread(d['all'])} ms")
+    if len(a.values) == 2:      # round by round, second variant minus first: the drift between rounds is common to both
+        x, y = res[a.values[0]], res[a.values[1]]
+        for ph in ("PA", "all"):
+            print(f"  paired, {a.values[1]} - {a.values[0]}, {ph}: {spread([q - p for p, q in zip(x[ph], y[ph])])} ms")
 
 
 if __name__ == "__main__":
