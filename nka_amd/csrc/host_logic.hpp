@@ -1,5 +1,6 @@
-// host_logic.hpp -- the PURE host-side arithmetic of libnka_hip.so: pass widths, the decoding of the list word and of a control-
-// block snapshot, who holds which buffer, launch groups of the vector hooks.  No HIP, no device state: the .hip files include it,
+// host_logic.hpp -- the PURE host-side arithmetic of libnka_hip.so: pass widths, the launch rules (ring sizes, persistent grids,
+// ticket counters), the decoding of the list word and of a control-block snapshot, who holds which buffer, launch groups of
+// the vector hooks.  No HIP, no device state: the .hip files include it,
 // and tests/c/host_logic_check.cpp compiles the same text with g++ -fsanitize=address,undefined and checks every function
 // against a brute-force model on the CPU (`make -C nka_amd/csrc hostcheck`, tests/test_sanitizers_cpu.py) -- the part of the
 // host code a sanitizer can see without a GPU (the reference's stand-in is its `defined` invariant check,
@@ -45,6 +46,50 @@ inline void balanced_widths(int total, int np, int *w) {
 // Launch groups of the batched hooks of the abstract-vector flavour: balanced too (25 = 13 + 12, not 24 + 1).
 inline int many_groups(int count) { return count <= kManyMax ? 1 : (count + kManyMax - 1) / kManyMax; }
 inline int many_group_width(int count, int p) { const int np = many_groups(count); return count / np + (p < count % np ? 1 : 0); }
+
+// THE LAUNCH RULES of the streaming kernels, one definition for the array flavour (nka_hip.hip) and the vector workspace
+// (vec_ops.hip).
+// The ring size of the rolling-window kernels: a small divisor of the width (4, 5, 6, 3 or 7), or the width itself when it
+// is prime (then every load of a tile is in flight and each is re-issued for the next tile as soon as it has been consumed).
+// Rings of 2, width/4 and width/2 measured slower than 4 (profiles/r02/ab_inproc_pipelined_passes.txt).
+constexpr int win_ring(int width) {
+  return width % 4 == 0 ? 4 : width % 5 == 0 ? 5 : width % 6 == 0 ? 6 : width % 3 == 0 ? 3 : width % 7 == 0 ? 7 : width;
+}
+// What streams TWO vectors per entry (the flavours F08 and F08-vector, the pair lists of the vector workspace) keeps the same
+// number of loads in flight with half the ring: 2 pairs where the width is even (in-process A/B at m = 20: -3.5 % at
+// n = 1.25e7, equal at 1e8; the compact flavour loses 13 % with a ring of 2 single loads).
+constexpr int win_ring_pairs(int width) {
+  return width % 2 == 0 ? 2 : width % 3 == 0 ? 3 : width % 5 == 0 ? 5 : width % 7 == 0 ? 7 : width;
+}
+// Blocks per CU when each thread keeps `nloads` 16-byte loads in flight per tile.  Measured on MI355X (n = 1.25e7 and 1e8,
+// m = 20): ONE block per CU is fastest once a block has >= 22 loads per thread in flight (88 KiB per CU); more blocks per CU
+// only add write/read interleaving in the mixed pass (PB 0.46 -> 0.52 ms at 4 per CU).  Narrow instantiations get
+// proportionally more blocks to keep ~88 KiB in flight.
+inline int blocks_per_cu(int nloads) { return std::max(1, (22 + nloads - 1) / nloads); }
+// Persistent grid: `per_cu` blocks on each CU (the caller caps it by the occupancy of its kernel), so every block is
+// co-resident and the grid-stride loops stay balanced; at most one block per tile and kMaxGrid in all, at least one.
+inline int persistent_grid(int num_cu, int per_cu, int64_t ntile) {
+  const int64_t g = std::min<int64_t>((int64_t)num_cu * per_cu, std::max<int64_t>(ntile, 1));
+  return (int)std::max<int64_t>(std::min<int64_t>(g, nka::kMaxGrid), 1);
+}
+// Tile tickets (k_combine_win, k_update_many_keep_win), in-process A/B (profiles/r02/ab_inproc_tile_tickets.txt): PB
+// -3...-10 % at n = 1e8 (the slower the box's static pass, the larger the gain), -2...-4 % at 1.25e7, 0 (m = 20) to -10 %
+// (m = 10) at 1e7, +3 % at 3e6 -> from 64 tiles of 512 elements per block.  ONE counter while a tile carries >= 22 words per
+// element and 512 elements (<= ~60 tickets/us), two below that (a single counter saturates).
+constexpr int kTicketTilesPerBlock = 64;
+// How many counters hand out the `ntile` tiles of `T` * 512 elements to `grid` blocks; 0 = static mapping.  `forced` >= 0 is
+// the caller's tuning field, < 0 the rule above.  None where the grid does not divide among the counters, where the tickets
+// (32-bit: the tiles plus what the blocks draw past the end) could wrap, or where the handle has no counters.
+inline int ticket_counters(int forced, bool have_counters, int64_t ntile, int T, int grid, int words) {
+  int ng = forced;
+  if (ng < 0) ng = (ntile * T >= (int64_t)kTicketTilesPerBlock * grid) ? (words >= 22 ? 1 : 2) : 0;
+  if (ng > 0 && (grid % ng != 0 || ntile >= ((int64_t)1 << 31) - 2 * nka::kMaxGrid || !have_counters)) ng = 0;
+  return ng;
+}
+// The same decision before the grid is known (one block per CU): will the automatic rule hand out `ntile` tiles by tickets?
+inline bool tickets_expected(int forced, bool have_counters, int64_t ntile, int num_cu) {
+  return forced != 0 && have_counters && ntile >= (int64_t)kTicketTilesPerBlock * num_cu;
+}
 
 // THE LIST WORD (include/nka_hip_ext.h: nka_hip_list_bound).  PB of update number u publishes (u, list length at its exit).
 // The host's upper bound on the list length at the entry of the next update: its own count `ub`, tightened by the word if the

@@ -52,6 +52,7 @@ enum {
 };
 
 constexpr int kMaxPerPass = 32;  // largest MAXL / MAXK instantiated
+constexpr int kMaxGrid = 4096;   // upper bound on persistent grid size (partials buffer)
 
 constexpr int kStamps = 16;      // s_memtime stamps of the scalar step, written only when NKA_SOLVE_STAMPS is defined
 

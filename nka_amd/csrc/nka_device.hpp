@@ -15,8 +15,7 @@
 namespace nka {
 
 constexpr int kBlock = 256;  // 4 wavefronts of 64
-constexpr int kWavesPerBlock = kBlock / 64;
-constexpr int kMaxGrid = 4096;  // upper bound on persistent grid size (partials buffer)
+constexpr int kWavesPerBlock = kBlock / 64;   // (kMaxGrid, the bound on a persistent grid: nka_ctl.hpp)
 
 #ifdef NKA_SOLVE_STAMPS
 #define NKA_STAMP(ctl, i) do { if (threadIdx.x == 0) (ctl).stamps()[i] = (double)__builtin_amdgcn_s_memtime(); } while (0)

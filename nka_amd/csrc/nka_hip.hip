@@ -192,9 +192,12 @@ static inline double *buffer_at(const nka_hip_state *a, long long off) {
 
 namespace {
 
-// Persistent grid: one block per resident slot (occupancy of THIS instantiation
-// x CU count, capped by the tunable blocks-per-CU and by the number of tiles),
-// so every block is co-resident and the grid-stride loops stay balanced.
+// Persistent grid (host_logic.hpp: persistent_grid, blocks_per_cu, with the measurements behind them; ring sizes and
+// ticket counters of the rolling-window kernels: win_ring, win_ring_pairs, ticket_counters): one block per resident slot
+// -- occupancy of THIS instantiation x CU count, capped by the tunable blocks-per-CU and by the number of tiles.
+using nka_host::persistent_grid;
+using nka_host::win_ring;
+using nka_host::win_ring_pairs;
 template <typename K>
 int occupancy_of(K kernel) {
   int nb = 0;
@@ -202,18 +205,10 @@ int occupancy_of(K kernel) {
   return nb;
 }
 
-// `nloads` = 16-byte loads each thread keeps in flight per tile.  Measured on
-// MI355X (n = 1.25e7 and 1e8, m = 20): ONE block per CU is fastest once a block
-// has >= 22 loads per thread in flight (88 KiB per CU); more blocks per CU only
-// add write/read interleaving in the mixed pass (PB 0.46 -> 0.52 ms at 4 per CU).
-// Narrow instantiations get proportionally more blocks to keep ~88 KiB in flight.
+// `nloads` = 16-byte loads each thread keeps in flight per tile
 int grid_for(const nka_hip_state *a, int which, int vec, int occ, int nloads) {
-  const int64_t ntile = a->n / (kBlock * vec);
-  const int want = a->bpc[which] > 0 ? a->bpc[which] : std::max(1, (22 + nloads - 1) / nloads);
-  int64_t g = (int64_t)a->num_cu * std::min(occ, want);
-  g = std::min<int64_t>(g, std::max<int64_t>(ntile, 1));
-  g = std::min<int64_t>(g, kMaxGrid);
-  return (int)std::max<int64_t>(g, 1);
+  const int want = a->bpc[which] > 0 ? a->bpc[which] : nka_host::blocks_per_cu(nloads);
+  return persistent_grid(a->num_cu, std::min(occ, want), a->n / (kBlock * vec));
 }
 
 int rccl_allreduce(void *ctx, double *buf, int32_t count, void *stream) {
@@ -257,38 +252,19 @@ int launch_dots_1(const nka_hip_state *a, const double *f, int pass, int npass) 
 template <int MAXL, int W>
 int launch_dots_win_1(const nka_hip_state *a, const double *f, int bpc, int base, int pass, int ncover) {
   static const int occ = occupancy_of(k_dots_win<MAXL, W>);
-  const int64_t ntile = a->n / (kBlock * 2);
-  int64_t g = (int64_t)a->num_cu * std::min(occ, std::max(1, bpc));
-  g = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(g, std::max<int64_t>(ntile, 1)), kMaxGrid));
+  const int g = persistent_grid(a->num_cu, std::min(occ, std::max(1, bpc)), a->n / (kBlock * 2));
   if (a->weighted)
-    hipLaunchKernelGGL((k_dots_win<MAXL, W, true>), dim3((int)g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base,
+    hipLaunchKernelGGL((k_dots_win<MAXL, W, true>), dim3(g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base,
                        a->pa_normed, a->pa_skip);
   else
-    hipLaunchKernelGGL((k_dots_win<MAXL, W>), dim3((int)g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base, a->pa_normed,
+    hipLaunchKernelGGL((k_dots_win<MAXL, W>), dim3(g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f, a->partials, base, a->pa_normed,
                        a->pa_skip);
   // (Round 3 measured forming these sums -- and the scalar step -- in the tail of the PA launch, by the block that
   //  finishes last: 2-4 us SLOWER per update than the launches it saves, profiles/r03/ab_small_pa_tail_not_kept.txt.)
   hipLaunchKernelGGL((k_finalize_dots<MAXL>), dim3(2 * MAXL + 2), dim3(kFinThreads), 0, a->stream, a->ctl,
-                     a->partials, (int)g, pass, ncover < 0 ? MAXL : ncover, base, a->p2p_fused ? a->p2p : P2P{}, a->pa_normed ? 1 : 0,
+                     a->partials, g, pass, ncover < 0 ? MAXL : ncover, base, a->p2p_fused ? a->p2p : P2P{}, a->pa_normed ? 1 : 0,
                      a->pa_skip);
-  return (int)g;
-}
-
-// The ring size: a small divisor of the width (4, 5, 6, 3 or 7), or the width itself when it
-// is prime (then every load of a tile is in flight and each is re-issued for the next tile
-// as soon as it has been consumed).  Rings of 2, MAXL/4 and MAXL/2 measured slower than 4
-// (profiles/r02/ab_inproc_pipelined_passes.txt).
-template <int MAXL>
-constexpr int win_ring() {
-  return MAXL % 4 == 0 ? 4 : MAXL % 5 == 0 ? 5 : MAXL % 6 == 0 ? 6 : MAXL % 3 == 0 ? 3 : MAXL % 7 == 0 ? 7 : MAXL;
-}
-
-// The flavours that stream TWO vectors per pair (F08, F08-vector) keep the same number of loads in
-// flight with half the ring: 2 pairs where the width is even (in-process A/B at m = 20: -3.5 % at
-// n = 1.25e7, equal at 1e8; the compact flavour loses 13 % with a ring of 2 single loads).
-template <int MAXK>
-constexpr int win_ring_pairs() {
-  return MAXK % 2 == 0 ? 2 : MAXK % 3 == 0 ? 3 : MAXK % 5 == 0 ? 5 : MAXK % 7 == 0 ? 7 : MAXK;
+  return g;
 }
 
 // Instantiated for EVERY width 1..32 so that no list length needs padding: a padded ring slot is a cache hit that starves
@@ -313,7 +289,7 @@ static inline int window_width(int w) { return ((std::max(w, 1) + 3) / 4) * 4; }
 // (base, pass, ncover: the balanced passes of a list longer than kMaxPerPass, enqueue_pa; one launch: 0, 0, its own width)
 int launch_dots_win(int width, const nka_hip_state *a, const double *f, int bpc, int base = 0, int pass = 0, int ncover = -1) {
 #define CASE(L) \
-  case L: return launch_dots_win_1<L, win_ring<L>()>(a, f, bpc, base, pass, ncover);
+  case L: return launch_dots_win_1<L, win_ring(L)>(a, f, bpc, base, pass, ncover);
   switch (window_width(width)) {
     NKA_WIDTH_CASES
   }
@@ -362,25 +338,18 @@ template <int MAXK, int COMB, int W, int T = 1>
 int launch_combine_win_1(const nka_hip_state *a, double *f, int bpc, int base) {
   static const int occ = occupancy_of(k_combine_win<MAXK, COMB, W, T>);
   const int64_t ntile = a->n / (kBlock * 2 * T);
-  int64_t g = (int64_t)a->num_cu * std::min(occ, std::max(1, bpc));
-  g = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(g, std::max<int64_t>(ntile, 1)), kMaxGrid));
-  // Tile tickets (k_combine_win), in-process A/B (profiles/r02/ab_inproc_tile_tickets.txt): PB -3...-10 %
-  // at n = 1e8 (the slower the box's static pass, the larger the gain), -2...-4 % at 1.25e7, 0 (m = 20) to
-  // -10 % (m = 10) at 1e7, +3 % at 3e6 -> from 64 tiles of 512 elements per block.  ONE counter while a tile carries >= 22
-  // words per element and 512 elements (<= ~60 tickets/us), two below that (a single counter saturates).
-  constexpr int words = ((COMB == 2 ? MAXK + 2 : 2 * MAXK + 1) + 5) * T;
-  int ng = a->pb_tickets;
-  if (ng < 0) ng = (ntile * T >= 64 * g) ? (words >= 22 ? 1 : 2) : 0;
-  if (ng > 0 && (g % ng != 0 || ntile >= ((int64_t)1 << 31) - 2 * kMaxGrid || !a->tickets)) ng = 0;
+  const int g = persistent_grid(a->num_cu, std::min(occ, std::max(1, bpc)), ntile);
+  constexpr int words = ((COMB == 2 ? MAXK + 2 : 2 * MAXK + 1) + 5) * T;      // per element of a tile
+  const int ng = nka_host::ticket_counters(a->pb_tickets, a->tickets != nullptr, ntile, T, g, words);
   const int tail = (ntile * (kBlock * 2 * T) < a->n) ? 1 : 0;     // the ragged tail has a block of its own (k_combine_win)
-  hipLaunchKernelGGL((k_combine_win<MAXK, COMB, W, T>), dim3((int)g + tail), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f,
+  hipLaunchKernelGGL((k_combine_win<MAXK, COMB, W, T>), dim3(g + tail), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f,
                      ng > 0 ? a->tickets : nullptr, std::max(ng, 1), a->pb_flags, base);
-  return (int)g;
+  return g;
 }
 
-// does the automatic rule hand out the tiles of this accelerator's PB by tickets? (see launch_combine_win_1)
+// does the automatic rule hand out the tiles of this accelerator's PB by tickets? (before the grid is known)
 bool pb_tickets_apply(const nka_hip_state *a) {
-  return a->pb_tickets != 0 && a->tickets && a->n / (kBlock * 2) >= (int64_t)64 * a->num_cu;
+  return nka_host::tickets_expected(a->pb_tickets, a->tickets != nullptr, a->n / (kBlock * 2), a->num_cu);
 }
 
 // One width: the shortest lists (a 512-element tile carries <= 14 words per element) exist with
@@ -390,7 +359,7 @@ bool pb_tickets_apply(const nka_hip_state *a) {
 // (2.110 vs 2.148 ms; two-vector m = 5, 16 words: 2.040 vs 2.028) -- profiles/r02/ab_inproc_tile_tickets.txt.
 template <int K, int COMB>
 int launch_combine_win_k(const nka_hip_state *a, double *f, int bpc, int base) {
-  constexpr int W = (COMB == 2 ? win_ring<K>() : win_ring_pairs<K>());
+  constexpr int W = (COMB == 2 ? win_ring(K) : win_ring_pairs(K));
   constexpr int words = (COMB == 2 ? K + 2 : 2 * K + 1) + 5;
   if constexpr (words <= 14) {
     if (a->pb_tile == 2 || (a->pb_tile < 0 && pb_tickets_apply(a))) return launch_combine_win_1<K, COMB, W, 2>(a, f, bpc, base);

@@ -526,15 +526,12 @@ __global__ __launch_bounds__(kBlock) void k_update_many_keep(int64_t n, double *
 // requested one tile ahead.  4-6 loads in flight per wave move more bytes per second
 // than all of a tile's loads at once (profiles/r02/hbm_probe_rolling_window.txt).  Same
 // arithmetic in the same order => same bits as the kernels above.
-// The ring size: a small divisor of the width (4, 5, 6, 3 or 7), or the width itself when it is
-// prime.  The window kernels are instantiated for EVERY width 1..kManyMax: a padded entry is a
-// cache hit that occupies a ring slot and starves the window (nka_hip.hip:win_ring).
-template <int NV>
-constexpr int win_ring() {
-  return NV % 4 == 0 ? 4 : NV % 5 == 0 ? 5 : NV % 6 == 0 ? 6 : NV % 3 == 0 ? 3 : NV % 7 == 0 ? 7 : NV;
-}
+// The ring size: host_logic.hpp (win_ring; two vectors per entry: win_ring_pairs).  The window kernels are instantiated
+// for EVERY width 1..kManyMax: a padded entry is a cache hit that occupies a ring slot and starves the window.
+using nka_host::win_ring;
+using nka_host::win_ring_pairs;
 
-template <int NV, bool SUB, bool PRE, bool DD = false, int kWin = win_ring<NV>()>
+template <int NV, bool SUB, bool PRE, bool DD = false, int kWin = win_ring(NV)>
 __global__ __launch_bounds__(kBlock) void k_scale_dot_pair_many_win(int64_t n, double *w, double *v, double a,
                                                                     double pre_a, const double *__restrict__ f,
                                                                     ManyArgs m, double *__restrict__ partials, int store) {
@@ -626,13 +623,7 @@ __global__ __launch_bounds__(kBlock) void k_scale_dot_pair_many_win(int64_t n, d
   block_reduce_store<NA>(acc, partials, G);
 }
 
-// two vectors per entry: half the ring keeps the same number of loads in flight (nka_hip.hip:win_ring_pairs)
-template <int NV>
-constexpr int win_ring_pairs() {
-  return NV % 2 == 0 ? 2 : NV % 3 == 0 ? 3 : NV % 5 == 0 ? 5 : NV % 7 == 0 ? 7 : NV;
-}
-
-template <int NV, bool PAIRS, int kWin = (PAIRS ? win_ring_pairs<NV>() : win_ring<NV>())>
+template <int NV, bool PAIRS, int kWin = (PAIRS ? win_ring_pairs(NV) : win_ring(NV))>
 __global__ __launch_bounds__(kBlock) void k_update_many_keep_win(int64_t n, double *z, ManyArgs m, double *keep_in,
                                                                  double *keep_out, unsigned *tickets, int ng, Pend pd) {
   // `tickets` != nullptr: tiles from global ticket counters (compact front), as in k_combine_win
@@ -751,12 +742,9 @@ __global__ __launch_bounds__(kBlock) void k_update_many_keep_win(int64_t n, doub
 // Persistent grid.  Light kernels (a few loads per thread) fill the chip with 8
 // blocks per CU; the fused many-vector kernels keep `nloads` 16-byte loads per
 // thread in flight and follow the rule measured for the array flavour (ONE block
-// per CU once a block has >= 22 loads per thread in flight; nka_hip.hip:grid_for).
+// per CU once a block has >= 22 loads per thread in flight; host_logic.hpp: blocks_per_cu, persistent_grid).
 int grid_for(const nka_hip_vec_ws *ws, int64_t n, int vec, int nloads = 2) {
-  const int per_cu = std::max(1, std::min(8, (22 + nloads - 1) / nloads));
-  int64_t g = (int64_t)ws->num_cu * per_cu;
-  g = std::min<int64_t>(g, std::max<int64_t>(n / (kBlock * vec), 1));
-  return (int)std::min<int64_t>(g, kMaxGrid);
+  return nka_host::persistent_grid(ws->num_cu, std::min(8, nka_host::blocks_per_cu(nloads)), n / (kBlock * vec));
 }
 
 int width_for(int count) { return std::max(4, ((count + 3) / 4) * 4); }   // unroll width 4, 8, ..., kManyMax
@@ -783,6 +771,35 @@ int width_for(int count) { return std::max(4, ((count + 3) / 4) * 4); }   // unr
 static_assert(kManyMax == 24, "NKA_DISPATCH_EXACT covers widths 1..24");
 
 bool al16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// One launch group of a list: entries [base, base + count) of xs (with a) and, where given, ys (with b).  Returns whether
+// every vector of the group is 16-byte aligned.
+bool fill_many(ManyArgs &m, const double *const *xs, const double *a, const double *const *ys, const double *b, int base,
+               int count) {
+  bool v2 = true;
+  m.count = count;
+  for (int j = 0; j < count; j++) {
+    m.x[j] = xs[base + j];
+    if (a) m.a[j] = a[base + j];
+    v2 = v2 && al16(m.x[j]);
+    if (ys) {
+      m.y[j] = ys[base + j];
+      m.b[j] = b[base + j];
+      v2 = v2 && al16(m.y[j]);
+    }
+  }
+  return v2;
+}
+
+// the pointer check of a list (of two lists, entry by entry: ys may be null)
+int check_list_spans(const double *const *xs, const double *const *ys, int count, int64_t n, const char *whox,
+                     const char *whoy = nullptr) {
+  for (int j = 0; j < count; j++) {
+    if (int rc = nka_detail::check_device_span(xs[j], n, whox)) return rc;
+    if (ys) if (int rc = nka_detail::check_device_span(ys[j], n, whoy)) return rc;
+  }
+  return 0;
+}
 
 template <int OP>
 int run_elementwise(nka_hip_vec_ws *ws, int64_t n, double *z, const double *x, const double *y, double a, double b,
@@ -821,38 +838,23 @@ int update_many_keep(nka_hip_vec_ws_t ws, int64_t n, double *z, const double *a,
   if (int rc = nka_detail::check_device_span(z, n, who)) return rc;
   if (keep_in) if (int rc = nka_detail::check_device_span(keep_in, n, who)) return rc;
   if (keep_out) if (int rc = nka_detail::check_device_span(keep_out, n, who)) return rc;
-  for (int j = 0; j < count; j++) {
-    if (int rc = nka_detail::check_device_span(xs[j], n, who)) return rc;
-    if (PAIRS) if (int rc = nka_detail::check_device_span(ys[j], n, who)) return rc;
-  }
+  if (int rc = check_list_spans(xs, PAIRS ? ys : nullptr, count, n, who, who)) return rc;
   int base = 0;
   const int ngroups = many_groups(count);
   for (int grp = 0; grp < ngroups; grp++) {   // at least one launch: with count == 0 the two keeps are still written
     ManyArgs m{};
-    m.count = many_group_width(count, grp);
     double *kin = (grp == 0) ? keep_in : nullptr;
     double *kout = (grp == ngroups - 1) ? keep_out : nullptr;
-    bool v2 = al16(z) && (!kin || al16(kin)) && (!kout || al16(kout));
-    for (int j = 0; j < m.count; j++) {
-      m.x[j] = xs[base + j];
-      m.a[j] = a[base + j];
-      v2 = v2 && al16(m.x[j]);
-      if (PAIRS) {
-        m.y[j] = ys[base + j];
-        m.b[j] = b[base + j];
-        v2 = v2 && al16(m.y[j]);
-      }
-    }
+    bool v2 = fill_many(m, xs, a, PAIRS ? ys : nullptr, b, base, many_group_width(count, grp)) && al16(z) &&
+              (!kin || al16(kin)) && (!kout || al16(kout));
     Pend pd = (base == 0) ? pend : Pend();     // the pending pair is entry 0 of the first launch
     if ((pd.flags & 1) && !PAIRS) v2 = v2 && al16(pd.w);
     const bool win = v2;                                                    // 16-byte path = the rolling-window kernel
     const int nv = win ? std::max(m.count, 1) : width_for(m.count);      // window kernels: exact width, no padding
     const int g = grid_for(ws, n, v2 ? 2 : 1, win ? 22 : (PAIRS ? 2 : 1) * nv + 1);   // rolling-window kernels: one block per CU
-    // tile tickets (k_combine_win): one counter while a tile carries >= 22 words per element, else two
+    // tile tickets, window kernels only (host_logic.hpp: ticket_counters; `words` per element of a tile)
     const int words = (PAIRS ? 2 : 1) * nv + 1 + 1 + (kin ? 1 : 0) + (kout ? 1 : 0) + ((pd.flags & 1) ? (PAIRS ? 2 : 3) : 0);
-    int ng = ws->ticket_groups;
-    if (ng < 0) ng = (win && n / (kBlock * 2) >= (int64_t)64 * g) ? (words >= 22 ? 1 : 2) : 0;
-    if (!win || !ws->tickets || g % std::max(ng, 1) != 0 || n / (kBlock * 2) >= ((int64_t)1 << 31) - 2 * kMaxGrid) ng = 0;
+    const int ng = win ? nka_host::ticket_counters(ws->ticket_groups, ws->tickets != nullptr, n / (kBlock * 2), 1, g, words) : 0;
     unsigned *const tix = ng > 0 ? ws->tickets : nullptr;
 #define LAUNCHW(NV) hipLaunchKernelGGL((k_update_many_keep_win<NV, PAIRS>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, m, kin, kout, tix, std::max(ng, 1), pd)
 #define LAUNCH1(NV) hipLaunchKernelGGL((k_update_many_keep<NV, 1, PAIRS>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, m, kin, kout, pd)
@@ -955,6 +957,24 @@ int fetch_sums(nka_hip_vec_ws_t ws, int g, int rows, int nv, int count, int extr
   HIP_TRY(hipMemcpyAsync(ws->host_results, ws->red_dev, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ws->stream));
   HIP_TRY(hipStreamSynchronize(ws->stream));
   return run_host_hook(ws, ws->host_results, total);
+}
+
+// ... and out of ws->host_results: the canonical layout [row 0, row 1, cross, <d,d>] of `count` columns (null: not wanted)
+void take_sums(const nka_hip_vec_ws *ws, int count, double *row0, double *row1, double *cross, double *dd) {
+  for (int j = 0; j < count; j++) {
+    row0[j] = ws->host_results[j];
+    if (row1) row1[j] = ws->host_results[count + j];
+  }
+  if (cross) *cross = ws->host_results[2 * count];
+  if (dd) *dd = ws->host_results[2 * count + 1];
+}
+
+// The batched reductions sum in blocks: refused under reference-order sums (the vector types fall back to the deferred hooks
+// then: dot(), whose sum IS ordered).
+int blocked_sums_only(const nka_hip_vec_ws *ws) {
+  if (!ws || ws->sum_order != 1) return 0;
+  return nka_detail::set_error(NKA_HIP_ESTATE, "this batched reduction sums in blocks; with reference-order sums "
+                               "(nka_hip_vec_set_sum_order) the vector type must use dot() / norm2()");
 }
 
 int rccl_vec_allreduce(void *ctx, double *buf, int32_t count, void *stream) {
@@ -1097,41 +1117,31 @@ int nka_hip_vec_norm2(nka_hip_vec_ws_t ws, int64_t n, const double *x, double *h
 // vals[j] = <x, ys[j]>, j < count: x is read once per group of kManyMax vectors.
 static int nka_hip_vec_dot_many_entry(nka_hip_vec_ws_t ws, int64_t n, const double *x, const double *const *ys, int32_t count,
                          double *host_vals) {
-  if (ws && ws->sum_order == 1)     // (the vector types fall back to the deferred hooks then: dot(), whose sum IS ordered)
-    return nka_detail::set_error(NKA_HIP_ESTATE, "this batched reduction sums in blocks; with reference-order sums "
-                                 "(nka_hip_vec_set_sum_order) the vector type must use dot() / norm2()");
+  if (int rc = blocked_sums_only(ws)) return rc;
   if (!ws || n < 0 || count < 0 || (count > 0 && (!ys || !host_vals))) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   for (int j = 0; j < count; j++) host_vals[j] = 0.0;
   if (count == 0 || (n == 0 && !ws_parallel(ws))) return 0;
   HIP_TRY(hipSetDevice(ws->device));
   if (n > 0) {
     if (int rc = nka_detail::check_device_span(x, n, "vec_dot_many: x")) return rc;
-    for (int j = 0; j < count; j++)
-      if (int rc = nka_detail::check_device_span(ys[j], n, "vec_dot_many: ys[j]")) return rc;
+    if (int rc = check_list_spans(ys, nullptr, count, n, "vec_dot_many: ys[j]")) return rc;
   }
   for (int base = 0; base < count; base += kManyMax) {
     ManyArgs m{};
-    m.count = std::min(kManyMax, count - base);
-    if (n == 0) {                      // empty slice: zeros, but the collective is still joined
-      if (int rc = fetch_sums(ws, 1, 1, m.count, m.count, 0, false)) return rc;
-      for (int j = 0; j < m.count; j++) host_vals[base + j] = ws->host_results[j];
-      continue;
-    }
-    bool v2 = al16(x);
-    for (int j = 0; j < m.count; j++) {
-      m.x[j] = ys[base + j];
-      v2 = v2 && al16(m.x[j]);
-    }
-    const int nv = width_for(m.count);
-    const int g = grid_for(ws, n, v2 ? 2 : 1, nv + 1);
+    const bool v2 = fill_many(m, ys, nullptr, nullptr, nullptr, base, std::min(kManyMax, count - base)) && al16(x);
+    int nv = std::max(m.count, 1), g = 1;     // empty slice (n == 0): no launch, zeros, but the collective is still joined
+    if (n > 0) {
+      nv = width_for(m.count);
+      g = grid_for(ws, n, v2 ? 2 : 1, nv + 1);
 #define LAUNCH2(NV) hipLaunchKernelGGL((k_dot_many<NV, 2>), dim3(g), dim3(kBlock), 0, ws->stream, n, x, m, ws->partials)
 #define LAUNCH1(NV) hipLaunchKernelGGL((k_dot_many<NV, 1>), dim3(g), dim3(kBlock), 0, ws->stream, n, x, m, ws->partials)
-    if (v2) { NKA_DISPATCH_NV(nv, LAUNCH2) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }
+      if (v2) { NKA_DISPATCH_NV(nv, LAUNCH2) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }
 #undef LAUNCH2
 #undef LAUNCH1
-    HIP_TRY(hipGetLastError());
-    if (int rc = fetch_sums(ws, g, 1, nv, m.count, 0, true)) return rc;
-    for (int j = 0; j < m.count; j++) host_vals[base + j] = ws->host_results[j];
+      HIP_TRY(hipGetLastError());
+    }
+    if (int rc = fetch_sums(ws, g, 1, nv, m.count, 0, n > 0)) return rc;
+    take_sums(ws, m.count, host_vals + base, nullptr, nullptr, nullptr);
   }
   return 0;
 }
@@ -1145,9 +1155,7 @@ int nka_hip_vec_dot_many(nka_hip_vec_ws_t ws, int64_t n, const double *x, const 
 static int nka_hip_vec_dot_pair_many_entry(nka_hip_vec_ws_t ws, int64_t n, const double *x0, const double *x1,
                               const double *const *ys, int32_t count, double *host_vals0, double *host_vals1,
                               double *host_cross) {
-  if (ws && ws->sum_order == 1)     // (the vector types fall back to the deferred hooks then: dot(), whose sum IS ordered)
-    return nka_detail::set_error(NKA_HIP_ESTATE, "this batched reduction sums in blocks; with reference-order sums "
-                                 "(nka_hip_vec_set_sum_order) the vector type must use dot() / norm2()");
+  if (int rc = blocked_sums_only(ws)) return rc;
   if (!ws || n < 0 || count < 0 || !host_cross || (count > 0 && (!ys || !host_vals0 || !host_vals1)))
     return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   *host_cross = 0.0;
@@ -1157,42 +1165,26 @@ static int nka_hip_vec_dot_pair_many_entry(nka_hip_vec_ws_t ws, int64_t n, const
   if (n > 0) {
     if (int rc = nka_detail::check_device_span(x0, n, "vec_dot_pair_many: x0")) return rc;
     if (int rc = nka_detail::check_device_span(x1, n, "vec_dot_pair_many: x1")) return rc;
-    for (int j = 0; j < count; j++)
-      if (int rc = nka_detail::check_device_span(ys[j], n, "vec_dot_pair_many: ys[j]")) return rc;
+    if (int rc = check_list_spans(ys, nullptr, count, n, "vec_dot_pair_many: ys[j]")) return rc;
   }
   int base = 0;
   do {  // at least one launch so that <x0,x1> is computed even when count == 0
     ManyArgs m{};
-    m.count = std::max(0, std::min(kManyMax, count - base));
-    if (n == 0) {                      // empty slice: zeros, but the collective is still joined
-      if (int rc = fetch_sums(ws, 1, 2, std::max(m.count, 1), m.count, 1, false)) return rc;
-      for (int j = 0; j < m.count; j++) {
-        host_vals0[base + j] = ws->host_results[j];
-        host_vals1[base + j] = ws->host_results[m.count + j];
-      }
-      if (base == 0) *host_cross = ws->host_results[2 * m.count];
-      base += kManyMax;
-      continue;
-    }
-    bool v2 = al16(x0) && al16(x1);
-    for (int j = 0; j < m.count; j++) {
-      m.x[j] = ys[base + j];
-      v2 = v2 && al16(m.x[j]);
-    }
-    const int nv = width_for(m.count);
-    const int g = grid_for(ws, n, v2 ? 2 : 1, nv + 2);
+    const bool v2 = fill_many(m, ys, nullptr, nullptr, nullptr, base, std::max(0, std::min(kManyMax, count - base))) &&
+                    al16(x0) && al16(x1);
+    int nv = std::max(m.count, 1), g = 1;     // empty slice (n == 0): no launch, zeros, but the collective is still joined
+    if (n > 0) {
+      nv = width_for(m.count);
+      g = grid_for(ws, n, v2 ? 2 : 1, nv + 2);
 #define LAUNCH2(NV) hipLaunchKernelGGL((k_dot_pair_many<NV, 2>), dim3(g), dim3(kBlock), 0, ws->stream, n, x0, x1, m, ws->partials)
 #define LAUNCH1(NV) hipLaunchKernelGGL((k_dot_pair_many<NV, 1>), dim3(g), dim3(kBlock), 0, ws->stream, n, x0, x1, m, ws->partials)
-    if (v2) { NKA_DISPATCH_NV(nv, LAUNCH2) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }
+      if (v2) { NKA_DISPATCH_NV(nv, LAUNCH2) } else { NKA_DISPATCH_NV(nv, LAUNCH1) }
 #undef LAUNCH2
 #undef LAUNCH1
-    HIP_TRY(hipGetLastError());
-    if (int rc = fetch_sums(ws, g, 2, nv, m.count, 1, true)) return rc;
-    for (int j = 0; j < m.count; j++) {
-      host_vals0[base + j] = ws->host_results[j];
-      host_vals1[base + j] = ws->host_results[m.count + j];
+      HIP_TRY(hipGetLastError());
     }
-    if (base == 0) *host_cross = ws->host_results[2 * m.count];
+    if (int rc = fetch_sums(ws, g, 2, nv, m.count, 1, n > 0)) return rc;
+    take_sums(ws, m.count, host_vals0 + base, host_vals1 + base, base == 0 ? host_cross : nullptr, nullptr);
     base += kManyMax;
   } while (base < count);
   return 0;
@@ -1211,21 +1203,10 @@ int nka_hip_vec_update_many(nka_hip_vec_ws_t ws, int64_t n, double *z, const dou
   if (n == 0 || count == 0) return 0;
   HIP_TRY(hipSetDevice(ws->device));
   if (int rc = nka_detail::check_device_span(z, n, "vec_update_many: z")) return rc;
-  for (int j = 0; j < count; j++) {
-    if (int rc = nka_detail::check_device_span(xs[j], n, "vec_update_many: xs[j]")) return rc;
-    if (int rc = nka_detail::check_device_span(ys[j], n, "vec_update_many: ys[j]")) return rc;
-  }
+  if (int rc = check_list_spans(xs, ys, count, n, "vec_update_many: xs[j]", "vec_update_many: ys[j]")) return rc;
   for (int base = 0; base < count; base += kManyMax) {
     ManyArgs m{};
-    m.count = std::min(kManyMax, count - base);
-    bool v2 = al16(z);
-    for (int j = 0; j < m.count; j++) {
-      m.x[j] = xs[base + j];
-      m.y[j] = ys[base + j];
-      m.a[j] = a[base + j];
-      m.b[j] = b[base + j];
-      v2 = v2 && al16(m.x[j]) && al16(m.y[j]);
-    }
+    const bool v2 = fill_many(m, xs, a, ys, b, base, std::min(kManyMax, count - base)) && al16(z);
     const int nv = width_for(m.count);
     const int g = grid_for(ws, n, v2 ? 2 : 1, 2 * nv + 1);
 #define LAUNCH2(NV) hipLaunchKernelGGL((k_update_many<NV, 2>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, m)
@@ -1246,17 +1227,10 @@ int nka_hip_vec_axpy_many(nka_hip_vec_ws_t ws, int64_t n, double *z, const doubl
   if (n == 0 || count == 0) return 0;
   HIP_TRY(hipSetDevice(ws->device));
   if (int rc = nka_detail::check_device_span(z, n, "vec_axpy_many: z")) return rc;
-  for (int j = 0; j < count; j++)
-    if (int rc = nka_detail::check_device_span(xs[j], n, "vec_axpy_many: xs[j]")) return rc;
+  if (int rc = check_list_spans(xs, nullptr, count, n, "vec_axpy_many: xs[j]")) return rc;
   for (int base = 0; base < count; base += kManyMax) {
     ManyArgs m{};
-    m.count = std::min(kManyMax, count - base);
-    bool v2 = al16(z);
-    for (int j = 0; j < m.count; j++) {
-      m.x[j] = xs[base + j];
-      m.a[j] = a[base + j];
-      v2 = v2 && al16(m.x[j]);
-    }
+    const bool v2 = fill_many(m, xs, a, nullptr, nullptr, base, std::min(kManyMax, count - base)) && al16(z);
     const int nv = width_for(m.count);
     const int g = grid_for(ws, n, v2 ? 2 : 1, nv + 1);
 #define LAUNCH2(NV) hipLaunchKernelGGL((k_axpy_many<NV, 2>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, m)
@@ -1276,32 +1250,28 @@ int nka_hip_vec_axpy_many(nka_hip_vec_ws_t ws, int64_t n, double *z, const doubl
 // caller applies the update in the next stage, nka_hip_vec_scale_dot_pair_many with pre).
 static int nka_hip_vec_update_norm2_entry(nka_hip_vec_ws_t ws, int64_t n, double *z, double a, const double *x, int32_t store,
                              double *host_norm) {
-  if (ws && ws->sum_order == 1)     // (the vector types fall back to the deferred hooks then: dot(), whose sum IS ordered)
-    return nka_detail::set_error(NKA_HIP_ESTATE, "this batched reduction sums in blocks; with reference-order sums "
-                                 "(nka_hip_vec_set_sum_order) the vector type must use dot() / norm2()");
+  if (int rc = blocked_sums_only(ws)) return rc;
   if (!ws || !host_norm || n < 0) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   *host_norm = 0.0;
   if (n == 0 && !ws_parallel(ws)) return 0;
   HIP_TRY(hipSetDevice(ws->device));
-  if (n == 0) {                        // empty slice: zero, but the collective is still joined
-    if (int rc = fetch_sums(ws, 1, 1, 1, 1, 0, false)) return rc;
-    *host_norm = std::sqrt(ws->host_results[0]);
-    return 0;
+  int g = 1;                           // empty slice (n == 0): no launch, zero, but the collective is still joined
+  if (n > 0) {
+    if (int rc = nka_detail::check_device_span(z, n, "vec_update_norm2: z")) return rc;
+    if (int rc = nka_detail::check_device_span(x, n, "vec_update_norm2: x")) return rc;
+    const bool v2 = al16(z) && al16(x);
+    g = grid_for(ws, n, v2 ? 2 : 1);
+    if (v2 && store)
+      hipLaunchKernelGGL((k_update_norm2<2, true>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
+    else if (v2)
+      hipLaunchKernelGGL((k_update_norm2<2, false>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
+    else if (store)
+      hipLaunchKernelGGL((k_update_norm2<1, true>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
+    else
+      hipLaunchKernelGGL((k_update_norm2<1, false>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
+    HIP_TRY(hipGetLastError());
   }
-  if (int rc = nka_detail::check_device_span(z, n, "vec_update_norm2: z")) return rc;
-  if (int rc = nka_detail::check_device_span(x, n, "vec_update_norm2: x")) return rc;
-  const bool v2 = al16(z) && al16(x);
-  const int g = grid_for(ws, n, v2 ? 2 : 1);
-  if (v2 && store)
-    hipLaunchKernelGGL((k_update_norm2<2, true>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
-  else if (v2)
-    hipLaunchKernelGGL((k_update_norm2<2, false>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
-  else if (store)
-    hipLaunchKernelGGL((k_update_norm2<1, true>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
-  else
-    hipLaunchKernelGGL((k_update_norm2<1, false>), dim3(g), dim3(kBlock), 0, ws->stream, n, z, x, a, ws->partials);
-  HIP_TRY(hipGetLastError());
-  if (int rc = fetch_sums(ws, g, 1, 1, 1, 0, true)) return rc;
+  if (int rc = fetch_sums(ws, g, 1, 1, 1, 0, n > 0)) return rc;
   *host_norm = std::sqrt(ws->host_results[0]);     // the square root of the GLOBAL sum
   return 0;
 }
@@ -1321,9 +1291,7 @@ static int scale_dot_pair_many_impl(nka_hip_vec_ws_t ws, int64_t n, double *w, d
 static int nka_hip_vec_scale_dot_pair_many_entry(nka_hip_vec_ws_t ws, int64_t n, double *w, double *v, double a, int32_t subtract,
                                     int32_t pre, double pre_a, const double *f, const double *const *ys, int32_t count,
                                     double *host_vals_w, double *host_vals_f, double *host_cross) {
-  if (ws && ws->sum_order == 1)     // (the vector types fall back to the deferred hooks then: dot(), whose sum IS ordered)
-    return nka_detail::set_error(NKA_HIP_ESTATE, "this batched reduction sums in blocks; with reference-order sums "
-                                 "(nka_hip_vec_set_sum_order) the vector type must use dot() / norm2()");
+  if (int rc = blocked_sums_only(ws)) return rc;
   return scale_dot_pair_many_impl(ws, n, w, v, a, subtract, pre, pre_a, f, ys, count, host_vals_w, host_vals_f, host_cross, 1);
 }
 int nka_hip_vec_scale_dot_pair_many(nka_hip_vec_ws_t ws, int64_t n, double *w, double *v, double a, int32_t subtract,
@@ -1338,9 +1306,7 @@ int nka_hip_vec_scale_dot_pair_many(nka_hip_vec_ws_t ws, int64_t n, double *w, d
 static int nka_hip_vec_dot_pair_many_scaled_entry(nka_hip_vec_ws_t ws, int64_t n, const double *w, double a, int32_t pre, double pre_a,
                                      const double *f, const double *const *ys, int32_t count, double *host_vals_w,
                                      double *host_vals_f, double *host_cross) {
-  if (ws && ws->sum_order == 1)     // (the vector types fall back to the deferred hooks then: dot(), whose sum IS ordered)
-    return nka_detail::set_error(NKA_HIP_ESTATE, "this batched reduction sums in blocks; with reference-order sums "
-                                 "(nka_hip_vec_set_sum_order) the vector type must use dot() / norm2()");
+  if (int rc = blocked_sums_only(ws)) return rc;
   // (a list longer than one launch: balanced groups, each forming w' in registers again -- a pure-read stage, nothing to undo;
   //  <f,w'> comes from the first group)
   const int ngroups = many_groups(count);
@@ -1368,9 +1334,7 @@ int nka_hip_vec_dot_pair_many_scaled(nka_hip_vec_ws_t ws, int64_t n, const doubl
 static int nka_hip_vec_diff_norm_dot_pair_many_entry(nka_hip_vec_ws_t ws, int64_t n, const double *z, double a, const double *x,
                                         const double *const *ys, int32_t count, double *host_dd, double *host_vals_z,
                                         double *host_vals_x, double *host_cross) {
-  if (ws && ws->sum_order == 1)     // (the vector types fall back to the deferred hooks then: dot(), whose sum IS ordered)
-    return nka_detail::set_error(NKA_HIP_ESTATE, "this batched reduction sums in blocks; with reference-order sums "
-                                 "(nka_hip_vec_set_sum_order) the vector type must use dot() / norm2()");
+  if (int rc = blocked_sums_only(ws)) return rc;
   if (!host_dd) return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
   // (a list longer than one launch: balanced groups, d = a*x + z formed in registers again by each -- pure read; <d,d> and
   //  <x,d> come from the first group)
@@ -1401,43 +1365,21 @@ static int scale_dot_pair_many_impl(nka_hip_vec_ws_t ws, int64_t n, double *w, d
                                     double *host_dd) {
   if (!ws || n < 0 || count < 0 || !host_cross || (count > 0 && (!ys || !host_vals_w || !host_vals_f)))
     return nka_detail::set_error(NKA_HIP_EINVAL, "bad argument");
-  const int extra = host_dd ? 2 : 1;
   *host_cross = 0.0;
   for (int j = 0; j < count; j++) host_vals_w[j] = host_vals_f[j] = 0.0;
   if (n == 0 && !ws_parallel(ws)) return 0;
   HIP_TRY(hipSetDevice(ws->device));
-  if (n == 0) {                        // empty slice: zeros, but every collective is still joined
-    const int c0 = std::min(kManyMax, count);
-    if (int rc = fetch_sums(ws, 1, 2, std::max(c0, 1), c0, extra, false)) return rc;
-    for (int j = 0; j < c0; j++) {
-      host_vals_w[j] = ws->host_results[j];
-      host_vals_f[j] = ws->host_results[c0 + j];
-    }
-    *host_cross = ws->host_results[2 * c0];
-    if (host_dd) *host_dd = ws->host_results[2 * c0 + 1];
-    if (count > kManyMax) {
-      double cross_again = 0.0;
-      return nka_hip_vec_dot_pair_many(ws, n, w, f, ys + kManyMax, count - kManyMax, host_vals_w + kManyMax,
-                                       host_vals_f + kManyMax, &cross_again);
-    }
-    return 0;
-  }
-  if (int rc = nka_detail::check_device_span(w, n, "vec_scale_dot_pair_many: w")) return rc;
-  if (int rc = nka_detail::check_device_span(v, n, "vec_scale_dot_pair_many: v")) return rc;
-  if (int rc = nka_detail::check_device_span(f, n, "vec_scale_dot_pair_many: f")) return rc;
-  for (int j = 0; j < count; j++)
-    if (int rc = nka_detail::check_device_span(ys[j], n, "vec_scale_dot_pair_many: ys[j]")) return rc;
-  {
-    ManyArgs m{};
-    m.count = std::min(kManyMax, count);
-    bool v2 = al16(w) && al16(v) && al16(f);
-    for (int j = 0; j < m.count; j++) {
-      m.x[j] = ys[j];
-      v2 = v2 && al16(m.x[j]);
-    }
+  ManyArgs m{};
+  const bool v2 = fill_many(m, ys, nullptr, nullptr, nullptr, 0, std::min(kManyMax, count)) && al16(w) && al16(v) && al16(f);
+  int nv = std::max(m.count, 1), g = 1;       // empty slice (n == 0): no launch, zeros, but every collective is still joined
+  if (n > 0) {
+    if (int rc = nka_detail::check_device_span(w, n, "vec_scale_dot_pair_many: w")) return rc;
+    if (int rc = nka_detail::check_device_span(v, n, "vec_scale_dot_pair_many: v")) return rc;
+    if (int rc = nka_detail::check_device_span(f, n, "vec_scale_dot_pair_many: f")) return rc;
+    if (int rc = check_list_spans(ys, nullptr, count, n, "vec_scale_dot_pair_many: ys[j]")) return rc;
     const bool win = v2;                                                    // 16-byte path = the rolling-window kernel
-    const int nv = win ? std::max(m.count, 1) : width_for(m.count);      // window kernel: exact width, no padding
-    const int g = grid_for(ws, n, v2 ? 2 : 1, win ? 22 : nv + 3);   // rolling-window kernel: one block per CU
+    nv = win ? std::max(m.count, 1) : width_for(m.count);                // window kernel: exact width, no padding
+    g = grid_for(ws, n, v2 ? 2 : 1, win ? 22 : nv + 3);             // rolling-window kernel: one block per CU
 #define NKA_SDPM(NV, VEC, SUB, PRE)                                                                              \
   hipLaunchKernelGGL((k_scale_dot_pair_many<NV, VEC, SUB, PRE>), dim3(g), dim3(kBlock), 0, ws->stream, n, w, v, a, pre_a, f, m, \
                      ws->partials, store)
@@ -1476,14 +1418,9 @@ static int scale_dot_pair_many_impl(nka_hip_vec_ws_t ws, int64_t n, double *w, d
 #undef LWDD
 #undef L1DD
     HIP_TRY(hipGetLastError());
-    if (int rc = fetch_sums(ws, g, 2, nv, m.count, extra, true)) return rc;
-    for (int j = 0; j < m.count; j++) {
-      host_vals_w[j] = ws->host_results[j];
-      host_vals_f[j] = ws->host_results[m.count + j];
-    }
-    *host_cross = ws->host_results[2 * m.count];
-    if (host_dd) *host_dd = ws->host_results[2 * m.count + 1];
   }
+  if (int rc = fetch_sums(ws, g, 2, nv, m.count, host_dd ? 2 : 1, n > 0)) return rc;
+  take_sums(ws, m.count, host_vals_w, host_vals_f, host_cross, host_dd);
   if (count > kManyMax) {   // the rest of a long list: plain two-row dots against the already scaled w
     double cross_again = 0.0;
     return nka_hip_vec_dot_pair_many(ws, n, w, f, ys + kManyMax, count - kManyMax, host_vals_w + kManyMax,

@@ -59,6 +59,81 @@ static void check_pass_widths() {
   }
 }
 
+// THE LAUNCH RULES.  Rings: properties, and a literal table (a changed ring is a deliberate edit of the table).
+static void check_rings() {
+  static const int ring[32] = {1, 2, 3, 4, 5, 6, 7, 4, 3, 5, 11, 4, 13, 7, 5, 4, 17, 6, 19, 4, 3, 22, 23, 4, 5, 26, 3, 4, 29, 5, 31, 4};
+  static const int pairs[32] = {1, 2, 3, 2, 5, 2, 7, 2, 3, 2, 11, 2, 13, 2, 3, 2, 17, 2, 19, 2, 3, 2, 23, 2, 5, 2, 3, 2, 29, 2, 31, 2};
+  static_assert(win_ring(20) == 4 && win_ring_pairs(20) == 2, "the rings are compile-time values: template arguments of the kernels");
+  for (int w = 1; w <= 32; w++) {
+    const int r = win_ring(w), rp = win_ring_pairs(w);
+    CHECK(r >= 1 && w % r == 0 && rp >= 1 && w % rp == 0, "width %d: rings %d, %d must divide it", w, r, rp);
+    CHECK(r == ring[w - 1] && rp == pairs[w - 1], "width %d: rings %d, %d, the table says %d, %d", w, r, rp, ring[w - 1], pairs[w - 1]);
+    // the whole width as the ring: beyond 7 exactly the primes and 22, 26 (heavy_prime and the note on 22 / 26 rely on it)
+    bool prime = w > 1;
+    for (int d = 2; d * d <= w; d++) prime = prime && w % d != 0;
+    if (w > 7) CHECK((r == w) == (prime || w == 22 || w == 26), "width %d: ring %d", w, r);
+    if (heavy_prime(w)) CHECK(r == w && rp == w, "heavy prime %d: rings %d, %d", w, r, rp);
+  }
+}
+
+// Ticket counters: the two spellings the rule had before it moved to host_logic.hpp, transcribed literally.
+static int tickets_array_model(int pb_tickets, bool tickets, int64_t ntile, int T, int64_t g, int words) {      // launch_combine_win_1
+  int ng = pb_tickets;
+  if (ng < 0) ng = (ntile * T >= 64 * g) ? (words >= 22 ? 1 : 2) : 0;
+  if (ng > 0 && (g % ng != 0 || ntile >= ((int64_t)1 << 31) - 2 * nka::kMaxGrid || !tickets)) ng = 0;
+  return ng;
+}
+static int tickets_vector_model(int ticket_groups, bool tickets, int64_t ntile, int g, int words) {      // update_many_keep, T = 1
+  const bool win = true;                      // (the 8-byte kernels take no tickets: the caller does not ask)
+  int ng = ticket_groups;
+  if (ng < 0) ng = (win && ntile >= (int64_t)64 * g) ? (words >= 22 ? 1 : 2) : 0;
+  if (!win || !tickets || g % std::max(ng, 1) != 0 || ntile >= ((int64_t)1 << 31) - 2 * nka::kMaxGrid) ng = 0;
+  return ng;
+}
+static void check_tickets() {
+  const int64_t wrap = ((int64_t)1 << 31) - 2 * 4096;
+  for (int forced : {-1, 0, 1, 2, 4, 8})
+    for (int have = 0; have < 2; have++)
+      for (int T : {1, 2})
+        for (int grid : {1, 2, 3, 255, 256, 4096})
+          for (int words : {21, 22})
+            for (int64_t ntile : {(int64_t)0, (int64_t)64 * grid - 1, (int64_t)64 * grid, wrap - 1, wrap}) {
+              const int ng = ticket_counters(forced, have != 0, ntile, T, grid, words);
+              const int a = tickets_array_model(forced, have != 0, ntile, T, grid, words);
+              CHECK(ng == a, "tickets(%d, %d, %lld, %d, %d, %d) = %d, the array spelling gives %d", forced, have, (long long)ntile, T, grid, words, ng, a);
+              if (T == 1) {
+                const int v = tickets_vector_model(forced, have != 0, ntile, grid, words);
+                CHECK(ng == v, "tickets(%d, %d, %lld, 1, %d, %d) = %d, the vector spelling gives %d", forced, have, (long long)ntile, grid, words, ng, v);
+              }
+              CHECK(ng >= 0 && (ng == 0 || (have && grid % ng == 0 && ntile < wrap)), "tickets: %d counters for a grid of %d", ng, grid);
+              // the prediction before the grid is known (one block per CU) is the rule's own answer where one or two counters divide the grid
+              CHECK(tickets_expected(forced, have != 0, ntile, grid) == (forced != 0 && have && ntile >= (int64_t)64 * grid), "tickets_expected");
+              if (forced < 0 && grid % 2 == 0 && ntile < wrap)
+                CHECK(tickets_expected(forced, have != 0, ntile, grid) == (ticket_counters(forced, have != 0, ntile, 1, grid, words) > 0), "tickets_expected against ticket_counters");
+            }
+}
+
+// The persistent grid and the blocks per CU against brute force; the values tests/test_exact_sums_cpu.py pins from Python.
+static void check_grid() {
+  for (int nloads = 1; nloads <= 70; nloads++) {
+    int b = 1;
+    while (b * nloads < 22) b++;                // the fewest blocks that keep 22 loads per thread in flight on a CU
+    CHECK(blocks_per_cu(nloads) == b, "blocks_per_cu(%d) = %d, brute force %d", nloads, blocks_per_cu(nloads), b);
+  }
+  for (int num_cu : {1, 8, 256})
+    for (int per_cu = 1; per_cu <= 8; per_cu++)
+      for (int64_t ntile : {(int64_t)0, (int64_t)1, (int64_t)num_cu * per_cu - 1, (int64_t)num_cu * per_cu, (int64_t)num_cu * per_cu + 1, (int64_t)1000000000}) {
+        int g = nka::kMaxGrid;                  // the largest grid of at most kMaxGrid blocks, per_cu per CU, one per tile -- but one at least
+        while (g > 1 && (g > num_cu * per_cu || g > ntile)) g--;
+        CHECK(persistent_grid(num_cu, per_cu, ntile) == g, "persistent_grid(%d, %d, %lld) = %d, brute force %d", num_cu, per_cu, (long long)ntile, persistent_grid(num_cu, per_cu, ntile), g);
+      }
+  auto vec_grid = [](int64_t n, int num_cu, int vec, int nloads) { return persistent_grid(num_cu, std::min(8, blocks_per_cu(nloads)), n / (256 * vec)); };
+  const int nl[9] = {2, 3, 5, 6, 9, 10, 11, 22, 27}, want[9] = {2048, 2048, 1280, 1024, 768, 768, 512, 256, 256};
+  for (int i = 0; i < 9; i++) CHECK(vec_grid(100000000, 256, 2, nl[i]) == want[i], "vector grid at %d loads: %d", nl[i], vec_grid(100000000, 256, 2, nl[i]));
+  CHECK(vec_grid(100000000, 1024, 2, 2) == 4096, "kMaxGrid");
+  CHECK(vec_grid(1, 256, 2, 2) == 1 && vec_grid(1023, 256, 2, 2) == 1 && vec_grid(1024, 256, 2, 2) == 2 && vec_grid(1023, 256, 1, 2) == 3, "short vectors");
+}
+
 // The list word against a model of device and host: updates (with dependence drops the host cannot see), relax, restart, and
 // a word that reaches host memory whenever the device gets that far (any published word not older than the last one seen).
 // SAFETY: the bound is never below the true list length at the entry of an update (the passes are launched at its width);
@@ -233,6 +308,9 @@ static void check_snapshot() {
 
 int main(int argc, char **argv) {
   check_pass_widths();
+  check_rings();
+  check_tickets();
+  check_grid();
   check_list_word();
   check_buffer_book();
   check_snapshot();
@@ -240,7 +318,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "host_logic_check: %d check(s) FAILED\n", failures);
     return 1;
   }
-  std::printf("host_logic_check: pass widths, launch groups, list word, buffer book, snapshot decoding: OK\n");
+  std::printf("host_logic_check: pass widths, launch groups, rings, ticket counters, grids, list word, buffer book, snapshot decoding: OK\n");
   if (argc > 1 && !std::strcmp(argv[1], "plant")) {
     // PLANTED: balanced_widths asked for one pass more than its array holds
     int *w = static_cast<int *>(std::malloc(sizeof(int) * 2));

@@ -289,15 +289,15 @@ BATCH_CAP_SHAPES = [BATCH_MAX_VLEN - 1, BATCH_MAX_VLEN]
 # way: a persistent grid of G blocks, block b takes the tiles b, b + G, ... of 256 * VEC elements, the last block the
 # ragged tail, block_reduce_store leaves one partial per block and column, k_finalize_rows sums a column's partials.
 
-VEC_MAX_GRID = 4096             # kMaxGrid (nka_device.hpp:19)
-VEC_PER_CU_MAX = 8              # grid_for: at most 8 blocks per CU (vec_ops.hip:756)
-VEC_LOADS_PER_CU = 22           # grid_for: one block per CU once a thread keeps 22 loads in flight
+VEC_MAX_GRID = 4096             # kMaxGrid (nka_ctl.hpp)
+VEC_PER_CU_MAX = 8              # grid_for (vec_ops.hip): at most 8 blocks per CU
+VEC_LOADS_PER_CU = 22           # blocks_per_cu (host_logic.hpp): one block per CU once a thread keeps 22 loads in flight
 VEC_MANY_MAX = 24               # kManyMax (host_logic.hpp): vectors per launch
-VEC_FIN_THREADS = BLOCK         # k_finalize_rows runs kBlock threads (vec_ops.hip:877, 938)
+VEC_FIN_THREADS = BLOCK         # k_finalize_rows runs kBlock threads (vec_ops.hip: fetch_sums)
 
 
 def vec_width(count):
-    """width_for (vec_ops.hip:762): the unroll width 4, 8, ..., 24 of a padded kernel for `count` vectors."""
+    """width_for (vec_ops.hip): the unroll width 4, 8, ..., 24 of a padded kernel for `count` vectors."""
     return max(4, _cdiv(count, 4) * 4)
 
 
@@ -309,11 +309,12 @@ def vec_groups(count):
 
 
 def vec_grid(n, ncu, vec, nloads):
-    """grid_for (vec_ops.hip:755-760): per_cu = max(1, min(8, (22 + nloads - 1) / nloads)) blocks per CU, at most one
+    """grid_for (vec_ops.hip) = persistent_grid(ncu, min(8, blocks_per_cu(nloads)), tiles) of host_logic.hpp:
+    per_cu = max(1, min(8, (22 + nloads - 1) / nloads)) blocks per CU, at most one
     block per tile of 256 * vec elements (at least one block), at most kMaxGrid.  `nloads` is what the entry passes: 2
-    (dot :1074, update_norm2 :1294), nv + 1 (dot_many :1126), nv + 2 (dot_pair_many :1183), 22 for the window kernels and
-    nv + 3 for the 8-byte k_scale_dot_pair_many (:1440); nv = vec_width(count) but for the window kernels, whose width
-    is max(count, 1) (:1439)."""
+    (dot, update_norm2), nv + 1 (dot_many), nv + 2 (dot_pair_many), 22 for the window kernels and
+    nv + 3 for the 8-byte k_scale_dot_pair_many; nv = vec_width(count) but for the window kernels, whose width
+    is max(count, 1) (scale_dot_pair_many_impl)."""
     per_cu = max(1, min(VEC_PER_CU_MAX, _cdiv(VEC_LOADS_PER_CU, nloads)))
     return min(ncu * per_cu, max(n // (BLOCK * vec), 1), VEC_MAX_GRID)
 
@@ -327,7 +328,7 @@ def vec_k(n, G, vec):
                           order): vec * ceil(ntile / G) fma;
       ragged tail         the last block walks the tail at stride 256 (:79-80, :209-212, :245-254, :348-353, :407-426,
                           :606-625): ceil(tail / 256) more fma, tail < 256 * vec;
-      block_reduce_store  (nka_device.hpp:165) the 64-lane butterfly of WAVE_LEVELS = 6 additions, then the four wave
+      block_reduce_store  (nka_device.hpp) the 64-lane butterfly of WAVE_LEVELS = 6 additions, then the four wave
                           sums in turn: 3 additions;
       k_finalize_rows     (:877-901) thread t adds the partials t, t + 256, ... of its column -- ceil(G / 256) additions,
                           256 threads, not the 64 of k_finalize_dots --, the butterfly (6) and the four wave sums (3).
@@ -398,7 +399,7 @@ def vec_planted_input(n, G, vec, rng, background=0.125, prev=None):
 
 
 def vec_boundary_shapes(G, vec):
-    """The lengths where the workspace's kernels change hands on a grid of up to G blocks (grid_for, vec_ops.hip:755-760:
+    """The lengths where the workspace's kernels change hands on a grid of up to G blocks (grid_for, vec_ops.hip; persistent_grid, host_logic.hpp:
     one block per tile until G is reached), t = 256 * vec: the fixed small
     ones around one wavefront's stride and one tile, every block's first tile being its last (G t +- 1), one block with a
     second tile ((G + 1) t), and two tiles per block with and without a tail, the longest tail included."""

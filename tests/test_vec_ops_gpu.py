@@ -391,3 +391,84 @@ def test_reduction_hooks_see_every_sum_in_the_canonical_layout(ws):
         L.nka_hip_vec_set_host_allreduce(h, C.cast(None, _lib.HOST_ALLREDUCE_FN), None)
     r = C.c_double()
     assert L.nka_hip_vec_dot(h, n, P(w), P(f), C.byref(r)) == 0 and r.value == plain["dot"]
+
+
+def test_an_empty_slice_joins_the_collectives_of_a_full_one(ws):
+    """A rank whose slice is empty (n = 0) must join exactly the collectives its peers join, with the same lengths: every
+    reduction entry, at list lengths that take one launch (0, 1, 5, 24), the first split (25) and two splits (49), makes
+    the same sequence of all-reduce calls at n = 0 as at n = 1000 -- the sequence that follows from the list length alone:
+    groups of 24 for dot_many / dot_pair_many (and for the rest of a long list in scale_dot_pair_many), balanced groups for
+    the two pure-read stages; [row 0, row 1, cross(, <d,d>)] per group.  An empty slice returns zeros everywhere and writes
+    nothing behind its result arrays."""
+    from nka_amd import _lib
+    L, h, torch = ws
+    kmax, canary = 24, -7.25
+    rng = np.random.default_rng(11)
+    vecs = [torch.from_numpy(rng.standard_normal(1000)).cuda() for _ in range(49 + 3)]
+    w, v, f, ys = vecs[0], vecs[1], vecs[2], vecs[3:]
+    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    seen = []
+
+    def host_hook(_ctx, _vals, cnt):
+        seen.append(cnt)
+        return 0
+
+    def groups24(c):
+        return [min(kmax, c - b) for b in range(0, c, kmax)]
+
+    def balanced(c):
+        ng = max(1, -(-c // kmax))
+        return [c // ng + (1 if p < c % ng else 0) for p in range(ng)]
+
+    def expected(c):
+        return {"dot": [1], "dot_many": groups24(c), "dot_pair_many": [2 * g + 1 for g in (groups24(c) or [0])],
+                "update_norm2": [1],
+                "scale_dot_pair_many": [2 * min(kmax, c) + 1] + [2 * g + 1 for g in groups24(max(c - kmax, 0))],
+                "dot_pair_many_scaled": [2 * g + 1 for g in balanced(c)],
+                "diff_norm_dot_pair_many": [2 * g + 2 for g in balanced(c)]}
+
+    def run(n, c):
+        ptrs = (C.c_void_p * c)(*[y.data_ptr() for y in ys[:c]])
+        arr = lambda: (C.c_double * (c + 4))(*([canary] * (c + 4)))  # noqa: E731
+        sc = lambda: C.c_double(canary)  # noqa: E731
+        calls, scalars, arrays = {}, {}, {}
+
+        def entry(name, rc, s, a):
+            assert rc == 0, (name, n, c, L.nka_hip_last_error())
+            calls[name], scalars[name], arrays[name] = list(seen), [x.value for x in s], [list(x) for x in a]
+            seen.clear()
+
+        seen.clear()
+        r = sc()
+        entry("dot", L.nka_hip_vec_dot(h, n, P(w), P(f), C.byref(r)), [r], [])
+        a0 = arr()
+        entry("dot_many", L.nka_hip_vec_dot_many(h, n, P(f), ptrs, c, a0), [], [a0])
+        a0, a1, cr = arr(), arr(), sc()
+        entry("dot_pair_many", L.nka_hip_vec_dot_pair_many(h, n, P(w), P(f), ptrs, c, a0, a1, C.byref(cr)), [cr], [a0, a1])
+        r = sc()
+        entry("update_norm2", L.nka_hip_vec_update_norm2(h, n, P(w), -1.0, P(f), 0, C.byref(r)), [r], [])
+        a0, a1, cr = arr(), arr(), sc()
+        entry("scale_dot_pair_many", L.nka_hip_vec_scale_dot_pair_many(h, n, P(w), P(v), 0.5, 1, 1, -1.0, P(f), ptrs, c, a0, a1,
+                                                                       C.byref(cr)), [cr], [a0, a1])
+        a0, a1, cr = arr(), arr(), sc()
+        entry("dot_pair_many_scaled", L.nka_hip_vec_dot_pair_many_scaled(h, n, P(w), 0.5, 1, -1.0, P(f), ptrs, c, a0, a1,
+                                                                         C.byref(cr)), [cr], [a0, a1])
+        a0, a1, cr, dd = arr(), arr(), sc(), sc()
+        entry("diff_norm_dot_pair_many", L.nka_hip_vec_diff_norm_dot_pair_many(h, n, P(w), -1.0, P(f), ptrs, c, C.byref(dd), a0, a1,
+                                                                               C.byref(cr)), [dd, cr], [a0, a1])
+        return calls, scalars, arrays
+
+    hcb = _lib.HOST_ALLREDUCE_FN(host_hook)
+    assert L.nka_hip_vec_set_host_allreduce(h, hcb, None) == 0
+    try:
+        for c in (0, 1, 5, 24, 25, 49):
+            full, _, full_arrays = run(1000, c)
+            empty, scalars, arrays = run(0, c)
+            assert full == empty, (c, full, empty)
+            assert empty == expected(c), (c, empty, expected(c))
+            for name in empty:
+                assert all(x == 0.0 for x in scalars[name]), (c, name, scalars[name])
+                for a, fa in zip(arrays[name], full_arrays[name]):
+                    assert a[:c] == [0.0] * c and a[c:] == [canary] * 4 and fa[c:] == [canary] * 4, (c, name, a, fa)
+    finally:
+        L.nka_hip_vec_set_host_allreduce(h, C.cast(None, _lib.HOST_ALLREDUCE_FN), None)

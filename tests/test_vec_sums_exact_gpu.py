@@ -178,7 +178,7 @@ def _canaries(count, *arrs):
 # ---- the grid of every launch an entry makes, as (first vector, vectors, G) per launch --------------------------------------
 
 def _win_nloads(width, vec):
-    """scale_dot_pair_many_impl (vec_ops.hip:1438-1440): the window kernel (22) for aligned operands, else nv + 3."""
+    """scale_dot_pair_many_impl (vec_ops.hip): the window kernel (22) for aligned operands, else nv + 3."""
     return X.VEC_LOADS_PER_CU if vec == 2 else X.vec_width(width) + 3
 
 
