@@ -17,6 +17,10 @@ was active:
                normalised pair as stored (compact storage: v holds fl(v1' - w1')), the combine in list order with the
                flavour's association, w_new = f_in, v_new = f_out, the row of f; the row untouched when nothing was combined.
 
+BatchRun.update takes the sum order of that one update (nka_hip_batch_set_sum_order on the live batch); on a reference-order
+update part 1 holds every live entry of red[] to numpy's sequential accumulate of the rounded products, bit for bit
+(test_the_sum_order_changes_with_every_update: all nine ordered pairs of AUTO, BLOCKED_ROUNDED and REFERENCE_ORDER).
+
 Only the slots an update wrote are read back (and held bit for bit on the way); every other operand comes from the mirror.
 Systems that sat a call out keep their row, their red[] and their digest.  Inputs of part 1 carry planted sentinels where the
 kernel changes hands (exact_sums.batch_sentinel_indices); tests/test_exact_sums_cpu.py shows on the CPU that losing or doubling
@@ -31,7 +35,7 @@ import pytest
 import batch_seq as B
 import exact_sums as X
 import scenarios as S
-from split_update import _bits_equal
+from split_update import _bits_equal, ordered_dot
 
 pytestmark = pytest.mark.gpu
 
@@ -106,11 +110,14 @@ class BatchRun:
         self.lengths_differed = self.saw_zero_s = self.saw_after_restart = False
         self.widest = 0
         self.outcomes = []                                   # (system, call, older entries -- by position -- this update dropped)
+        self.ordered_sums = 0                                # entries held to the sequential sum's bits
 
     def _device(self, odd_ld):
         import nka_amd
         torch, n, nsys, ld = self.torch, self.n, self.nsys, self.ld
         self.b = nka_amd.nka_batch().init(nsys, n, self.m, flavor=self.flavor).set_sum_order(nka_amd.SUMS_BLOCKED_ROUNDED)
+        self.order, self.orders_met = nka_amd.SUMS_BLOCKED_ROUNDED, set()     # the order in force; {(previous, this)} per update
+        self.reference = nka_amd.SUMS_REFERENCE_ORDER
         assert self.b.flavor() == self.flavor
         self.raw = torch.zeros(nsys * ld, dtype=torch.float64, device="cuda")
         self.F = self.raw.view(nsys, ld)[:, :n]
@@ -139,8 +146,16 @@ class BatchRun:
         return self.ld == self.n or not bool(self.raw.view(self.nsys, self.ld)[:, self.n:].any())
 
     # -- the calls ------------------------------------------------------------------------------------------------------
-    def update(self, inputs):
-        """accel_update for the systems of `inputs` ({system: f}), the others masked out; every check of the docstring."""
+    def update(self, inputs, order=None):
+        """accel_update for the systems of `inputs` ({system: f}), the others masked out; every check of the docstring.
+        `order`: the sum order of THIS update (nka_hip_batch_set_sum_order on the live batch: SUMS_AUTO, which is the rounded
+        order beyond 64 elements, SUMS_BLOCKED_ROUNDED or SUMS_REFERENCE_ORDER); without one the order stays."""
+        if order is not None and order != self.order:
+            self.b.set_sum_order(order)
+            self.orders_met.add((self.order, order))
+            self.order = order
+        elif order is not None:
+            self.orders_met.add((order, order))
         ks = sorted(inputs)
         entry = {k: self.b.state(k) for k in ks}
         if len({(st.pending, len(st.list_order())) for st in entry.values()}) > 1:
@@ -206,6 +221,16 @@ class BatchRun:
         live = sn.list_order()
         assert all(sd.prev[i - 1] == sn.prev[i - 1] for i in live), (where, "prev")
 
+    def _sum(self, what, red, x, y, where):
+        """One live entry of red[]: the fast sums within gamma(K) of the exact sum; in the reference's order the bits of numpy's
+        sequential accumulate of the rounded products."""
+        if self.order == self.reference or (self.order == 0 and self.n <= 64):
+            want = ordered_dot(x, y)
+            assert _bits_equal(np.array([red]), np.array([want])), (what, where, "not the sequential sum's bits", red, want)
+            self.ordered_sums += 1
+        else:
+            _hold(what, red, x, y, self.k, where)
+
     def _check(self, k, st0, x, out, where):
         b, n, m, fl = self.b, self.n, self.m, self.flavor
         W, V = self.W[k], self.V[k]
@@ -219,7 +244,7 @@ class BatchRun:
         s, normed, w1n, v1n = 0.0, False, None, None
         if pending:
             d = W[first0] - x                                             # F08:266
-            _hold("<d,d>", red[0], d, d, self.k, where)
+            self._sum("<d,d>", red[0], d, d, where)
             s = np.sqrt(np.float64(red[0]))                               # the device's s, IEEE sqrt (NaN, Inf, 0 included)
             normed = not s == 0.0                                         # (NaN goes on, like the reference)
         if normed:
@@ -229,9 +254,9 @@ class BatchRun:
                     w1n, v1n = r * d, r * V[first0]
                 else:                                                     # F08:282-283
                     w1n, v1n = d / s, V[first0] / s
-            _hold("<f,w1'>", red[1], x, w1n, self.k, where)
+            self._sum("<f,w1'>", red[1], x, w1n, where)
             for p, slot in enumerate(olders):
-                _hold(f"<w1',w_{p}>", red[2 + p], w1n, W[slot], self.k, where)
+                self._sum(f"<w1',w_{p}>", red[2 + p], w1n, W[slot], where)
             self.nolder_normed.add(len(olders))
         else:                                                             # no pending pair, or s == 0: exactly 0
             assert red[1] == 0.0 and not red[2:2 + m].any(), (where, "sums on w1' without a normalised pair", red[1:2 + m])
@@ -241,7 +266,7 @@ class BatchRun:
             else:
                 self.saw_zero_s = True
         for p, slot in enumerate(olders):
-            _hold(f"<f,w_{p}>", red[2 + m + p], x, W[slot], self.k, where)
+            self._sum(f"<f,w_{p}>", red[2 + m + p], x, W[slot], where)
         for p in range(len(olders), m):                                   # beyond the list: exactly 0, both halves
             assert red[2 + p] == 0.0 and red[2 + m + p] == 0.0, (where, p, red[2 + p], red[2 + m + p])
 
@@ -468,6 +493,41 @@ def test_scalar_step_through_capacity_drops(torch_cuda, oracle, mvec, flavor):
         run.update({k: seq.next() for k, seq in enumerate(seqs)})
     assert run.widest == mvec, run.widest                    # a full list at the entry of an update: the capacity drop
     assert any(gone for _, _, gone in run.outcomes)
+
+
+# ---- the sum order changed on a live batch ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [513, 1025])
+def test_the_sum_order_changes_with_every_update(torch_cuda, oracle, n):
+    """nka_hip_batch_set_sum_order on a live batch: SUMS_AUTO, SUMS_BLOCKED_ROUNDED and SUMS_REFERENCE_ORDER in a circuit through
+    all nine ordered pairs, a new order on every update; mvec = 5, three systems with an odd row stride, the last of them
+    masked out on every third call; dependent and repeated inputs, a relax and a restart by mask.  Rounded updates are held as
+    everywhere in this module; on reference-order updates red[] carries the sequential sums' bits."""
+    import nka_amd
+    from split_update import circuit
+    orders = [nka_amd.SUMS_AUTO, nka_amd.SUMS_BLOCKED_ROUNDED, nka_amd.SUMS_REFERENCE_ORDER]
+    walk = [orders[i] for i in circuit(3)] * 2               # ten updates, twice: the list fills and drops by capacity
+    for flavor in (0, 1, 2):
+        run = BatchRun(torch_cuda, oracle, flavor, n, 5, 3, odd_ld=True)
+        rngs, prev, before = [np.random.default_rng([n, k]) for k in range(3)], [None] * 3, [None] * 3
+        for t, order in enumerate(walk):
+            ks = [0, 1] if t % 3 == 2 else [0, 1, 2]
+            if t == 9:
+                run.relax([1])
+            if t == 13:
+                run.restart([0])
+            inputs = {}
+            for k in ks:
+                if t % 7 == 5 and prev[k] is not None:
+                    x = prev[k].copy()                               # s == 0
+                elif t % 5 == 4 and before[k] is not None:
+                    x = 1.5 * prev[k] - 0.5 * before[k]              # parallel to the stored difference: a dependence drop
+                else:
+                    x = X.batch_planted_input(n, rngs[k], prev[k])
+                inputs[k], before[k], prev[k] = x, prev[k], x
+            run.update(inputs, order=order)
+        assert {(p, c) for p, c in run.orders_met} >= {(p, c) for p in orders for c in orders}, run.orders_met
+        assert run.ordered_sums > 50 and run.saw_zero_s and run.saw_after_restart and run.widest == 5
+        assert any(gone == [4] for _, _, gone in run.outcomes) and any(gone == [0] for _, _, gone in run.outcomes), run.outcomes
 
 
 # ---- the record (keep this test last) ------------------------------------------------------------------------------------------

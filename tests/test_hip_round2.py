@@ -172,7 +172,7 @@ def test_mvec_beyond_the_lds_limit_works_from_global_memory(torch_cuda, oracle, 
     spread = P.Spread(oracle, n, m)
     # the scalar step given the device's own sums: bit for bit (h by slot, coefficients), and the elementwise statements given
     # the device's scalars -- asserted inside every split.update / relax / restart (tests/split_update.py)
-    split = SplitRun(torch_cuda, oracle, acc, acc.flavor(), n, m, nka_amd.SUMS_AUTO)
+    split = SplitRun(torch_cuda, oracle, acc, acc.flavor(), n, m, nka_amd.SUMS_AUTO, check_sums=False)
     basis = rng.standard_normal((3, n))
     for t in range(34):
         x = rng.standard_normal(n) if t % 11 != 7 else rng.standard_normal(3) @ basis

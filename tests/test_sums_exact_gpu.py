@@ -15,31 +15,30 @@ The inputs carry planted sentinels where the kernels change hands (exact_sums.se
 tests/test_exact_sums_cpu.py shows that losing or doubling any one of them breaks the bound at these shapes.
 """
 import json
-import math
 import os
 
 import numpy as np
 import pytest
 
 import exact_sums as X
-from split_update import _bits_equal
+import split_update as U
 
 pytestmark = pytest.mark.gpu
 
 ROUNDED, BLOCKED = 3, 2             # nka_amd.SUMS_BLOCKED_ROUNDED, nka_amd.SUMS_BLOCKED (the default first)
 MODES = pytest.mark.parametrize("mode", [ROUNDED, BLOCKED], ids=["rounded", "blocked"])
-WORST = {}                          # mode -> worst |red - exact| / (u sum|xy|) seen, and the K it was held to
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _report_worst(request):
     """At the end of the module: per mode, the worst |red - exact| / (u sum|xy|) seen and the K it was held to."""
+    U.WORST.clear()
     yield
     import parity_util as P
     tr = request.config.pluginmanager.get_plugin("terminalreporter")
     rows = {}
-    for mode, (ratio, k, where) in sorted(WORST.items()):
-        name = "rounded" if mode == ROUNDED else "blocked"
+    for way, (ratio, k, where) in sorted(U.WORST.items()):
+        name = "rounded" if way == "R" else "blocked"
         rows[name] = {"worst_err_over_u_sum_abs": ratio, "k": k, "where": where}
         line = f"sums mode {name}: worst |red - exact| = {ratio:.3f} u sum|xy| against K = {k} there ({where})"
         tr.write_line(line) if tr is not None else print(line)
@@ -68,106 +67,37 @@ def ncu(torch_cuda):
     return g
 
 
-def _hold(mode, what, red, x, y, k, where):
-    ex = X.exact_dot(x, y)
-    if math.isnan(ex):
-        assert math.isnan(red), (what, where, red)
-        return
-    if math.isinf(ex):
-        assert red == ex, (what, where, red, ex)
-        return
-    tot = X.abs_dot(x, y)
-    err = abs(red - ex)
-    assert err <= X.gamma(k) * tot, (what, where, red, ex, err / (X.U * tot) if tot else err, k)
-    if tot > 0:
-        r = WORST.setdefault(mode, [0.0, 0, ""])
-        ratio = err / (X.U * tot)
-        if ratio >= r[0]:
-            r[:] = [ratio, k, f"{what} {where}"]
-
-
 class Run:
-    """One accelerator in a fast sum mode, its host mirror, and the checks after each update."""
+    """One accelerator in a fast sum mode for life: tests/split_update.py's SplitRun -- which holds the sums as described above
+    and, on the way, the scalar step and the elementwise statements -- behind the calls of this module."""
 
     def __init__(self, torch, ncu, mode, flavor, n, mvec, aligned=True, seed=0):
         import nka_amd
-        self.torch, self.mode, self.flavor, self.n, self.m = torch, mode, flavor, n, mvec
-        self.acc = nka_amd.nka().init(n, mvec, flavor=flavor).set_sum_order(mode)
-        self.G = ncu
-        self.k = X.device_k(n, ncu, aligned)
-        self.aligned = aligned
+        from oracle import oracle_py
+        self.mode, self.flavor, self.n, self.m, self.G, self.aligned = mode, flavor, n, mvec, ncu, aligned
+        self.acc = nka_amd.nka().init(n, mvec, flavor=flavor)
+        self.run = U.SplitRun(torch, oracle_py, self.acc, flavor, n, mvec, mode, aligned=aligned)
+        assert self.run.ncu == ncu
         self.rng = np.random.default_rng(seed)
-        self.W = {}                  # slot -> stored w (host mirror)
         self.prev = None
-        self.widest = 0              # longest list of older vectors seen at the entry of an update
-        if aligned:
-            self.buf = torch.zeros(n, dtype=torch.float64, device="cuda")
-            self.view = self.buf
-        else:
-            self.buf = torch.zeros(n + 1, dtype=torch.float64, device="cuda")
-            self.view = self.buf[1:]                                 # 8-byte but not 16-byte aligned
-            assert self.view.data_ptr() % 16 == 8
+
+    @property
+    def widest(self):
+        """The longest list of older vectors seen at the entry of an update."""
+        return self.run.widest
 
     def next_input(self, repeat=False):
         return self.prev.copy() if repeat else X.planted_input(self.n, self.G, self.rng, self.prev)
 
-    def update(self, x, where=""):
+    def update(self, x):
         """accel_update(x) on the device, then every check of the module docstring; returns the output f."""
-        torch, n, m = self.torch, self.n, self.m
-        st0 = self.acc.state()
-        order0 = st0.list_order()
-        pending = st0.pending
-        olders = order0[1:] if pending else order0
-        self.widest = max(self.widest, len(olders))
-        self.view.copy_(torch.from_numpy(x))
-        self.acc.accel_update(self.view)
-        out = self.view.cpu().numpy()
-        red = self.acc.reductions()
-        where = (self.mode, self.flavor, n, m, self.aligned, where)
-        w1n = None
-        if pending:
-            d = self.W[order0[0]] - x                                   # F08:266
-            self._hold("<d,d>", red[0], d, d, where)
-            s = np.sqrt(np.float64(red[0]))                             # the device's s, IEEE sqrt (NaN, Inf, 0 included)
-            with np.errstate(invalid="ignore", divide="ignore"):
-                w1n = (np.float64(1.0) / s) * d if self.flavor == 1 else d / s      # F08:283, F08V:256
-            if self.mode == ROUNDED:
-                op = np.zeros(n) if s == 0.0 else w1n                   # (s == 0: the scalar step relaxes, these are 0)
-                if s == 0.0:
-                    assert red[1] == 0.0 and all(red[2 + p] == 0.0 for p in range(len(olders))), (where, red)
-                self._hold("<f,w1'>", red[1], x, op, where)
-                for p, k in enumerate(olders):
-                    self._hold(f"<w1',w_{p}>", red[2 + p], op, self.W[k], where)
-            else:
-                self._hold("<f,d>", red[1], x, d, where)
-                for p, k in enumerate(olders):
-                    self._hold(f"<d,w_{p}>", red[2 + p], d, self.W[k], where)
-        if pending or olders:
-            for p, k in enumerate(olders):
-                self._hold(f"<f,w_{p}>", red[2 + m + p], x, self.W[k], where)
-            for p in range(len(olders), m):                              # past the list: exactly 0
-                assert red[2 + p] == 0.0 and red[2 + m + p] == 0.0, (where, p, red[2 + p], red[2 + m + p])
-        # the mirror: read back only the slots this update wrote
-        order = self.acc.state().list_order()
-        new = order[0]
-        w_new = self.acc.w(new)
-        assert _bits_equal(w_new, x), (where, "the new pair's w is not the input")
-        W = {k: self.W[k] for k in order[1:] if k in self.W and k != (order0[0] if pending else None)}
-        if pending and order0[0] in order[1:]:
-            w1 = self.acc.w(order0[0])
-            assert _bits_equal(w1, w1n), (where, "stored w1' is not fl(d/s)", int(np.sum(w1 != w1n)))
-            W[order0[0]] = w1
-        W[new] = w_new
-        self.W = W
+        out = self.run.update(x)
         self.prev = x
         return out
 
-    def _hold(self, what, red, x, y, where):
-        _hold(self.mode, what, red, x, y, self.k, where)
-
     def sequence(self, nupd, repeat_at=()):
         for t in range(nupd):
-            self.update(self.next_input(repeat=t in repeat_at and self.prev is not None), where=t)
+            self.update(self.next_input(repeat=t in repeat_at and self.prev is not None))
         assert self.acc.defined()
         return self
 
@@ -237,7 +167,7 @@ def test_non_finite_input_in_the_default_mode(torch_cuda, ncu, oracle, bad, flav
             x[5] = bad
         f = x.copy()
         ora.accel_update(f)
-        out = r.update(x, where=t)
+        out = r.update(x)
         assert r.acc.num_vec() == ora.num_vec(), t
         assert r.acc.state().list_order() == ora.state().list_order(), t
         assert np.array_equal(np.isnan(out), np.isnan(f)), t
