@@ -41,9 +41,35 @@
  *            256, 23 x with 4096 (0.55 of 8 TB/s); at vlen = 1024, mvec = 10: 9.2 x / 151 x / 444 x.  Beyond it a 16-system
  *            batch -- 16 of 256 compute units -- loses (0.99 x at 32 768, mvec = 20): longer systems are for lone handles.  A
  *            batch of ONE is slower than a lone handle at most shapes (0.10 ... 1.76 x, recorded without a bar).
- *   OUT OF SCOPE  sharding and all-reduce hooks, the user dot product, diagonal weights, the out-of-place entry, the
- *            abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs any
- *            of these uses lone handles.
+ *   WEIGHTS  nka_hip_batch_set_dot_weights: the dp  <x,y>_w = sum_i w_i x_i y_i  per system, on the device, inside the same
+ *            one launch (unknowns of different scale, masks on ghost or fixed entries, ragged batches).  a_w = fl(w_i * a_i)
+ *            is the FIRST operand of every product; with d = fl(w1 - f) and w1' the flavour's rounding as above:
+ *                          NKA_HIP_SUMS_BLOCKED_ROUNDED                 NKA_HIP_SUMS_REFERENCE_ORDER
+ *              red[0]      sum fma(fl(w d),   d,   .)                   acc = acc + fl(w d)   * d       dp(d, d)
+ *              red[1]      sum fma(fl(w f),   w1', .)                   acc = acc + fl(w f)   * w1'     dp(f, w1')
+ *              red[2+p]    sum fma(fl(w w1'), w_p, .)                   acc = acc + fl(w w1') * w_p     dp(w1', w_p)
+ *              red[2+m+p]  sum fma(fl(w f),   w_p, .)                   acc = acc + fl(w f)   * w_p     dp(f, w_p)
+ *            The fast column is the NKA_HIP_SUMS_BLOCKED_ROUNDED column of the table under nka_hip_set_dot_weights (nka_hip.h)
+ *            with the batch's element -> thread map, per-thread order and workgroup reduction unchanged; fl(w f) is formed once
+ *            per element and sweep.  In reference order a system carries the bits of the reference run with
+ *            dp(x, y) = sum in order of fl(fl(w_i x_i) * y_i), the operands in the order the reference passes them.  UNLIKE A
+ *            LONE HANDLE, a batch therefore does NOT refuse weights in reference order, and NKA_HIP_SUMS_AUTO resolves as
+ *            without weights: reference order up to 64 elements.  The combine does not read the weights.  Exact consequences
+ *            (tests/test_batch_weights_gpu.py): w == 1 returns the plain batch's bits; w_i = 4^k per system returns
+ *            2^-k o (a plain batch on 2^k o F), bit for bit, with the same decisions; w_i = 0 keeps entry i out of every sum
+ *            and every decision while the values there stay finite (0 * Inf is NaN, as in the reference's dp).
+ *            RAGGED BATCHES: systems of different length L_sys <= vlen are padded to vlen, with w = 1 below L_sys and 0 from
+ *            there on.  Sums, decisions and f[0 .. L_sys) of such a system are then BIT-EQUAL to those of a batch of
+ *            vlen = L_sys -- fma(+-0, b, acc) = acc for finite b, and a thread meets its elements in the same order at either
+ *            length -- whatever finite values the padding of f holds (the combine still runs over it: keep it finite).
+ *            COST, MEASURED (profiles/r09/batch_weights_throughput.txt, 1 x MI355X; nsys 256 / 4096 x vlen 1024 / 16 384 x
+ *            mvec 10 / 20): a weighted update takes 0.93 ... 1.03 x the time of a plain one with the shared row, 0.93 ... 1.14 x
+ *            with one row per system -- the 1.14 (mvec 10; 1.10 at mvec 20) at 4096 x 16 384, where 512 MB of weights stream
+ *            from memory and the count of streams per element (norm pass 2 -> 3, each sweep of four 6 -> 7, combine unchanged:
+ *            +10.8 % / +10.2 %) is what it costs.
+ *   OUT OF SCOPE  sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
+ *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
+ *            any of these uses lone handles.
  */
 #ifndef NKA_HIP_BATCH_H
 #define NKA_HIP_BATCH_H
@@ -74,6 +100,26 @@ int nka_hip_batch_relax(nka_hip_batch_t b, const int32_t *active_dev);
 /* call a%set_vec_tol(vtol) for ALL systems (F08:202-207); stream-ordered like the updates around it. */
 int nka_hip_batch_set_vec_tol(nka_hip_batch_t b, double vtol);
 int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order);
+/* DIAGONAL WEIGHTS (WEIGHTS above), as nka_hip_set_dot_weights of a lone handle, per system:
+ *   ldw >= vlen  nsys rows of ldw doubles, row `sys` weights system `sys`; what lies between two rows is never read
+ *   ldw == 0     ONE row of vlen doubles that all systems share
+ *   other ldw    NKA_HIP_EINVAL
+ *   w == NULL    plain sums again (ldw is ignored)
+ * _set_dot_weights takes device memory -- its span, (nsys-1)*ldw + vlen doubles for rows and vlen for the shared row, is
+ * checked against its allocation before any read --, _set_dot_weights_host host memory.  The values are COPIED into a buffer
+ * of the batch and checked on the device row by row: every weight must be finite and >= 0, otherwise NKA_HIP_EINVAL and the
+ * previous weighting stays in force.  The call synchronises, and the caller's memory is free again when it returns; it is
+ * refused with NKA_HIP_ESTATE while the batch's stream is capturing.  A change applies from the next update on and to ALL
+ * systems (there is no mask); the subspaces then mix two metrics, so follow it with nka_hip_batch_restart.
+ * The buffer -- nsys rows at the slot stride, so every row is 16-byte aligned -- is allocated at the FIRST set, freed by
+ * nka_hip_batch_destroy only, and never moves; it serves both forms (the shared form writes row 0 and runs with row stride
+ * 0).  Whether an update is weighted, the buffer's address and the row stride are arguments of its launch: a captured update
+ * keeps whether it was weighted and which form it ran, and reads the buffer's VALUES at replay, so new values of the same
+ * form set between replays apply to the next replay.
+ * nka_hip_batch_dot_weighted: 1 = the next update is weighted, 0 = plain; < 0 on error. */
+int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_t ldw);
+int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, int64_t ldw);
+int nka_hip_batch_dot_weighted(nka_hip_batch_t b);
 /* Rebind to another hipStream_t; work already enqueued stays ordered before. */
 int nka_hip_batch_set_stream(nka_hip_batch_t b, void *stream);
 

@@ -122,6 +122,51 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         _check(self._L.nka_hip_batch_set_sum_order(self._handle(), int(order)), "batch_set_sum_order", self._L)
         return self
 
+    def set_dot_weights(self, w):
+        """Diagonal weights of the dot product, <x,y>_w = sum_i w_i x_i y_i per system (include/nka_hip_batch.h, WEIGHTS): a
+        float64 CUDA tensor on the batch's device or a numpy array, 1-d of vlen entries (one row shared by all systems) or 2-d
+        nsys x vlen (row `sys` weights system `sys`; element stride 1, the row stride is `ldw`); None: plain sums again.
+        Finite and >= 0; copied, so `w` is free again on return.  Synchronises; applies from the next update on -- follow it
+        with restart().  Returns self."""
+        import torch
+        h = self._handle()
+        what = "batch set_dot_weights"
+        if w is None:
+            self._follow()
+            _check(self._L.nka_hip_batch_set_dot_weights(h, None, 0), "batch_set_dot_weights", self._L)
+            return self
+        if isinstance(w, torch.Tensor):
+            if not (w.is_cuda and w.dtype == torch.float64 and w.device.index == self._device):
+                raise NKAError(f"{what}: a tensor must be float64 and live on the batch's device")
+            shape, strides = tuple(w.shape), tuple(w.stride())
+            entry, ptr = self._L.nka_hip_batch_set_dot_weights, w.data_ptr()
+        elif isinstance(w, np.ndarray):
+            if w.dtype != np.float64 or w.strides is None or any(st % 8 for st in w.strides):
+                raise NKAError(f"{what}: an array must be float64")
+            shape, strides = tuple(w.shape), tuple(st // 8 for st in w.strides)
+            entry, ptr = self._L.nka_hip_batch_set_dot_weights_host, w.ctypes.data
+        else:
+            raise NKAError(f"{what}: need a float64 CUDA tensor, a numpy array or None")
+        if shape == (self._vlen,):
+            if self._vlen > 1 and strides[0] != 1:
+                raise NKAError(f"{what}: the element stride must be 1")
+            ldw = 0
+        elif shape == (self._nsys, self._vlen):
+            if (self._vlen > 1 and strides[1] != 1) or (self._nsys > 1 and strides[0] < self._vlen):
+                raise NKAError(f"{what}: the rows must be contiguous (element stride 1) and must not overlap")
+            ldw = int(strides[0]) if self._nsys > 1 else max(int(strides[0]), self._vlen)
+        else:
+            raise NKAError(f"{what}: need {self._vlen} entries (shared) or {self._nsys} rows of {self._vlen}, got {shape}")
+        self._follow()
+        _check(entry(h, C.c_void_p(ptr), ldw), "batch_set_dot_weights", self._L)
+        return self
+
+    def dot_weighted(self) -> bool:
+        """True while diagonal dot-product weights are set (nka_hip_batch_dot_weighted)."""
+        r = self._L.nka_hip_batch_dot_weighted(self._handle())
+        _check(min(r, 0), "batch_dot_weighted", self._L)
+        return r == 1
+
     # -- queries (synchronise) ---------------------------------------------
     def num_sys(self) -> int:
         return self._nsys

@@ -17,6 +17,8 @@
 // mapping (pairs 2t, 2t+1 of every 512) and every accumulation order are the same whether a row of f is 16-byte aligned
 // (16-byte loads) or not (two 8-byte loads), so results do not depend on ld, on nsys, or on a system's position.
 // ORDERED = true is the reference-order sibling: every sum element after element, unfused, one thread per sum.
+// WGT = true forms the weighted sums of nka_hip_batch_set_dot_weights in phases 2 and 3 (either order); phase 6 never reads
+// the weights.
 #include "handles.hpp"
 #include "nka_device.hpp"
 #include "../../include/nka_hip_batch.h"
@@ -132,9 +134,14 @@ __device__ __forceinline__ void batch_block_sum(const double (&acc)[NACC], doubl
 
 enum { HDR_PENDING = 0, HDR_FIRST = 1, HDR_NOLDER = 2, HDR_NCOMB = 3, HDR_NEW = 4, HDR_NORMED = 5 };
 
-template <int COMB, bool ORDERED>
+// WGT = true: the diagonal weights of nka_hip_batch_set_dot_weights.  Row `sys` of the batch's weight buffer -- wgt_all +
+// sys * wgt_stride, wgt_stride = 0 for the form all systems share -- is read like a stored vector, and fl(w_i * a_i) is the
+// FIRST operand of every product (nka_device.hpp, DIAGONAL WEIGHTS); element -> thread map, per-thread order and reduction
+// are those of WGT = false, which reads neither argument and is the unweighted kernel instruction for instruction.
+template <int COMB, bool ORDERED, bool WGT>
 __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, double *__restrict__ f_all, int64_t ld,
-                                                                const int32_t *__restrict__ active) {
+                                                                const int32_t *__restrict__ active,
+                                                                const double *__restrict__ wgt_all, int64_t wgt_stride) {
 #pragma clang fp contract(off)      // elementwise statements and the reference-order sums round like the reference; fma is explicit
   constexpr bool RCP = (COMB == 1);
   constexpr bool COMPACT = (COMB == 2);
@@ -149,6 +156,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
   double *const f = f_all + (size_t)sys * ld;
   double *const W = a.w + (size_t)sys * a.sys_stride, *const V = a.v + (size_t)sys * a.sys_stride;
   const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;      // (stored vectors: always 16-byte aligned)
+  const double *wg = nullptr;                                        // this system's weights (rows: 16-byte aligned)
+  if constexpr (WGT) wg = wgt_all + (size_t)sys * wgt_stride;
 
   const nka_host::BatchLds lds = nka_host::batch_lds(mvec);
   double *const shd = reinterpret_cast<double *>(smem);
@@ -201,7 +210,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
         double dd = 0.0;
         for (int64_t i = 0; i < n; i++) {
           const double d = w1[i] - f[i];
-          dd = dd + d * d;
+          if constexpr (WGT) dd = dd + (wg[i] * d) * d; else dd = dd + d * d;
         }
         res[kBatchAcc] = dd;
       }
@@ -211,11 +220,13 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
       batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
         constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
         const d2 fv = ld_tile<FULL, FV>(f, i, n), wv = ld_tile<FULL, true>(w1, i, n);
+        d2 gv;
+        if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);
 #pragma unroll
         for (int q = 0; q < 2; q++)
           if (FULL || i + q < n) {
             const double d = wv[q] - fv[q];
-            acc[0] = fma(d, d, acc[0]);
+            if constexpr (WGT) acc[0] = fma(gv[q] * d, d, acc[0]); else acc[0] = fma(d, d, acc[0]);
           }
       });
       batch_block_sum<1>(acc, sm, res + kBatchAcc);
@@ -234,13 +245,16 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
       double acc = 0.0;
       for (int64_t i = 0; i < n; i++) {
         const double wn = batch_nrm<RCP>(w1[i] - f[i], s, rs);
-        acc = acc + wn * y[i];
+        if constexpr (WGT) acc = t == 0 ? acc + (wg[i] * y[i]) * wn : acc + (wg[i] * wn) * y[i];      // dp(f, w1'), dp(w1', w_p)
+        else acc = acc + wn * y[i];
       }
       red[t == 0 ? 1 : 2 + (t - 1)] = acc;
     } else if (t >= 64 && t - 64 < nolder) {
       const double *y = W + (size_t)(ps[t - 64] - 1) * a.stride;
       double acc = 0.0;
-      for (int64_t i = 0; i < n; i++) acc = acc + f[i] * y[i];
+      for (int64_t i = 0; i < n; i++) {
+        if constexpr (WGT) acc = acc + (wg[i] * f[i]) * y[i]; else acc = acc + f[i] * y[i];
+      }
       red[2 + mvec + (t - 64)] = acc;
     }
   } else {
@@ -262,18 +276,24 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
         d2 wv[kBatchGroup];
 #pragma unroll
         for (int j = 0; j < kBatchGroup; j++) wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+        d2 gv;
+        if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);
 #pragma unroll
         for (int q = 0; q < 2; q++)
           if (FULL || i + q < n) {
             const double fq = fv[q];
+            double fa = fq;                                  // first operand of the products on f: fl(w f), formed once
+            if constexpr (WGT) fa = gv[q] * fq;
             if (normed) {
               const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
-              if (g == 0) acc[2 * kBatchGroup] = fma(fq, wn, acc[2 * kBatchGroup]);
+              double wa = wn;                                // first operand of the Gram row: fl(w w1')
+              if constexpr (WGT) wa = gv[q] * wn;
+              if (g == 0) acc[2 * kBatchGroup] = fma(fa, wn, acc[2 * kBatchGroup]);
 #pragma unroll
-              for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wn, wv[j][q], acc[j]);
+              for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wa, wv[j][q], acc[j]);
             }
 #pragma unroll
-            for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fq, wv[j][q], acc[kBatchGroup + j]);
+            for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fa, wv[j][q], acc[kBatchGroup + j]);
           }
       });
       batch_block_sum<kBatchAcc>(acc, sm, res);
@@ -408,6 +428,32 @@ __global__ __launch_bounds__(64) void k_batch_set_vtol(BatchArgs a, double vtol)
   if (sys < a.nsys) batch_ctl(a, sys).dc[DC_VTOL] = vtol;
 }
 
+// Set-time check of `rows` weight rows of n doubles, `ldw` apart (the strided sibling of k_check_weights, nka_kernels.hpp;
+// the elements between two rows are never read): out[0] += entries that are not finite or below zero, out[1] = min over
+// row * n + column of them (starts at ~0).  Grid-stride; runs once per set, not in an update.
+__global__ __launch_bounds__(kBatchThreads) void k_batch_check_weights(const double *__restrict__ w, int64_t n, int64_t ldw,
+                                                                       int64_t rows, unsigned long long *out) {
+  unsigned long long bad = 0, first = ~0ull;
+  for (int64_t e = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; e < rows * n; e += (int64_t)gridDim.x * kBatchThreads) {
+    const double x = w[(e / n) * ldw + e % n];
+    if (!(x >= 0.0 && x <= __DBL_MAX__)) {      // NaN, -Inf, +Inf, negative (-0.0 is >= 0)
+      bad++;
+      if ((unsigned long long)e < first) first = (unsigned long long)e;
+    }
+  }
+  if (bad) {
+    atomicAdd(out, bad);
+    atomicMin(out + 1, first);
+  }
+}
+// ... and the copy of the checked rows into the batch's buffer (rows `dld` apart)
+__global__ __launch_bounds__(kBatchThreads) void k_batch_copy_weights(double *__restrict__ dst, int64_t dld,
+                                                                      const double *__restrict__ w, int64_t n, int64_t ldw,
+                                                                      int64_t rows) {
+  for (int64_t e = (int64_t)blockIdx.x * kBatchThreads + threadIdx.x; e < rows * n; e += (int64_t)gridDim.x * kBatchThreads)
+    dst[(e / n) * dld + e % n] = w[(e / n) * ldw + e % n];
+}
+
 }  // namespace
 
 struct nka_hip_batch_state {
@@ -417,6 +463,13 @@ struct nka_hip_batch_state {
   int sum_order = NKA_HIP_SUMS_AUTO;
   double vtol = 0.01;
   BatchArgs k{};
+  // diagonal dot-product weights (nka_hip_batch_set_dot_weights): nsys rows at the slot stride, allocated at the first set,
+  // freed at destroy only and never moved -- a captured update holds the address.  The form all systems share lives in row 0.
+  double *wgt = nullptr;
+  double *wgt_stage = nullptr;              // the same shape: where the host entry puts the caller's rows for the check
+  unsigned long long *wgt_chk = nullptr;    // two words of k_batch_check_weights
+  bool weighted = false;
+  int64_t wgt_stride = 0;                   // row stride the updates run with: k.stride, or 0 in the shared form
 };
 
 namespace {
@@ -457,13 +510,64 @@ int list_op(nka_hip_batch_t b, int op, const int32_t *active, const char *who) {
   return 0;
 }
 
+// (whether an update is weighted, and in which form, travels in the launch: the kernel instance, the weight pointer and the
+// row stride are fixed when the update is enqueued -- or captured -- and only the buffer's VALUES are read when it runs)
+template <int COMB, bool ORDERED, bool WGT>
+void launch_update_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active) {
+  const size_t lds = nka_host::batch_lds(b->k.mvec).bytes();
+  hipLaunchKernelGGL((k_batch_update<COMB, ORDERED, WGT>), dim3((unsigned)b->k.nsys), dim3(kBatchThreads), lds, b->stream, b->k, f, ld,
+                     active, WGT ? (const double *)b->wgt : (const double *)nullptr, WGT ? b->wgt_stride : (int64_t)0);
+}
 template <int COMB>
 void launch_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active) {
-  const size_t lds = nka_host::batch_lds(b->k.mvec).bytes();
-  if (batch_ordered(b))
-    hipLaunchKernelGGL((k_batch_update<COMB, true>), dim3((unsigned)b->k.nsys), dim3(kBatchThreads), lds, b->stream, b->k, f, ld, active);
-  else
-    hipLaunchKernelGGL((k_batch_update<COMB, false>), dim3((unsigned)b->k.nsys), dim3(kBatchThreads), lds, b->stream, b->k, f, ld, active);
+  if (batch_ordered(b)) {
+    if (b->weighted) launch_update_as<COMB, true, true>(b, f, ld, active); else launch_update_as<COMB, true, false>(b, f, ld, active);
+  } else {
+    if (b->weighted) launch_update_as<COMB, false, true>(b, f, ld, active); else launch_update_as<COMB, false, false>(b, f, ld, active);
+  }
+}
+
+// what both weight setters check first
+int weights_settable(nka_hip_batch_t b, const char *what) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(b->stream, &cs) != hipSuccess) (void)hipGetLastError();
+  if (cs != hipStreamCaptureStatusNone) return fail(NKA_HIP_ESTATE, std::string(what) + ": the batch's stream is capturing");
+  return 0;
+}
+int weights_ldw(nka_hip_batch_t b, int64_t ldw, const char *what) {
+  if (ldw != 0 && ldw < b->k.n) return fail(NKA_HIP_EINVAL, std::string(what) + ": ldw must be >= vlen (one row per system) or 0 (one row for all)");
+  if (ldw > (INT64_MAX / (int64_t)sizeof(double) - b->k.n) / (int64_t)b->k.nsys)
+    return fail(NKA_HIP_EINVAL, std::string(what) + ": ldw is larger than any allocation");
+  return 0;
+}
+int weights_alloc(nka_hip_batch_t b, double **buf) {
+  if (!b->wgt_chk) HIP_TRY(hipMalloc((void **)&b->wgt_chk, 2 * sizeof(unsigned long long)));
+  if (!*buf) HIP_TRY(hipMalloc((void **)buf, sizeof(double) * (size_t)b->k.stride * (size_t)b->k.nsys));
+  return 0;
+}
+// `src`: device memory, nsys rows `ldw` apart, or one row with ldw == 0.  Checked where it lies, row by row, and only then
+// copied into the batch's buffer: invalid weights leave the previous weighting in force.  Synchronises.
+int set_weights_from_device(nka_hip_batch_t b, const double *src, int64_t ldw, const char *what) {
+  hipStream_t s = b->stream;
+  const int64_t n = b->k.n, rows = ldw == 0 ? 1 : b->k.nsys;
+  if (int rc = weights_alloc(b, &b->wgt)) return rc;
+  unsigned long long res[2] = {0ull, ~0ull};
+  HIP_TRY(hipMemcpyAsync(b->wgt_chk, res, sizeof res, hipMemcpyHostToDevice, s));
+  const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, (rows * n + kBatchThreads - 1) / kBatchThreads));
+  hipLaunchKernelGGL(k_batch_check_weights, dim3(g), dim3(kBatchThreads), 0, s, src, n, ldw, rows, b->wgt_chk);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(res, b->wgt_chk, sizeof res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (res[0] != 0)
+    return fail(NKA_HIP_EINVAL, std::string(what) + ": " + std::to_string(res[0]) + " weight(s) negative or not finite, the first in row " +
+                                    std::to_string(res[1] / (unsigned long long)n) + " at index " + std::to_string(res[1] % (unsigned long long)n) +
+                                    " (the previous weighting stays in force)");
+  hipLaunchKernelGGL(k_batch_copy_weights, dim3(g), dim3(kBatchThreads), 0, s, b->wgt, b->k.stride, src, n, ldw, rows);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  b->weighted = true;
+  b->wgt_stride = ldw == 0 ? 0 : b->k.stride;
+  return 0;
 }
 
 }  // namespace
@@ -551,6 +655,9 @@ int nka_hip_batch_destroy(nka_hip_batch_t b) {
   hipFree(b->k.v);
   hipFree(b->k.ic);
   hipFree(b->k.dc);
+  hipFree(b->wgt);
+  hipFree(b->wgt_stage);
+  hipFree(b->wgt_chk);
   delete b;
   return 0;
 }
@@ -595,6 +702,43 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
     return fail(NKA_HIP_EINVAL, "batch_set_sum_order: unknown sum order");
   b->sum_order = order;
   return 0;
+}
+
+int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_t ldw) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: null handle");
+  HIP_TRY(hipSetDevice(b->device));
+  if (int rc = weights_settable(b, "batch_set_dot_weights")) return rc;
+  if (!w_dev) {
+    b->weighted = false;      // (the buffer stays: a captured update may hold its address)
+    return 0;
+  }
+  if (int rc = weights_ldw(b, ldw, "batch_set_dot_weights")) return rc;
+  const int64_t span = ldw == 0 ? b->k.n : (int64_t)(b->k.nsys - 1) * ldw + b->k.n;
+  if (int rc = nka_detail::check_device_span(w_dev, span, "batch_set_dot_weights: w")) return rc;
+  return set_weights_from_device(b, w_dev, ldw, "batch_set_dot_weights");
+}
+
+int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, int64_t ldw) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: null handle");
+  HIP_TRY(hipSetDevice(b->device));
+  if (int rc = weights_settable(b, "batch_set_dot_weights_host")) return rc;
+  if (!w_host) {
+    b->weighted = false;
+    return 0;
+  }
+  if (int rc = weights_ldw(b, ldw, "batch_set_dot_weights_host")) return rc;
+  // the caller's rows, without the padding between them, into a staging buffer of the batch's own row stride; checked there
+  if (int rc = weights_alloc(b, &b->wgt_stage)) return rc;
+  const int64_t rows = ldw == 0 ? 1 : b->k.nsys;
+  for (int64_t r = 0; r < rows; r++)
+    HIP_TRY(hipMemcpyAsync(b->wgt_stage + (size_t)r * b->k.stride, w_host + (size_t)r * ldw, sizeof(double) * (size_t)b->k.n,
+                           hipMemcpyHostToDevice, b->stream));
+  return set_weights_from_device(b, b->wgt_stage, ldw == 0 ? 0 : b->k.stride, "batch_set_dot_weights_host");
+}
+
+int nka_hip_batch_dot_weighted(nka_hip_batch_t b) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_dot_weighted: null handle");
+  return b->weighted ? 1 : 0;
 }
 
 int nka_hip_batch_set_stream(nka_hip_batch_t b, void *stream) {

@@ -13,7 +13,13 @@ anything, understated): inputs must not repeat while their difference is still i
 Per grid point: updates/s of the whole batch (a), bytes moved 8*nsys*vlen*(11+L+k) (compact storage, L = mvec - 1 older
 vectors in the sums, k = mvec combined) over time as a share of 8 TB/s, and the ratio time(b)/time(a); the bar for
 nsys >= 16 is 1.06.  --probe-vlens / --probe-nsys add points beyond the grid (to find the length at which the loop over
-lone handles catches up: the cap NKA_HIP_BATCH_MAX_VLEN).  Every line is flushed as it is measured."""
+lone handles catches up: the cap NKA_HIP_BATCH_MAX_VLEN).  Every line is flushed as it is measured.
+
+--weights measures something else, with the same windows and the same alternation: three batches on the same inputs -- plain
+sums, diagonal weights in the form all systems share (nka_hip_batch_set_dot_weights, ldw = 0) and one row of weights per
+system -- and no lone handles.  Weights 2^U(-3, 3).  Per point: the time of an update of each and the two ratios
+weighted / plain, beside the ratio of the streams an update reads or writes per element: 2 + 6 G + (7 + k) without weights
+(norm pass 2; G = ceil(L / 4) sweeps of 6; combine 7 + k in compact storage), 3 + 7 G + (7 + k) with them.  No bar."""
 import argparse
 import ctypes as C
 import os
@@ -94,6 +100,86 @@ def measure(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
     return out
 
 
+def measure_weights(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
+    npool = mvec + 3
+    need = 8.0 * nsys * vlen * (3 * 2 * (mvec + 1) + npool + 3 + 2)       # three batches' slots, the pool, three f, weights
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    w = torch.exp2(6.0 * torch.rand(nsys, vlen, dtype=torch.float64, device="cuda") - 3.0)
+    forms = {"plain": None, "shared": w[0], "rows": w}
+    Fs, hs, batches = {}, {}, {}
+    for name, wf in forms.items():
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+        batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec).set_dot_weights(wf)
+        hs[name] = batches[name]._handle()
+    assert [b.dot_weighted() for b in batches.values()] == [False, True, True]
+    ld = int(Fs["plain"].stride(0)) if nsys > 1 else vlen
+    upd = L.nka_hip_batch_accel_update
+    step = [0]
+
+    def run(name, reps):
+        F, h = Fs[name], hs[name]
+        p = C.c_void_p(F.data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[step[0] % npool])
+            step[0] += 1
+            assert upd(h, p, ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in forms}
+    for name in forms:                             # warm: fill the lists (steady state), settle clocks and caches
+        step[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    for name in forms:
+        assert (batches[name].num_vec() == mvec).all(), name
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in forms:
+            ts[name].append(timed(name, reps[name]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    for name in forms:
+        assert (batches[name].num_vec() == mvec).all(), name
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+        batches[name].delete()
+    del pool, w, forms, Fs
+    torch.cuda.empty_cache()
+    return out
+
+
+def weights_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    emit(f"# one update of a batch with plain sums, with diagonal weights all systems share (ldw = 0) and with one row of "
+         f"weights per system; {torch.cuda.get_device_name(0)}; windows >= {args.window} s, median of {args.repeats}, the three "
+         f"alternated; default flavour and sums, full list; weights 2^U(-3,3)")
+    emit("# streams per element and update: 2 + 6 G + (7 + k) plain, 3 + 7 G + (7 + k) weighted, G = ceil((mvec - 1) / 4), k = mvec")
+    emit(f"{'nsys':>5} {'vlen':>6} {'mvec':>4} {'plain us':>10} {'shared us':>10} {'rows us':>10} {'shared/plain':>12} "
+         f"{'rows/plain':>10} {'streams w/p':>11}")
+    t0 = time.time()
+    for n, v, m in points:
+        r = measure_weights(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9)
+        if r is None:
+            emit(f"{n:5d} {v:6d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        g = (m - 1 + 3) // 4
+        pred = (3 + 7 * g + 7 + m) / (2 + 6 * g + 7 + m)
+        emit(f"{n:5d} {v:6d} {m:4d} {r['plain'] * 1e6:10.1f} {r['shared'] * 1e6:10.1f} {r['rows'] * 1e6:10.1f} "
+             f"{r['shared'] / r['plain']:12.3f} {r['rows'] / r['plain']:10.3f} {pred:11.3f}   "
+             f"(spread plain {100 * r['spread_plain']:.1f} % shared {100 * r['spread_shared']:.1f} % rows {100 * r['spread_rows']:.1f} %)")
+    emit(f"# {len(points)} points in {time.time() - t0:.0f} s")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--nsys", default="1,16,256,1024,4096")
@@ -105,6 +191,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--mem-gb", type=float, default=200.0, help="skip (and say so) a point that needs more device memory")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--weights", action="store_true",
+                    help="time a weighted batch (shared and per-system weights) beside the plain one; without --nsys / --vlens / "
+                         "--mvecs: nsys 256,4096 x vlen 1024,16384 x mvec 10,20")
     args = ap.parse_args()
     import torch
     import nka_amd
@@ -126,6 +215,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.weights:
+        for name, grid_w in (("nsys", "256,4096"), ("vlens", "1024,16384"), ("mvecs", "10,20")):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+        return weights_main(args, torch, nka_amd, L, emit)
     emit(f"# batched update (a) against nsys lone handles in a loop on one stream (b); {torch.cuda.get_device_name(0)}; "
          f"windows >= {args.window} s, median of {args.repeats}, contenders alternated; cap = {cap}; default flavour and sums, "
          f"full list")
