@@ -17,7 +17,7 @@
  *   MASKS    active_dev: nsys int32 in DEVICE memory (0 = the system sits this call out), or NULL for all systems.  The mask
  *            stays on the device, so a caller's per-system convergence test never reaches the host.  For a system that sits
  *            out, its row of f and every byte of its state are left exactly as they were.
- *   ASYNC    accel_update, restart, relax and set_vec_tol only enqueue on the batch's stream: no allocation, no
+ *   ASYNC    accel_update, accel_step, restart, relax and set_vec_tol only enqueue on the batch's stream: no allocation, no
  *            synchronisation.  The queries synchronise it.  Not thread-safe per batch; distinct batches are independent.
  *   GRAPHS   The list length is read on the device, per system: no kernel width depends on what the host knows.  An update
  *            can therefore be captured into a hipGraph FROM THE FIRST UPDATE ON and replayed through drops, relax and
@@ -67,6 +67,33 @@
  *            with one row per system -- the 1.14 (mvec 10; 1.10 at mvec 20) at 4096 x 16 384, where 512 MB of weights stream
  *            from memory and the count of streams per element (norm pass 2 -> 3, each sweep of four 6 -> 7, combine unchanged:
  *            +10.8 % / +10.2 %) is what it costs.
+ *   STEP     nka_hip_batch_accel_step: the loop around an update -- f = residual(x); test ||f||; accel_update(f); x -= f, the
+ *            reference's own example (nka_example.F90:243-254) -- with everything but the residual inside the SAME one launch.
+ *            Per system with active[sys] != 0 on entry (active_dev == NULL: all):
+ *              1  r = sqrt(dp(f, f)) with the dot product the batch runs at that moment, weights and sum order: fast sums
+ *                 sum fma(a, f_i, .) with a = f_i, or fl(w_i f_i) when weighted, in the element -> thread map, per-thread order
+ *                 and workgroup reduction of every other sum; reference order acc = acc + a * f_i, element after element.
+ *                 fnorm_dev[sys] = r if fnorm_dev is given.  The stop rule therefore measures what the accelerator minimises.
+ *              2  if tol_dev is given and r <= tol_dev[sys], the system RETIRES ITSELF: active_dev[sys] = 0, and nothing else of
+ *                 it is written -- its rows of f and x, its control block, red[], slots and digest stay as they were.  A NaN on
+ *                 either side compares false and the system goes on, like the reference with a NaN norm.  The reference's
+ *                 example stops at `<`; this entry stops at `<=`, so that tol = 0 retires an exactly zero residual.
+ *              3  otherwise the update of nka_hip_batch_accel_update -- the row of f, the state and red[] BIT-EQUAL to that
+ *                 entry's -- and then, if x_dev is given, x_i = fl(x_i - f_out_i) over the row (f_out: what the update leaves
+ *                 in f).  Rows of x that are 16-byte aligned use 16-byte accesses, others go element by element: the same bits.
+ *            A system inactive on entry has nothing read or written, fnorm_dev[sys] included.  One launch on the batch's
+ *            stream, nothing allocated or synchronised, capturable from the first call on; each workgroup writes only its own
+ *            entries of active and fnorm, so BITS above holds unchanged.  NKA_HIP_EINVAL, the batch staying usable: tol_dev
+ *            without active_dev (a system cannot retire without a mask); ldx < vlen; the span of x overlapping the span of f;
+ *            fnorm overlapping tol (a threshold would be overwritten while it is read); the span of x ((nsys-1)*ldx + vlen
+ *            doubles), fnorm, tol or active (nsys entries each) not inside its allocation.
+ *            RELATIVE TOLERANCES: call once with tol_dev = NULL and fnorm_dev given, then form tol = TOL * fnorm with a device
+ *            operation of the caller's: no host round trip.
+ *            COST, MEASURED (profiles/r10/batch_step_throughput.txt, 1 x MI355X; nsys 256 / 4096 x vlen 64 / 1024 / 16 384 x
+ *            mvec 10 / 20): a step with x, mask, tol and fnorm takes 0.92 ... 1.10 x the time of a plain update (the combine
+ *            moves 9 + k streams per element instead of 7 + k) and 0.75 ... 0.99 x the time of the same loop composed from
+ *            accel_update and three kernels of the caller -- EXCEPT at 4096 x 64, which runs in reference order: 1.21 / 1.07 x
+ *            a plain update and 1.06 / 1.03 x the composed loop (mvec 10 / 20; dp(f, f) is one more dependent chain there).
  *   OUT OF SCOPE  sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -94,6 +121,10 @@ int nka_hip_batch_destroy(nka_hip_batch_t b);
 
 /* call a%accel_update(f) for every active system, one launch.  Rows of inactive systems are not touched. */
 int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, const int32_t *active_dev);
+/* STEP above: norm, stop rule, update and correction of every active system, one launch.  x_dev (iterate rows, ldx apart),
+ * active_dev (READ AND WRITTEN), tol_dev (nsys thresholds) and fnorm_dev (nsys doubles out) may each be NULL. */
+int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, double *x_dev, int64_t ldx, int32_t *active_dev,
+                             const double *tol_dev, double *fnorm_dev);
 /* call a%restart() / a%relax() for every active system (F08:422-457). */
 int nka_hip_batch_restart(nka_hip_batch_t b, const int32_t *active_dev);
 int nka_hip_batch_relax(nka_hip_batch_t b, const int32_t *active_dev);

@@ -130,6 +130,7 @@ BATCH_SIGNATURES = {
                                        C.c_void_p]),
     "nka_hip_batch_destroy": (C.c_int, [C.c_void_p]),
     "nka_hip_batch_accel_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "nka_hip_batch_accel_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nka_hip_batch_restart": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nka_hip_batch_relax": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nka_hip_batch_set_vec_tol": (C.c_int, [C.c_void_p, C.c_double]),

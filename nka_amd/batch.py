@@ -81,24 +81,59 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         _check(self._L.nka_hip_batch_set_stream(self._handle(), C.c_void_p(int(stream))), "batch_set_stream", self._L)
         self._stream = int(stream)
 
+    def _rows(self, F, what):
+        """-> (device address, row stride) of nsys rows of vlen float64 elements."""
+        import torch
+        if not (isinstance(F, torch.Tensor) and F.is_cuda and F.dtype == torch.float64 and F.dim() == 2):
+            raise NKAError(f"{what}: need a 2-d float64 CUDA tensor, one row per system")
+        if F.shape[0] != self._nsys or F.shape[1] != self._vlen:
+            raise NKAError(f"{what}: need {self._nsys} rows of {self._vlen} elements, got {tuple(F.shape)}")
+        if (self._vlen > 1 and F.stride(1) != 1) or (self._nsys > 1 and F.stride(0) < self._vlen):
+            raise NKAError(f"{what}: the rows must be contiguous (element stride 1) and must not overlap")
+        if F.device.index != self._device:
+            raise NKAError(f"{what}: tensor lives on another device than the batch")
+        ld = int(F.stride(0)) if self._nsys > 1 else max(int(F.stride(0)), self._vlen)
+        return C.c_void_p(F.data_ptr()), ld
+
+    def _per_system(self, v, what, name):
+        """-> device address of nsys float64 entries, or None."""
+        if v is None:
+            return None
+        import torch
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float64 and v.is_contiguous() and v.dim() == 1
+                and v.device.index == self._device):
+            raise NKAError(f"{what}: {name} must be a contiguous 1-d float64 CUDA tensor on the batch's device, or None")
+        if v.numel() != self._nsys:
+            raise NKAError(f"{what}: {name} must have one entry per system ({self._nsys}), got {v.numel()}")
+        return C.c_void_p(v.data_ptr())
+
     def accel_update(self, F, active=None):
         """F: 2-d float64 CUDA tensor, one row per system (nsys x vlen; rows contiguous, the row stride is `ld`), updated in
         place, asynchronously on the batch's stream.  active: optional int32 CUDA tensor of nsys entries, 0 = the system sits
         this call out (its row and its state are not touched)."""
-        import torch
         h = self._handle()
-        if not (isinstance(F, torch.Tensor) and F.is_cuda and F.dtype == torch.float64 and F.dim() == 2):
-            raise NKAError("batch accel_update: need a 2-d float64 CUDA tensor, one row per system")
-        if F.shape[0] != self._nsys or F.shape[1] != self._vlen:
-            raise NKAError(f"batch accel_update: need {self._nsys} rows of {self._vlen} elements, got {tuple(F.shape)}")
-        if (self._vlen > 1 and F.stride(1) != 1) or (self._nsys > 1 and F.stride(0) < self._vlen):
-            raise NKAError("batch accel_update: the rows must be contiguous (element stride 1) and must not overlap")
-        if F.device.index != self._device:
-            raise NKAError("batch accel_update: tensor lives on another device than the batch")
-        ld = int(F.stride(0)) if self._nsys > 1 else max(int(F.stride(0)), self._vlen)
+        ptr, ld = self._rows(F, "batch accel_update")
         mask = self._mask(active, "batch accel_update")
         self._follow()
-        _check(self._L.nka_hip_batch_accel_update(h, C.c_void_p(F.data_ptr()), ld, mask), "batch_accel_update", self._L)
+        _check(self._L.nka_hip_batch_accel_update(h, ptr, ld, mask), "batch_accel_update", self._L)
+        return F
+
+    def accel_step(self, F, X=None, active=None, tol=None, fnorm=None):
+        """One solve step per system active on entry, in the one launch of accel_update (nka_hip_batch_accel_step; include/
+        nka_hip_batch.h, STEP): fnorm[sys] = sqrt(dp(f, f)) with the batch's own dot product; if that is <= tol[sys] the system
+        retires itself -- active[sys] = 0, nothing else of it written --, otherwise F's row is updated as by accel_update and
+        X's row becomes X - F.  X: like F, with its own row stride, not overlapping F.  active: as in accel_update, but WRITTEN.
+        tol, fnorm: contiguous 1-d float64 CUDA tensors of nsys entries; tol needs active.  Each may be None."""
+        h = self._handle()
+        what = "batch accel_step"
+        ptr, ld = self._rows(F, what)
+        xptr, ldx = self._rows(X, what + ": X") if X is not None else (None, 0)
+        mask = self._mask(active, what)
+        tolp, fnp = self._per_system(tol, what, "tol"), self._per_system(fnorm, what, "fnorm")
+        if tolp is not None and mask is None:
+            raise NKAError(f"{what}: tol needs a mask (a system retires by clearing its entry of `active`)")
+        self._follow()
+        _check(self._L.nka_hip_batch_accel_step(h, ptr, ld, xptr, ldx, mask, tolp, fnp), "batch_accel_step", self._L)
         return F
 
     def restart(self, active=None):

@@ -19,6 +19,10 @@
 // ORDERED = true is the reference-order sibling: every sum element after element, unfused, one thread per sum.
 // WGT = true forms the weighted sums of nka_hip_batch_set_dot_weights in phases 2 and 3 (either order); phase 6 never reads
 // the weights.
+// A trailing StepArgs argument makes the instance a SOLVE STEP (nka_hip_batch_accel_step): <f,f> rides along in phase 2 (or is
+// swept alone where there is no pending pair), the system may retire itself between phases 2 and 3 -- up to there a workgroup
+// has written LDS only --, and phase 6 also forms x = fl(x - f_out).  Without it every step statement is discarded at compile
+// time and the instance is the plain update, instruction for instruction.
 #include "handles.hpp"
 #include "nka_device.hpp"
 #include "../../include/nka_hip_batch.h"
@@ -48,6 +52,15 @@ struct BatchArgs {
   int64_t stride, sys_stride, n;
   int32_t ic_stride, dc_stride, mvec, nsys;
 };
+
+// what a solve step takes beside the update's arguments; each pointer may be NULL (a workgroup-uniform branch, not an instance)
+struct StepArgs {
+  double *x;            // iterate rows, ldx apart: x = fl(x - f_out) where the system updates
+  int64_t ldx;
+  const double *tol;    // r <= tol[sys]: the system retires itself (active[sys] = 0) and nothing else of it is written
+  double *fnorm;        // r = sqrt(dp(f, f)) of every system active on entry
+};
+__device__ __forceinline__ const StepArgs &step_args(const StepArgs &st) { return st; }
 
 __host__ __device__ inline Ctl batch_ctl(const BatchArgs &a, int sys) {
   Ctl c{};
@@ -138,11 +151,15 @@ enum { HDR_PENDING = 0, HDR_FIRST = 1, HDR_NOLDER = 2, HDR_NCOMB = 3, HDR_NEW = 
 // sys * wgt_stride, wgt_stride = 0 for the form all systems share -- is read like a stored vector, and fl(w_i * a_i) is the
 // FIRST operand of every product (nka_device.hpp, DIAGONAL WEIGHTS); element -> thread map, per-thread order and reduction
 // are those of WGT = false, which reads neither argument and is the unweighted kernel instruction for instruction.
-template <int COMB, bool ORDERED, bool WGT>
+// Step...: nothing (the update) or one StepArgs (the solve step, above); a step writes active[sys] = 0 when the system retires.
+template <int COMB, bool ORDERED, bool WGT, class... Step>
 __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, double *__restrict__ f_all, int64_t ld,
                                                                 const int32_t *__restrict__ active,
-                                                                const double *__restrict__ wgt_all, int64_t wgt_stride) {
+                                                                const double *__restrict__ wgt_all, int64_t wgt_stride, Step... step) {
 #pragma clang fp contract(off)      // elementwise statements and the reference-order sums round like the reference; fma is explicit
+  constexpr bool STEP = sizeof...(Step) != 0;
+  static_assert(sizeof...(Step) <= 1, "at most one StepArgs");
+  constexpr int NNRM = STEP ? 2 : 1;             // sums of phase 2: [<f,f>,] <d,d>, landing in res[kBatchAcc + 1 - NNRM ...]
   constexpr bool RCP = (COMB == 1);
   constexpr bool COMPACT = (COMB == 2);
   const int sys = blockIdx.x;
@@ -204,6 +221,15 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
 
   // ---- phase 2: the norm (F08:266-267) ----
   double s = 0.0;
+  if constexpr (STEP && ORDERED)
+    if (t == 64) {      // dp(f, f), one chain, on a wavefront of its own: beside thread 0's chain where there is a pending pair
+      double ff = 0.0;
+#pragma unroll 4      // (the loads of four elements in flight; the additions stay one chain)
+      for (int64_t i = 0; i < n; i++) {
+        if constexpr (WGT) ff = ff + (wg[i] * f[i]) * f[i]; else ff = ff + f[i] * f[i];
+      }
+      res[kBatchAcc - 1] = ff;
+    }
   if (pending) {
     if (ORDERED) {
       if (t == 0) {
@@ -216,7 +242,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
       }
       __syncthreads();
     } else {
-      double acc[1] = {0.0};
+      double acc[NNRM] = {};
       batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
         constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
         const d2 fv = ld_tile<FULL, FV>(f, i, n), wv = ld_tile<FULL, true>(w1, i, n);
@@ -226,13 +252,47 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
         for (int q = 0; q < 2; q++)
           if (FULL || i + q < n) {
             const double d = wv[q] - fv[q];
-            if constexpr (WGT) acc[0] = fma(gv[q] * d, d, acc[0]); else acc[0] = fma(d, d, acc[0]);
+            if constexpr (WGT) acc[NNRM - 1] = fma(gv[q] * d, d, acc[NNRM - 1]); else acc[NNRM - 1] = fma(d, d, acc[NNRM - 1]);
+            if constexpr (STEP) acc[0] = fma(WGT ? gv[q] * fv[q] : fv[q], fv[q], acc[0]);
           }
       });
-      batch_block_sum<1>(acc, sm, res + kBatchAcc);
+      batch_block_sum<NNRM>(acc, sm, res + kBatchAcc + 1 - NNRM);
     }
     s = sqrt(res[kBatchAcc]);
     if (t == 0) red[0] = res[kBatchAcc];
+  } else if constexpr (STEP) {      // no pending pair (first update, after a restart): f is swept alone
+    if (ORDERED) {
+      __syncthreads();      // (thread 64's chain)
+    } else {
+      double acc[1] = {0.0};
+      batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+        constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+        const d2 fv = ld_tile<FULL, FV>(f, i, n);
+        d2 gv;
+        if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);
+#pragma unroll
+        for (int q = 0; q < 2; q++)
+          if (FULL || i + q < n) acc[0] = fma(WGT ? gv[q] * fv[q] : fv[q], fv[q], acc[0]);
+      });
+      batch_block_sum<1>(acc, sm, res + kBatchAcc - 1);
+    }
+  }
+  // ---- STEP: the residual norm and the stop rule.  r comes from LDS behind a barrier and tol[sys] is written by nobody, so the
+  // return is uniform across the workgroup; nothing but LDS has been written so far ----
+  [[maybe_unused]] double *xrow = nullptr;      // this system's row of the iterate, if there is one
+  [[maybe_unused]] bool xvec = false;
+  if constexpr (STEP) {
+    const StepArgs &st = step_args(step...);
+    const double r = sqrt(res[kBatchAcc - 1]);
+    if (t == 0 && st.fnorm != nullptr) st.fnorm[sys] = r;
+    if (st.tol != nullptr && r <= st.tol[sys]) {      // (a NaN on either side: false, the system goes on)
+      if (t == 0) const_cast<int32_t *>(active)[sys] = 0;
+      return;
+    }
+    if (st.x != nullptr) {
+      xrow = st.x + (size_t)sys * st.ldx;
+      xvec = (reinterpret_cast<uintptr_t>(xrow) % 16) == 0;
+    }
   }
   const bool normed = pending && s != 0.0;      // (s == 0: the scalar step relaxes, F08:275; NaN: goes on, like the reference)
   const double rs = 1.0 / s;
@@ -367,6 +427,11 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
     if (!FULL && i >= n) return;
     const d2 fin = ld_tile<FULL, FV>(f, i, n);
     d2 x = fin;
+    // STEP: the iterate's pair, loaded with the other loads of the tile -- in reference order (validation speed) only where it
+    // is used, so that it holds no register across the combine: 60 VGPR like the plain instances, not 66
+    [[maybe_unused]] d2 xit = {0.0, 0.0};
+    if constexpr (STEP && !ORDERED)
+      if (xrow != nullptr) xit = xvec ? ld_tile<FULL, true>(xrow, i, n) : ld_tile<FULL, false>(xrow, i, n);
     int j0 = 0;
     if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
       double *const wk = W + (size_t)(cs[0] - 1) * a.stride, *const vk = V + (size_t)(cs[0] - 1) * a.stride;
@@ -406,6 +471,13 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
     st_tile<FULL, true>(wnew, i, n, fin);
     st_tile<FULL, true>(vnew, i, n, x);
     if (ncomb > 0) st_tile<FULL, FV>(f, i, n, x);      // (nothing to combine: f stays as it is)
+    if constexpr (STEP)
+      if (xrow != nullptr) {
+        if constexpr (ORDERED) xit = xvec ? ld_tile<FULL, true>(xrow, i, n) : ld_tile<FULL, false>(xrow, i, n);
+        xit[0] = xit[0] - x[0];
+        xit[1] = xit[1] - x[1];
+        if (xvec) st_tile<FULL, true>(xrow, i, n, xit); else st_tile<FULL, false>(xrow, i, n, xit);
+      }
   });
 }
 
@@ -512,19 +584,37 @@ int list_op(nka_hip_batch_t b, int op, const int32_t *active, const char *who) {
 
 // (whether an update is weighted, and in which form, travels in the launch: the kernel instance, the weight pointer and the
 // row stride are fixed when the update is enqueued -- or captured -- and only the buffer's VALUES are read when it runs)
-template <int COMB, bool ORDERED, bool WGT>
-void launch_update_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active) {
+// `step`: nothing for the update, one StepArgs for the solve step
+template <int COMB, bool ORDERED, bool WGT, class... Step>
+void launch_update_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
   const size_t lds = nka_host::batch_lds(b->k.mvec).bytes();
-  hipLaunchKernelGGL((k_batch_update<COMB, ORDERED, WGT>), dim3((unsigned)b->k.nsys), dim3(kBatchThreads), lds, b->stream, b->k, f, ld,
-                     active, WGT ? (const double *)b->wgt : (const double *)nullptr, WGT ? b->wgt_stride : (int64_t)0);
+  hipLaunchKernelGGL((k_batch_update<COMB, ORDERED, WGT, Step...>), dim3((unsigned)b->k.nsys), dim3(kBatchThreads), lds, b->stream, b->k, f,
+                     ld, active, WGT ? (const double *)b->wgt : (const double *)nullptr, WGT ? b->wgt_stride : (int64_t)0, step...);
 }
-template <int COMB>
-void launch_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active) {
+template <int COMB, class... Step>
+void launch_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
   if (batch_ordered(b)) {
-    if (b->weighted) launch_update_as<COMB, true, true>(b, f, ld, active); else launch_update_as<COMB, true, false>(b, f, ld, active);
+    if (b->weighted) launch_update_as<COMB, true, true>(b, f, ld, active, step...);
+    else launch_update_as<COMB, true, false>(b, f, ld, active, step...);
   } else {
-    if (b->weighted) launch_update_as<COMB, false, true>(b, f, ld, active); else launch_update_as<COMB, false, false>(b, f, ld, active);
+    if (b->weighted) launch_update_as<COMB, false, true>(b, f, ld, active, step...);
+    else launch_update_as<COMB, false, false>(b, f, ld, active, step...);
   }
+}
+template <class... Step>
+void launch_flavor(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+  switch (b->flavor) {
+    case NKA_HIP_FLAVOR_F08_VECTOR: launch_update<1>(b, f, ld, active, step...); break;
+    case NKA_HIP_FLAVOR_C: launch_update<2>(b, f, ld, active, step...); break;
+    default: launch_update<0>(b, f, ld, active, step...);
+  }
+}
+// what accel_update and accel_step check of f
+int check_rows(nka_hip_batch_t b, const double *p, int64_t ld, const std::string &who, const char *name, const char *ldname) {
+  if (ld < b->k.n) return fail(NKA_HIP_EINVAL, who + ": " + ldname + " must be >= vlen");
+  if (ld > (INT64_MAX / (int64_t)sizeof(double) - b->k.n) / (int64_t)b->k.nsys)      // (the span below, in bytes, stays inside 64 bits)
+    return fail(NKA_HIP_EINVAL, who + ": " + ldname + " is larger than any allocation");
+  return nka_detail::check_device_span(p, (int64_t)(b->k.nsys - 1) * ld + b->k.n, (who + ": " + name).c_str());
 }
 
 // what both weight setters check first
@@ -665,17 +755,38 @@ int nka_hip_batch_destroy(nka_hip_batch_t b) {
 int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, const int32_t *active_dev) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_accel_update: null handle");
   if (!f_dev) return fail(NKA_HIP_EINVAL, "batch_accel_update: f is NULL");
-  if (ld < b->k.n) return fail(NKA_HIP_EINVAL, "batch_accel_update: ld must be >= vlen");
-  if (ld > (INT64_MAX / (int64_t)sizeof(double) - b->k.n) / (int64_t)b->k.nsys)      // (the span below, in bytes, stays inside 64 bits)
-    return fail(NKA_HIP_EINVAL, "batch_accel_update: ld is larger than any allocation");
   HIP_TRY(hipSetDevice(b->device));
-  if (int rc = nka_detail::check_device_span(f_dev, (int64_t)(b->k.nsys - 1) * ld + b->k.n, "batch_accel_update: f")) return rc;
+  if (int rc = check_rows(b, f_dev, ld, "batch_accel_update", "f", "ld")) return rc;
   if (int rc = check_mask(b, active_dev, "batch_accel_update: active")) return rc;
-  switch (b->flavor) {
-    case NKA_HIP_FLAVOR_F08_VECTOR: launch_update<1>(b, f_dev, ld, active_dev); break;
-    case NKA_HIP_FLAVOR_C: launch_update<2>(b, f_dev, ld, active_dev); break;
-    default: launch_update<0>(b, f_dev, ld, active_dev);
+  launch_flavor(b, f_dev, ld, active_dev);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, double *x_dev, int64_t ldx, int32_t *active_dev,
+                             const double *tol_dev, double *fnorm_dev) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_accel_step: null handle");
+  if (!f_dev) return fail(NKA_HIP_EINVAL, "batch_accel_step: f is NULL");
+  if (tol_dev && !active_dev) return fail(NKA_HIP_EINVAL, "batch_accel_step: tol needs a mask (a system retires by clearing its entry)");
+  HIP_TRY(hipSetDevice(b->device));
+  if (int rc = check_rows(b, f_dev, ld, "batch_accel_step", "f", "ld")) return rc;
+  if (x_dev) {
+    if (int rc = check_rows(b, x_dev, ldx, "batch_accel_step", "x", "ldx")) return rc;
+    const int64_t nf = (int64_t)(b->k.nsys - 1) * ld + b->k.n, nx = (int64_t)(b->k.nsys - 1) * ldx + b->k.n;
+    const uintptr_t f0 = reinterpret_cast<uintptr_t>(f_dev), x0 = reinterpret_cast<uintptr_t>(x_dev);
+    if (f0 < x0 + sizeof(double) * (uintptr_t)nx && x0 < f0 + sizeof(double) * (uintptr_t)nf)
+      return fail(NKA_HIP_EINVAL, "batch_accel_step: the span of x overlaps the span of f");
   }
+  if (int rc = check_mask(b, active_dev, "batch_accel_step: active")) return rc;
+  if (tol_dev)
+    if (int rc = nka_detail::check_device_span(tol_dev, b->k.nsys, "batch_accel_step: tol")) return rc;
+  if (fnorm_dev)
+    if (int rc = nka_detail::check_device_span(fnorm_dev, b->k.nsys, "batch_accel_step: fnorm")) return rc;
+  if (tol_dev && fnorm_dev) {
+    const uintptr_t t0 = reinterpret_cast<uintptr_t>(tol_dev), n0 = reinterpret_cast<uintptr_t>(fnorm_dev), len = sizeof(double) * (uintptr_t)b->k.nsys;
+    if (t0 < n0 + len && n0 < t0 + len) return fail(NKA_HIP_EINVAL, "batch_accel_step: fnorm overlaps tol (a threshold would be overwritten while it is read)");
+  }
+  launch_flavor(b, f_dev, ld, active_dev, StepArgs{x_dev, x_dev ? ldx : 0, tol_dev, fnorm_dev});
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -19,7 +19,17 @@ lone handles catches up: the cap NKA_HIP_BATCH_MAX_VLEN).  Every line is flushed
 sums, diagonal weights in the form all systems share (nka_hip_batch_set_dot_weights, ldw = 0) and one row of weights per
 system -- and no lone handles.  Weights 2^U(-3, 3).  Per point: the time of an update of each and the two ratios
 weighted / plain, beside the ratio of the streams an update reads or writes per element: 2 + 6 G + (7 + k) without weights
-(norm pass 2; G = ceil(L / 4) sweeps of 6; combine 7 + k in compact storage), 3 + 7 G + (7 + k) with them.  No bar."""
+(norm pass 2; G = ceil(L / 4) sweeps of 6; combine 7 + k in compact storage), 3 + 7 G + (7 + k) with them.  No bar.
+
+--step measures the solve step (nka_hip_batch_accel_step), again with the same windows and alternation, three variants of one
+iteration on the same inputs (the copy of the next input into F stands for the caller's residual in all three):
+  (a) nka_hip_batch_accel_update alone;
+  (b) what a caller composes from accel_update: torch.linalg.vector_norm(F, dim=1), the mask update (r > tol, written straight
+      into the int32 mask: the cheapest form, one launch), accel_update under the mask, and the masked X -= F (one addcmul);
+  (c) accel_step with X, the mask, tol and fnorm.
+tol = 0 with residuals that are never zero, so no system retires in (b) or (c).  Per point: the three times, (c)/(b) with the
+spread of the windows -- the condition is that (c) is not slower than (b) by more than that spread -- and (c)/(a) beside the
+ratio of streams per element, 2 + 6 G + (9 + k) over 2 + 6 G + (7 + k): the step reads and writes x in the combine."""
 import argparse
 import ctypes as C
 import os
@@ -156,6 +166,100 @@ def measure_weights(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_bu
     return out
 
 
+def measure_step(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
+    npool = mvec + 3
+    need = 8.0 * nsys * vlen * (3 * 2 * (mvec + 1) + npool + 3 + 2)       # three batches' slots, the pool, three f, two x
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    names = ("a", "b", "c")
+    Fs = {v: torch.empty(nsys, vlen, dtype=torch.float64, device="cuda") for v in names}
+    Xs = {v: torch.zeros(nsys, vlen, dtype=torch.float64, device="cuda") for v in ("b", "c")}
+    masks = {v: torch.ones(nsys, dtype=torch.int32, device="cuda") for v in ("b", "c")}
+    tol = torch.zeros(nsys, dtype=torch.float64, device="cuda")
+    rb, rc = (torch.zeros(nsys, dtype=torch.float64, device="cuda") for _ in range(2))
+    batches = {v: nka_amd.nka_batch().init(nsys, vlen, mvec) for v in names}
+    hs = {v: batches[v]._handle() for v in names}
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    P = lambda t: C.c_void_p(t.data_ptr())                                           # noqa: E731
+    upd, stp = L.nka_hip_batch_accel_update, L.nka_hip_batch_accel_step
+    step = [0]
+
+    def run(name, reps):
+        F, h = Fs[name], hs[name]
+        for _ in range(reps):
+            F.copy_(pool[step[0] % npool])
+            step[0] += 1
+            if name == "a":
+                assert upd(h, P(F), ld, None) == 0
+            elif name == "b":
+                torch.linalg.vector_norm(F, dim=1, out=rb)
+                torch.gt(rb, tol, out=masks["b"])
+                assert upd(h, P(F), ld, P(masks["b"])) == 0
+                torch.addcmul(Xs["b"], F, masks["b"][:, None], value=-1.0, out=Xs["b"])
+            else:
+                assert stp(h, P(F), ld, P(Xs["c"]), ld, P(masks["c"]), P(tol), P(rc)) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {v: [] for v in names}
+    for v in names:                                # warm: fill the lists (steady state), settle clocks and caches
+        step[0] = 0
+        run(v, mvec + 4)
+    torch.cuda.synchronize()
+    assert torch.equal(Fs["b"], Fs["c"]) and torch.equal(Xs["b"], Xs["c"]) and torch.equal(Fs["a"], Fs["c"])      # the same work
+    for v in names:
+        assert (batches[v].num_vec() == mvec).all(), v
+        reps[v] = max(3, int(window / timed(v, 3)) + 1)
+    for _ in range(repeats):                       # alternate the variants
+        for v in names:
+            ts[v].append(timed(v, reps[v]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    assert masks["b"].all() and masks["c"].all()   # nothing retired
+    for v in names:
+        assert (batches[v].num_vec() == mvec).all(), v
+        med = statistics.median(ts[v])
+        out[v], out["spread_" + v] = med, (max(ts[v]) - min(ts[v])) / med
+        batches[v].delete()
+    del pool, Fs, Xs
+    torch.cuda.empty_cache()
+    return out
+
+
+def step_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    emit(f"# one iteration: (a) accel_update; (b) vector_norm + mask update + accel_update(mask) + masked X -= F; (c) accel_step "
+         f"with X, mask, tol, fnorm; {torch.cuda.get_device_name(0)}; windows >= {args.window} s, median of {args.repeats}, the "
+         f"three alternated; default flavour and sums, full list; tol = 0: no system retires")
+    emit("# streams per element and update: 2 + 6 G + (7 + k) for (a), 2 + 6 G + (9 + k) for (c), G = ceil((mvec - 1) / 4), k = mvec")
+    emit("# condition: (c) not slower than (b) by more than the spread of the windows (the larger of the two spreads)")
+    emit(f"{'nsys':>5} {'vlen':>6} {'mvec':>4} {'(a) us':>10} {'(b) us':>10} {'(c) us':>10} {'c/b':>7} {'c/a':>7} {'streams c/a':>11}  c vs b")
+    t0 = time.time()
+    missed = []
+    for n, v, m in points:
+        r = measure_step(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9)
+        if r is None:
+            emit(f"{n:5d} {v:6d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        g = (m - 1 + 3) // 4
+        pred = (2 + 6 * g + 9 + m) / (2 + 6 * g + 7 + m)
+        ok = r["c"] <= r["b"] * (1.0 + max(r["spread_b"], r["spread_c"]))
+        if not ok:
+            missed.append((n, v, m, round(r["c"] / r["b"], 3)))
+        emit(f"{n:5d} {v:6d} {m:4d} {r['a'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {r['c'] * 1e6:10.1f} {r['c'] / r['b']:7.3f} "
+             f"{r['c'] / r['a']:7.3f} {pred:11.3f}  {'ok' if ok else 'MISSED'}   "
+             f"(spread a {100 * r['spread_a']:.1f} % b {100 * r['spread_b']:.1f} % c {100 * r['spread_c']:.1f} %)")
+    emit(f"# {len(points)} points in {time.time() - t0:.0f} s; (c) slower than (b) beyond the spread: {missed if missed else 'nowhere'}")
+    return 0
+
+
 def weights_main(args, torch, nka_amd, L, emit):
     ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
     points = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
@@ -194,6 +298,9 @@ def main():
     ap.add_argument("--weights", action="store_true",
                     help="time a weighted batch (shared and per-system weights) beside the plain one; without --nsys / --vlens / "
                          "--mvecs: nsys 256,4096 x vlen 1024,16384 x mvec 10,20")
+    ap.add_argument("--step", action="store_true",
+                    help="time accel_step against accel_update and against the loop a caller composes from it; without --nsys / "
+                         "--vlens / --mvecs: nsys 256,4096 x vlen 64,1024,16384 x mvec 10,20")
     args = ap.parse_args()
     import torch
     import nka_amd
@@ -215,6 +322,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.step:
+        for name, grid_s in (("nsys", "256,4096"), ("vlens", "64,1024,16384"), ("mvecs", "10,20")):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_s)
+        return step_main(args, torch, nka_amd, L, emit)
     if args.weights:
         for name, grid_w in (("nsys", "256,4096"), ("vlens", "1024,16384"), ("mvecs", "10,20")):
             if getattr(args, name) == ap.get_default(name):
