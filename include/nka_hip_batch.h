@@ -39,7 +39,7 @@
  *            (profiles/r08/batch_throughput.txt, 1 x MI355X): the largest power of two at which the batch beats a loop over
  *            lone handles at every grid point from 16 systems on.  At the cap, mvec = 20: 1.52 x with 16 systems, 17 x with
  *            256, 23 x with 4096 (0.55 of 8 TB/s); at vlen = 1024, mvec = 10: 9.2 x / 151 x / 444 x.  Beyond it a 16-system
- *            batch -- 16 of 256 compute units -- loses (0.99 x at 32 768, mvec = 20): longer systems are for lone handles.  A
+ *            batch -- 16 of 256 compute units -- loses (0.99 x at 32 768, mvec = 20): longer systems are for WIDE below, or lone handles.  A
  *            batch of ONE is slower than a lone handle at most shapes (0.10 ... 1.76 x, recorded without a bar).
  *   WEIGHTS  nka_hip_batch_set_dot_weights: the dp  <x,y>_w = sum_i w_i x_i y_i  per system, on the device, inside the same
  *            one launch (unknowns of different scale, masks on ghost or fixed entries, ragged batches).  a_w = fl(w_i * a_i)
@@ -94,6 +94,39 @@
  *            moves 9 + k streams per element instead of 7 + k) and 0.75 ... 0.99 x the time of the same loop composed from
  *            accel_update and three kernels of the caller -- EXCEPT at 4096 x 64, which runs in reference order: 1.21 / 1.07 x
  *            a plain update and 1.06 / 1.03 x the composed loop (mvec 10 / 20; dp(f, f) is one more dependent chain there).
+ *   WIDE     nka_hip_batch_create_wide: the same handle type, every entry below and every guarantee above (MASKS, ASYNC, GRAPHS,
+ *            BITS), for systems too long for one workgroup: a system is ceil(vlen / NKA_HIP_BATCH_WIDE_CHUNK) chunks with ONE
+ *            WORKGROUP PER CHUNK, and an update is FOUR launches in a line on the batch's stream (nka_amd/csrc/
+ *            nka_batch_wide.hip: norm / other sums / scalar step / combine), the phases that need a sum over the whole system
+ *            separated by kernel boundaries.  Within a launch no workgroup reads what another writes: still no flags, no
+ *            spinning, no atomics, no cooperative launch.  A sum is formed per chunk exactly as the batch above forms it over a
+ *            system -- a chunk is whole tiles of 512 elements -- and the partials of the chunks are then added IN CHUNK ORDER,
+ *            starting from chunk 0, by one thread: the bits of a sum depend on NKA_HIP_BATCH_WIDE_CHUNK and on nothing else, and
+ *            a wide batch of at most one chunk returns the bits of the batch above in NKA_HIP_SUMS_BLOCKED_ROUNDED.  red[] keeps
+ *            its meaning, the zeros included; which partials are read is decided from the list, never from what the buffer
+ *            holds.  Captured into a graph it is four kernel nodes in a line, from the first update on.
+ *            1 <= vlen <= NKA_HIP_BATCH_WIDE_MAX_VLEN (short systems are legal), mvec as above, nsys <= 65 535 (the system is
+ *            the second grid index).  Beside the slots it allocates nsys * (2 + 2 mvec) * nchunk doubles of partial sums and
+ *            the combine plan (the control block's comb_slots / comb_c stay zero, so that its digest is the narrow batch's).
+ *            NKA_HIP_SUMS_AUTO and _BLOCKED_ROUNDED both mean the rounded fast sums, at every vlen.  REFUSED with NKA_HIP_EINVAL,
+ *            the batch staying usable: nka_hip_batch_accel_step; nka_hip_batch_set_dot_weights and _set_dot_weights_host
+ *            (nka_hip_batch_dot_weighted returns 0); NKA_HIP_SUMS_REFERENCE_ORDER and _BLOCKED through _set_sum_order.  A caller who
+ *            needs one of these has the batch above up to 16 384 elements and lone handles beyond.
+ *            BOTH CONSTANTS ARE MEASURED (profiles/r11/batch_wide_throughput.txt, 1 x MI355X) and frozen.  CHUNK = 2048: of
+ *            2048 / 4096 / 8192 the fastest at (nsys, vlen, mvec) = (16, 65 536, 20) and (64, 262 144, 10): 243.7 / 260.4 /
+ *            320.6 us and 828.0 / 831.7 / 853.5 us per update, windows spread 0.1 %.  MAX_VLEN = 1 048 576: by the rule of
+ *            NKA_HIP_BATCH_MAX_VLEN, 16 systems still beat the loop over lone handles there at both mvec (1.31 x at mvec 10, 1.18 x
+ *            at 20), and the grid holds no longer system; 1024 chunks would be the limit.
+ *            WHICH OF THE THREE ENTRIES (time of the loop over lone handles / time of the wide batch; default flavour, full
+ *            list): from 16 systems on the wide batch wins at every length measured -- at 32 768 and 65 536 elements, where the
+ *            batch above is not offered, 2.35 ... 15.2 x (16 systems: 6.05 / 4.69 x at mvec 10, 2.67 / 2.35 x at mvec 20; 256
+ *            systems: 15.2 / 8.15 x and 11.0 / 6.20 x, 0.50 ... 0.58 of 8 TB/s), at 262 144: 1.65 ... 3.03 x, at 1 048 576:
+ *            1.18 ... 1.42 x.  Up to 16 384 elements take the batch above for few or very many short systems and the wide one in
+ *            between: at 4096 elements the two are level (wide / narrow 0.90 ... 1.06), at 16 384 the wide batch is 1.04 ... 2.45 x
+ *            faster (2.45 x at 16 systems, 1.14 / 1.04 x at 256), and only the batch above has the step, the weights and the
+ *            reference order.  FOUR systems: the wide batch wins at mvec = 10 (1.05 ... 1.95 x) and LOSES to four lone handles at
+ *            mvec = 20 at every length (0.67 ... 0.86 x): the scalar step of a system runs on one thread, 127 us at mvec = 20 (59 %
+ *            of an update at 16 x 65 536), and a lone handle's does not.  A lone system stays with a lone handle.
  *   OUT OF SCOPE  sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -112,11 +145,19 @@ extern "C" {
 typedef struct nka_hip_batch_state *nka_hip_batch_t;
 
 enum { NKA_HIP_BATCH_MAX_VLEN = 16384, NKA_HIP_BATCH_MAX_MVEC = 32 };
+/* WIDE above: elements per workgroup of a wide batch, and its longest system */
+enum { NKA_HIP_BATCH_WIDE_CHUNK = 2048, NKA_HIP_BATCH_WIDE_MAX_VLEN = 1048576 };
 
 /* nsys accelerators of vlen elements and at most mvec vectors each, all restarted (F08:185-200 per system); `device` and
  * `stream` as in nka_hip_create.  Allocates 2*nsys*(mvec+1) slot vectors (slot stride: vlen rounded up to 32 doubles). */
 int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
                          int32_t flavor, int32_t device, void *stream);
+/* WIDE above: the same handle type with every system split across ceil(vlen / NKA_HIP_BATCH_WIDE_CHUNK) workgroups;
+ * 1 <= vlen <= NKA_HIP_BATCH_WIDE_MAX_VLEN, nsys <= 65535, mvec and vtol as above.  Allocates the partial sums beside the slots. */
+int nka_hip_batch_create_wide(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                              int32_t flavor, int32_t device, void *stream);
+int nka_hip_batch_is_wide(nka_hip_batch_t b);                      /* 1 = wide, 0 = one workgroup per system; < 0 on error */
+int nka_hip_batch_wide_limits(int64_t *chunk, int64_t *max_vlen);  /* the two constants, as the library was built */
 int nka_hip_batch_destroy(nka_hip_batch_t b);
 
 /* call a%accel_update(f) for every active system, one launch.  Rows of inactive systems are not touched. */

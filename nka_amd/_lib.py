@@ -128,6 +128,10 @@ SIGNATURES.update({
 BATCH_SIGNATURES = {
     "nka_hip_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                        C.c_void_p]),
+    "nka_hip_batch_create_wide": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                            C.c_void_p]),
+    "nka_hip_batch_is_wide": (C.c_int, [C.c_void_p]),
+    "nka_hip_batch_wide_limits": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "nka_hip_batch_destroy": (C.c_int, [C.c_void_p]),
     "nka_hip_batch_accel_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "nka_hip_batch_accel_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

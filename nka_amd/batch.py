@@ -1,5 +1,6 @@
 """Python mirror of the batched accelerator (include/nka_hip_batch.h): `nsys` independent NKA states of equal shape,
-advanced by ONE kernel launch per call, one workgroup per system.  Method names are those of `nka_amd.nka`; the
+advanced by ONE kernel launch per call, one workgroup per system -- or, with init(..., wide=True), by four launches with every
+system split across workgroups (systems too long for one workgroup).  Method names are those of `nka_amd.nka`; the
 per-system queries take the system's index first.  All arithmetic happens in libnka_hip.so on the GPU; this file is
 plumbing (ctypes + torch for device memory and streams)."""
 from __future__ import annotations
@@ -14,6 +15,15 @@ from .nka import FLAVOR_DEFAULT, NKAError, State, _check
 BATCH_MAX_VLEN, BATCH_MAX_MVEC = 16384, 32      # NKA_HIP_BATCH_MAX_VLEN / _MVEC (include/nka_hip_batch.h)
 
 
+def batch_wide_limits():
+    """(chunk, max_vlen) of a wide batch -- NKA_HIP_BATCH_WIDE_CHUNK and NKA_HIP_BATCH_WIDE_MAX_VLEN as the loaded library
+    was built (nka_hip_batch_wide_limits)."""
+    chunk, cap = C.c_int64(), C.c_int64()
+    L = _lib.load()
+    _check(L.nka_hip_batch_wide_limits(C.byref(chunk), C.byref(cap)), "nka_hip_batch_wide_limits", L)
+    return int(chunk.value), int(cap.value)
+
+
 class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
     """A batch of MI355X accelerator objects; see the module docstring."""
 
@@ -22,9 +32,11 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         self._L = _lib.load()          # raises if the HIP library is missing: no CPU path
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
-             stream: int | None = None):
+             stream: int | None = None, wide: bool = False):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
-        hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`)."""
+        hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
+        system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_step, weights
+        and the reference sum order are refused)."""
         import torch
 
         self.delete()
@@ -36,8 +48,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         if stream is None:
             stream = torch.cuda.current_stream(device).cuda_stream
         h = C.c_void_p()
-        _check(self._L.nka_hip_batch_create(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
-                                            C.c_void_p(stream)), "nka_hip_batch_create", self._L)
+        create = self._L.nka_hip_batch_create_wide if wide else self._L.nka_hip_batch_create
+        _check(create(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device), C.c_void_p(stream)),
+               "nka_hip_batch_create_wide" if wide else "nka_hip_batch_create", self._L)
         self._h, self._device, self._nsys, self._vlen, self._mvec = h, device, int(nsys), int(vlen), int(mvec)
         self._stream, self._follow_torch_stream = int(stream), explicit_stream is None
         return self
@@ -214,6 +227,12 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def flavor(self) -> int:
         return self._L.nka_hip_batch_flavor(self._handle())
+
+    def is_wide(self) -> bool:
+        """True for a batch created with wide=True (nka_hip_batch_is_wide)."""
+        r = self._L.nka_hip_batch_is_wide(self._handle())
+        _check(min(r, 0), "batch_is_wide", self._L)
+        return r == 1
 
     def num_vec(self) -> np.ndarray:
         out = np.zeros(self._nsys, np.int32)

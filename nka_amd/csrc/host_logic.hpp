@@ -227,4 +227,66 @@ NKA_HOST_DEVICE constexpr BatchLds batch_lds(int mvec) {
   return l;
 }
 
+// THE WIDE BATCH (nka_hip_batch_create_wide, nka_batch_wide.hip): a system is nchunk = ceil(vlen / kWideChunk) chunks, one
+// workgroup each, and an update is four launches: norm, sums, scalar, combine.  tests/c/batch_wide_layout_check.cpp paints
+// every piece below.  (NKA_BATCH_WIDE_CHUNK: the candidate builds that chose the constant, tools/batch_throughput.py --wide.)
+#ifndef NKA_BATCH_WIDE_CHUNK
+#define NKA_BATCH_WIDE_CHUNK 2048
+#endif
+constexpr int64_t kWideChunk = NKA_BATCH_WIDE_CHUNK;      // = NKA_HIP_BATCH_WIDE_CHUNK: a multiple of the tile of 512 elements
+constexpr int kWideMaxChunks = 1024;                      // bounds the chunk-order chain and the partial buffer
+static_assert(kWideChunk % 512 == 0 && kWideChunk >= 512, "a chunk is whole tiles");
+NKA_HOST_DEVICE constexpr int64_t wide_nchunk(int64_t vlen) { return ((vlen < 1 ? 1 : vlen) + kWideChunk - 1) / kWideChunk; }
+NKA_HOST_DEVICE constexpr int64_t wide_chunk_len(int64_t vlen, int64_t c) {
+  return vlen - c * kWideChunk < kWideChunk ? vlen - c * kWideChunk : kWideChunk;
+}
+// partial sums: entry j of red[] (0 <= j < 2 + 2 mvec) of system sys, chunk c -- the chunks of an entry lie together, in order
+NKA_HOST_DEVICE constexpr int64_t wide_part_count(int64_t nsys, int mvec, int64_t nchunk) { return nsys * (2 + 2 * mvec) * nchunk; }
+NKA_HOST_DEVICE constexpr int64_t wide_part_index(int64_t sys, int entry, int64_t c, int mvec, int64_t nchunk) {
+  return (sys * (2 + 2 * mvec) + entry) * nchunk + c;
+}
+// LDS of the sums and the combine kernel: doubles first, then int32 (a piece a kernel lacks has length 0; the norm kernel
+// holds sm [waves] and res [2] only, declared where it uses them)
+struct WideLds {
+  int stage, sm, res, cc, ndouble;      // stage [nchunk]: the partials of <d,d>; sm [waves][nacc]; res [nacc + 1]; cc [m1]
+  int next, ps, cs, hdr, nint;          // next [m1+1], ps [m1], cs [m1], hdr [8]
+  NKA_HOST_DEVICE constexpr size_t bytes() const { return sizeof(double) * (size_t)ndouble + sizeof(int32_t) * (size_t)nint; }
+};
+NKA_HOST_DEVICE constexpr WideLds wide_sums_lds(int mvec, int nchunk) {
+  const int m1 = mvec + 1;
+  WideLds l{};
+  l.stage = 0;
+  l.sm = l.stage + nchunk;
+  l.res = l.sm + kBatchWaves * kBatchAcc;
+  l.cc = l.res + kBatchAcc + 1;
+  l.ndouble = l.cc;
+  l.next = 0;
+  l.ps = l.next + (m1 + 1);
+  l.cs = l.ps + m1;
+  l.hdr = l.cs;
+  l.nint = l.hdr + 8;
+  return l;
+}
+NKA_HOST_DEVICE constexpr WideLds wide_combine_lds(int mvec) {
+  const int m1 = mvec + 1;
+  WideLds l{};
+  l.stage = l.sm = l.res = l.cc = 0;
+  l.ndouble = l.cc + m1;
+  l.next = l.ps = l.cs = 0;
+  l.hdr = l.cs + m1;
+  l.nint = l.hdr + 8;
+  return l;
+}
+// LDS of the scalar kernel: the working copy of the narrow kernel (batch_lds), then stage [nchunk] behind its doubles
+struct WideScalarLds {
+  BatchLds b;      // (b.ndouble counts the stage too: the int32 pieces start behind it)
+  int stage;
+};
+NKA_HOST_DEVICE constexpr WideScalarLds wide_scalar_lds(int mvec, int nchunk) {
+  WideScalarLds l{batch_lds(mvec), 0};
+  l.stage = l.b.ndouble;
+  l.b.ndouble += nchunk;
+  return l;
+}
+
 }  // namespace nka_host

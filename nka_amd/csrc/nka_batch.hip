@@ -23,9 +23,9 @@
 // swept alone where there is no pending pair), the system may retire itself between phases 2 and 3 -- up to there a workgroup
 // has written LDS only --, and phase 6 also forms x = fl(x - f_out).  Without it every step statement is discarded at compile
 // time and the instance is the plain update, instruction for instruction.
-#include "handles.hpp"
-#include "nka_device.hpp"
-#include "../../include/nka_hip_batch.h"
+// A WIDE batch (nka_hip_batch_create_wide) shares the handle, the storage and every host entry of this file; its update -- a
+// system split across workgroups, four launches -- is nka_batch_wide.hip, and what the two units share nka_batch_dev.hpp.
+#include "nka_batch_dev.hpp"      // BatchArgs, the tile loads and stores, batch_sweep, batch_block_sum, the scalar step, the handle
 
 #include <algorithm>
 #include <cmath>
@@ -39,20 +39,6 @@ using namespace nka;
 
 namespace {
 
-using nka_host::kBatchAcc;
-using nka_host::kBatchGroup;
-using nka_host::kBatchWaves;
-constexpr int kBatchThreads = 64 * kBatchWaves;
-constexpr int kBatchTile = 2 * kBatchThreads;   // elements per sweep step: thread t owns 2t, 2t+1
-
-struct BatchArgs {
-  double *w, *v;        // system sys, slot k (1-based) at base + sys*sys_stride + (k-1)*stride
-  int32_t *ic;          // control blocks in the layout of Ctl (nka_ctl.hpp), ic_stride / dc_stride apart
-  double *dc;
-  int64_t stride, sys_stride, n;
-  int32_t ic_stride, dc_stride, mvec, nsys;
-};
-
 // what a solve step takes beside the update's arguments; each pointer may be NULL (a workgroup-uniform branch, not an instance)
 struct StepArgs {
   double *x;            // iterate rows, ldx apart: x = fl(x - f_out) where the system updates
@@ -62,90 +48,9 @@ struct StepArgs {
 };
 __device__ __forceinline__ const StepArgs &step_args(const StepArgs &st) { return st; }
 
-__host__ __device__ inline Ctl batch_ctl(const BatchArgs &a, int sys) {
-  Ctl c{};
-  c.ic = a.ic + (size_t)sys * a.ic_stride;
-  c.dc = a.dc + (size_t)sys * a.dc_stride;
-  c.mvec = a.mvec;
-  return c;
-}
-
 // (where the pieces of a system lie, and the LDS of a workgroup -- 5.3 KB at mvec = 20, 11.2 KB at 32: host_logic.hpp)
 static_assert(nka_host::batch_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 40 * 1024, "four workgroups of a batch must fit the LDS of a CU");
 
-// pair (i, i+1) of a vector of n elements, i even; beyond n: zeros (never accumulated, never stored)
-__device__ __forceinline__ d2 ld_pair(const double *__restrict__ p, int64_t i, int64_t n, bool vec) {
-  if (vec && i + 1 < n) return *reinterpret_cast<const d2 *>(p + i);
-  d2 r;
-  r[0] = i < n ? p[i] : 0.0;
-  r[1] = i + 1 < n ? p[i + 1] : 0.0;
-  return r;
-}
-__device__ __forceinline__ void st_pair(double *__restrict__ p, int64_t i, int64_t n, bool vec, d2 x) {
-  if (vec && i + 1 < n) {
-    *reinterpret_cast<d2 *>(p + i) = x;
-    return;
-  }
-  if (i < n) p[i] = x[0];
-  if (i + 1 < n) p[i + 1] = x[1];
-}
-
-// The same inside a FULL tile (no element beyond n): straight-line code, so that every load of a tile is in flight before
-// the first is waited for; VEC = false (a row of f that is not 16-byte aligned): two 8-byte loads, the same values.
-template <bool FULL, bool VEC>
-__device__ __forceinline__ d2 ld_tile(const double *__restrict__ p, int64_t i, int64_t n) {
-  if (!FULL) return ld_pair(p, i, n, VEC);
-  if (VEC) return *reinterpret_cast<const d2 *>(p + i);
-  d2 r;
-  r[0] = p[i];
-  r[1] = p[i + 1];
-  return r;
-}
-template <bool FULL, bool VEC>
-__device__ __forceinline__ void st_tile(double *__restrict__ p, int64_t i, int64_t n, d2 x) {
-  if (!FULL) { st_pair(p, i, n, VEC, x); return; }
-  if (VEC) { *reinterpret_cast<d2 *>(p + i) = x; return; }
-  p[i] = x[0];
-  p[i + 1] = x[1];
-}
-// One sweep over a system's elements: body(FULL, FVEC, i) for this thread's pair i = 2t, 2t + 512, ... -- the full tiles
-// first, then the ragged one with guards.  The order in which a thread meets its elements is the same on every path.
-template <class Body>
-__device__ __forceinline__ void batch_sweep(int64_t n, bool fvec, Body body) {
-  using T = std::true_type;
-  using F = std::false_type;
-  int64_t base = 0;
-  if (fvec) for (; base + kBatchTile <= n; base += kBatchTile) body(T{}, T{}, base + 2 * threadIdx.x);
-  else for (; base + kBatchTile <= n; base += kBatchTile) body(T{}, F{}, base + 2 * threadIdx.x);
-  if (base < n) {
-    if (fvec) body(F{}, T{}, base + 2 * threadIdx.x); else body(F{}, F{}, base + 2 * threadIdx.x);
-  }
-}
-
-// the value PB stores as w1' (nka_device.hpp: pa_operand with `normed`)
-template <bool RCP> __device__ __forceinline__ double batch_nrm(double x, double s, double rs) { return RCP ? rs * x : x / s; }
-
-// Sums of NACC per-thread accumulators over the workgroup in a fixed order: lanes by the butterfly of wave_sum, then
-// wavefronts 0, 1, 2, 3.  Result a in res[a] (LDS), valid after the trailing barrier.
-template <int NACC>
-__device__ __forceinline__ void batch_block_sum(const double (&acc)[NACC], double *sm, double *res) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int a = 0; a < NACC; a++) {
-    const double x = wave_sum(acc[a]);
-    if (lane == 0) sm[wv * NACC + a] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < NACC) {
-    double r = sm[threadIdx.x];
-#pragma unroll
-    for (int q = 1; q < kBatchWaves; q++) r += sm[q * NACC + threadIdx.x];
-    res[threadIdx.x] = r;
-  }
-  __syncthreads();
-}
-
-enum { HDR_PENDING = 0, HDR_FIRST = 1, HDR_NOLDER = 2, HDR_NCOMB = 3, HDR_NEW = 4, HDR_NORMED = 5 };
 
 // WGT = true: the diagonal weights of nka_hip_batch_set_dot_weights.  Row `sys` of the batch's weight buffer -- wgt_all +
 // sys * wgt_stride, wgt_stride = 0 for the form all systems share -- is read like a stored vector, and fl(w_i * a_i) is the
@@ -369,6 +274,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
 
   // ---- phase 4: the scalar step, the statements of k_solve on this system's working copy ----
   if (t == 0) {
+    // (the statements of batch_scalar_step, nka_batch_dev.hpp, written out: as a call they moved registers of kernels held to
+    // their machine code)
     const int entry_first = L.first;
     bool nrm = false;
     int nrelax = ctl.ic[IC_NRELAX];
@@ -528,22 +435,6 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_copy_weights(double *__
 
 }  // namespace
 
-struct nka_hip_batch_state {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int flavor = NKA_HIP_FLAVOR_C;
-  int sum_order = NKA_HIP_SUMS_AUTO;
-  double vtol = 0.01;
-  BatchArgs k{};
-  // diagonal dot-product weights (nka_hip_batch_set_dot_weights): nsys rows at the slot stride, allocated at the first set,
-  // freed at destroy only and never moved -- a captured update holds the address.  The form all systems share lives in row 0.
-  double *wgt = nullptr;
-  double *wgt_stage = nullptr;              // the same shape: where the host entry puts the caller's rows for the check
-  unsigned long long *wgt_chk = nullptr;    // two words of k_batch_check_weights
-  bool weighted = false;
-  int64_t wgt_stride = 0;                   // row stride the updates run with: k.stride, or 0 in the shared form
-};
-
 namespace {
 
 bool batch_ordered(const nka_hip_batch_state *b) {
@@ -664,24 +555,33 @@ int set_weights_from_device(nka_hip_batch_t b, const double *src, int64_t ldw, c
 
 extern "C" {
 
-int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
-                         int32_t device, void *stream) {
-  if (!out) return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: out is NULL");
+// both kinds of batch: `wide` = a system split across workgroups (nka_batch_wide.hip)
+static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor, int32_t device,
+                        void *stream, bool wide) {
+  const std::string who = wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
+  if (!out) return fail(NKA_HIP_EINVAL, who + ": out is NULL");
   *out = nullptr;
-  if (nsys < 1) return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: nsys must be >= 1");
-  if (vlen < 1 || vlen > NKA_HIP_BATCH_MAX_VLEN)
+  if (nsys < 1) return fail(NKA_HIP_EINVAL, who + ": nsys must be >= 1");
+  if (wide) {
+    int64_t chunk = 0, cap = 0;
+    nka_hip_batch_wide_limits(&chunk, &cap);
+    if (nsys > 65535) return fail(NKA_HIP_EINVAL, who + ": nsys must be <= 65535 (the system is the second grid index)");
+    if (vlen < 1 || vlen > cap)
+      return fail(NKA_HIP_EINVAL, who + ": vlen must be 1 ... " + std::to_string((long long)cap) + " (longer systems: lone handles, nka_hip_create)");
+  } else if (vlen < 1 || vlen > NKA_HIP_BATCH_MAX_VLEN)
     return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: vlen must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_VLEN) +
-                                    " (longer systems: lone handles, nka_hip_create)");
+                                    " (longer systems: nka_hip_batch_create_wide, or lone handles, nka_hip_create)");
   if (mvec < 1 || mvec > NKA_HIP_BATCH_MAX_MVEC)
-    return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: mvec must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_MVEC));
-  if (!(vtol > 0.0)) return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: vtol must be > 0");
-  if (int rc = nka_detail::resolve_flavor(&flavor, "nka_hip_batch_create")) return rc;
+    return fail(NKA_HIP_EINVAL, who + ": mvec must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_MVEC));
+  if (!(vtol > 0.0)) return fail(NKA_HIP_EINVAL, who + ": vtol must be > 0");
+  if (int rc = nka_detail::resolve_flavor(&flavor, who.c_str())) return rc;
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: no such HIP device");
+  if (device < 0 || device >= ndev) return fail(NKA_HIP_EINVAL, who + ": no such HIP device");
   HIP_TRY(hipSetDevice(device));
 
   auto *b = new nka_hip_batch_state();
+  b->wide = wide;
   b->device = device;
   b->stream = (hipStream_t)stream;
   b->flavor = flavor;
@@ -698,7 +598,7 @@ int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32
   const double slot_bytes = (double)k.sys_stride * 8.0 * (double)nsys;
   if (slot_bytes > 1.0e13) {      // (beyond any device: also keeps the size arithmetic below inside 64 bits)
     delete b;
-    return fail(NKA_HIP_ENOMEM, "nka_hip_batch_create: the batch needs more device memory than any device has");
+    return fail(NKA_HIP_ENOMEM, who + ": the batch needs more device memory than any device has");
   }
   int rc = 0;
   auto alloc = [&](void **p, size_t bytes) {
@@ -718,15 +618,16 @@ int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32
               hipMemsetAsync(k.w, 0, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys, b->stream) != hipSuccess ||
               hipMemsetAsync(k.v, 0, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys, b->stream) != hipSuccess)) {
     (void)hipGetLastError();
-    rc = fail(NKA_HIP_EHIP, "nka_hip_batch_create: initialising the batch failed");
+    rc = fail(NKA_HIP_EHIP, who + ": initialising the batch failed");
   }
+  if (!rc && wide) rc = nka_batch_wide_alloc(b);
   if (!rc) {
     hipLaunchKernelGGL(k_batch_set_vtol, dim3((unsigned)((nsys + 63) / 64)), dim3(64), 0, b->stream, k, vtol);
     hipLaunchKernelGGL(k_batch_list_op, dim3((unsigned)((nsys + 63) / 64)), dim3(64), 0, b->stream, k, (int)kBatchOpRestart,
                        (const int32_t *)nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-    if (e != hipSuccess) rc = fail(NKA_HIP_EHIP, std::string("nka_hip_batch_create: ") + hipGetErrorString(e));
+    if (e != hipSuccess) rc = fail(NKA_HIP_EHIP, who + ": " + hipGetErrorString(e));
   }
   if (rc) {
     nka_hip_batch_destroy(b);
@@ -735,6 +636,16 @@ int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32
   *out = b;
   return 0;
 }
+
+int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                         int32_t device, void *stream) {
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false);
+}
+int nka_hip_batch_create_wide(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                              int32_t device, void *stream) {
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, true);
+}
+int nka_hip_batch_is_wide(nka_hip_batch_t b) { return b ? (b->wide ? 1 : 0) : fail(NKA_HIP_EINVAL, "batch_is_wide: null handle"); }
 
 int nka_hip_batch_destroy(nka_hip_batch_t b) {
   if (!b) return 0;
@@ -748,6 +659,7 @@ int nka_hip_batch_destroy(nka_hip_batch_t b) {
   hipFree(b->wgt);
   hipFree(b->wgt_stage);
   hipFree(b->wgt_chk);
+  nka_batch_wide_free(b);
   delete b;
   return 0;
 }
@@ -758,7 +670,7 @@ int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, con
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = check_rows(b, f_dev, ld, "batch_accel_update", "f", "ld")) return rc;
   if (int rc = check_mask(b, active_dev, "batch_accel_update: active")) return rc;
-  launch_flavor(b, f_dev, ld, active_dev);
+  if (b->wide) nka_batch_wide_update(b, f_dev, ld, active_dev); else launch_flavor(b, f_dev, ld, active_dev);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -766,6 +678,7 @@ int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, con
 int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, double *x_dev, int64_t ldx, int32_t *active_dev,
                              const double *tol_dev, double *fnorm_dev) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_accel_step: null handle");
+  if (b->wide) return fail(NKA_HIP_EINVAL, "batch_accel_step: not offered by a wide batch (nka_hip_batch_create_wide): accel_update");
   if (!f_dev) return fail(NKA_HIP_EINVAL, "batch_accel_step: f is NULL");
   if (tol_dev && !active_dev) return fail(NKA_HIP_EINVAL, "batch_accel_step: tol needs a mask (a system retires by clearing its entry)");
   HIP_TRY(hipSetDevice(b->device));
@@ -806,6 +719,8 @@ int nka_hip_batch_set_vec_tol(nka_hip_batch_t b, double vtol) {
 
 int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_sum_order: null handle");
+  if (b->wide && order != NKA_HIP_SUMS_AUTO && order != NKA_HIP_SUMS_BLOCKED_ROUNDED)
+    return fail(NKA_HIP_EINVAL, "batch_set_sum_order: a wide batch forms the rounded fast sums only: NKA_HIP_SUMS_BLOCKED_ROUNDED or _AUTO");
   if (order == NKA_HIP_SUMS_BLOCKED)
     return fail(NKA_HIP_EINVAL, "batch_set_sum_order: NKA_HIP_SUMS_BLOCKED is not offered by a batch (it has no exchange to save): "
                                 "NKA_HIP_SUMS_BLOCKED_ROUNDED, _REFERENCE_ORDER or _AUTO");
@@ -817,6 +732,7 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
 
 int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_t ldw) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: null handle");
+  if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wide batch (nka_hip_batch_create_wide)");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_dot_weights")) return rc;
   if (!w_dev) {
@@ -831,6 +747,7 @@ int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_
 
 int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, int64_t ldw) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: null handle");
+  if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wide batch (nka_hip_batch_create_wide)");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_dot_weights_host")) return rc;
   if (!w_host) {

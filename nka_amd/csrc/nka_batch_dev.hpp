@@ -1,0 +1,185 @@
+// nka_batch_dev.hpp -- what the two translation units of the batched accelerator share: nka_batch.hip (one workgroup per
+// system, one launch per update) and nka_batch_wide.hip (a system split across workgroups, four launches per update).  The
+// launch arguments, the loads and stores of a tile, the sweep over a span of elements, the fixed-order sums of a workgroup,
+// the scalar step on a working copy, and the handle.  The device functions and BatchArgs sit in an unnamed namespace, as they
+// did in nka_batch.hip: each unit compiles its own copy of the same text, and the kernels of nka_batch.hip keep their names.
+#pragma once
+#include "handles.hpp"
+#include "nka_device.hpp"
+#include "../../include/nka_hip_batch.h"
+
+#include <cstdint>
+#include <type_traits>
+
+namespace {
+
+using namespace nka;
+using nka_host::kBatchAcc;
+using nka_host::kBatchGroup;
+using nka_host::kBatchWaves;
+constexpr int kBatchThreads = 64 * kBatchWaves;
+constexpr int kBatchTile = 2 * kBatchThreads;   // elements per sweep step: thread t owns 2t, 2t+1
+
+struct BatchArgs {
+  double *w, *v;        // system sys, slot k (1-based) at base + sys*sys_stride + (k-1)*stride
+  int32_t *ic;          // control blocks in the layout of Ctl (nka_ctl.hpp), ic_stride / dc_stride apart
+  double *dc;
+  int64_t stride, sys_stride, n;
+  int32_t ic_stride, dc_stride, mvec, nsys;
+};
+
+__host__ __device__ inline Ctl batch_ctl(const BatchArgs &a, int sys) {
+  Ctl c{};
+  c.ic = a.ic + (size_t)sys * a.ic_stride;
+  c.dc = a.dc + (size_t)sys * a.dc_stride;
+  c.mvec = a.mvec;
+  return c;
+}
+
+// pair (i, i+1) of a vector of n elements, i even; beyond n: zeros (never accumulated, never stored)
+__device__ __forceinline__ d2 ld_pair(const double *__restrict__ p, int64_t i, int64_t n, bool vec) {
+  if (vec && i + 1 < n) return *reinterpret_cast<const d2 *>(p + i);
+  d2 r;
+  r[0] = i < n ? p[i] : 0.0;
+  r[1] = i + 1 < n ? p[i + 1] : 0.0;
+  return r;
+}
+__device__ __forceinline__ void st_pair(double *__restrict__ p, int64_t i, int64_t n, bool vec, d2 x) {
+  if (vec && i + 1 < n) {
+    *reinterpret_cast<d2 *>(p + i) = x;
+    return;
+  }
+  if (i < n) p[i] = x[0];
+  if (i + 1 < n) p[i + 1] = x[1];
+}
+
+// The same inside a FULL tile (no element beyond n): straight-line code, so that every load of a tile is in flight before
+// the first is waited for; VEC = false (a row of f that is not 16-byte aligned): two 8-byte loads, the same values.
+template <bool FULL, bool VEC>
+__device__ __forceinline__ d2 ld_tile(const double *__restrict__ p, int64_t i, int64_t n) {
+  if (!FULL) return ld_pair(p, i, n, VEC);
+  if (VEC) return *reinterpret_cast<const d2 *>(p + i);
+  d2 r;
+  r[0] = p[i];
+  r[1] = p[i + 1];
+  return r;
+}
+template <bool FULL, bool VEC>
+__device__ __forceinline__ void st_tile(double *__restrict__ p, int64_t i, int64_t n, d2 x) {
+  if (!FULL) { st_pair(p, i, n, VEC, x); return; }
+  if (VEC) { *reinterpret_cast<d2 *>(p + i) = x; return; }
+  p[i] = x[0];
+  p[i + 1] = x[1];
+}
+// One sweep over a system's elements: body(FULL, FVEC, i) for this thread's pair i = 2t, 2t + 512, ... -- the full tiles
+// first, then the ragged one with guards.  The order in which a thread meets its elements is the same on every path.
+template <class Body>
+__device__ __forceinline__ void batch_sweep(int64_t n, bool fvec, Body body) {
+  using T = std::true_type;
+  using F = std::false_type;
+  int64_t base = 0;
+  if (fvec) for (; base + kBatchTile <= n; base += kBatchTile) body(T{}, T{}, base + 2 * threadIdx.x);
+  else for (; base + kBatchTile <= n; base += kBatchTile) body(T{}, F{}, base + 2 * threadIdx.x);
+  if (base < n) {
+    if (fvec) body(F{}, T{}, base + 2 * threadIdx.x); else body(F{}, F{}, base + 2 * threadIdx.x);
+  }
+}
+
+// the value PB stores as w1' (nka_device.hpp: pa_operand with `normed`)
+template <bool RCP> __device__ __forceinline__ double batch_nrm(double x, double s, double rs) { return RCP ? rs * x : x / s; }
+
+// Sums of NACC per-thread accumulators over the workgroup in a fixed order: lanes by the butterfly of wave_sum, then
+// wavefronts 0, 1, 2, 3.  Result a in res[a] (LDS), valid after the trailing barrier.
+template <int NACC>
+__device__ __forceinline__ void batch_block_sum(const double (&acc)[NACC], double *sm, double *res) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int a = 0; a < NACC; a++) {
+    const double x = wave_sum(acc[a]);
+    if (lane == 0) sm[wv * NACC + a] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < NACC) {
+    double r = sm[threadIdx.x];
+#pragma unroll
+    for (int q = 1; q < kBatchWaves; q++) r += sm[q * NACC + threadIdx.x];
+    res[threadIdx.x] = r;
+  }
+  __syncthreads();
+}
+
+enum { HDR_PENDING = 0, HDR_FIRST = 1, HDR_NOLDER = 2, HDR_NCOMB = 3, HDR_NEW = 4, HDR_NORMED = 5 };
+
+// THE SCALAR STEP of one system, the statements of k_solve on the working copy L (one thread): s == 0 relaxes (F08:275), the
+// Gram row of w1' and the factor, the right-hand side and the solve, the combine plan (cs, cc: slots and coefficients in list
+// order), the new slot at the head of the list.  ps: the nolder older entries at entry, in list order; red: the system's
+// sums.  Writes the five list scalars, DC_S and the plan's header to the control block.
+__device__ __forceinline__ void batch_scalar_step(Lst &L, const Ctl &ctl, double s, int nolder, int mvec, const int32_t *ps,
+                                                  const double *red, int32_t *cs, double *cc, int32_t *hdr) {
+  const int entry_first = L.first;
+  bool nrm = false;
+  int nrelax = ctl.ic[IC_NRELAX];
+  if (L.pending) {
+    ctl.dc[DC_S] = s;
+    if (s == 0.0) {                       // F08:275
+      lst_relax(L);
+      nrelax++;
+    }
+  }
+  if (L.pending) {
+    nrm = true;
+    for (int p = 0; p < nolder; p++) L.H(L.first, ps[p]) = red[2 + p];      // Gram row of w1' (F08:286-290)
+    lst_factor(L);
+  }
+  const int slot = L.free_;
+  L.free_ = L.next[slot];
+  int ncomb = 0;
+  if (L.subspace) {
+    if (nrm) L.c[entry_first] = red[1];
+    for (int p = 0; p < nolder; p++) L.c[ps[p]] = red[2 + mvec + p];
+    lst_solve(L);
+    for (int k = L.first; k != 0; k = L.next[k]) {
+      cs[ncomb] = k;
+      cc[ncomb] = L.c[k];
+      ncomb++;
+    }
+  }
+  lst_prepend(L, slot);
+  hdr[HDR_NCOMB] = ncomb;
+  hdr[HDR_NEW] = slot;
+  hdr[HDR_NORMED] = nrm ? 1 : 0;
+  lst_store_scalars(L, ctl);
+  ctl.ic[IC_NEW] = slot;
+  ctl.ic[IC_NCOMB] = ncomb;
+  ctl.ic[IC_NORMED] = nrm ? 1 : 0;
+  ctl.ic[IC_NRELAX] = nrelax;
+}
+
+}  // namespace
+
+struct nka_hip_batch_state {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int flavor = NKA_HIP_FLAVOR_C;
+  int sum_order = NKA_HIP_SUMS_AUTO;
+  double vtol = 0.01;
+  BatchArgs k{};
+  // diagonal dot-product weights (nka_hip_batch_set_dot_weights): nsys rows at the slot stride, allocated at the first set,
+  // freed at destroy only and never moved -- a captured update holds the address.  The form all systems share lives in row 0.
+  double *wgt = nullptr;
+  double *wgt_stage = nullptr;              // the same shape: where the host entry puts the caller's rows for the check
+  unsigned long long *wgt_chk = nullptr;    // two words of k_batch_check_weights
+  bool weighted = false;
+  int64_t wgt_stride = 0;                   // row stride the updates run with: k.stride, or 0 in the shared form
+  // a WIDE batch (nka_hip_batch_create_wide, nka_batch_wide.hip): a system is nchunk chunks of NKA_HIP_BATCH_WIDE_CHUNK elements
+  bool wide = false;
+  int32_t nchunk = 0;
+  double *part = nullptr;                   // partial sums, nka_host::wide_part_index: nsys x (2 + 2 mvec) x nchunk
+  double *plan_c = nullptr;                 // the combine plan from the scalar kernel to the combine: nsys x (mvec + 1) coefficients
+  int32_t *plan_s = nullptr;                //   ... and slots, in list order (the control block's comb_c / comb_slots stay zero)
+};
+
+// nka_batch_wide.hip: the buffers of a wide batch (b->k is complete), and one update of it -- four launches on b->stream
+int nka_batch_wide_alloc(nka_hip_batch_t b);
+void nka_batch_wide_free(nka_hip_batch_t b);
+void nka_batch_wide_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);

@@ -29,7 +29,17 @@ iteration on the same inputs (the copy of the next input into F stands for the c
   (c) accel_step with X, the mask, tol and fnorm.
 tol = 0 with residuals that are never zero, so no system retires in (b) or (c).  Per point: the three times, (c)/(b) with the
 spread of the windows -- the condition is that (c) is not slower than (b) by more than that spread -- and (c)/(a) beside the
-ratio of streams per element, 2 + 6 G + (9 + k) over 2 + 6 G + (7 + k): the step reads and writes x in the combine."""
+ratio of streams per element, 2 + 6 G + (9 + k) over 2 + 6 G + (7 + k): the step reads and writes x in the combine.
+
+--wide measures the wide batch (nka_hip_batch_create_wide: a system split across workgroups, four launches per update), same
+windows, same alternation, on the same inputs:
+  (a) the wide batch;
+  (b) the same systems as lone handles in a loop on one stream;
+  (c) the narrow batch, where vlen <= NKA_HIP_BATCH_MAX_VLEN.
+Grid nsys 4,16,64,256 x vlen 4096,16384,32768,65536,262144,1048576 x mvec 10,20; a point whose stored vectors (one contender's
+slots) exceed --slots-gb is skipped and listed.  The bar of 1.06 on time(b)/time(a) applies at nsys >= 16 and vlen 32768 or
+65536; every other point is recorded without one.  The line at the top names the chunk and the cap of the library loaded
+(NKA_HIP_LIB: a candidate build of another chunk)."""
 import argparse
 import ctypes as C
 import os
@@ -232,6 +242,118 @@ def measure_step(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budge
     return out
 
 
+def measure_wide(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
+    npool = mvec + 3
+    narrow = vlen <= nka_amd.BATCH_MAX_VLEN
+    names = ("a", "b", "c") if narrow else ("a", "b")
+    need = 8.0 * nsys * vlen * (len(names) * 2 * (mvec + 1) + npool + len(names))      # the contenders' slots, the pool, their f
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    Fs = {v: torch.empty(nsys, vlen, dtype=torch.float64, device="cuda") for v in names}
+    wide = nka_amd.nka_batch().init(nsys, vlen, mvec, wide=True)
+    batches = {"a": wide}
+    if narrow:
+        batches["c"] = nka_amd.nka_batch().init(nsys, vlen, mvec)
+    lones = [nka_amd.nka().init(vlen, mvec) for _ in range(nsys)]
+    hl = [a._handle() for a in lones]
+    pl = [C.c_void_p(Fs["b"][k].data_ptr()) for k in range(nsys)]
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    upd_batch, upd_lone = L.nka_hip_batch_accel_update, L.nka_hip_accel_update
+    step = [0]
+
+    def run(name, reps):
+        F = Fs[name]
+        for _ in range(reps):
+            F.copy_(pool[step[0] % npool])
+            step[0] += 1
+            if name == "b":
+                for k in range(nsys):
+                    if upd_lone(hl[k], pl[k]) != 0:
+                        raise RuntimeError(L.nka_hip_last_error())
+            else:
+                assert upd_batch(batches[name]._handle(), C.c_void_p(F.data_ptr()), ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    def full():
+        return all((b.num_vec() == mvec).all() for b in batches.values()) and lones[0].num_vec() == mvec and lones[-1].num_vec() == mvec
+
+    reps, ts = {}, {v: [] for v in names}
+    for v in names:                                # warm: fill the lists (steady state), settle clocks and caches
+        step[0] = 0
+        run(v, mvec + 4)
+    torch.cuda.synchronize()
+    assert full()
+    assert torch.allclose(Fs["a"], Fs["b"], rtol=0, atol=1e-9 * float(Fs["b"].abs().max()))      # the same work
+    for v in names:
+        reps[v] = max(3, int(window / timed(v, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for v in names:
+            ts[v].append(timed(v, reps[v]))
+    assert full()
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    for v in names:
+        med = statistics.median(ts[v])
+        out[v], out["spread_" + v] = med, (max(ts[v]) - min(ts[v])) / med
+    out["share"] = 8.0 * nsys * vlen * (11 + (mvec - 1) + mvec) / out["a"] / PEAK
+    for x in lones:
+        x.delete()
+    for b in batches.values():
+        b.delete()
+    del pool, Fs
+    torch.cuda.empty_cache()
+    return out
+
+
+WIDE_BARRED_VLENS = (32768, 65536)
+
+
+def wide_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    chunk, cap = nka_amd.batch_wide_limits()
+    emit(f"# wide batch (a) against nsys lone handles in a loop on one stream (b) and the narrow batch (c, vlen <= "
+         f"{nka_amd.BATCH_MAX_VLEN}); {torch.cuda.get_device_name(0)}; chunk = {chunk}, cap = {cap} ({nka_amd.lib_path()}); windows >= "
+         f"{args.window} s, median of {args.repeats}, contenders alternated; default flavour and sums, full list")
+    emit(f"# share = 8*nsys*vlen*(11 + L + k) / time(a) / 8 TB/s; bar at nsys >= 16 and vlen in {WIDE_BARRED_VLENS}: b/a >= {BAR}; "
+         f"every other point is recorded without a bar")
+    emit(f"{'nsys':>5} {'vlen':>8} {'mvec':>4} {'(a) wide us':>12} {'(b) loop us':>12} {'(c) narrow us':>13} {'share':>6} {'b/a':>7} "
+         f"{'c/a':>7}  bar")
+    t0 = time.time()
+    missed, skipped = [], []
+    for n, v, m in points:
+        if v > cap:
+            emit(f"{n:5d} {v:8d} {m:4d}   beyond the cap of this library")
+            continue
+        slots = 8.0 * n * v * 2 * (m + 1)
+        r = None if slots > args.slots_gb * 1e9 else measure_wide(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9)
+        if r is None:
+            skipped.append((n, v, m))
+            emit(f"{n:5d} {v:8d} {m:4d}   SKIPPED: one contender's stored vectors take {slots / 1e9:.0f} GB (limit {args.slots_gb:g} GB), or "
+                 f"all contenders together more than {args.mem_gb:g} GB")
+            continue
+        barred = n >= 16 and v in WIDE_BARRED_VLENS
+        ratio = r["b"] / r["a"]
+        bar = "-" if not barred else ("ok" if ratio >= BAR else "MISSED")
+        if bar == "MISSED":
+            missed.append((n, v, m, round(ratio, 3)))
+        c_us = f"{r['c'] * 1e6:13.1f}" if "c" in r else f"{'-':>13}"
+        c_ratio = f"{r['c'] / r['a']:7.2f}" if "c" in r else f"{'-':>7}"
+        spreads = " ".join(f"{k} {100 * r['spread_' + k]:.1f} %" for k in ("a", "b", "c") if k in r)
+        emit(f"{n:5d} {v:8d} {m:4d} {r['a'] * 1e6:12.1f} {r['b'] * 1e6:12.1f} {c_us} {r['share']:6.3f} {ratio:7.2f} {c_ratio}  {bar}   "
+             f"(spread {spreads})")
+    emit(f"# {len(points)} points in {time.time() - t0:.0f} s; skipped: {skipped if skipped else 'none'}; missed the bar: "
+         f"{missed if missed else 'none'}")
+    return 0
+
+
 def step_main(args, torch, nka_amd, L, emit):
     ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
     points = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
@@ -301,6 +423,10 @@ def main():
     ap.add_argument("--step", action="store_true",
                     help="time accel_step against accel_update and against the loop a caller composes from it; without --nsys / "
                          "--vlens / --mvecs: nsys 256,4096 x vlen 64,1024,16384 x mvec 10,20")
+    ap.add_argument("--wide", action="store_true",
+                    help="time the wide batch against the loop over lone handles and the narrow batch; without --nsys / --vlens / "
+                         "--mvecs: nsys 4,16,64,256 x vlen 4096,16384,32768,65536,262144,1048576 x mvec 10,20")
+    ap.add_argument("--slots-gb", type=float, default=64.0, help="--wide: skip a point whose stored vectors exceed this")
     args = ap.parse_args()
     import torch
     import nka_amd
@@ -322,6 +448,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.wide:
+        for name, grid_w in (("nsys", "4,16,64,256"), ("vlens", "4096,16384,32768,65536,262144,1048576"), ("mvecs", "10,20")):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+        return wide_main(args, torch, nka_amd, L, emit)
     if args.step:
         for name, grid_s in (("nsys", "256,4096"), ("vlens", "64,1024,16384"), ("mvecs", "10,20")):
             if getattr(args, name) == ap.get_default(name):
