@@ -62,6 +62,8 @@
  *            there on.  Sums, decisions and f[0 .. L_sys) of such a system are then BIT-EQUAL to those of a batch of
  *            vlen = L_sys -- fma(+-0, b, acc) = acc for finite b, and a thread meets its elements in the same order at either
  *            length -- whatever finite values the padding of f holds (the combine still runs over it: keep it finite).
+ *            The recipe costs a stream, runs every pass over the padding, uses up the weights and does not exist for a wide
+ *            batch: LENGTHS below gives a system its own length natively, on both kinds of batch.
  *            COST, MEASURED (profiles/r09/batch_weights_throughput.txt, 1 x MI355X; nsys 256 / 4096 x vlen 1024 / 16 384 x
  *            mvec 10 / 20): a weighted update takes 0.93 ... 1.03 x the time of a plain one with the shared row, 0.93 ... 1.14 x
  *            with one row per system -- the 1.14 (mvec 10; 1.10 at mvec 20) at 4096 x 16 384, where 512 MB of weights stream
@@ -127,7 +129,28 @@
  *            reference order.  FOUR systems: the wide batch wins at mvec = 10 (1.05 ... 1.95 x) and LOSES to four lone handles at
  *            mvec = 20 at every length (0.67 ... 0.86 x): the scalar step of a system runs on one thread, 127 us at mvec = 20 (59 %
  *            of an update at 16 x 65 536), and a lone handle's does not.  A lone system stays with a lone handle.
- *   OUT OF SCOPE  sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
+ *   LENGTHS  nka_hip_batch_set_lengths: RAGGED BATCHES without padding weights, on both kinds of batch.  System `sys` is
+ *            len[sys] elements long, 1 <= len[sys] <= vlen, in EVERY phase of accel_update and accel_step: the norm and the
+ *            other sums in either order, the step's dp(f, f) and x -= f_out, the weight loads, the combine and the ring stores.
+ *            The kernel reads len[sys] once at entry (one uniform scalar load per workgroup); NOTHING at an index >= len[sys]
+ *            of the system's rows of f and x, of its weight row or of any of its slots is read or written, so the tails may
+ *            hold anything, NaN included.  In a wide batch the system owns its first ceil(len[sys] / CHUNK) chunks; the
+ *            workgroups of its other chunks return before they read anything, and only its own partials are added, in chunk
+ *            order from chunk 0 (the partials keep the batch's stride; the grid stays nchunk x nsys).  Still no workgroup reads
+ *            what another writes: no flags, no atomics, no spinning, no cooperative launch.
+ *            THE CONTRACT: for a system of length L in a batch of length vlen >= L that has had that length since creation or
+ *            since its last restart, after every accel_update / accel_step the following are BIT-EQUAL to those of the same
+ *            system in a batch of the same kind created with vlen = L: f[0 .. L), x[0 .. L), red[], the state, num_vec, the
+ *            digest, fnorm and the retirement decision, and [0 .. L) of every slot.  Same kind: narrow against narrow, wide
+ *            against wide, the same flavour, the same EXPLICIT sum order, the same weights on [0 .. L).  The elements from L on
+ *            are untouched.  This is derived, not fitted: the element -> thread map and the order in which a thread meets its
+ *            elements do not depend on the length, and a chunk is whole tiles (tests/test_batch_lengths_gpu.py holds it with ==).
+ *            UNCHANGED BY LENGTHS: f_dev, x_dev and the weight rows keep their shape -- nsys rows of ld / ldx / ldw >= vlen --
+ *            and their span checks; nka_hip_batch_get_w / _get_v return vlen doubles; NKA_HIP_SUMS_AUTO keeps resolving from the
+ *            batch's vlen, never from a system's length (the host needs no length to pick a kernel, which is what keeps a
+ *            replay valid); everything a wide batch refuses stays refused; a batch without lengths computes and launches
+ *            exactly what it did.  A length of 0 is refused: a system that should sit out is what `active` is for.
+ *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
  */
@@ -192,6 +215,23 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order);
 int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_t ldw);
 int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, int64_t ldw);
 int nka_hip_batch_dot_weighted(nka_hip_batch_t b);
+/* PER-SYSTEM LENGTHS (LENGTHS above), on the model of nka_hip_batch_set_dot_weights: nsys int32, 1 <= len[sys] <= vlen.
+ * _set_lengths takes device memory -- its span, nsys entries, is checked against its allocation before any read --,
+ * _set_lengths_host host memory; NULL makes all systems vlen long again.  The values are COPIED into a buffer of the batch and
+ * VALIDATED BEFORE THEY GET THERE (the device entry stages its span on the host): any length outside 1 ... vlen -- 0 included --
+ * returns NKA_HIP_EINVAL and the previous lengths stay in force, so no update kernel ever reads a length that did not pass.
+ * The call synchronises, and the caller's memory is free again when it returns; it is refused with NKA_HIP_ESTATE while the
+ * batch's stream is capturing.  A change applies from the next update on; the stored vectors of a system whose length changed
+ * hold a tail of the other length, so follow it with nka_hip_batch_restart for those systems (there is no automatic restart).
+ * The buffer is allocated at the FIRST set, freed by nka_hip_batch_destroy only, and never moves.  Whether an update runs with
+ * lengths, and the buffer's address, are arguments of its launch -- the kernel instance and a pointer appended after the
+ * existing arguments --: a captured update keeps whether it had lengths and reads the buffer's VALUES at replay, so new lengths
+ * set between replays apply to the next replay (NULL writes vlen into every entry for such a replay).
+ * _get_lengths: nsys int32 to host memory, vlen everywhere while none are set.  _has_lengths: 1 / 0; < 0 on error. */
+int nka_hip_batch_set_lengths(nka_hip_batch_t b, const int32_t *len_dev);
+int nka_hip_batch_set_lengths_host(nka_hip_batch_t b, const int32_t *len_host);
+int nka_hip_batch_get_lengths(nka_hip_batch_t b, int32_t *len_host);
+int nka_hip_batch_has_lengths(nka_hip_batch_t b);
 /* Rebind to another hipStream_t; work already enqueued stays ordered before. */
 int nka_hip_batch_set_stream(nka_hip_batch_t b, void *stream);
 

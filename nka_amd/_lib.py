@@ -143,6 +143,10 @@ BATCH_SIGNATURES = {
     "nka_hip_batch_set_dot_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "nka_hip_batch_set_dot_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "nka_hip_batch_dot_weighted": (C.c_int, [C.c_void_p]),
+    "nka_hip_batch_set_lengths": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nka_hip_batch_set_lengths_host": (C.c_int, [C.c_void_p, _i32p]),
+    "nka_hip_batch_get_lengths": (C.c_int, [C.c_void_p, _i32p]),
+    "nka_hip_batch_has_lengths": (C.c_int, [C.c_void_p]),
     "nka_hip_batch_num_vec": (C.c_int, [C.c_void_p, _i32p]),
     "nka_hip_batch_flavor": (C.c_int, [C.c_void_p]),
     "nka_hip_batch_get_state": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _dp, _dp]),

@@ -35,8 +35,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
              stream: int | None = None, wide: bool = False):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
-        system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_step, weights
-        and the reference sum order are refused)."""
+        system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
+        restart / relax, graphs and per-system lengths -- set_lengths -- are offered; accel_step, weights and the reference
+        sum order are refused)."""
         import torch
 
         self.delete()
@@ -213,6 +214,53 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         """True while diagonal dot-product weights are set (nka_hip_batch_dot_weighted)."""
         r = self._L.nka_hip_batch_dot_weighted(self._handle())
         _check(min(r, 0), "batch_dot_weighted", self._L)
+        return r == 1
+
+    def set_lengths(self, lens):
+        """Per-system lengths, 1 <= lens[sys] <= vlen (include/nka_hip_batch.h, LENGTHS): system `sys` is lens[sys] elements
+        long in every phase of an update or step, and nothing from there on is read or written in its rows of F and X, its
+        weight row or its slots -- a ragged batch without padding weights, on both kinds of batch.  lens: a contiguous 1-d
+        int32 CUDA tensor on the batch's device, a numpy integer array or a sequence, nsys entries; None: vlen everywhere
+        again.  Copied and validated (an invalid length raises and leaves the previous lengths in force).  Synchronises;
+        applies from the next update on -- follow it with restart() for the systems whose length changed.  The tensors F and
+        X keep their shape, nsys x vlen.  Returns self."""
+        import torch
+        h = self._handle()
+        what = "batch set_lengths"
+        if lens is None:
+            self._follow()
+            _check(self._L.nka_hip_batch_set_lengths(h, None), "batch_set_lengths", self._L)
+            return self
+        if isinstance(lens, torch.Tensor):
+            if not (lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and lens.dim() == 1
+                    and lens.device.index == self._device):
+                raise NKAError(f"{what}: a tensor must be a contiguous 1-d int32 CUDA tensor on the batch's device")
+            if lens.numel() != self._nsys:
+                raise NKAError(f"{what}: need one length per system ({self._nsys}), got {lens.numel()}")
+            self._follow()
+            _check(self._L.nka_hip_batch_set_lengths(h, C.c_void_p(lens.data_ptr())), "batch_set_lengths", self._L)
+            return self
+        arr = np.asarray(lens)
+        if arr.ndim != 1 or arr.size != self._nsys or not np.issubdtype(arr.dtype, np.integer):
+            raise NKAError(f"{what}: need {self._nsys} integers (an int32 CUDA tensor, a numpy integer array, a sequence or None)")
+        if (arr < -2**31).any() or (arr >= 2**31).any():      # (the cast to int32 below must not wrap a wide integer into range)
+            raise NKAError(f"{what}: every length must be 1 ... vlen = {self._vlen} (the previous lengths stay in force)")
+        arr = np.ascontiguousarray(arr, dtype=np.int32)
+        self._follow()
+        _check(self._L.nka_hip_batch_set_lengths_host(h, arr.ctypes.data_as(_lib._i32p)), "batch_set_lengths_host", self._L)
+        return self
+
+    def lengths(self) -> np.ndarray:
+        """The length every system runs with at the next update: vlen everywhere while none are set."""
+        h = self._handle()
+        out = np.zeros(self._nsys, np.int32)
+        _check(self._L.nka_hip_batch_get_lengths(h, out.ctypes.data_as(_lib._i32p)), "batch_get_lengths", self._L)
+        return out
+
+    def has_lengths(self) -> bool:
+        """True while per-system lengths are set (nka_hip_batch_has_lengths)."""
+        r = self._L.nka_hip_batch_has_lengths(self._handle())
+        _check(min(r, 0), "batch_has_lengths", self._L)
         return r == 1
 
     # -- queries (synchronise) ---------------------------------------------

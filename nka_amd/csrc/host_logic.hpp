@@ -245,6 +245,14 @@ NKA_HOST_DEVICE constexpr int64_t wide_part_count(int64_t nsys, int mvec, int64_
 NKA_HOST_DEVICE constexpr int64_t wide_part_index(int64_t sys, int entry, int64_t c, int mvec, int64_t nchunk) {
   return (sys * (2 + 2 * mvec) + entry) * nchunk + c;
 }
+// PER-SYSTEM LENGTHS (nka_hip_batch_set_lengths): a system of len elements, 1 <= len <= vlen, in a batch laid out for vlen.  It
+// owns the first wide_len_nchunk(len) chunks of its row -- the chunks of a batch created with vlen = len, of the same lengths --
+// and its partials keep the BATCH's nchunk as stride, so every index it reads lies in its own cells.  The workgroups of the
+// other chunks return before they read anything.  tests/c/batch_lengths_check.cpp holds all of it for every len.
+NKA_HOST_DEVICE constexpr bool batch_len_valid(int64_t len, int64_t vlen) { return len >= 1 && len <= vlen; }
+NKA_HOST_DEVICE constexpr int64_t wide_len_nchunk(int64_t len) { return wide_nchunk(len); }
+NKA_HOST_DEVICE constexpr bool wide_len_owns(int64_t len, int64_t c) { return c >= 0 && c < wide_len_nchunk(len); }
+NKA_HOST_DEVICE constexpr int64_t wide_len_chunk_len(int64_t len, int64_t c) { return wide_chunk_len(len, c); }      // (c owned)
 // LDS of the sums and the combine kernel: doubles first, then int32 (a piece a kernel lacks has length 0; the norm kernel
 // holds sm [waves] and res [2] only, declared where it uses them)
 struct WideLds {

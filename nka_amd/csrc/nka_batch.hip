@@ -47,6 +47,14 @@ struct StepArgs {
   double *fnorm;        // r = sqrt(dp(f, f)) of every system active on entry
 };
 __device__ __forceinline__ const StepArgs &step_args(const StepArgs &st) { return st; }
+// PER-SYSTEM LENGTHS (nka_hip_batch_set_lengths): the batch's buffer of nsys validated lengths, 1 <= len[sys] <= vlen.  It is the
+// LAST member of the trailing pack, behind the StepArgs if there is one, so an instance without it keeps its arguments.
+struct LenArgs {
+  const int32_t *len;
+};
+__device__ __forceinline__ const StepArgs &step_args(const StepArgs &st, const LenArgs &) { return st; }
+__device__ __forceinline__ const int32_t *len_args(const LenArgs &l) { return l.len; }
+__device__ __forceinline__ const int32_t *len_args(const StepArgs &, const LenArgs &l) { return l.len; }
 
 // (where the pieces of a system lie, and the LDS of a workgroup -- 5.3 KB at mvec = 20, 11.2 KB at 32: host_logic.hpp)
 static_assert(nka_host::batch_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 40 * 1024, "four workgroups of a batch must fit the LDS of a CU");
@@ -57,13 +65,18 @@ static_assert(nka_host::batch_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 40 * 1024, 
 // FIRST operand of every product (nka_device.hpp, DIAGONAL WEIGHTS); element -> thread map, per-thread order and reduction
 // are those of WGT = false, which reads neither argument and is the unweighted kernel instruction for instruction.
 // Step...: nothing (the update) or one StepArgs (the solve step, above); a step writes active[sys] = 0 when the system retires.
+// A trailing LenArgs makes n = len[sys] -- one uniform scalar load at entry -- the length of EVERY phase: the ordered chains, the
+// sweeps, the step's dp(f, f) and x -= f_out, the weight loads.  Nothing at an index >= len[sys] of f, x, the weight row or a slot
+// is read or written; the element -> thread map and the per-thread order do not depend on n, so the system carries the bits of
+// a batch created with vlen = len[sys].  Without it the instance is the one it was, instruction for instruction.
 template <int COMB, bool ORDERED, bool WGT, class... Step>
 __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, double *__restrict__ f_all, int64_t ld,
                                                                 const int32_t *__restrict__ active,
                                                                 const double *__restrict__ wgt_all, int64_t wgt_stride, Step... step) {
 #pragma clang fp contract(off)      // elementwise statements and the reference-order sums round like the reference; fma is explicit
-  constexpr bool STEP = sizeof...(Step) != 0;
-  static_assert(sizeof...(Step) <= 1, "at most one StepArgs");
+  constexpr bool STEP = (std::is_same<Step, StepArgs>::value || ...);
+  constexpr bool LEN = (std::is_same<Step, LenArgs>::value || ...);
+  static_assert(sizeof...(Step) == (STEP ? 1 : 0) + (LEN ? 1 : 0), "at most one StepArgs, then at most one LenArgs");
   constexpr int NNRM = STEP ? 2 : 1;             // sums of phase 2: [<f,f>,] <d,d>, landing in res[kBatchAcc + 1 - NNRM ...]
   constexpr bool RCP = (COMB == 1);
   constexpr bool COMPACT = (COMB == 2);
@@ -73,7 +86,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int t = threadIdx.x;
   const int mvec = a.mvec, m1 = mvec + 1, nh = (m1 + 1) * (m1 + 1);
-  const int64_t n = a.n;
+  const int64_t n = [&]() -> int64_t {
+    if constexpr (LEN) return len_args(step...)[sys]; else return a.n;      // (validated when it was set: 1 <= len[sys] <= a.n)
+  }();
   const Ctl ctl = batch_ctl(a, sys);
   double *const f = f_all + (size_t)sys * ld;
   double *const W = a.w + (size_t)sys * a.sys_stride, *const V = a.v + (size_t)sys * a.sys_stride;
@@ -493,12 +508,18 @@ void launch_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *acti
   }
 }
 template <class... Step>
-void launch_flavor(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+void launch_flavor_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
   switch (b->flavor) {
     case NKA_HIP_FLAVOR_F08_VECTOR: launch_update<1>(b, f, ld, active, step...); break;
     case NKA_HIP_FLAVOR_C: launch_update<2>(b, f, ld, active, step...); break;
     default: launch_update<0>(b, f, ld, active, step...);
   }
+}
+// (per-system lengths travel like the weights: the instance and the buffer's address are fixed when the update is enqueued or
+// captured, the buffer's VALUES are read when it runs)
+template <class... Step>
+void launch_flavor(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+  if (b->has_len) launch_flavor_as(b, f, ld, active, step..., LenArgs{b->len}); else launch_flavor_as(b, f, ld, active, step...);
 }
 // what accel_update and accel_step check of f
 int check_rows(nka_hip_batch_t b, const double *p, int64_t ld, const std::string &who, const char *name, const char *ldname) {
@@ -659,6 +680,7 @@ int nka_hip_batch_destroy(nka_hip_batch_t b) {
   hipFree(b->wgt);
   hipFree(b->wgt_stage);
   hipFree(b->wgt_chk);
+  hipFree(b->len);
   nka_batch_wide_free(b);
   delete b;
   return 0;
@@ -767,6 +789,84 @@ int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, 
 int nka_hip_batch_dot_weighted(nka_hip_batch_t b) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_dot_weighted: null handle");
   return b->weighted ? 1 : 0;
+}
+
+// PER-SYSTEM LENGTHS (nka_hip_batch.h, LENGTHS).  Both setters end in set_lengths_checked: the values are on the HOST by then
+// -- the device entry stages its checked span there --, every one is held to 1 <= len <= vlen, and only then are they copied
+// into the batch's buffer, which therefore never holds a length that an update kernel may not use as a bound.
+static int lengths_alloc(nka_hip_batch_t b) {
+  if (b->len) return 0;
+  int32_t *p = nullptr;
+  HIP_TRY(hipMalloc((void **)&p, sizeof(int32_t) * (size_t)b->k.nsys));
+  const std::vector<int32_t> full((size_t)b->k.nsys, (int32_t)b->k.n);      // (vlen everywhere until a set succeeds)
+  hipError_t e = hipMemcpyAsync(p, full.data(), sizeof(int32_t) * full.size(), hipMemcpyHostToDevice, b->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    hipFree(p);
+    return fail(NKA_HIP_EHIP, std::string("batch_set_lengths: ") + hipGetErrorString(e));
+  }
+  b->len = p;
+  return 0;
+}
+static int set_lengths_checked(nka_hip_batch_t b, const int32_t *len_host, const char *what) {
+  for (int32_t sys = 0; sys < b->k.nsys; sys++)
+    if (!nka_host::batch_len_valid(len_host[sys], b->k.n))
+      return fail(NKA_HIP_EINVAL, std::string(what) + ": length " + std::to_string(len_host[sys]) + " of system " + std::to_string(sys) +
+                                      " is outside 1 ... vlen = " + std::to_string((long long)b->k.n) +
+                                      " (the previous lengths stay in force; a system that should sit out: the mask)");
+  if (int rc = lengths_alloc(b)) return rc;
+  HIP_TRY(hipMemcpyAsync(b->len, len_host, sizeof(int32_t) * (size_t)b->k.nsys, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  b->has_len = true;
+  return 0;
+}
+// NULL: every system vlen long again.  The buffer stays -- a captured update may hold its address -- and is filled with vlen.
+static int clear_lengths(nka_hip_batch_t b) {
+  b->has_len = false;
+  if (!b->len) return 0;
+  const std::vector<int32_t> full((size_t)b->k.nsys, (int32_t)b->k.n);
+  HIP_TRY(hipMemcpyAsync(b->len, full.data(), sizeof(int32_t) * full.size(), hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int nka_hip_batch_set_lengths(nka_hip_batch_t b, const int32_t *len_dev) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_set_lengths: null handle");
+  HIP_TRY(hipSetDevice(b->device));
+  if (int rc = weights_settable(b, "batch_set_lengths")) return rc;
+  if (!len_dev) return clear_lengths(b);
+  if (int rc = nka_detail::check_device_span_i32(len_dev, b->k.nsys, "batch_set_lengths: len")) return rc;
+  std::vector<int32_t> stage((size_t)b->k.nsys);
+  HIP_TRY(hipMemcpyAsync(stage.data(), len_dev, sizeof(int32_t) * stage.size(), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return set_lengths_checked(b, stage.data(), "batch_set_lengths");
+}
+
+int nka_hip_batch_set_lengths_host(nka_hip_batch_t b, const int32_t *len_host) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: null handle");
+  HIP_TRY(hipSetDevice(b->device));
+  if (int rc = weights_settable(b, "batch_set_lengths_host")) return rc;
+  if (!len_host) return clear_lengths(b);
+  const std::vector<int32_t> stage(len_host, len_host + b->k.nsys);      // (pageable memory of the caller's is free again at once)
+  return set_lengths_checked(b, stage.data(), "batch_set_lengths_host");
+}
+
+int nka_hip_batch_get_lengths(nka_hip_batch_t b, int32_t *len_host) {
+  if (!b || !len_host) return fail(NKA_HIP_EINVAL, "batch_get_lengths: null argument");
+  if (!b->has_len) {
+    std::fill(len_host, len_host + b->k.nsys, (int32_t)b->k.n);
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipMemcpyAsync(len_host, b->len, sizeof(int32_t) * (size_t)b->k.nsys, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int nka_hip_batch_has_lengths(nka_hip_batch_t b) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_has_lengths: null handle");
+  return b->has_len ? 1 : 0;
 }
 
 int nka_hip_batch_set_stream(nka_hip_batch_t b, void *stream) {

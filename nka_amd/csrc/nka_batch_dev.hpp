@@ -171,6 +171,10 @@ struct nka_hip_batch_state {
   unsigned long long *wgt_chk = nullptr;    // two words of k_batch_check_weights
   bool weighted = false;
   int64_t wgt_stride = 0;                   // row stride the updates run with: k.stride, or 0 in the shared form
+  // per-system lengths (nka_hip_batch_set_lengths): nsys int32, allocated at the first set, freed at destroy only and never
+  // moved -- a captured update holds the address.  It only ever holds values that passed the check 1 <= len <= vlen.
+  int32_t *len = nullptr;
+  bool has_len = false;                     // the next update runs the instances that read it
   // a WIDE batch (nka_hip_batch_create_wide, nka_batch_wide.hip): a system is nchunk chunks of NKA_HIP_BATCH_WIDE_CHUNK elements
   bool wide = false;
   int32_t nchunk = 0;

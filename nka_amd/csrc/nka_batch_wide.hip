@@ -351,10 +351,328 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_combine(BatchArgs a, Wid
   });
 }
 
+// ---- THE SAME FOUR KERNELS WITH PER-SYSTEM LENGTHS (nka_hip_batch_set_lengths) ----
+// The system is len[sys] elements long -- one uniform scalar load behind the `active` test, a value that was validated when it was
+// set: 1 <= len[sys] <= a.n --, it owns the first wide_len_nchunk(len[sys]) chunks, and a workgroup of another chunk returns
+// before it reads anything else.  The partials keep the batch's nchunk as stride (wide_part_index does not change); only the
+// system's own are added, in chunk order from chunk 0.  The grid stays nchunk x nsys.  Every other statement is the one of the
+// kernel above: the text is WRITTEN OUT a second time because sharing it -- the four bodies as functions of a bool, called by
+// both kernels -- changed the machine code of the kernels above, which are held to it (docs/design/12_batched_systems.md).
+// A change to a phase is made in both places.
+
+// ---- 1 ----
+__global__ __launch_bounds__(kBatchThreads) void k_wide_norm_len(BatchArgs a, WideArgs wa, const double *__restrict__ f_all, int64_t ld,
+                                          const int32_t *__restrict__ active, const int32_t *__restrict__ len) {
+#pragma clang fp contract(off)
+  const int sys = blockIdx.y;
+  if (active != nullptr && active[sys] == 0) return;
+  const int64_t sn = len[sys];
+  if (!nka_host::wide_len_owns(sn, blockIdx.x)) return;      // (uniform: a chunk beyond the system's own; nothing was read)
+  const Ctl ctl = batch_ctl(a, sys);
+  if (ctl.ic[IC_PENDING] == 0) return;      // (uniform: no pending pair, no norm -- and nobody reads this partial)
+  __shared__ double sm[kBatchWaves], res[2];
+  const int64_t lo = (int64_t)blockIdx.x * kWideChunk, n = nka_host::wide_len_chunk_len(sn, blockIdx.x);
+  const double *const f = f_all + (size_t)sys * ld + lo;
+  const double *const w1 = a.w + (size_t)sys * a.sys_stride + (size_t)(ctl.ic[IC_FIRST] - 1) * a.stride + lo;
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
+  double acc[1] = {};
+  batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+    constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+    const d2 fv = ld_tile<FULL, FV>(f, i, n), wv = ld_tile<FULL, true>(w1, i, n);
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+      if (FULL || i + q < n) {
+        const double d = wv[q] - fv[q];
+        acc[0] = fma(d, d, acc[0]);
+      }
+  });
+  batch_block_sum<1>(acc, sm, res);
+  if (threadIdx.x == 0) wa.part[nka_host::wide_part_index(sys, 0, blockIdx.x, a.mvec, wa.nchunk)] = res[0];
+}
+
+// ---- 2 ----
+template <int COMB>
+__global__ __launch_bounds__(kBatchThreads) void k_wide_sums_len(BatchArgs a, WideArgs wa, const double *__restrict__ f_all, int64_t ld,
+                                          const int32_t *__restrict__ active, const int32_t *__restrict__ len) {
+#pragma clang fp contract(off)
+  constexpr bool RCP = (COMB == 1);
+  const int sys = blockIdx.y, chunk = blockIdx.x;
+  if (active != nullptr && active[sys] == 0) return;
+  const int64_t sn = len[sys];
+  if (!nka_host::wide_len_owns(sn, chunk)) return;      // (uniform, before the first barrier)
+  const int nown = (int)nka_host::wide_len_nchunk(sn);      // the partials of <d,d> that are added
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int mvec = a.mvec, m1 = mvec + 1, nchunk = wa.nchunk;
+  const Ctl ctl = batch_ctl(a, sys);
+  const nka_host::WideLds lds = nka_host::wide_sums_lds(mvec, nchunk);
+  double *const shd = reinterpret_cast<double *>(smem);
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  double *const stage = shd + lds.stage, *const sm = shd + lds.sm, *const res = shd + lds.res;
+  int32_t *const next = shi + lds.next, *const ps = shi + lds.ps, *const hdr = shi + lds.hdr;
+
+  wide_list(ctl, m1, next, ps, hdr);
+  const int pending = hdr[HDR_PENDING], nolder = hdr[HDR_NOLDER];
+  double s = 0.0;
+  if (pending) {
+    wide_norm_sum(wa.part + nka_host::wide_part_index(sys, 0, 0, mvec, nchunk), nown, stage, res + kBatchAcc);
+    s = sqrt(res[kBatchAcc]);
+  }
+  const bool normed = pending && s != 0.0;
+  const double rs = 1.0 / s;
+
+  const int64_t lo = (int64_t)chunk * kWideChunk, n = nka_host::wide_len_chunk_len(sn, chunk);
+  const double *const f = f_all + (size_t)sys * ld + lo;
+  const double *const W = a.w + (size_t)sys * a.sys_stride + lo;
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
+  const double *const w1s = pending ? W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride : W;      // always a stored vector
+  auto out = [&](int entry) -> double & { return wa.part[nka_host::wide_part_index(sys, entry, chunk, mvec, nchunk)]; };
+
+  const int ngroup = (nolder + kBatchGroup - 1) / kBatchGroup;
+  for (int g = 0; g < (ngroup > 0 ? ngroup : (normed ? 1 : 0)); g++) {
+    const double *wk[kBatchGroup];
+#pragma unroll
+    for (int j = 0; j < kBatchGroup; j++) {
+      const int p = g * kBatchGroup + j;
+      wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1s;   // (beyond the list: a re-read, discarded)
+    }
+    double acc[kBatchAcc];
+#pragma unroll
+    for (int q = 0; q < kBatchAcc; q++) acc[q] = 0.0;
+    batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+      constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+      const d2 fv = ld_tile<FULL, FV>(f, i, n);
+      const d2 dv = ld_tile<FULL, true>(w1s, i, n);     // (no pending pair: a stored vector whose value is not used)
+      d2 wv[kBatchGroup];
+#pragma unroll
+      for (int j = 0; j < kBatchGroup; j++) wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+        if (FULL || i + q < n) {
+          const double fq = fv[q];
+          if (normed) {
+            const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
+            if (g == 0) acc[2 * kBatchGroup] = fma(fq, wn, acc[2 * kBatchGroup]);
+#pragma unroll
+            for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wn, wv[j][q], acc[j]);
+          }
+#pragma unroll
+          for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fq, wv[j][q], acc[kBatchGroup + j]);
+        }
+    });
+    batch_block_sum<kBatchAcc>(acc, sm, res);
+    if (t < kBatchGroup && g * kBatchGroup + t < nolder) {
+      if (normed) out(2 + g * kBatchGroup + t) = res[t];
+      out(2 + mvec + g * kBatchGroup + t) = res[kBatchGroup + t];
+    }
+    if (t == 0 && g == 0 && normed) out(1) = res[2 * kBatchGroup];
+    // (res is rewritten only behind the two barriers of the next batch_block_sum)
+  }
+}
+
+// ---- 3 ----
+__global__ __launch_bounds__(kBatchThreads) void k_wide_scalar_len(BatchArgs a, WideArgs wa, const int32_t *__restrict__ active,
+                                            const int32_t *__restrict__ len) {
+#pragma clang fp contract(off)
+  const int sys = blockIdx.x;
+  if (active != nullptr && active[sys] == 0) return;
+  const int nown = (int)nka_host::wide_len_nchunk(len[sys]);      // the partials that are added
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int mvec = a.mvec, m1 = mvec + 1, nh = (m1 + 1) * (m1 + 1), nchunk = wa.nchunk;
+  const Ctl ctl = batch_ctl(a, sys);
+  const nka_host::WideScalarLds wl = nka_host::wide_scalar_lds(mvec, nchunk);
+  const nka_host::BatchLds &lds = wl.b;
+  double *const shd = reinterpret_cast<double *>(smem);
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  Lst L;
+  L.h = shd + lds.h;
+  L.c = shd + lds.c;
+  double *const red = shd + lds.red;
+  double *const cc = shd + lds.cc;
+  double *const res = shd + lds.res;
+  double *const stage = shd + wl.stage;
+  L.next = shi + lds.next;
+  L.prev = shi + lds.prev;
+  int32_t *const ps = shi + lds.ps;
+  int32_t *const cs = shi + lds.cs;
+  int32_t *const hdr = shi + lds.hdr;
+  L.m1 = m1;
+  L.mvec = mvec;
+
+  // the working copy (phase 1 of k_batch_update)
+  for (int i = t; i < nh; i += kBatchThreads) L.h[i] = ctl.h()[i];
+  for (int i = t; i < m1 + 1; i += kBatchThreads) {
+    L.c[i] = ctl.c()[i];
+    L.next[i] = ctl.next()[i];
+    L.prev[i] = ctl.prev()[i];
+  }
+  L.subspace = L.pending = L.first = L.last = L.free_ = 0;
+  L.vtol = 0.0;
+  __syncthreads();
+  if (t == 0) {
+    lst_load_scalars(L, ctl);
+    L.vtol = ctl.dc[DC_VTOL];
+    int no = 0;
+    for (int k = L.pending ? L.next[L.first] : L.first; k != 0 && no < m1; k = L.next[k]) ps[no++] = k;
+    hdr[HDR_PENDING] = L.pending;
+    hdr[HDR_FIRST] = L.first;
+    hdr[HDR_NOLDER] = no;
+  }
+  __syncthreads();
+  const int pending = hdr[HDR_PENDING], nolder = hdr[HDR_NOLDER];
+  double s = 0.0;
+  if (pending) {      // the same chunk-order sum as k_wide_sums
+    wide_norm_sum(wa.part + nka_host::wide_part_index(sys, 0, 0, mvec, nchunk), nown, stage, res + kBatchAcc);
+    s = sqrt(res[kBatchAcc]);
+  }
+  const bool normed = pending && s != 0.0;
+  // red[j], one thread per entry: the chunk-order sum of the partials k_wide_sums wrote in this update, zero everywhere else
+  if (t < 2 + 2 * mvec) {
+    double r = 0.0;
+    if (t == 0) {
+      if (pending) r = res[kBatchAcc];
+    } else {
+      const bool formed = t == 1 ? normed : t < 2 + mvec ? (normed && t - 2 < nolder) : (t - 2 - mvec < nolder);
+      if (formed) {
+        const double *const p = wa.part + nka_host::wide_part_index(sys, t, 0, mvec, nchunk);
+        r = p[0];
+        int c = 1;
+        for (; c + 8 <= nown; c += 8) {      // (eight loads in flight; the additions stay one chain, in chunk order)
+          double x[8];
+#pragma unroll
+          for (int u = 0; u < 8; u++) x[u] = p[c + u];
+#pragma unroll
+          for (int u = 0; u < 8; u++) r += x[u];
+        }
+        for (; c < nown; c++) r += p[c];
+      }
+    }
+    red[t] = r;
+  }
+  __syncthreads();
+
+  // phase 4: the scalar step on the working copy
+  if (t == 0) batch_scalar_step(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr);
+  __syncthreads();
+
+  // phase 5: the working copy back; the plan to the combine
+  for (int i = t; i < nh; i += kBatchThreads) ctl.h()[i] = L.h[i];
+  for (int i = t; i < m1 + 1; i += kBatchThreads) {
+    ctl.c()[i] = L.c[i];
+    ctl.next()[i] = L.next[i];
+    ctl.prev()[i] = L.prev[i];
+  }
+  for (int i = t; i < 2 + 2 * mvec; i += kBatchThreads) ctl.red()[i] = red[i];
+  if (t < hdr[HDR_NCOMB]) {
+    wa.plan_c[(size_t)sys * m1 + t] = cc[t];
+    wa.plan_s[(size_t)sys * m1 + t] = cs[t];
+  }
+}
+
+// ---- 4 ----
+template <int COMB>
+__global__ __launch_bounds__(kBatchThreads) void k_wide_combine_len(BatchArgs a, WideArgs wa, double *__restrict__ f_all, int64_t ld,
+                                             const int32_t *__restrict__ active, const int32_t *__restrict__ len) {
+#pragma clang fp contract(off)
+  constexpr bool RCP = (COMB == 1);
+  constexpr bool COMPACT = (COMB == 2);
+  const int sys = blockIdx.y;
+  if (active != nullptr && active[sys] == 0) return;
+  const int64_t sn = len[sys];
+  if (!nka_host::wide_len_owns(sn, blockIdx.x)) return;      // (uniform, before the first barrier)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int m1 = a.mvec + 1;
+  const Ctl ctl = batch_ctl(a, sys);
+  const nka_host::WideLds lds = nka_host::wide_combine_lds(a.mvec);
+  double *const shd = reinterpret_cast<double *>(smem);
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  double *const cc = shd + lds.cc;
+  int32_t *const cs = shi + lds.cs, *const hdr = shi + lds.hdr;
+  // the plan into LDS
+  if (t == 64) hdr[HDR_NCOMB] = ctl.ic[IC_NCOMB];
+  if (t == 65) hdr[HDR_NEW] = ctl.ic[IC_NEW];
+  if (t == 66) hdr[HDR_NORMED] = ctl.ic[IC_NORMED];
+  if (t < m1) {      // (entries beyond the plan are never applied)
+    cc[t] = wa.plan_c[(size_t)sys * m1 + t];
+    cs[t] = wa.plan_s[(size_t)sys * m1 + t];
+  }
+  __syncthreads();
+  const int ncomb = hdr[HDR_NCOMB];
+  const bool norm0 = hdr[HDR_NORMED] != 0;      // pair 0 of the plan is the pending pair, still raw
+  const double s = norm0 ? ctl.dc[DC_S] : 0.0;
+  const double rs = 1.0 / s;
+
+  const int64_t lo = (int64_t)blockIdx.x * kWideChunk, n = nka_host::wide_len_chunk_len(sn, blockIdx.x);
+  double *const f = f_all + (size_t)sys * ld + lo;
+  double *const W = a.w + (size_t)sys * a.sys_stride + lo, *const V = a.v + (size_t)sys * a.sys_stride + lo;
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
+  double *const wnew = W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
+  batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+    constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+    if (!FULL && i >= n) return;
+    const d2 fin = ld_tile<FULL, FV>(f, i, n);
+    d2 x = fin;
+    int j0 = 0;
+    if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
+      double *const wk = W + (size_t)(cs[0] - 1) * a.stride, *const vk = V + (size_t)(cs[0] - 1) * a.stride;
+      d2 wv = ld_tile<FULL, true>(wk, i, n), vv = ld_tile<FULL, true>(vk, i, n);
+      const double c = cc[0];
+#pragma unroll
+      for (int q = 0; q < 2; q++) {
+        const double wn = batch_nrm<RCP>(wv[q] - fin[q], s, rs);
+        const double vn = batch_nrm<RCP>(vv[q], s, rs);
+        wv[q] = wn;
+        vv[q] = COMPACT ? vn - wn : vn;
+        x[q] = COMPACT ? x[q] + c * vv[q] : comb1<COMB>(x[q], c, wv[q], vv[q]);
+      }
+      st_tile<FULL, true>(wk, i, n, wv);
+      st_tile<FULL, true>(vk, i, n, vv);
+      j0 = 1;
+    }
+    constexpr int U = 4;      // pairs whose loads are in flight together (beyond the plan: the last pair again, not applied)
+    for (int j = j0; j < ncomb; j += U) {
+      d2 wv[U], vv[U];
+      double c[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int jj = j + u < ncomb ? j + u : ncomb - 1;
+        const size_t off = (size_t)(cs[jj] - 1) * a.stride;
+        c[u] = cc[jj];
+        vv[u] = ld_tile<FULL, true>(V + off, i, n);
+        if (!COMPACT) wv[u] = ld_tile<FULL, true>(W + off, i, n); else wv[u] = vv[u];
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (j + u < ncomb) {
+#pragma unroll
+          for (int q = 0; q < 2; q++) x[q] = COMPACT ? x[q] + c[u] * vv[u][q] : comb1<COMB>(x[q], c[u], wv[u][q], vv[u][q]);
+        }
+    }
+    st_tile<FULL, true>(wnew, i, n, fin);
+    st_tile<FULL, true>(vnew, i, n, x);
+    if (ncomb > 0) st_tile<FULL, FV>(f, i, n, x);      // (nothing to combine: f stays as it is)
+  });
+}
+
+// (whether an update runs with per-system lengths, and the buffer's address, are fixed when it is enqueued or captured; the grid
+// is nchunk x nsys either way, so the host needs no length to launch)
 template <int COMB>
 void launch_wide(nka_hip_batch_t b, const WideArgs &wa, double *f, int64_t ld, const int32_t *active) {
   const int mvec = b->k.mvec, nchunk = b->nchunk;
   const dim3 grid((unsigned)nchunk, (unsigned)b->k.nsys), block(kBatchThreads);
+  if (b->has_len) {
+    const int32_t *const len = b->len;
+    hipLaunchKernelGGL(k_wide_norm_len, grid, block, 0, b->stream, b->k, wa, (const double *)f, ld, active, len);
+    hipLaunchKernelGGL((k_wide_sums_len<COMB>), grid, block, nka_host::wide_sums_lds(mvec, nchunk).bytes(), b->stream, b->k, wa,
+                       (const double *)f, ld, active, len);
+    hipLaunchKernelGGL(k_wide_scalar_len, dim3((unsigned)b->k.nsys), block, nka_host::wide_scalar_lds(mvec, nchunk).b.bytes(), b->stream,
+                       b->k, wa, active, len);
+    hipLaunchKernelGGL((k_wide_combine_len<COMB>), grid, block, nka_host::wide_combine_lds(mvec).bytes(), b->stream, b->k, wa, f, ld, active,
+                       len);
+    return;
+  }
   hipLaunchKernelGGL(k_wide_norm, grid, block, 0, b->stream, b->k, wa, (const double *)f, ld, active);
   hipLaunchKernelGGL((k_wide_sums<COMB>), grid, block, nka_host::wide_sums_lds(mvec, nchunk).bytes(), b->stream, b->k, wa, (const double *)f,
                      ld, active);

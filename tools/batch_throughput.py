@@ -39,7 +39,17 @@ windows, same alternation, on the same inputs:
 Grid nsys 4,16,64,256 x vlen 4096,16384,32768,65536,262144,1048576 x mvec 10,20; a point whose stored vectors (one contender's
 slots) exceed --slots-gb is skipped and listed.  The bar of 1.06 on time(b)/time(a) applies at nsys >= 16 and vlen 32768 or
 65536; every other point is recorded without one.  The line at the top names the chunk and the cap of the library loaded
-(NKA_HIP_LIB: a candidate build of another chunk)."""
+(NKA_HIP_LIB: a candidate build of another chunk).
+
+--lengths measures per-system lengths (nka_hip_batch_set_lengths) with the method of --weights -- same inputs, variants
+alternated in one process, the same windows:
+  (a) a plain batch at vlen;
+  (b) the zero-weight recipe: one weight row per system, 1 below the system's length and 0 from there on (narrow only);
+  (c) per-system lengths;
+(b) and (c) twice: every length = vlen, and lengths from a fixed seed, uniform in [vlen / 4, vlen].  Narrow points nsys 256,4096 x
+vlen 1024,16384 x mvec 10,20; wide points, (a) and (c) only, (16, 65 536) and (64, 262 144) x mvec 10,20.  Two conditions, both
+against code that exists without (c): with every length = vlen (c) is not slower than (a) beyond the spread of the five windows;
+with ragged lengths (c) is not slower than (b) on the same lengths beyond that spread.  A point that misses is marked, not tuned."""
 import argparse
 import ctypes as C
 import os
@@ -174,6 +184,119 @@ def measure_weights(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_bu
     del pool, w, forms, Fs
     torch.cuda.empty_cache()
     return out
+
+
+LENGTHS_SEED = 2024
+
+
+def ragged_lengths(nsys, vlen):
+    """The ragged lengths of --lengths: fixed seed, uniform in [vlen / 4, vlen]."""
+    import numpy as np
+    return np.random.default_rng([LENGTHS_SEED, nsys, vlen]).integers(vlen // 4, vlen + 1, nsys).astype(np.int32)
+
+
+def measure_lengths(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, wide):
+    """--lengths: (a) a plain batch at vlen; (b) the zero-weight recipe, one weight row per system (narrow only); (c) per-system
+    lengths -- (b) and (c) once with every length = vlen and once with ragged_lengths.  The same inputs for all, alternated."""
+    import numpy as np
+    names = ["a", "c_full", "c_ragged"] if wide else ["a", "b_full", "c_full", "b_ragged", "c_ragged"]
+    npool = mvec + 3
+    need = 8.0 * nsys * vlen * (len(names) * (2 * (mvec + 1) + 1) + npool + 2 * 2)
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    lens = {"full": np.full(nsys, vlen, np.int32), "ragged": ragged_lengths(nsys, vlen)}
+    Fs, hs, batches = {}, {}, {}
+    for name in names:
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+        b = batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, wide=wide)
+        kind, _, which = name.partition("_")
+        if kind == "b":
+            w = (torch.arange(vlen, device="cuda")[None, :] < torch.from_numpy(lens[which]).cuda()[:, None]).to(torch.float64)
+            b.set_dot_weights(w)
+            del w
+        if kind == "c":
+            b.set_lengths(lens[which])
+        hs[name] = b._handle()
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    upd = L.nka_hip_batch_accel_update
+    step = [0]
+
+    def run(name, reps):
+        F, h = Fs[name], hs[name]
+        p = C.c_void_p(F.data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[step[0] % npool])
+            step[0] += 1
+            assert upd(h, p, ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in names}
+    for name in names:                             # warm: fill the lists (steady state), settle clocks and caches
+        step[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    for name in names:
+        assert (batches[name].num_vec() == mvec).all(), name
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in names:
+            ts[name].append(timed(name, reps[name]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec, mean_len=float(lens["ragged"].mean()))
+    for name in names:
+        assert (batches[name].num_vec() == mvec).all(), name
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+        batches[name].delete()
+    del pool, Fs
+    torch.cuda.empty_cache()
+    return out
+
+
+def lengths_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    narrow = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    wide = [(n, v, m) for n, v in ((16, 65536), (64, 262144)) for m in ints(args.mvecs)] if args.lengths_wide else []
+    emit(f"# one update of (a) a plain batch at vlen, (b) the zero-weight recipe (one weight row per system: 1 below the length, 0 "
+         f"from there on), (c) per-system lengths (nka_hip_batch_set_lengths); (b) and (c) with every length = vlen (full) and with "
+         f"lengths uniform in [vlen/4, vlen], seed {LENGTHS_SEED} (ragged); {torch.cuda.get_device_name(0)}; windows >= {args.window} s, "
+         f"median of {args.repeats}, the variants alternated; default flavour and sums, full list")
+    emit("# conditions: c_full / a <= 1 + spread (the same work plus one scalar load); c_ragged / b_ragged <= 1 + spread (fewer "
+         "streams over fewer elements); spread = the larger of the two variants' (max - min) / median over the windows")
+    t0, missed = time.time(), []
+    for kind, points in (("narrow", narrow), ("wide", wide)):
+        if not points:
+            continue
+        emit(f"# {kind}")
+        emit(f"{'nsys':>5} {'vlen':>7} {'mvec':>4} {'mean len':>9} {'a us':>9} {'b full':>9} {'c full':>9} {'b ragged':>9} {'c ragged':>9} "
+             f"{'c_full/a':>8} {'c_rag/b_rag':>11} {'c_rag/a':>8}")
+        for n, v, m in points:
+            r = measure_lengths(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9, kind == "wide")
+            if r is None:
+                emit(f"{n:5d} {v:7d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+                continue
+            us = lambda k: f"{r[k] * 1e6:9.1f}" if k in r else f"{'-':>9}"              # noqa: E731
+            full = r["c_full"] / r["a"]
+            rag = r["c_ragged"] / r["b_ragged"] if "b_ragged" in r else float("nan")
+            verdict = []
+            if full > 1.0 + max(r["spread_c_full"], r["spread_a"]):
+                verdict.append("c_full/a MISSED")
+            if "b_ragged" in r and rag > 1.0 + max(r["spread_c_ragged"], r["spread_b_ragged"]):
+                verdict.append("c_rag/b_rag MISSED")
+            if verdict:
+                missed.append((kind, n, v, m) + tuple(verdict))
+            spreads = " ".join(f"{k} {100 * r['spread_' + k]:.1f} %" for k in ("a", "b_full", "c_full", "b_ragged", "c_ragged") if k in r)
+            emit(f"{n:5d} {v:7d} {m:4d} {r['mean_len']:9.0f} {us('a')} {us('b_full')} {us('c_full')} {us('b_ragged')} {us('c_ragged')} "
+                 f"{full:8.3f} {rag:11.3f} {r['c_ragged'] / r['a']:8.3f}   {'; '.join(verdict) if verdict else 'ok'}   (spread {spreads})")
+    emit(f"# {len(narrow) + len(wide)} points in {time.time() - t0:.0f} s; missed a condition: {missed if missed else 'nowhere'}")
+    return 0
 
 
 def measure_step(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
@@ -427,6 +550,10 @@ def main():
                     help="time the wide batch against the loop over lone handles and the narrow batch; without --nsys / --vlens / "
                          "--mvecs: nsys 4,16,64,256 x vlen 4096,16384,32768,65536,262144,1048576 x mvec 10,20")
     ap.add_argument("--slots-gb", type=float, default=64.0, help="--wide: skip a point whose stored vectors exceed this")
+    ap.add_argument("--lengths", action="store_true",
+                    help="time per-system lengths beside a plain batch and the zero-weight recipe; without --nsys / --vlens / --mvecs: "
+                         "nsys 256,4096 x vlen 1024,16384 x mvec 10,20, then the wide batch at (16, 65536) and (64, 262144)")
+    ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
     import torch
     import nka_amd
@@ -448,6 +575,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.lengths:
+        for name, grid_l in (("nsys", "256,4096"), ("vlens", "1024,16384"), ("mvecs", "10,20")):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_l)
+        return lengths_main(args, torch, nka_amd, L, emit)
     if args.wide:
         for name, grid_w in (("nsys", "4,16,64,256"), ("vlens", "4096,16384,32768,65536,262144,1048576"), ("mvecs", "10,20")):
             if getattr(args, name) == ap.get_default(name):
