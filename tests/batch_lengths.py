@@ -23,6 +23,19 @@ def wide_shape(c):
     return 3 * c + 33, (1, 511, c - 1, c, c + 1, 2 * c, 2 * c + 513, 3 * c, 3 * c + 32, 3 * c + 33)
 
 
+def wide_medium_shape(c):
+    """(vlen, lengths): 18 chunks, of which the systems add 1, 2, 9, 9, 10, 16, 17 and 18 partials at a stride of 18 -- the
+    eight-way chain over a system's own partials (k_wide_scalar_len) with no trip, one and two, and a remainder of none, one and
+    seven.  Every twin's vlen but 9 C, 1 and the full row is a shape that tests/test_batch_wide_gpu.py holds to the exact sums."""
+    return 17 * c + 33, (1, c + 1, 8 * c + 1, 9 * c, 9 * c + 1, 15 * c + 513, 16 * c + 1, 17 * c + 33)
+
+
+def wide_long_shape(c):
+    """(vlen, lengths): 257 chunks; a system that ends with the first trip of the staging loop of <d,d> (256 partials), one
+    partial into the second trip, the full row, and one that gives 256 chunks up."""
+    return 256 * c + 513, (256 * c, 256 * c + 1, 256 * c + 513, c)
+
+
 def nan_paint(nsys, vlen, salt):
     """nsys x vlen quiet NaNs, every one with a payload of its own (salt tells F from X)."""
     bits = np.uint64(0x7FF8000000000000) | (np.uint64(salt) << np.uint64(32)) | (np.arange(nsys * vlen, dtype=np.uint64) + np.uint64(1))

@@ -80,11 +80,40 @@ def _workgroup_sum(prod):
     return r
 
 
+def model_partials(x, y, C):
+    """The partial of every chunk as a workgroup forms it -> float64[nchunk]."""
+    prod = x * y
+    return np.array([_workgroup_sum(prod[lo:lo + C]) for lo in range(0, x.size, C)])
+
+
+def model_sum_of(parts, chunks):
+    """The chunk-order chain over the partials `parts`, adding the chunks of the list `chunks` in the order given: range(nchunk)
+    is what the kernels do; a list without c is a sum that lost chunk c's partial, one with c twice a sum that added it twice."""
+    chunks = list(chunks)
+    r = parts[chunks[0]]
+    for c in chunks[1:]:
+        r = r + parts[c]
+    return float(r)
+
+
 def model_sum(x, y, C):
     """The summation order of a wide batch restated on the host: per chunk the workgroup's sum, then the chunks in order."""
-    prod = x * y
-    parts = [_workgroup_sum(prod[lo:lo + C]) for lo in range(0, x.size, C)]
-    r = parts[0]
-    for p in parts[1:]:
-        r = r + p
-    return float(r)
+    parts = model_partials(x, y, C)
+    return model_sum_of(parts, range(parts.size))
+
+
+def chunk_products(x, y, C):
+    """sum of x_i y_i over every chunk, plain numpy -> float64[nchunk]: what a sum loses when it loses that chunk's partial."""
+    return np.add.reduceat(x * y, np.arange(0, x.size, C))
+
+
+def undetectable_chunks(x, y, k, C):
+    """The chunks whose partial a sum held to gamma(k) * sum|xy| could lose or add twice unseen (exact_sums.detectable): a
+    condition on the operands alone.  Operands whose products are all zero have none: every subset of their partials sums to 0.
+    Nor have operands with a NaN or an Inf, whose sum is held to be NaN / Inf exactly and not to a bound."""
+    with np.errstate(all="ignore"):
+        tot = X.abs_dot(x, y)
+    if tot == 0.0 or not np.isfinite(tot):
+        return []
+    bound = X.gamma(k)
+    return [c for c, p in enumerate(chunk_products(x, y, C)) if not X.detectable(p, bound, tot)]

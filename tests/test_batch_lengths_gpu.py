@@ -6,7 +6,8 @@ and held byte for byte after every call.
 
   1 narrow, twins        13 lengths in one batch of 1100; 3 flavours x both explicit sum orders x plain / weighted x ld 1100 / 1101
   2 narrow step          the same through accel_step with X, mask, tol and fnorm; tol is the twin's own fnorm where a system retires
-  3 wide, twins          10 lengths around every chunk edge in one batch of 3 C + 33; and no stale partial after a shrink
+  3 wide, twins          10 lengths around every chunk edge in one batch of 3 C + 33; 8 lengths of 1 ... 18 chunks and 4 of 1 ... 257,
+                         where the loops over a system's own partials take whole trips; and no stale partial after a shrink
   4 set to NULL          set_lengths(None) and a restart: the bits of a batch that never had lengths
   5 the older recipe     lengths against weights 1 / 0 on a finite padding
   6 graph                captured before the first update; new lengths and a masked restart between two replays
@@ -250,6 +251,33 @@ def test_wide_lengths_carry_the_bits_of_a_wide_batch_of_that_length(torch_cuda, 
             r.update([g.standard_normal(L) for g, L in zip(rngs, lens)], ("wide", flavor, mvec, "call", t))
         assert (r.b.num_vec()[1:] == 9).all(), r.b.num_vec()
         r.check_slot_tails(("wide", flavor, mvec))
+
+
+@pytest.mark.parametrize("flavor", [0, 2])
+def test_wide_lengths_where_the_chain_over_the_own_partials_takes_whole_trips(torch_cuda, CH, flavor):
+    """Eight systems in one wide batch of 17 C + 33 (18 chunks) against eight wide batches of one system: the systems add 1, 2,
+    9, 9, 10, 16, 17 and 18 of their partials at a stride of 18, so the eight-way chain of k_wide_scalar_len runs no trip, one
+    and two over nown, with a remainder of none, one and seven.  mvec = 3 over 9 calls: the lists fill, the capacity drop runs.
+    The twins at 9, 10, 16 and 17 chunks are shapes tests/test_batch_wide_gpu.py holds to the exact sums."""
+    c = CH[0]
+    vlen, lens = BL.wide_medium_shape(c)
+    assert [BW.nchunk(L, c) for L in lens] == [1, 2, 9, 9, 10, 16, 17, 18] and BW.nchunk(vlen, c) == 18
+    r = Ragged(torch_cuda, lens, vlen, 3, flavor, wide=True, odd_ld=True)
+    assert r.b.is_wide() and all(t.is_wide() for t in r.twins)
+    assert _run_updates(r, 9, 500 + flavor, ("wide, 18 chunks", flavor)), "the lists never filled"
+
+
+def test_wide_lengths_on_both_sides_of_one_staging_trip(torch_cuda, CH):
+    """Four systems in one wide batch of 256 C + 513 (257 chunks) against four wide batches of one system: a system that ends
+    with the 256 partials one trip of the staging loop of wide_norm_sum holds, one that is one partial into the second trip, the
+    full row, and one of a single chunk that gives 256 chunks up.  Default flavour, mvec = 3, five calls."""
+    c, cap = CH
+    vlen, lens = BL.wide_long_shape(c)
+    assert vlen <= cap and [BW.nchunk(L, c) for L in lens] == [256, 257, 257, 1] and BW.nchunk(vlen, c) == 257
+    r = Ragged(torch_cuda, lens, vlen, 3, 2, wide=True, odd_ld=True)
+    assert r.b.is_wide() and all(t.is_wide() for t in r.twins)
+    _run_updates(r, 5, 600, ("wide, 257 chunks",))
+    assert (r.b.num_vec() >= 1).all(), r.b.num_vec()
 
 
 def test_wide_system_reads_no_partial_of_a_chunk_it_gave_up(torch_cuda, CH):

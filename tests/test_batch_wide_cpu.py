@@ -43,7 +43,12 @@ def test_wide_k_equals_batch_k_up_to_one_chunk_and_follows_the_kernels_beyond():
         assert BW.wide_k(c + 1, c) == 2 * (c // 512) + 9 + 1
         assert BW.wide_k(2 * c + 513, c) == 2 * (c // 512) + 9 + 2
         assert BW.wide_k(1024 * c, c) == 2 * (c // 512) + 9 + 1023
+        # the chunk counts at which the chain of k_wide_scalar and the staging loop of wide_norm_sum change behaviour
+        for n, chunks in ((8 * c + 1, 9), (9 * c, 9), (9 * c + 1, 10), (15 * c + 513, 16), (16 * c + 1, 17), (17 * c + 33, 18),
+                          (256 * c, 256), (256 * c + 1, 257), (256 * c + 513, 257), (512 * c, 512)):
+            assert BW.nchunk(n, c) == chunks and BW.wide_k(n, c) == 2 * (c // 512) + 9 + (chunks - 1), (c, n)
     assert [BW.wide_k(n, 4096) for n in (4096, 4097, 8705, 1 << 20)] == [25, 26, 27, 280]
+    assert [BW.wide_k(n, 2048) for n in (16 * 2048 + 1, 256 * 2048 + 1, 1 << 20)] == [33, 273, 528]
 
 
 def test_wide_sentinels_are_those_of_every_chunk_and_its_two_ends():
@@ -102,6 +107,43 @@ def test_the_host_model_of_the_chunked_sum_is_inside_the_bound_and_every_sentine
                     xp[i] *= factor
                     yp = xp if y is x else y
                     assert abs(BW.model_sum(xp, yp, c) - ex) > bound * tot, (c, n, what, i, factor)
+
+
+@pytest.mark.parametrize("which", ["8C+1", "9C+1", "16C+1", "256C+1", "cap"])
+def test_a_chunk_partial_lost_or_added_twice_breaks_the_bound_at_every_chunk_count_the_gpu_tests_run(which):
+    """9, 10, 17, 257 and 512 chunks of the library's C, the four operand pairs of an update from planted inputs: the host
+    model of the chunked sum (batch_wide.model_partials, model_sum_of) is inside gamma(wide_k(n)) * sum|xy| of the exact sum,
+    and with ANY ONE chunk's partial lost, or added twice, it lies outside -- so the bound of tests/test_batch_wide_gpu.py
+    sees either at these shapes.  The condition the GPU tests put on their own operands (batch_wide.undetectable_chunks) holds
+    for every (pair, chunk) cell.  Two failures by name: the eight-way chain of k_wide_scalar or its remainder dropping the
+    last partial when (nchunk - 1) % 8 == 0, and the staging loop of wide_norm_sum dropping the partials 256 and up."""
+    c, cap = BW.limits()
+    n = {"8C+1": 8 * c + 1, "9C+1": 9 * c + 1, "16C+1": 16 * c + 1, "256C+1": 256 * c + 1, "cap": cap}[which]
+    chunks = BW.nchunk(n, c)
+    assert n <= cap and chunks == {"8C+1": 9, "9C+1": 10, "16C+1": 17, "256C+1": 257, "cap": 512}[which], (c, cap, n, chunks)
+    k = BW.wide_k(n, c)
+    assert k == 2 * (c // 512) + 9 + (chunks - 1)
+    bound = X.gamma(k)
+    whole = list(range(chunks))
+    smallest = math.inf
+    for what, (x, y) in _pairs(n, c, np.random.default_rng([14, c, n])).items():
+        ex, tot = X.exact_dot(x, y), X.abs_dot(x, y)
+        parts = BW.model_partials(x, y, c)
+        assert parts.size == chunks
+        assert BW.model_sum_of(parts, whole) == BW.model_sum(x, y, c)
+        assert abs(BW.model_sum_of(parts, whole) - ex) <= bound * tot, (which, what)
+        assert BW.undetectable_chunks(x, y, k, c) == [], (which, what)
+        smallest = min(smallest, float(np.abs(BW.chunk_products(x, y, c)).min()) / tot)
+        for j in whole:
+            lost, twice = whole[:j] + whole[j + 1:], whole[:j + 1] + whole[j:]
+            assert len(lost) == chunks - 1 and len(twice) == chunks + 1 and twice.count(j) == 2
+            assert abs(BW.model_sum_of(parts, lost) - ex) > bound * tot, (which, what, "lost", j)
+            assert abs(BW.model_sum_of(parts, twice) - ex) > bound * tot, (which, what, "twice", j)
+        if (chunks - 1) % 8 == 0:      # whole trips of eight behind partial 0 and nothing for the remainder loop
+            assert abs(BW.model_sum_of(parts, whole[:-1]) - ex) > bound * tot, (which, what, "the last partial")
+        if chunks > X.BATCH_THREADS:   # one trip of the staging loop fills stage[0 .. 255]
+            assert abs(BW.model_sum_of(parts, whole[:X.BATCH_THREADS]) - ex) > bound * tot, (which, what, "one staging trip")
+    print(f"  {which}: smallest |p_c| / sum|xy| = {smallest:.3g}, threshold {2.0 * bound + X.U:.3g}")
 
 
 def test_wide_layout_arithmetic_against_a_brute_force_model_under_sanitizers():

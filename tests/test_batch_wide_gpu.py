@@ -5,15 +5,23 @@ C, read from the library.
   1 one chunk            a wide batch of at most C elements is the narrow batch in SUMS_BLOCKED_ROUNDED, bit for bit
   2 several chunks       the three layers of tests/test_batch_sums_exact_gpu.py (sums within gamma(wide_k(n)) of the exact sums,
                          the oracle's scalar step on the device's own sums with ==, the elementwise statements bit for bit)
-  3 partition and order  red[0] == ((p0 + p1) + p2), p_c from narrow batches run on the chunks
+                         at 2 and 3 chunks; at 9, 10, 16 and 17, where the eight-way chain over the partials (k_wide_scalar) runs
+                         one trip or two with every kind of remainder; with the longest list, mvec = 32, over 3 and 9 chunks
+  3 partition and order  red[0] == ((p0 + p1) + p2) + ..., p_c from narrow batches run on the chunks: 3, 10, 17 and 257 chunks
   4 independence         the same bits at every position, under every mask of the others, at both parities of ld
   5 sitting out          nothing of a masked system is written, nor the padding between rows
   6 no stale partial     a system that saw NaN / Inf and was restarted equals a twin that never saw them
   7 graph                captured before the first update, replayed through growth, drops and a masked relax
   8 refusals, lifecycle  what a wide batch refuses leaves it usable
-  9 one long shape       vlen = NKA_HIP_BATCH_WIDE_MAX_VLEN once: the last chunk and the largest nchunk
+  9 the long shapes      the three layers of part 2 at 256 and 257 chunks (one and two trips of the staging loop of wide_norm_sum)
+                         and at vlen = NKA_HIP_BATCH_WIDE_MAX_VLEN: the last chunk and the largest nchunk
 
-The worst |red - exact| / (u sum|xy|) of part 2 and the K it was held to go to batch_wide_exact_worst.json."""
+A bound only proves something where the error it looks for exceeds it: every sum over several chunks that WideRun holds is first
+held, from its host operands alone, to the condition that each chunk's partial is detectable (batch_wide.undetectable_chunks);
+tests/test_batch_wide_cpu.py shows on the host model that a partial lost or added twice then breaks the bound.
+
+The worst |red - exact| / (u sum|xy|) of parts 2 and 9 and the K it was held to go to batch_wide_exact_worst.json, overall and
+per chunk count."""
 import ctypes as C
 import itertools
 import json
@@ -32,6 +40,7 @@ from split_update import _bits_equal
 pytestmark = pytest.mark.gpu
 
 WORST = [0.0, 0, ""]               # worst |red - exact| / (u sum|xy|) seen, the K it was held to, where
+WORST_AT = {}                      # K -> [the worst ratio among the sums held to that K, where]
 
 
 def _worst_line():
@@ -51,7 +60,9 @@ def _record_worst():
     if out is not None:
         os.makedirs(out, exist_ok=True)
         with open(os.path.join(out, "batch_wide_exact_worst.json"), "w") as fh:
-            json.dump({"wide": {"worst_err_over_u_sum_abs": ratio, "k": k, "where": where}}, fh, indent=1, sort_keys=True)
+            json.dump({"wide": {"worst_err_over_u_sum_abs": ratio, "k": k, "where": where},
+                       "wide_by_k": {str(kk): {"worst_err_over_u_sum_abs": r, "where": w} for kk, (r, w) in sorted(WORST_AT.items())}},
+                      fh, indent=1, sort_keys=True)
 
 
 @pytest.fixture(scope="module")
@@ -167,14 +178,21 @@ def _hold(what, red, x, y, k, where):
     assert err <= X.gamma(k) * tot, (what, where, red, ex, ratio, k)
     if tot > 0 and ratio >= WORST[0]:
         WORST[:] = [ratio, k, f"{what} {where}"]
+    if tot > 0 and ratio >= WORST_AT.get(k, [0.0])[0]:
+        WORST_AT[k] = [ratio, f"{what} {where}"]
 
 
 class WideRun(T.BatchRun):
-    """BatchRun on a wide batch: the sums are held to wide_k(n); layers 2 and 3 are inherited unchanged."""
+    """BatchRun on a wide batch: the sums are held to wide_k(n); layers 2 and 3 are inherited unchanged.  Every sum that is held
+    is first asked, from its HOST operands alone, whether the bound can see a lost or a doubled partial of each of its chunks
+    (batch_wide.undetectable_chunks): no (entry, chunk) cell may fail that."""
 
     def __init__(self, torch, oracle, flavor, n, mvec, nsys, odd_ld=False):
         super().__init__(torch, oracle, flavor, n, mvec, nsys, odd_ld)
         self.k = BW.wide_k(n)
+        self.chunk = BW.limits()[0]
+        self.held = {}                 # name of the entry -> how often it was held having been formed non-zero
+        self.cells = 0                 # (entry, chunk) cells that passed the condition
 
     def _device(self, odd_ld):
         import nka_amd
@@ -192,7 +210,26 @@ class WideRun(T.BatchRun):
             assert ld % 2 == 0 and not any(align), align
 
     def _sum(self, what, red, x, y, where):
+        if self.n > self.chunk:
+            unseen = BW.undetectable_chunks(x, y, self.k, self.chunk)
+            assert not unseen, (what, where, "the bound could not see these chunks' partials lost: another seed", unseen)
+            self.cells += BW.nchunk(self.n, self.chunk)
         _hold(what, red, x, y, self.k, where)
+        if red != 0.0:
+            self.held[what] = self.held.get(what, 0) + 1
+
+
+def _late_second_system(run, calls, seed):
+    """Two systems on fresh planted inputs, the second one call late (with odd ld: on a row that is not 16-byte aligned)."""
+    rngs, prev = [np.random.default_rng([seed, run.n, k]) for k in range(2)], [None, None]
+    for t in range(calls):
+        inputs = {}
+        for k in range(2):
+            if t >= k:
+                inputs[k] = prev[k] = BW.wide_planted_input(run.n, rngs[k], prev[k])
+        run.update(inputs)
+    assert run.lengths_differed and run.cells > 0
+    return run
 
 
 def _planned_run(run, seed):
@@ -234,6 +271,61 @@ def test_every_part_of_a_wide_update_in_the_other_flavours(torch_cuda, oracle, C
     T._assert_planned_coverage(run)
 
 
+def _ladder_shape(which, c):
+    """n, chunks: the smallest shapes at which the loops over the partials change behaviour -- the eight-way chain of
+    k_wide_scalar behind partial 0 and its remainder loop, the staging loop of wide_norm_sum (256 partials a trip), the cap."""
+    n, chunks = {"8C+1": (8 * c + 1, 9),          # one trip of eight, empty remainder, a last chunk of one element
+                 "9C+1": (9 * c + 1, 10),         # one trip and a remainder of one
+                 "15C+513": (15 * c + 513, 16),   # one trip and the longest remainder, seven
+                 "16C+1": (16 * c + 1, 17),       # two trips, empty remainder
+                 "256C": (256 * c, 256),          # the last single trip of the staging loop
+                 "256C+1": (256 * c + 1, 257)}[which]      # its first second trip, a last chunk of one element
+    assert BW.nchunk(n, c) == chunks and BW.wide_k(n) == 2 * (c // 512) + 9 + (chunks - 1), (which, c, n)
+    return n, chunks
+
+
+@pytest.mark.parametrize("which", ["8C+1", "9C+1", "15C+513", "16C+1"])
+def test_every_part_of_a_wide_update_up_the_ladder_of_chunk_counts(torch_cuda, oracle, CH, which):
+    """9, 10, 16 and 17 chunks: every live entry of red[] within gamma(wide_k(n)) of the exact sum where the eight-way unrolled
+    chain of k_wide_scalar runs one trip or two, with an empty remainder, one of one and one of seven.  At 9 (odd ld) and 17
+    (even ld) chunks the whole plan of six systems in the default flavour; at 10 and 16 two systems, the second one call late on
+    an unaligned row, mvec = 3, five updates, flavours 0 and 1."""
+    n, chunks = _ladder_shape(which, CH[0])
+    if chunks in (9, 17):
+        run = _planned_run(WideRun(torch_cuda, oracle, 2, n, T.SHAPE_MVEC, len(T.PLAN), odd_ld=(chunks == 9)), seed=n)
+        T._assert_planned_coverage(run)
+        assert run.cells > 0
+    else:
+        for flavor in (0, 1):
+            run = _late_second_system(WideRun(torch_cuda, oracle, flavor, n, 3, 2, odd_ld=True), 5, seed=flavor)
+            assert run.widest == 3
+
+
+@pytest.mark.parametrize("which,flavor", [("2C+513", 0), ("8C+1", 2)])
+def test_every_older_count_of_a_wide_system_up_to_the_largest_subspace(torch_cuda, oracle, CH, which, flavor):
+    """The wide sibling of test_batch_sums_exact_gpu.test_every_older_count_up_to_the_largest_subspace: mvec = 32, fresh planted
+    inputs for mvec + 2 updates, system 1 one call late on an unaligned row.  The older count visits 0..32 -- every group count
+    of k_wide_sums, up to eight groups of four --, red[] has 66 entries of which 64 and 65 (<f,w_30>, <f,w_31>) are formed by
+    the second wavefront of k_wide_scalar, and the LDS of both kernels is carved for the largest working copy.  Over three
+    chunks in flavour 0; over nine in flavour 2, where those two threads run the eight-way chain."""
+    c = CH[0]
+    n = 2 * c + 513 if which == "2C+513" else _ladder_shape(which, c)[0]
+    mvec = 32
+    run = _late_second_system(WideRun(torch_cuda, oracle, flavor, n, mvec, 2, odd_ld=True), mvec + 2, seed=mvec)
+    assert run.widest == mvec == 32 and run.nolder_normed == set(range(mvec + 1)), run.nolder_normed
+    assert 2 + mvec + 31 == 65 and run.held.get("<f,w_30>", 0) >= 1 and run.held.get("<f,w_31>", 0) >= 1, run.held
+
+
+def test_a_wide_system_that_keeps_one_vector(torch_cuda, oracle, CH):
+    """mvec = 1 once at C + 1: red[] of four entries, the smallest working copy; ngroup == 0 with a normalised pair at the second
+    update, and from the third on one older vector, which every update drops by capacity."""
+    n = CH[0] + 1
+    run = _late_second_system(WideRun(torch_cuda, oracle, 2, n, 1, 2, odd_ld=True), 6, seed=1)
+    assert run.widest == 1 and run.nolder_normed == {0, 1}, (run.widest, run.nolder_normed)
+    assert run.held["<w1',w_0>"] >= 1 and run.held["<f,w_0>"] >= 1, run.held
+    assert any(gone == [0] for _, _, gone in run.outcomes), run.outcomes
+
+
 # ---- 3. the partition and the chunk order, in bits ----------------------------------------------------------------------------------
 
 def test_red0_is_the_chunk_order_sum_of_the_narrow_batches_on_the_chunks(torch_cuda, CH):
@@ -256,6 +348,40 @@ def test_red0_is_the_chunk_order_sum_of_the_narrow_batches_on_the_chunks(torch_c
          for lo, hi in ((0, c), (c, 2 * c), (2 * c, vlen))]
     want = (p[0] + p[1]) + p[2]
     assert got > 0 and _bits_equal(np.array([got]), np.array([want])), (got, want, p)
+
+
+@pytest.mark.parametrize("which", ["9C+1", "16C+1", "256C+1"])
+def test_red0_is_the_chunk_order_sum_of_one_narrow_batch_of_the_chunks(torch_cuda, CH, which):
+    """The same at 10, 17 and 257 chunks, where the bound cannot tell the chunk order from a pairwise sum of the partials:
+    red[0] of the second update of a fresh wide system is ((p0 + p1) + p2) + ..., bit for bit.  p_c is red[0] of system c of ONE
+    narrow batch (SUMS_BLOCKED_ROUNDED) of nchunk systems whose row c is chunk c; the last chunk, of one element, through
+    set_lengths with NaN behind it.  (That a narrow system's bits depend neither on its position nor on nsys, and that a length
+    gives the bits of a batch of that length, is held in tests/test_batch_gpu.py and tests/test_batch_lengths_gpu.py.)"""
+    import nka_amd
+    torch = torch_cuda
+    c = CH[0]
+    vlen, chunks = _ladder_shape(which, c)
+    rng = np.random.default_rng([31, vlen])
+    x0 = BW.wide_planted_input(vlen, rng)
+    x1 = BW.wide_planted_input(vlen, rng, prev=x0)
+    last = vlen - (chunks - 1) * c
+    wide = nka_amd.nka_batch().init(1, vlen, 3, wide=True)
+    narrow = nka_amd.nka_batch().init(chunks, c, 3).set_sum_order(nka_amd.SUMS_BLOCKED_ROUNDED)
+    narrow.set_lengths(np.array([c] * (chunks - 1) + [last], np.int64))
+    for x in (x0, x1):          # second update of a fresh system: a pending pair, no older vector
+        wide.accel_update(torch.from_numpy(x.copy()).cuda().view(1, vlen))
+        rows = np.full(chunks * c, np.nan)
+        rows[:vlen] = x
+        narrow.accel_update(torch.from_numpy(rows).cuda().view(chunks, c))
+    got = np.float64(wide.reductions(0)[0])
+    p = [np.float64(narrow.reductions(k)[0]) for k in range(chunks)]
+    want = p[0]
+    for q in p[1:]:
+        want = want + q
+    assert got > 0 and all(q > 0 for q in p), (got, p)
+    assert _bits_equal(np.array([got]), np.array([want])), (which, got, want)
+    pairwise = np.float64(np.sum(np.array(p)))      # (numpy's pairwise sum: what the comparison would accept if the order were free)
+    print(f"  {which}: red[0] = {got!r}; the pairwise sum of the partials differs: {bool(pairwise != want)}")
 
 
 # ---- 4. independence ---------------------------------------------------------------------------------------------------------------------
@@ -487,23 +613,27 @@ def test_what_a_wide_batch_refuses_leaves_it_usable(torch_cuda, CH):
 
 # ---- 9. one long shape ------------------------------------------------------------------------------------------------------------------------------
 
-class LongRun(WideRun):
-    """Layer 3 only (and the scalar step, which costs nothing): the sums are asked to be finite."""
-
-    def _sum(self, what, red, x, y, where):
-        assert math.isfinite(red), (what, where, red)
+@pytest.mark.parametrize("which", ["256C", "256C+1"])
+def test_every_part_of_a_wide_update_on_both_sides_of_one_staging_trip(torch_cuda, oracle, CH, which):
+    """256 chunks, the last length at which the 256 threads of wide_norm_sum stage the partials of <d,d> in one trip, and 257,
+    the first at which a thread stages a second one (a last chunk of one element): the sum that becomes s, formed by every
+    workgroup of k_wide_sums and by k_wide_scalar, and every other live entry within gamma(wide_k(n)) of the exact sums.  Two
+    systems, the second one call late on an unaligned row where the length is odd, mvec = 3, four updates."""
+    n, chunks = _ladder_shape(which, CH[0])
+    assert n <= CH[1] and (chunks > X.BATCH_THREADS) == (which == "256C+1")
+    run = _late_second_system(WideRun(torch_cuda, oracle, 2, n, 3, 2, odd_ld=bool(n % 2)), 4, seed=9)
+    assert run.widest == 2 and run.held["<d,d>"] == 5
 
 
 def test_the_longest_system_once(torch_cuda, oracle, CH):
     """vlen = NKA_HIP_BATCH_WIDE_MAX_VLEN, two systems (the second on a row that starts one call late), mvec = 3, four updates:
-    the last chunk and the largest nchunk; the elementwise statements bit for bit from the device's s and c, red[] finite."""
+    the last chunk and the largest nchunk; every live entry of red[] within gamma(wide_k(cap)) of the exact sum (K = 528 with
+    the chunk of 2048), the elementwise statements bit for bit from the device's s and c."""
     c, cap = CH
-    run = LongRun(torch_cuda, oracle, 2, cap, 3, 2, odd_ld=False)
-    assert BW.nchunk(cap, c) == cap // c <= 1024
-    rngs = [np.random.default_rng([cap, k]) for k in range(2)]
-    for t in range(4):
-        run.update({k: rngs[k].standard_normal(cap) for k in range(2) if t >= k})
-    assert run.widest == 2 and run.lengths_differed
+    run = WideRun(torch_cuda, oracle, 2, cap, 3, 2, odd_ld=False)
+    assert BW.nchunk(cap, c) == cap // c <= 1024 and run.k == 2 * (c // 512) + 9 + (cap // c - 1)
+    _late_second_system(run, 4, seed=9)
+    assert run.widest == 2 and run.lengths_differed and run.held["<d,d>"] == 5
     assert all(np.isfinite(run.b.reductions(k)).all() for k in range(2))
 
 
