@@ -40,7 +40,9 @@
  *            lone handles at every grid point from 16 systems on.  At the cap, mvec = 20: 1.52 x with 16 systems, 17 x with
  *            256, 23 x with 4096 (0.55 of 8 TB/s); at vlen = 1024, mvec = 10: 9.2 x / 151 x / 444 x.  Beyond it a 16-system
  *            batch -- 16 of 256 compute units -- loses (0.99 x at 32 768, mvec = 20): longer systems are for WIDE below, or lone handles.  A
- *            batch of ONE is slower than a lone handle at most shapes (0.10 ... 1.76 x, recorded without a bar).
+ *            batch of ONE is slower than a lone handle at most shapes (0.10 ... 1.76 x, recorded without a bar).  Every offset
+ *            into w, v, f, x and the weight rows is formed in 64 bits, in both kinds of batch and with lengths: systems beyond
+ *            4 GiB and beyond 2^31 elements are held to a small twin batch with == (tests/test_batch_large_gpu.py).
  *   WEIGHTS  nka_hip_batch_set_dot_weights: the dp  <x,y>_w = sum_i w_i x_i y_i  per system, on the device, inside the same
  *            one launch (unknowns of different scale, masks on ghost or fixed entries, ragged batches).  a_w = fl(w_i * a_i)
  *            is the FIRST operand of every product; with d = fl(w1 - f) and w1' the flavour's rounding as above:
