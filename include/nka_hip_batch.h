@@ -152,6 +152,44 @@
  *            batch's vlen, never from a system's length (the host needs no length to pick a kernel, which is what keeps a
  *            replay valid); everything a wide batch refuses stays refused; a batch without lengths computes and launches
  *            exactly what it did.  A length of 0 is refused: a system that should sit out is what `active` is for.
+ *   STORAGE  nka_hip_batch_create_stored(..., NKA_HIP_BATCH_STORE_F32): OPT-IN binary32 storage of the NORMALISED subspace vectors.
+ *            Everything a batch stores except the pending pair is a normalised vector -- w' has norm 1, v' is scaled by the
+ *            same 1/s -- used only as an operand of sums and of the combine; the stored vectors are nearly all of an update's
+ *            memory traffic and the memory limit on nsys.  With q(x) = conversion to binary32, round to nearest even, widened
+ *            back exactly, EVERY PRODUCT AND ACCUMULATION STAYS binary64, and:
+ *              1  it runs the default flavour (NKA_HIP_FLAVOR_C: compact storage) and NKA_HIP_SUMS_BLOCKED_ROUNDED only;
+ *                 NKA_HIP_SUMS_AUTO resolves to _BLOCKED_ROUNDED at EVERY vlen, vlen <= 64 included.  REFUSED with NKA_HIP_EINVAL:
+ *                 the two F08 flavours and NKA_HIP_SUMS_REFERENCE_ORDER (their point is the reference's bits, which this storage
+ *                 gives up), and a WIDE batch with this storage (the follow-up: nka_hip_batch_create_wide stays binary64).
+ *              2  THE PENDING PAIR STAYS binary64: the raw pair (w_new = f_in, v_new = f_out) lives in two buffers of the batch,
+ *                 one row per system at the slot stride, not in the ring slot.  d = fl(w1 - f), red[0] and s = sqrt(red[0]) are
+ *                 therefore exactly those of binary64 storage.
+ *              3  w1' = q(fl(d/s)).  This rounded value is the operand of every sum of phase 3 (fl(w w1') the first operand under
+ *                 weights, as in WEIGHTS), the value stored in the ring slot, and the value the compact difference is formed from.
+ *              4  the ring slot's v holds q(fl(fl(v1/s) - w1')), w1' the rounded value of 3, and the combine applies exactly that
+ *                 stored value for pair 0 and every older pair: x = fl(x + fl(c v_p)) in list order, in binary64.  WHAT IS STORED
+ *                 IS WHAT WAS USED: Gram rows, right-hand sides and the combine see one and the same set of vectors.
+ *              5  binary32 SUBNORMAL results are kept (the kernels run with f32 denormals enabled; the stored bits are numpy's
+ *                 astype(float32), tests/test_batch_store32_gpu.py).  |w1'| <= 1 cannot overflow.  A component of
+ *                 fl(v1/s) - w1' beyond the binary32 range is stored as +-Inf, and the system then carries non-finite values
+ *                 inside its own rows, like a system that was fed them; no other system is affected.  Systems whose unknowns
+ *                 differ by more than about 1e38 in scale between a moving and a frozen entry are for binary64 storage.
+ *              6  every other guarantee above holds unchanged: MASKS, ASYNC, GRAPHS from the first update, BITS, WEIGHTS, STEP and
+ *                 LENGTHS (nothing at or beyond len[sys] of the binary32 slots or the pending buffers is read or written),
+ *                 restart / relax / set_vec_tol and the span checks.
+ *              7  nka_hip_batch_get_w / _get_v return binary64 arrays: for the slot of the pending pair the pending buffers'
+ *                 rows, for any other slot the widened stored values; a never-written slot reads zeros.  state_digest,
+ *                 get_state, num_vec and get_reductions keep their meaning.
+ *            MEMORY: the stored vectors take 2 nsys stride (4 (mvec + 1) + 8) bytes instead of 2 nsys stride 8 (mvec + 1)
+ *            (stride: vlen rounded up to 32; nka_hip_batch_vector_bytes), 0.55 of binary64 storage at mvec = 20 and 0.59 at 10.
+ *            A batch created with nka_hip_batch_create, or with NKA_HIP_BATCH_STORE_F64, computes and launches exactly what it did.
+ *            COST, MEASURED (profiles/r13/batch_store32_throughput.txt, 1 x MI355X; a binary64 batch, a second one as a control and
+ *            the binary32 batch alternated on the same inputs; nsys 256 / 4096 x vlen 1024 / 16 384 x mvec 10 / 20): at
+ *            4096 x 16 384, where an update is bound by the bytes it moves, 0.760 (mvec 10) and 0.714 (mvec 20) of the time of
+ *            the binary64 update -- the byte model (per element: norm pass 16 B; each sweep of four 48 -> 32 B; combine
+ *            8 (7 + k) -> 56 + 4 (k - 1) B) predicts 0.69 and 0.65 --, the two binary64 batches differing by 2.1 % and 0.8 %;
+ *            0.82 / 0.87 at 4096 x 1024, 0.89 / 0.90 at 256 x 16 384, 0.98 / 1.02 at 256 x 1024.  At 4096 x 64 x 10 it takes
+ *            1.22 x: binary64 storage runs such systems in reference order under NKA_HIP_SUMS_AUTO, this storage the fast sums.
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -181,7 +219,18 @@ int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32
  * 1 <= vlen <= NKA_HIP_BATCH_WIDE_MAX_VLEN, nsys <= 65535, mvec and vtol as above.  Allocates the partial sums beside the slots. */
 int nka_hip_batch_create_wide(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
                               int32_t flavor, int32_t device, void *stream);
-int nka_hip_batch_is_wide(nka_hip_batch_t b);                      /* 1 = wide, 0 = one workgroup per system; < 0 on error */
+/* STORAGE above: how the normalised subspace vectors are kept.  _create_stored with NKA_HIP_BATCH_STORE_F64 is
+ * nka_hip_batch_create; with NKA_HIP_BATCH_STORE_F32 it allocates 2*nsys*(mvec+1) slot vectors of binary32 elements at the same
+ * stride in elements and two pending buffers of nsys*stride doubles (zero-initialised, freed by destroy only, never moved), and
+ * refuses every flavour but NKA_HIP_FLAVOR_C (NKA_HIP_EINVAL, nothing left allocated).  Any other storage: NKA_HIP_EINVAL.
+ * _storage: the value the batch was created with; < 0 on error.  _vector_bytes: the bytes of device memory the batch allocated
+ * for its stored vectors (slots and pending buffers); < 0 on error. */
+enum { NKA_HIP_BATCH_STORE_F64 = 0, NKA_HIP_BATCH_STORE_F32 = 1 };
+int nka_hip_batch_create_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                                int32_t flavor, int32_t device, void *stream, int32_t storage);
+int nka_hip_batch_storage(nka_hip_batch_t b);
+int64_t nka_hip_batch_vector_bytes(nka_hip_batch_t b);
+int nka_hip_batch_is_wide(nka_hip_batch_t b);                    /* 1 = wide, 0 = one workgroup per system; < 0 on error */
 int nka_hip_batch_wide_limits(int64_t *chunk, int64_t *max_vlen);  /* the two constants, as the library was built */
 int nka_hip_batch_destroy(nka_hip_batch_t b);
 

@@ -13,4 +13,4 @@ There is NO CPU fallback: without the HIP library every entry point raises.
 from ._lib import build, lib_path, load  # noqa: F401
 from .nka import (FLAVOR_C, FLAVOR_DEFAULT, FLAVOR_F08, FLAVOR_F08_VECTOR, SUMS_AUTO, SUMS_BLOCKED, SUMS_BLOCKED_ROUNDED,  # noqa: F401
                   SUMS_REFERENCE_ORDER, NKAError, nka)
-from .batch import BATCH_MAX_MVEC, BATCH_MAX_VLEN, batch_wide_limits, nka_batch  # noqa: F401
+from .batch import BATCH_MAX_MVEC, BATCH_MAX_VLEN, STORE_F32, STORE_F64, batch_wide_limits, nka_batch  # noqa: F401

@@ -13,6 +13,7 @@ from . import _lib
 from .nka import FLAVOR_DEFAULT, NKAError, State, _check
 
 BATCH_MAX_VLEN, BATCH_MAX_MVEC = 16384, 32      # NKA_HIP_BATCH_MAX_VLEN / _MVEC (include/nka_hip_batch.h)
+STORE_F64, STORE_F32 = 0, 1                     # NKA_HIP_BATCH_STORE_F64 / _F32 (include/nka_hip_batch.h, STORAGE)
 
 
 def batch_wide_limits():
@@ -32,12 +33,15 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         self._L = _lib.load()          # raises if the HIP library is missing: no CPU path
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
-             stream: int | None = None, wide: bool = False):
+             stream: int | None = None, wide: bool = False, storage: int = STORE_F64):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
         restart / relax, graphs and per-system lengths -- set_lengths -- are offered; accel_step, weights and the reference
-        sum order are refused)."""
+        sum order are refused).  storage=STORE_F32 (nka_hip_batch_create_stored; include/nka_hip_batch.h, STORAGE): the
+        normalised subspace vectors are kept in binary32 -- 0.55 of the slot memory at mvec = 20 --, every product and sum
+        still binary64, the pending pair still binary64.  Such a batch runs the default flavour (FLAVOR_C) and the rounded fast
+        sums only: the F08 flavours, set_sum_order(SUMS_REFERENCE_ORDER) and wide=True are refused (NKAError)."""
         import torch
 
         self.delete()
@@ -49,9 +53,15 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         if stream is None:
             stream = torch.cuda.current_stream(device).cuda_stream
         h = C.c_void_p()
-        create = self._L.nka_hip_batch_create_wide if wide else self._L.nka_hip_batch_create
-        _check(create(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device), C.c_void_p(stream)),
-               "nka_hip_batch_create_wide" if wide else "nka_hip_batch_create", self._L)
+        if int(storage) != STORE_F64:
+            if wide:
+                raise NKAError("nka_batch init: binary32 storage is not offered by a wide batch (storage=STORE_F64)")
+            _check(self._L.nka_hip_batch_create_stored(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                       C.c_void_p(stream), int(storage)), "nka_hip_batch_create_stored", self._L)
+        else:
+            create = self._L.nka_hip_batch_create_wide if wide else self._L.nka_hip_batch_create
+            _check(create(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device), C.c_void_p(stream)),
+                   "nka_hip_batch_create_wide" if wide else "nka_hip_batch_create", self._L)
         self._h, self._device, self._nsys, self._vlen, self._mvec = h, device, int(nsys), int(vlen), int(mvec)
         self._stream, self._follow_torch_stream = int(stream), explicit_stream is None
         return self
@@ -167,7 +177,8 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def set_sum_order(self, order: int):
         """SUMS_AUTO (reference order up to 64 elements, else SUMS_BLOCKED_ROUNDED), SUMS_REFERENCE_ORDER or
-        SUMS_BLOCKED_ROUNDED; SUMS_BLOCKED is refused.  Returns self."""
+        SUMS_BLOCKED_ROUNDED; SUMS_BLOCKED is refused.  A batch with binary32 storage refuses SUMS_REFERENCE_ORDER, and its
+        SUMS_AUTO is SUMS_BLOCKED_ROUNDED at every length.  Returns self."""
         _check(self._L.nka_hip_batch_set_sum_order(self._handle(), int(order)), "batch_set_sum_order", self._L)
         return self
 
@@ -275,6 +286,19 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def flavor(self) -> int:
         return self._L.nka_hip_batch_flavor(self._handle())
+
+    def storage(self) -> int:
+        """STORE_F64 or STORE_F32: how the batch keeps its normalised subspace vectors (nka_hip_batch_storage)."""
+        r = self._L.nka_hip_batch_storage(self._handle())
+        _check(min(r, 0), "batch_storage", self._L)
+        return r
+
+    def vector_bytes(self) -> int:
+        """Bytes of device memory the batch allocated for its stored vectors: slots and, with binary32 storage, the two
+        pending buffers (nka_hip_batch_vector_bytes)."""
+        r = int(self._L.nka_hip_batch_vector_bytes(self._handle()))
+        _check(min(r, 0), "batch_vector_bytes", self._L)
+        return r
 
     def is_wide(self) -> bool:
         """True for a batch created with wide=True (nka_hip_batch_is_wide)."""

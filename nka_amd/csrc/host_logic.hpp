@@ -202,6 +202,28 @@ NKA_HOST_DEVICE constexpr BatchLayout batch_layout(int64_t vlen, int mvec) {
   const int64_t stride = ((vlen < 1 ? 1 : vlen) + 31) / 32 * 32;
   return BatchLayout{stride, stride * (mvec + 1), (batch_ic_count(mvec) + 31) / 32 * 32, (batch_dc_count(mvec) + 31) / 32 * 32};
 }
+// BINARY32 STORAGE (nka_hip_batch_create_stored, NKA_HIP_BATCH_STORE_F32): the w and the v allocation hold binary32 elements at
+// the SAME strides in elements -- a row then starts on a multiple of 32 floats, 128 bytes, and a pair (2t, 2t + 1) on a multiple
+// of 8 bytes --, and the raw pending pair lives in two allocations of one binary64 row per system at the slot stride.  Offsets
+// are in ELEMENTS of the allocation they index and formed in 64 bits.  tests/c/batch_store32_check.cpp holds all of it against a
+// brute-force layout, the largest legal arguments included.
+constexpr int kBatchStoreF64 = 0, kBatchStoreF32 = 1;      // = NKA_HIP_BATCH_STORE_F64 / _F32
+NKA_HOST_DEVICE constexpr int64_t batch_slot_elem_bytes(int storage) { return storage == kBatchStoreF32 ? 4 : 8; }
+NKA_HOST_DEVICE constexpr int64_t batch_slot_offset(const BatchLayout &l, int64_t sys, int slot /* 1-based */) {
+  return sys * l.sys_stride + (int64_t)(slot - 1) * l.stride;
+}
+NKA_HOST_DEVICE constexpr int64_t batch_pending_offset(const BatchLayout &l, int64_t sys) { return sys * l.stride; }
+// bytes of EACH of the two slot allocations (w, v) and of EACH of the two pending buffers (none with binary64 storage)
+NKA_HOST_DEVICE constexpr int64_t batch_slot_alloc_bytes(const BatchLayout &l, int64_t nsys, int storage) {
+  return batch_slot_elem_bytes(storage) * l.sys_stride * nsys;
+}
+NKA_HOST_DEVICE constexpr int64_t batch_pending_alloc_bytes(const BatchLayout &l, int64_t nsys, int storage) {
+  return storage == kBatchStoreF32 ? 8 * l.stride * nsys : 0;
+}
+// all stored vectors of a batch: 2 nsys stride 8 (mvec + 1) bytes in binary64, 2 nsys stride (4 (mvec + 1) + 8) in binary32
+NKA_HOST_DEVICE constexpr int64_t batch_vector_bytes(const BatchLayout &l, int64_t nsys, int storage) {
+  return 2 * (batch_slot_alloc_bytes(l, nsys, storage) + batch_pending_alloc_bytes(l, nsys, storage));
+}
 // LDS of one workgroup: doubles first (offsets in doubles), then int32 (offsets in int32 from the end of the doubles)
 struct BatchLds {
   int h, c, red, cc, sm, res, ndouble;      // h [(m1+1)^2], c [m1+1], red [2+2 mvec], cc [m1], sm [waves][kBatchAcc], res [kBatchAcc+1]

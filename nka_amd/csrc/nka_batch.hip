@@ -55,6 +55,19 @@ struct LenArgs {
 __device__ __forceinline__ const StepArgs &step_args(const StepArgs &st, const LenArgs &) { return st; }
 __device__ __forceinline__ const int32_t *len_args(const LenArgs &l) { return l.len; }
 __device__ __forceinline__ const int32_t *len_args(const StepArgs &, const LenArgs &l) { return l.len; }
+// BINARY32 STORAGE (nka_hip_batch_create_stored): the two pending buffers, nsys binary64 rows at the slot stride.  It is the LAST
+// member of the trailing pack, behind the StepArgs and the LenArgs if there are any, so an instance without it keeps its arguments.
+struct Store32Args {
+  double *pw, *pv;
+};
+__device__ __forceinline__ const StepArgs &step_args(const StepArgs &st, const Store32Args &) { return st; }
+__device__ __forceinline__ const StepArgs &step_args(const StepArgs &st, const LenArgs &, const Store32Args &) { return st; }
+__device__ __forceinline__ const int32_t *len_args(const LenArgs &l, const Store32Args &) { return l.len; }
+__device__ __forceinline__ const int32_t *len_args(const StepArgs &, const LenArgs &l, const Store32Args &) { return l.len; }
+__device__ __forceinline__ const Store32Args &store32_args(const Store32Args &s) { return s; }
+template <class A> __device__ __forceinline__ const Store32Args &store32_args(const A &, const Store32Args &s) { return s; }
+template <class A, class B>
+__device__ __forceinline__ const Store32Args &store32_args(const A &, const B &, const Store32Args &s) { return s; }
 
 // (where the pieces of a system lie, and the LDS of a workgroup -- 5.3 KB at mvec = 20, 11.2 KB at 32: host_logic.hpp)
 static_assert(nka_host::batch_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 40 * 1024, "four workgroups of a batch must fit the LDS of a CU");
@@ -69,6 +82,12 @@ static_assert(nka_host::batch_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 40 * 1024, 
 // sweeps, the step's dp(f, f) and x -= f_out, the weight loads.  Nothing at an index >= len[sys] of f, x, the weight row or a slot
 // is read or written; the element -> thread map and the per-thread order do not depend on n, so the system carries the bits of
 // a batch created with vlen = len[sys].  Without it the instance is the one it was, instruction for instruction.
+// A trailing Store32Args makes the instance one of BINARY32 STORAGE (COMB = 2 and the fast sums only): a.w / a.v are float
+// allocations of the same strides in elements, an older pair is one 8-byte load widened exactly, the raw pending pair is read
+// from and written to the binary64 rows pw / pv, and the normalised pair is narrowed once -- w1' = q(fl(d/s)) in phases 3 and 6
+// alike, v = q(fl(fl(v1/s) - w1')) -- before it is used or stored, so the sums, the combine and the slot hold the same values.
+// Element -> thread map, per-thread order, sweeps, block sums and the scalar step are those of every other instance.  Without
+// it every such statement is discarded at compile time and the instance is the one it was, instruction for instruction.
 template <int COMB, bool ORDERED, bool WGT, class... Step>
 __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, double *__restrict__ f_all, int64_t ld,
                                                                 const int32_t *__restrict__ active,
@@ -76,7 +95,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
 #pragma clang fp contract(off)      // elementwise statements and the reference-order sums round like the reference; fma is explicit
   constexpr bool STEP = (std::is_same<Step, StepArgs>::value || ...);
   constexpr bool LEN = (std::is_same<Step, LenArgs>::value || ...);
-  static_assert(sizeof...(Step) == (STEP ? 1 : 0) + (LEN ? 1 : 0), "at most one StepArgs, then at most one LenArgs");
+  constexpr bool S32 = (std::is_same<Step, Store32Args>::value || ...);
+  static_assert(sizeof...(Step) == (STEP ? 1 : 0) + (LEN ? 1 : 0) + (S32 ? 1 : 0), "at most one StepArgs, then at most one LenArgs, then at most one Store32Args");
+  static_assert(!S32 || (COMB == 2 && !ORDERED), "binary32 storage: the default flavour and the fast sums only");
   constexpr int NNRM = STEP ? 2 : 1;             // sums of phase 2: [<f,f>,] <d,d>, landing in res[kBatchAcc + 1 - NNRM ...]
   constexpr bool RCP = (COMB == 1);
   constexpr bool COMPACT = (COMB == 2);
@@ -95,6 +116,14 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
   const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;      // (stored vectors: always 16-byte aligned)
   const double *wg = nullptr;                                        // this system's weights (rows: 16-byte aligned)
   if constexpr (WGT) wg = wgt_all + (size_t)sys * wgt_stride;
+  [[maybe_unused]] float *W32 = nullptr, *V32 = nullptr;      // binary32 storage: this system's slots ...
+  [[maybe_unused]] double *pw = nullptr, *pv = nullptr;       // ... and its rows of the pending buffers (16-byte aligned)
+  if constexpr (S32) {
+    W32 = reinterpret_cast<float *>(a.w) + (size_t)sys * a.sys_stride;
+    V32 = reinterpret_cast<float *>(a.v) + (size_t)sys * a.sys_stride;
+    pw = store32_args(step...).pw + (size_t)sys * a.stride;
+    pv = store32_args(step...).pv + (size_t)sys * a.stride;
+  }
 
   const nka_host::BatchLds lds = nka_host::batch_lds(mvec);
   double *const shd = reinterpret_cast<double *>(smem);
@@ -136,8 +165,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
   }
   __syncthreads();
   const int pending = hdr[HDR_PENDING], nolder = hdr[HDR_NOLDER];
-  const double *const w1 = pending ? W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride : f;
-  const double *const w1s = pending ? w1 : W;      // always a stored (16-byte aligned) vector: for loads whose value may go unused
+  const double *const w1 = pending ? (S32 ? pw : W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride) : f;      // (binary32 storage: the pending row)
+  const double *const w1s = S32 ? pw : pending ? w1 : W;      // always a stored (16-byte aligned) vector: for loads whose value may go unused
 
   // ---- phase 2: the norm (F08:266-267) ----
   double s = 0.0;
@@ -241,10 +270,12 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
     const int ngroup = (nolder + kBatchGroup - 1) / kBatchGroup;
     for (int g = 0; g < (ngroup > 0 ? ngroup : (normed ? 1 : 0)); g++) {
       const double *wk[kBatchGroup];
+      [[maybe_unused]] const float *wk32[kBatchGroup];
 #pragma unroll
       for (int j = 0; j < kBatchGroup; j++) {
         const int p = g * kBatchGroup + j;
-        wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1s;   // (beyond the list: a re-read, discarded)
+        if constexpr (S32) wk32[j] = W32 + (nolder > 0 ? (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : (size_t)0);
+        else wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1s;   // (beyond the list: a re-read, discarded)
       }
       double acc[kBatchAcc];
 #pragma unroll
@@ -255,7 +286,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
         const d2 dv = ld_tile<FULL, true>(w1s, i, n);     // (no pending pair: a stored vector whose value is not used)
         d2 wv[kBatchGroup];
 #pragma unroll
-        for (int j = 0; j < kBatchGroup; j++) wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+        for (int j = 0; j < kBatchGroup; j++) {
+          if constexpr (S32) wv[j] = ld_tile32<FULL>(wk32[j], i, n); else wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+        }
         d2 gv;
         if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);
 #pragma unroll
@@ -265,8 +298,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
             double fa = fq;                                  // first operand of the products on f: fl(w f), formed once
             if constexpr (WGT) fa = gv[q] * fq;
             if (normed) {
-              const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
-              double wa = wn;                                // first operand of the Gram row: fl(w w1')
+              double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
+              if constexpr (S32) wn = batch_q32(wn);         // (binary32 storage: the value the slot will hold)
+              double wa = wn;                               // first operand of the Gram row: fl(w w1')
               if constexpr (WGT) wa = gv[q] * wn;
               if (g == 0) acc[2 * kBatchGroup] = fma(fa, wn, acc[2 * kBatchGroup]);
 #pragma unroll
@@ -343,7 +377,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
   // ---- phase 6: normalise the pending pair, combine, ring stores (F08:282-283, 361, 395-404) ----
   const int ncomb = hdr[HDR_NCOMB];
   const bool norm0 = hdr[HDR_NORMED] != 0;      // pair 0 of the plan is the pending pair, still raw
-  double *const wnew = W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
+  double *const wnew = S32 ? pw : W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = S32 ? pv : V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
   batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
     constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
     if (!FULL && i >= n) return;
@@ -355,7 +389,24 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
     if constexpr (STEP && !ORDERED)
       if (xrow != nullptr) xit = xvec ? ld_tile<FULL, true>(xrow, i, n) : ld_tile<FULL, false>(xrow, i, n);
     int j0 = 0;
-    if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
+    if constexpr (S32) {
+      if (norm0) {      // pair 0 of the plan: raw in the pending rows; narrowed once, applied and stored as narrowed
+        const size_t off = (size_t)(cs[0] - 1) * a.stride;
+        d2 wv = ld_tile<FULL, true>(pw, i, n), vv = ld_tile<FULL, true>(pv, i, n);
+        const double c = cc[0];
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+          const double wn = batch_q32(batch_nrm<RCP>(wv[q] - fin[q], s, rs));
+          const double vn = batch_nrm<RCP>(vv[q], s, rs);
+          wv[q] = wn;
+          vv[q] = batch_q32(vn - wn);
+          x[q] = x[q] + c * vv[q];
+        }
+        st_tile32<FULL>(W32 + off, i, n, wv);
+        st_tile32<FULL>(V32 + off, i, n, vv);
+        j0 = 1;
+      }
+    } else if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
       double *const wk = W + (size_t)(cs[0] - 1) * a.stride, *const vk = V + (size_t)(cs[0] - 1) * a.stride;
       d2 wv = ld_tile<FULL, true>(wk, i, n), vv = ld_tile<FULL, true>(vk, i, n);
       const double c = cc[0];
@@ -380,7 +431,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_update(BatchArgs a, dou
         const int jj = j + u < ncomb ? j + u : ncomb - 1;
         const size_t off = (size_t)(cs[jj] - 1) * a.stride;
         c[u] = cc[jj];
-        vv[u] = ld_tile<FULL, true>(V + off, i, n);
+        if constexpr (S32) vv[u] = ld_tile32<FULL>(V32 + off, i, n); else vv[u] = ld_tile<FULL, true>(V + off, i, n);
         if (!COMPACT) wv[u] = ld_tile<FULL, true>(W + off, i, n); else wv[u] = vv[u];
       }
 #pragma unroll
@@ -453,6 +504,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_batch_copy_weights(double *__
 namespace {
 
 bool batch_ordered(const nka_hip_batch_state *b) {
+  if (b->storage == NKA_HIP_BATCH_STORE_F32) return false;      // (AUTO: the rounded fast sums at every vlen)
   return b->sum_order == NKA_HIP_SUMS_REFERENCE_ORDER || (b->sum_order == NKA_HIP_SUMS_AUTO && b->k.n <= kOrdAutoMax);
 }
 
@@ -517,8 +569,20 @@ void launch_flavor_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *a
 }
 // (per-system lengths travel like the weights: the instance and the buffer's address are fixed when the update is enqueued or
 // captured, the buffer's VALUES are read when it runs)
+// binary32 storage: the default flavour and the fast sums only (refused otherwise at creation and in set_sum_order) -- eight
+// instances, x weights x step x lengths; the pending buffers' addresses travel in the launch like the weights'
+template <class... Step>
+void launch_store32(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+  if (b->weighted) launch_update_as<2, false, true>(b, f, ld, active, step...);
+  else launch_update_as<2, false, false>(b, f, ld, active, step...);
+}
 template <class... Step>
 void launch_flavor(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+  if (b->storage == NKA_HIP_BATCH_STORE_F32) {
+    const Store32Args s32{b->pend_w, b->pend_v};
+    if (b->has_len) launch_store32(b, f, ld, active, step..., LenArgs{b->len}, s32); else launch_store32(b, f, ld, active, step..., s32);
+    return;
+  }
   if (b->has_len) launch_flavor_as(b, f, ld, active, step..., LenArgs{b->len}); else launch_flavor_as(b, f, ld, active, step...);
 }
 // what accel_update and accel_step check of f
@@ -578,11 +642,15 @@ extern "C" {
 
 // both kinds of batch: `wide` = a system split across workgroups (nka_batch_wide.hip)
 static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor, int32_t device,
-                        void *stream, bool wide) {
-  const std::string who = wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
+                        void *stream, bool wide, int32_t storage = NKA_HIP_BATCH_STORE_F64, const char *entry = nullptr) {
+  const std::string who = entry ? entry : wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
+  const bool s32 = storage == NKA_HIP_BATCH_STORE_F32;
   if (!out) return fail(NKA_HIP_EINVAL, who + ": out is NULL");
   *out = nullptr;
   if (nsys < 1) return fail(NKA_HIP_EINVAL, who + ": nsys must be >= 1");
+  if (storage != NKA_HIP_BATCH_STORE_F64 && !s32) return fail(NKA_HIP_EINVAL, who + ": unknown storage (NKA_HIP_BATCH_STORE_F64 or _F32)");
+  if (wide && s32)
+    return fail(NKA_HIP_EINVAL, who + ": binary32 storage is not offered by a wide batch yet (the follow-up): NKA_HIP_BATCH_STORE_F64");
   if (wide) {
     int64_t chunk = 0, cap = 0;
     nka_hip_batch_wide_limits(&chunk, &cap);
@@ -596,6 +664,9 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
     return fail(NKA_HIP_EINVAL, who + ": mvec must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_MVEC));
   if (!(vtol > 0.0)) return fail(NKA_HIP_EINVAL, who + ": vtol must be > 0");
   if (int rc = nka_detail::resolve_flavor(&flavor, who.c_str())) return rc;
+  if (s32 && flavor != NKA_HIP_FLAVOR_C)
+    return fail(NKA_HIP_EINVAL, who + ": binary32 storage runs the default flavour only (NKA_HIP_FLAVOR_C); the F08 flavours are there "
+                                      "for the reference's bits, which this storage gives up");
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(NKA_HIP_EINVAL, who + ": no such HIP device");
@@ -607,6 +678,7 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
   b->stream = (hipStream_t)stream;
   b->flavor = flavor;
   b->vtol = vtol;
+  b->storage = storage;
   BatchArgs &k = b->k;
   k.n = vlen;
   k.mvec = mvec;
@@ -630,14 +702,24 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
       rc = fail(NKA_HIP_ENOMEM, std::string("hipMalloc(") + std::to_string(bytes) + " B): " + hipGetErrorString(e));
     }
   };
-  alloc((void **)&k.w, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys);
-  alloc((void **)&k.v, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys);
+  // (binary32 storage: float allocations of the same strides in elements behind k.w / k.v, and the two pending buffers)
+  const size_t slot_bytes_each = (size_t)nka_host::batch_slot_alloc_bytes(lay, nsys, storage);
+  const size_t pend_bytes_each = (size_t)nka_host::batch_pending_alloc_bytes(lay, nsys, storage);
+  alloc((void **)&k.w, slot_bytes_each);
+  alloc((void **)&k.v, slot_bytes_each);
+  if (s32) {
+    alloc((void **)&b->pend_w, pend_bytes_each);
+    alloc((void **)&b->pend_v, pend_bytes_each);
+  }
+  b->vector_bytes = nka_host::batch_vector_bytes(lay, nsys, storage);
   alloc((void **)&k.ic, sizeof(int32_t) * (size_t)k.ic_stride * (size_t)nsys);
   alloc((void **)&k.dc, sizeof(double) * (size_t)k.dc_stride * (size_t)nsys);
   if (!rc && (hipMemsetAsync(k.ic, 0, sizeof(int32_t) * (size_t)k.ic_stride * (size_t)nsys, b->stream) != hipSuccess ||
               hipMemsetAsync(k.dc, 0, sizeof(double) * (size_t)k.dc_stride * (size_t)nsys, b->stream) != hipSuccess ||
-              hipMemsetAsync(k.w, 0, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys, b->stream) != hipSuccess ||
-              hipMemsetAsync(k.v, 0, sizeof(double) * (size_t)k.sys_stride * (size_t)nsys, b->stream) != hipSuccess)) {
+              hipMemsetAsync(k.w, 0, slot_bytes_each, b->stream) != hipSuccess ||
+              hipMemsetAsync(k.v, 0, slot_bytes_each, b->stream) != hipSuccess ||
+              (s32 && (hipMemsetAsync(b->pend_w, 0, pend_bytes_each, b->stream) != hipSuccess ||
+                       hipMemsetAsync(b->pend_v, 0, pend_bytes_each, b->stream) != hipSuccess)))) {
     (void)hipGetLastError();
     rc = fail(NKA_HIP_EHIP, who + ": initialising the batch failed");
   }
@@ -666,6 +748,12 @@ int nka_hip_batch_create_wide(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, 
                               int32_t device, void *stream) {
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, true);
 }
+int nka_hip_batch_create_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                                int32_t device, void *stream, int32_t storage) {
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, storage, "nka_hip_batch_create_stored");
+}
+int nka_hip_batch_storage(nka_hip_batch_t b) { return b ? b->storage : fail(NKA_HIP_EINVAL, "batch_storage: null handle"); }
+int64_t nka_hip_batch_vector_bytes(nka_hip_batch_t b) { return b ? b->vector_bytes : (int64_t)fail(NKA_HIP_EINVAL, "batch_vector_bytes: null handle"); }
 int nka_hip_batch_is_wide(nka_hip_batch_t b) { return b ? (b->wide ? 1 : 0) : fail(NKA_HIP_EINVAL, "batch_is_wide: null handle"); }
 
 int nka_hip_batch_destroy(nka_hip_batch_t b) {
@@ -681,6 +769,8 @@ int nka_hip_batch_destroy(nka_hip_batch_t b) {
   hipFree(b->wgt_stage);
   hipFree(b->wgt_chk);
   hipFree(b->len);
+  hipFree(b->pend_w);
+  hipFree(b->pend_v);
   nka_batch_wide_free(b);
   delete b;
   return 0;
@@ -743,6 +833,9 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_sum_order: null handle");
   if (b->wide && order != NKA_HIP_SUMS_AUTO && order != NKA_HIP_SUMS_BLOCKED_ROUNDED)
     return fail(NKA_HIP_EINVAL, "batch_set_sum_order: a wide batch forms the rounded fast sums only: NKA_HIP_SUMS_BLOCKED_ROUNDED or _AUTO");
+  if (b->storage == NKA_HIP_BATCH_STORE_F32 && order == NKA_HIP_SUMS_REFERENCE_ORDER)
+    return fail(NKA_HIP_EINVAL, "batch_set_sum_order: a batch with binary32 storage forms the rounded fast sums only (the reference order is "
+                                "there for the reference's bits, which this storage gives up): NKA_HIP_SUMS_BLOCKED_ROUNDED or _AUTO");
   if (order == NKA_HIP_SUMS_BLOCKED)
     return fail(NKA_HIP_EINVAL, "batch_set_sum_order: NKA_HIP_SUMS_BLOCKED is not offered by a batch (it has no exchange to save): "
                                 "NKA_HIP_SUMS_BLOCKED_ROUNDED, _REFERENCE_ORDER or _AUTO");
@@ -922,6 +1015,26 @@ static int batch_get_slot(nka_hip_batch_t b, bool v, int32_t sys, int32_t slot, 
   if (slot < 1 || slot > b->k.mvec + 1) return fail(NKA_HIP_EINVAL, "batch_get_w/v: slot out of range");
   if (!host_out) return fail(NKA_HIP_EINVAL, "batch_get_w/v: null argument");
   HIP_TRY(hipSetDevice(b->device));
+  if (b->storage == NKA_HIP_BATCH_STORE_F32) {
+    // the slot of the pending pair: its binary64 row of the pending buffers; any other slot: the stored floats, widened
+    std::vector<int32_t> ic;
+    std::vector<double> dc;
+    if (int rc = fetch_sys(b, sys, ic, dc)) return rc;
+    int32_t pending = 0, first = 0;
+    nka_host::snapshot_unpack(ic.data(), dc.data(), b->k.mvec, nullptr, &pending, &first, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (pending && first == slot) {
+      const double *src = (v ? b->pend_v : b->pend_w) + (size_t)sys * b->k.stride;
+      HIP_TRY(hipMemcpyAsync(host_out, src, sizeof(double) * (size_t)b->k.n, hipMemcpyDeviceToHost, b->stream));
+      HIP_TRY(hipStreamSynchronize(b->stream));
+      return 0;
+    }
+    const float *src = reinterpret_cast<const float *>(v ? b->k.v : b->k.w) + (size_t)sys * b->k.sys_stride + (size_t)(slot - 1) * b->k.stride;
+    std::vector<float> stage((size_t)b->k.n);
+    HIP_TRY(hipMemcpyAsync(stage.data(), src, sizeof(float) * stage.size(), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (size_t i = 0; i < stage.size(); i++) host_out[i] = (double)stage[i];
+    return 0;
+  }
   const double *src = (v ? b->k.v : b->k.w) + (size_t)sys * b->k.sys_stride + (size_t)(slot - 1) * b->k.stride;
   HIP_TRY(hipMemcpyAsync(host_out, src, sizeof(double) * (size_t)b->k.n, hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));

@@ -71,6 +71,34 @@ __device__ __forceinline__ void st_tile(double *__restrict__ p, int64_t i, int64
   p[i] = x[0];
   p[i + 1] = x[1];
 }
+// BINARY32 STORAGE (nka_hip_batch.h, STORAGE): the same pair of a stored binary32 vector, one 8-byte access (rows start on 128
+// bytes, i is even), widened exactly on the way in and narrowed on the way out -- round to nearest even, subnormals kept,
+// beyond the range +-Inf -- so that what is stored is what a later load returns.
+typedef float f2 __attribute__((ext_vector_type(2)));
+template <bool FULL>
+__device__ __forceinline__ d2 ld_tile32(const float *__restrict__ p, int64_t i, int64_t n) {
+  d2 r;
+  if (FULL || i + 1 < n) {
+    const f2 x = *reinterpret_cast<const f2 *>(p + i);
+    r[0] = (double)x[0];
+    r[1] = (double)x[1];
+    return r;
+  }
+  r[0] = i < n ? (double)p[i] : 0.0;
+  r[1] = 0.0;
+  return r;
+}
+template <bool FULL>
+__device__ __forceinline__ void st_tile32(float *__restrict__ p, int64_t i, int64_t n, d2 x) {
+  f2 y;
+  y[0] = (float)x[0];
+  y[1] = (float)x[1];
+  if (FULL || i + 1 < n) { *reinterpret_cast<f2 *>(p + i) = y; return; }
+  if (i < n) p[i] = y[0];
+}
+// q(x) of the STORAGE paragraph: the binary64 value a binary32 slot returns for x
+__device__ __forceinline__ double batch_q32(double x) { return (double)(float)x; }
+
 // One sweep over a system's elements: body(FULL, FVEC, i) for this thread's pair i = 2t, 2t + 512, ... -- the full tiles
 // first, then the ragged one with guards.  The order in which a thread meets its elements is the same on every path.
 template <class Body>
@@ -175,6 +203,12 @@ struct nka_hip_batch_state {
   // moved -- a captured update holds the address.  It only ever holds values that passed the check 1 <= len <= vlen.
   int32_t *len = nullptr;
   bool has_len = false;                     // the next update runs the instances that read it
+  // binary32 storage (nka_hip_batch_create_stored): k.w / k.v then point at FLOAT allocations of the same strides in elements,
+  // and the raw pending pair lives in pend_w / pend_v, nsys binary64 rows at the slot stride, allocated at creation, freed at
+  // destroy only and never moved -- a captured update holds the addresses
+  int storage = NKA_HIP_BATCH_STORE_F64;
+  double *pend_w = nullptr, *pend_v = nullptr;
+  int64_t vector_bytes = 0;                 // what the slots and the pending buffers asked of hipMalloc
   // a WIDE batch (nka_hip_batch_create_wide, nka_batch_wide.hip): a system is nchunk chunks of NKA_HIP_BATCH_WIDE_CHUNK elements
   bool wide = false;
   int32_t nchunk = 0;

@@ -186,6 +186,108 @@ def measure_weights(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_bu
     return out
 
 
+def store32_bytes_model(mvec):
+    """Bytes an update moves per element at a full list, default flavour, re-reads of f and w1 counted as memory: norm pass 16;
+    each sweep of four older vectors 48 with binary64 storage, 32 with binary32; combine of k = mvec pairs 8 (7 + k) and
+    56 + 4 (k - 1).  -> (binary64, binary32)"""
+    g = (mvec - 1 + 3) // 4
+    return 16 + 48 * g + 8 * (7 + mvec), 16 + 32 * g + 56 + 4 * (mvec - 1)
+
+
+def measure_store32(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
+    """(a) a binary64 batch, flavour C; (a') a second one of the same shape, the control for what two allocations alone do to
+    two batches of equal work; (b) the binary32 batch.  Same inputs, alternated, as measure_weights."""
+    npool = mvec + 3
+    stride = (vlen + 31) // 32 * 32
+    vec = {s: 2 * nsys * stride * (8 * (mvec + 1) if s == nka_amd.STORE_F64 else 4 * (mvec + 1) + 8) for s in (nka_amd.STORE_F64, nka_amd.STORE_F32)}
+    need = 2 * vec[nka_amd.STORE_F64] + vec[nka_amd.STORE_F32] + 8.0 * nsys * vlen * (npool + 3)
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    forms = {"a": nka_amd.STORE_F64, "a2": nka_amd.STORE_F64, "b": nka_amd.STORE_F32}
+    Fs, hs, batches = {}, {}, {}
+    for name, storage in forms.items():
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+        batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, storage=storage)
+        assert batches[name].storage() == storage and batches[name].vector_bytes() == vec[storage], name
+        hs[name] = batches[name]._handle()
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    upd = L.nka_hip_batch_accel_update
+    step = [0]
+
+    def run(name, reps):
+        F, h = Fs[name], hs[name]
+        p = C.c_void_p(F.data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[step[0] % npool])
+            step[0] += 1
+            assert upd(h, p, ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in forms}
+    for name in forms:                             # warm: fill the lists (steady state), settle clocks and caches
+        step[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    for name in forms:
+        assert (batches[name].num_vec() == mvec).all(), name
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in forms:
+            ts[name].append(timed(name, reps[name]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec, bytes_a=vec[nka_amd.STORE_F64], bytes_b=vec[nka_amd.STORE_F32])
+    for name in forms:
+        assert (batches[name].num_vec() == mvec).all(), name
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+        batches[name].delete()
+    del pool, Fs
+    torch.cuda.empty_cache()
+    return out
+
+
+def store32_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    if args.store32_extra:
+        points.append((4096, 64, 10))
+    emit(f"# one update of (a) a binary64 batch, (a') a second binary64 batch of the same shape -- the control -- and (b) a batch "
+         f"with binary32 storage (nka_hip_batch_create_stored); {torch.cuda.get_device_name(0)}; windows >= {args.window} s, median "
+         f"of {args.repeats}, the three alternated on the same inputs; flavour C, default sums, full list")
+    emit("# byte model per element: 16 + 48 G + 8 (7 + k) binary64, 16 + 32 G + 56 + 4 (k - 1) binary32, G = ceil((mvec - 1) / 4), "
+         "k = mvec: 308 / 472 = 0.65 at mvec 20, 204 / 296 = 0.69 at 10 (a prediction, not a bar)")
+    emit("# CONDITION at 4096 x 16384, both mvec: b/a below 1 by more than the larger of the window spread and |a - a'| / a")
+    emit(f"{'nsys':>5} {'vlen':>6} {'mvec':>4} {'a us':>10} {'a2 us':>10} {'b us':>10} {'b/a':>6} {'|a-a2|/a':>8} {'model':>6} "
+         f"{'vectors a MB':>12} {'vectors b MB':>12} {'b/a mem':>7}  condition")
+    t0 = time.time()
+    verdicts = []
+    for n, v, m in points:
+        r = measure_store32(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9)
+        if r is None:
+            emit(f"{n:5d} {v:6d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        b64, b32 = store32_bytes_model(m)
+        ratio, ctl = r["b"] / r["a"], abs(r["a"] - r["a2"]) / r["a"]
+        noise = max(ctl, r["spread_a"], r["spread_a2"], r["spread_b"])
+        cond = "-"
+        if (n, v) == (4096, 16384):
+            cond = "HELD" if 1.0 - ratio > noise else "MISSED"
+            verdicts.append(cond)
+        emit(f"{n:5d} {v:6d} {m:4d} {r['a'] * 1e6:10.1f} {r['a2'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {ratio:6.3f} {ctl:8.3f} "
+             f"{b32 / b64:6.3f} {r['bytes_a'] / 1e6:12.1f} {r['bytes_b'] / 1e6:12.1f} {r['bytes_b'] / r['bytes_a']:7.3f}  {cond}   "
+             f"(spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
+    emit(f"# condition: {', '.join(verdicts) if verdicts else 'not measured (no point at 4096 x 16384)'}; {len(points)} points in "
+         f"{time.time() - t0:.0f} s")
+    return 0
+
+
 LENGTHS_SEED = 2024
 
 
@@ -553,6 +655,10 @@ def main():
     ap.add_argument("--lengths", action="store_true",
                     help="time per-system lengths beside a plain batch and the zero-weight recipe; without --nsys / --vlens / --mvecs: "
                          "nsys 256,4096 x vlen 1024,16384 x mvec 10,20, then the wide batch at (16, 65536) and (64, 262144)")
+    ap.add_argument("--store32", action="store_true",
+                    help="time a batch with binary32 storage beside two binary64 batches (the second: a control); without --nsys / "
+                         "--vlens / --mvecs: nsys 256,4096 x vlen 1024,16384 x mvec 10,20, plus 4096 x 64 x 10")
+    ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
     import torch
@@ -575,6 +681,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.store32:
+        for name, grid_s in (("nsys", "256,4096"), ("vlens", "1024,16384"), ("mvecs", "10,20")):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_s)
+        return store32_main(args, torch, nka_amd, L, emit)
     if args.lengths:
         for name, grid_l in (("nsys", "256,4096"), ("vlens", "1024,16384"), ("mvecs", "10,20")):
             if getattr(args, name) == ap.get_default(name):
