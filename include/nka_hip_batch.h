@@ -190,6 +190,45 @@
  *            8 (7 + k) -> 56 + 4 (k - 1) B) predicts 0.69 and 0.65 --, the two binary64 batches differing by 2.1 % and 0.8 %;
  *            0.82 / 0.87 at 4096 x 1024, 0.89 / 0.90 at 256 x 16 384, 0.98 / 1.02 at 256 x 1024.  At 4096 x 64 x 10 it takes
  *            1.22 x: binary64 storage runs such systems in reference order under NKA_HIP_SUMS_AUTO, this storage the fast sums.
+ *   LANES    nka_hip_batch_create_lanes: the same handle type for VERY SHORT systems, 1 <= vlen <= NKA_HIP_BATCH_LANES_MAX_VLEN = 64,
+ *            with ONE LANE PER SYSTEM (nka_amd/csrc/nka_batch_lanes.hip).  The batch above gives such a system a workgroup of
+ *            256 threads of which one forms each sum and one runs the scalar step; here a workgroup is one wavefront that
+ *            advances G systems -- nka_hip_batch_lanes_limits(mvec): the most working copies that fit 64 KiB of LDS, at most 64;
+ *            64 up to mvec = 6, 37 at 10, 13 at 20, 6 at 32 --, lane l of workgroup g owns system g * G + l through every phase,
+ *            and the grid is ceil(nsys / G).  One launch per call.  The cap is DERIVED, not measured: it is the range in which
+ *            NKA_HIP_SUMS_AUTO of the batch above already means the reference order, so a lane batch and a default batch from
+ *            nka_hip_batch_create are interchangeable bit for bit.  mvec, vtol, nsys >= 1 and all three flavours as above.
+ *            OFFERED with their signatures and guarantees (MASKS, ASYNC, GRAPHS from the first update, BITS, the span checks):
+ *            accel_update; accel_step with x, tol, fnorm and active each optional, and its refusals; restart, relax,
+ *            set_vec_tol, set_stream; num_vec, get_state, get_reductions, get_w, get_v (gathered from the interleaved slots),
+ *            state_digest, storage (NKA_HIP_BATCH_STORE_F64), vector_bytes (2 * 8 * ceil(nsys / G) * G * (mvec + 1) * vlen: the
+ *            slots are interleaved across the systems of a group, the last group whole, rows not padded); set_sum_order with
+ *            NKA_HIP_SUMS_AUTO and _REFERENCE_ORDER, which both mean the reference order.  nka_hip_batch_is_wide returns 0,
+ *            nka_hip_batch_kind 2.  REFUSED with NKA_HIP_EINVAL, the batch staying usable: nka_hip_batch_set_dot_weights and
+ *            _host (dot_weighted returns 0), nka_hip_batch_set_lengths and _host (has_lengths returns 0), NKA_HIP_SUMS_BLOCKED
+ *            and _BLOCKED_ROUNDED, and creation with vlen > 64; a caller who needs one of these has the batch above.  There is
+ *            no binary32 storage for this kind (nka_hip_batch_create_stored stays the batch above): a possible follow-up.
+ *            THE CONTRACT: for every system, after every call, the row of f, the row of x, red[] with its zeros, the state,
+ *            num_vec and the digest, fnorm and the retirement decision, and w and v of every slot are BIT-EQUAL to those of the
+ *            same system in a batch from nka_hip_batch_create of the same flavour in NKA_HIP_SUMS_REFERENCE_ORDER -- and
+ *            therefore to the reference flavour it runs.  This is derived, not fitted: each sum is one chain a = a + x * y in
+ *            element order on one lane, one rounding per product and per addition (contraction off), the operands in the order
+ *            of the reference-order kernel above; the scalar step is the same statements on the lane's own working copy; the
+ *            elementwise statements are the flavour's (fl(d/s) or fl(fl(1/s) d), the flavour's association of the combine,
+ *            compact storage in the C flavour).  The bits do not depend on nsys, on the position of the system, on the lane
+ *            or group it lands in, on the other systems' masks or values, or on ld / ldx.  A masked, retired or absent system
+ *            is a predicated lane: no byte of it is read or written, and no workgroup or lane reads what another's system owns
+ *            (tests/test_batch_lanes_gpu.py holds all of it with ==).
+ *            WHICH OF THE THREE KINDS, MEASURED (profiles/r14/batch_lanes_throughput.txt, 1 x MI355X): time of a call / time of
+ *            the batch above at NKA_HIP_SUMS_AUTO, default flavour, full lists, the two alternated with a second batch above as
+ *            the control (it differs by at most 2.2 %).  At 65 536 systems the lane batch WINS where a working copy is small:
+ *            mvec = 5: 0.32 / 0.46 / 0.58 at vlen 8 / 32 / 64; mvec = 10: 0.46 / 0.85 at vlen 8 / 32 (1.10 at 64); a step with x,
+ *            mask, tol and fnorm at vlen 32: 0.49 / 0.81.  It LOSES at mvec = 20 (1.41 / 1.09 / 1.74; 13 systems per wavefront,
+ *            two wavefronts per CU: LDS bounds residency), at 4096 systems nearly everywhere (1.00 ... 2.63; 0.97 at 32 x 20) and
+ *            at 256 systems everywhere (1.9 ... 5.5): a call then costs the latency of one wavefront that does serially what 256
+ *            threads share, 48 ... 470 us whatever nsys is.  So: tens of thousands of systems of at most 64 unknowns with mvec up
+ *            to about 10 -- this kind; fewer systems or mvec = 20 -- the batch above, which returns the same bits; systems
+ *            beyond 16 384 unknowns -- WIDE.
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -230,7 +269,18 @@ int nka_hip_batch_create_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen
                                 int32_t flavor, int32_t device, void *stream, int32_t storage);
 int nka_hip_batch_storage(nka_hip_batch_t b);
 int64_t nka_hip_batch_vector_bytes(nka_hip_batch_t b);
-int nka_hip_batch_is_wide(nka_hip_batch_t b);                    /* 1 = wide, 0 = one workgroup per system; < 0 on error */
+/* LANES above: the same handle type with ONE LANE PER SYSTEM; 1 <= vlen <= NKA_HIP_BATCH_LANES_MAX_VLEN, mvec, vtol and the three
+ * flavours as above, nsys >= 1.  Allocates the slots interleaved across the systems of a group (binary64 only).
+ * _lanes_limits: how many systems one workgroup advances at this mvec, as the library was built, and the cap on vlen (either
+ * output may be NULL); NKA_HIP_EINVAL for an mvec outside 1 ... NKA_HIP_BATCH_MAX_MVEC.
+ * _kind: 0 = one workgroup per system (narrow), 1 = wide, 2 = lanes; < 0 on error. */
+enum { NKA_HIP_BATCH_LANES_MAX_VLEN = 64 };
+enum { NKA_HIP_BATCH_KIND_NARROW = 0, NKA_HIP_BATCH_KIND_WIDE = 1, NKA_HIP_BATCH_KIND_LANES = 2 };
+int nka_hip_batch_create_lanes(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                               int32_t flavor, int32_t device, void *stream);
+int nka_hip_batch_lanes_limits(int32_t mvec, int32_t *systems_per_group, int64_t *max_vlen);
+int nka_hip_batch_kind(nka_hip_batch_t b);
+int nka_hip_batch_is_wide(nka_hip_batch_t b);                    /* 1 = wide, 0 = narrow or lanes; < 0 on error */
 int nka_hip_batch_wide_limits(int64_t *chunk, int64_t *max_vlen);  /* the two constants, as the library was built */
 int nka_hip_batch_destroy(nka_hip_batch_t b);
 

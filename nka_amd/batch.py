@@ -25,6 +25,19 @@ def batch_wide_limits():
     return int(chunk.value), int(cap.value)
 
 
+BATCH_LANES_MAX_VLEN = 64                       # NKA_HIP_BATCH_LANES_MAX_VLEN (include/nka_hip_batch.h, LANES)
+KIND_NARROW, KIND_WIDE, KIND_LANES = 0, 1, 2    # NKA_HIP_BATCH_KIND_*
+
+
+def batch_lanes_limits(mvec: int):
+    """(systems_per_group, max_vlen) of a lane batch at this mvec -- how many systems one workgroup advances, as the loaded
+    library was built, and NKA_HIP_BATCH_LANES_MAX_VLEN (nka_hip_batch_lanes_limits)."""
+    group, cap = C.c_int32(), C.c_int64()
+    L = _lib.load()
+    _check(L.nka_hip_batch_lanes_limits(int(mvec), C.byref(group), C.byref(cap)), "nka_hip_batch_lanes_limits", L)
+    return int(group.value), int(cap.value)
+
+
 class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
     """A batch of MI355X accelerator objects; see the module docstring."""
 
@@ -33,7 +46,7 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         self._L = _lib.load()          # raises if the HIP library is missing: no CPU path
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
-             stream: int | None = None, wide: bool = False, storage: int = STORE_F64):
+             stream: int | None = None, wide: bool = False, storage: int = STORE_F64, lanes: bool = False):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
@@ -41,9 +54,18 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         sum order are refused).  storage=STORE_F32 (nka_hip_batch_create_stored; include/nka_hip_batch.h, STORAGE): the
         normalised subspace vectors are kept in binary32 -- 0.55 of the slot memory at mvec = 20 --, every product and sum
         still binary64, the pending pair still binary64.  Such a batch runs the default flavour (FLAVOR_C) and the rounded fast
-        sums only: the F08 flavours, set_sum_order(SUMS_REFERENCE_ORDER) and wide=True are refused (NKAError)."""
+        sums only: the F08 flavours, set_sum_order(SUMS_REFERENCE_ORDER) and wide=True are refused (NKAError).
+        lanes: ONE LANE PER SYSTEM (nka_hip_batch_create_lanes; include/nka_hip_batch.h, LANES) for very short systems, vlen up
+        to batch_lanes_limits(mvec)[1] = 64: every sum in the reference's order, bit-equal to a narrow batch with
+        SUMS_REFERENCE_ORDER; accel_update, accel_step, masks, restart / relax and graphs are offered, weights, lengths and the
+        fast sums refused.  Together with wide=True or storage != STORE_F64 it raises NKAError."""
         import torch
 
+        if lanes and wide:
+            raise NKAError("nka_batch init: lanes=True and wide=True exclude each other (one lane per system, or a system split "
+                           "across workgroups)")
+        if lanes and int(storage) != STORE_F64:
+            raise NKAError("nka_batch init: binary32 storage is not offered by a lane batch (storage=STORE_F64)")
         self.delete()
         if not torch.cuda.is_available():
             raise NKAError("no HIP device visible: nka_amd has no CPU path")
@@ -58,6 +80,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
                 raise NKAError("nka_batch init: binary32 storage is not offered by a wide batch (storage=STORE_F64)")
             _check(self._L.nka_hip_batch_create_stored(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                        C.c_void_p(stream), int(storage)), "nka_hip_batch_create_stored", self._L)
+        elif lanes:
+            _check(self._L.nka_hip_batch_create_lanes(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                      C.c_void_p(stream)), "nka_hip_batch_create_lanes", self._L)
         else:
             create = self._L.nka_hip_batch_create_wide if wide else self._L.nka_hip_batch_create
             _check(create(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device), C.c_void_p(stream)),
@@ -305,6 +330,12 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         r = self._L.nka_hip_batch_is_wide(self._handle())
         _check(min(r, 0), "batch_is_wide", self._L)
         return r == 1
+
+    def kind(self) -> int:
+        """KIND_NARROW (one workgroup per system), KIND_WIDE or KIND_LANES (nka_hip_batch_kind)."""
+        r = self._L.nka_hip_batch_kind(self._handle())
+        _check(min(r, 0), "batch_kind", self._L)
+        return r
 
     def num_vec(self) -> np.ndarray:
         out = np.zeros(self._nsys, np.int32)

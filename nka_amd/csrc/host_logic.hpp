@@ -249,6 +249,71 @@ NKA_HOST_DEVICE constexpr BatchLds batch_lds(int mvec) {
   return l;
 }
 
+// THE LANE BATCH (nka_hip_batch_create_lanes, nka_batch_lanes.hip): ONE LANE PER SYSTEM.  A workgroup is one wavefront and
+// advances G = lanes_group(mvec) systems, lane l system g * G + l of group g; the grid is lanes_ngroup(nsys, G) workgroups.
+// tests/c/batch_lanes_layout_check.cpp paints every piece below.
+//   LDS      every lane owns a working copy -- the h, c, red, cc, next, prev, ps, cs, hdr pieces of batch_lds -- in two regions:
+//            the doubles of lane l at l * dstride doubles, and behind the doubles of all G lanes the int32 of lane l at
+//            l * istride int32.  THE BANK RULE: dstride is an ODD number of doubles and istride an ODD number of int32.  A
+//            ds_read_b64 is served in two groups of 32 lanes with bank (a / 4) mod 64, a ds_read_b32 with bank (a / 4) mod 32:
+//            with the lanes of a group at the same offset of their copies, lane l starts at dword 2 l dstride (mod 64), 32
+//            distinct even values for l = 0 ... 31 exactly when dstride is odd, and at dword l istride (mod 32), 32 distinct
+//            values exactly when istride is odd -- no two lanes of a group on one bank.
+//   G        the largest count, at most 64 (one wavefront), whose copies fit kLanesLdsBudget.  64 KiB: the dynamic LDS a
+//            launch may ask for without an attribute of the function, and two to three workgroups per CU (160 KiB).
+//   SLOTS    the batch's own storage is INTERLEAVED across the systems of a group: element i of slot k (1-based) of system sys
+//            lies at lanes_slot_offset = (((sys / G) (mvec + 1) + (k - 1)) vlen + i) G + sys % G doubles, so the load of
+//            element i by the lanes of a wavefront is one contiguous run of G doubles.  The last group is allocated whole.
+//            Every offset is formed in 64 bits.
+constexpr int kLanesThreads = 64;                       // one wavefront per workgroup
+constexpr int kLanesMaxVlen = 64;                       // = NKA_HIP_BATCH_LANES_MAX_VLEN = kOrdAutoMax (nka_device.hpp)
+constexpr int64_t kLanesLdsBudget = 64 * 1024;          // bytes of LDS of one workgroup, at most the 160 KiB of a CU
+constexpr int kLanesHdrLive = 6;                        // hdr[6]: the lane's system takes part (beside the HDR_ entries 0 ... 5)
+struct LanesLds {
+  int h, c, red, cc, ndouble, dstride;      // offsets in doubles inside a lane's doubles; dstride: doubles between lanes (odd)
+  int next, prev, ps, cs, hdr, nint, istride;   // offsets in int32 inside a lane's int32; istride: int32 between lanes (odd)
+  NKA_HOST_DEVICE constexpr int64_t lane_bytes() const { return 8 * (int64_t)dstride + 4 * (int64_t)istride; }
+  NKA_HOST_DEVICE constexpr int64_t bytes(int G) const { return lane_bytes() * G; }
+  // where the pieces of lane l start: in doubles from the start of the LDS, and in int32 from the end of all doubles
+  NKA_HOST_DEVICE constexpr int64_t dbase(int l) const { return (int64_t)l * dstride; }
+  NKA_HOST_DEVICE constexpr int64_t ibase(int l) const { return (int64_t)l * istride; }
+};
+NKA_HOST_DEVICE constexpr LanesLds lanes_lds(int mvec) {
+  const BatchLds b = batch_lds(mvec);
+  const int m1 = mvec + 1;
+  LanesLds l{};
+  l.h = b.h;
+  l.c = b.c;
+  l.red = b.red;
+  l.cc = b.cc;
+  l.ndouble = l.cc + m1;      // (no sm, no res: a lane's sums never leave its registers)
+  l.dstride = l.ndouble | 1;
+  l.next = b.next;
+  l.prev = b.prev;
+  l.ps = b.ps;
+  l.cs = b.cs;
+  l.hdr = b.hdr;
+  l.nint = b.nint;
+  l.istride = l.nint | 1;
+  return l;
+}
+NKA_HOST_DEVICE constexpr int lanes_group(int mvec) {
+  const int64_t g = kLanesLdsBudget / lanes_lds(mvec).lane_bytes();
+  return g > kLanesThreads ? kLanesThreads : (int)g;
+}
+NKA_HOST_DEVICE constexpr int64_t lanes_ngroup(int64_t nsys, int G) { return (nsys + G - 1) / G; }
+NKA_HOST_DEVICE constexpr int64_t lanes_group_stride(int64_t vlen, int mvec, int G) { return (int64_t)(mvec + 1) * vlen * G; }
+NKA_HOST_DEVICE constexpr int64_t lanes_slot_offset(int64_t vlen, int mvec, int G, int64_t sys, int slot /* 1-based */, int64_t i) {
+  return (((sys / G) * (mvec + 1) + (slot - 1)) * vlen + i) * G + sys % G;
+}
+// doubles of EACH of the two slot allocations (w, v), and the bytes of both together (nka_hip_batch_vector_bytes)
+NKA_HOST_DEVICE constexpr int64_t lanes_slot_alloc_elems(int64_t vlen, int mvec, int G, int64_t nsys) {
+  return lanes_ngroup(nsys, G) * lanes_group_stride(vlen, mvec, G);
+}
+NKA_HOST_DEVICE constexpr int64_t lanes_vector_bytes(int64_t vlen, int mvec, int G, int64_t nsys) {
+  return 2 * 8 * lanes_slot_alloc_elems(vlen, mvec, G, nsys);
+}
+
 // THE WIDE BATCH (nka_hip_batch_create_wide, nka_batch_wide.hip): a system is nchunk = ceil(vlen / kWideChunk) chunks, one
 // workgroup each, and an update is four launches: norm, sums, scalar, combine.  tests/c/batch_wide_layout_check.cpp paints
 // every piece below.  (NKA_BATCH_WIDE_CHUNK: the candidate builds that chose the constant, tools/batch_throughput.py --wide.)

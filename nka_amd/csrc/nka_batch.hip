@@ -640,9 +640,11 @@ int set_weights_from_device(nka_hip_batch_t b, const double *src, int64_t ldw, c
 
 extern "C" {
 
-// both kinds of batch: `wide` = a system split across workgroups (nka_batch_wide.hip)
+// the three kinds of batch: `wide` = a system split across workgroups (nka_batch_wide.hip), `lanes` = one lane per system
+// (nka_batch_lanes.hip), neither = one workgroup per system (this file)
 static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor, int32_t device,
-                        void *stream, bool wide, int32_t storage = NKA_HIP_BATCH_STORE_F64, const char *entry = nullptr) {
+                        void *stream, bool wide, int32_t storage = NKA_HIP_BATCH_STORE_F64, const char *entry = nullptr,
+                        bool lanes = false) {
   const std::string who = entry ? entry : wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
   const bool s32 = storage == NKA_HIP_BATCH_STORE_F32;
   if (!out) return fail(NKA_HIP_EINVAL, who + ": out is NULL");
@@ -657,6 +659,10 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
     if (nsys > 65535) return fail(NKA_HIP_EINVAL, who + ": nsys must be <= 65535 (the system is the second grid index)");
     if (vlen < 1 || vlen > cap)
       return fail(NKA_HIP_EINVAL, who + ": vlen must be 1 ... " + std::to_string((long long)cap) + " (longer systems: lone handles, nka_hip_create)");
+  } else if (lanes) {
+    if (vlen < 1 || vlen > NKA_HIP_BATCH_LANES_MAX_VLEN)
+      return fail(NKA_HIP_EINVAL, who + ": vlen must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_LANES_MAX_VLEN) +
+                                      " (one lane forms every sum of a system; longer systems: nka_hip_batch_create)");
   } else if (vlen < 1 || vlen > NKA_HIP_BATCH_MAX_VLEN)
     return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: vlen must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_VLEN) +
                                     " (longer systems: nka_hip_batch_create_wide, or lone handles, nka_hip_create)");
@@ -674,6 +680,7 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
 
   auto *b = new nka_hip_batch_state();
   b->wide = wide;
+  b->lanes = lanes;
   b->device = device;
   b->stream = (hipStream_t)stream;
   b->flavor = flavor;
@@ -688,7 +695,7 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
   k.sys_stride = lay.sys_stride;
   k.ic_stride = lay.ic_stride;
   k.dc_stride = lay.dc_stride;
-  const double slot_bytes = (double)k.sys_stride * 8.0 * (double)nsys;
+  const double slot_bytes = lanes ? 0.0 : (double)k.sys_stride * 8.0 * (double)nsys;      // (a lane batch: checked where it allocates)
   if (slot_bytes > 1.0e13) {      // (beyond any device: also keeps the size arithmetic below inside 64 bits)
     delete b;
     return fail(NKA_HIP_ENOMEM, who + ": the batch needs more device memory than any device has");
@@ -703,21 +710,26 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
     }
   };
   // (binary32 storage: float allocations of the same strides in elements behind k.w / k.v, and the two pending buffers)
-  const size_t slot_bytes_each = (size_t)nka_host::batch_slot_alloc_bytes(lay, nsys, storage);
+  // (a lane batch: its own interleaved slots, allocated and zeroed by nka_batch_lanes_alloc)
+  const size_t slot_bytes_each = lanes ? (size_t)0 : (size_t)nka_host::batch_slot_alloc_bytes(lay, nsys, storage);
   const size_t pend_bytes_each = (size_t)nka_host::batch_pending_alloc_bytes(lay, nsys, storage);
-  alloc((void **)&k.w, slot_bytes_each);
-  alloc((void **)&k.v, slot_bytes_each);
+  if (lanes) {
+    rc = nka_batch_lanes_alloc(b);
+  } else {
+    alloc((void **)&k.w, slot_bytes_each);
+    alloc((void **)&k.v, slot_bytes_each);
+  }
   if (s32) {
     alloc((void **)&b->pend_w, pend_bytes_each);
     alloc((void **)&b->pend_v, pend_bytes_each);
   }
-  b->vector_bytes = nka_host::batch_vector_bytes(lay, nsys, storage);
+  if (!lanes) b->vector_bytes = nka_host::batch_vector_bytes(lay, nsys, storage);
   alloc((void **)&k.ic, sizeof(int32_t) * (size_t)k.ic_stride * (size_t)nsys);
   alloc((void **)&k.dc, sizeof(double) * (size_t)k.dc_stride * (size_t)nsys);
   if (!rc && (hipMemsetAsync(k.ic, 0, sizeof(int32_t) * (size_t)k.ic_stride * (size_t)nsys, b->stream) != hipSuccess ||
               hipMemsetAsync(k.dc, 0, sizeof(double) * (size_t)k.dc_stride * (size_t)nsys, b->stream) != hipSuccess ||
-              hipMemsetAsync(k.w, 0, slot_bytes_each, b->stream) != hipSuccess ||
-              hipMemsetAsync(k.v, 0, slot_bytes_each, b->stream) != hipSuccess ||
+              (!lanes && (hipMemsetAsync(k.w, 0, slot_bytes_each, b->stream) != hipSuccess ||
+                          hipMemsetAsync(k.v, 0, slot_bytes_each, b->stream) != hipSuccess)) ||
               (s32 && (hipMemsetAsync(b->pend_w, 0, pend_bytes_each, b->stream) != hipSuccess ||
                        hipMemsetAsync(b->pend_v, 0, pend_bytes_each, b->stream) != hipSuccess)))) {
     (void)hipGetLastError();
@@ -752,6 +764,14 @@ int nka_hip_batch_create_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen
                                 int32_t device, void *stream, int32_t storage) {
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, storage, "nka_hip_batch_create_stored");
 }
+int nka_hip_batch_create_lanes(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                               int32_t device, void *stream) {
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_lanes", true);
+}
+int nka_hip_batch_kind(nka_hip_batch_t b) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_kind: null handle");
+  return b->lanes ? NKA_HIP_BATCH_KIND_LANES : b->wide ? NKA_HIP_BATCH_KIND_WIDE : NKA_HIP_BATCH_KIND_NARROW;
+}
 int nka_hip_batch_storage(nka_hip_batch_t b) { return b ? b->storage : fail(NKA_HIP_EINVAL, "batch_storage: null handle"); }
 int64_t nka_hip_batch_vector_bytes(nka_hip_batch_t b) { return b ? b->vector_bytes : (int64_t)fail(NKA_HIP_EINVAL, "batch_vector_bytes: null handle"); }
 int nka_hip_batch_is_wide(nka_hip_batch_t b) { return b ? (b->wide ? 1 : 0) : fail(NKA_HIP_EINVAL, "batch_is_wide: null handle"); }
@@ -772,6 +792,7 @@ int nka_hip_batch_destroy(nka_hip_batch_t b) {
   hipFree(b->pend_w);
   hipFree(b->pend_v);
   nka_batch_wide_free(b);
+  nka_batch_lanes_free(b);
   delete b;
   return 0;
 }
@@ -782,7 +803,9 @@ int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, con
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = check_rows(b, f_dev, ld, "batch_accel_update", "f", "ld")) return rc;
   if (int rc = check_mask(b, active_dev, "batch_accel_update: active")) return rc;
-  if (b->wide) nka_batch_wide_update(b, f_dev, ld, active_dev); else launch_flavor(b, f_dev, ld, active_dev);
+  if (b->wide) nka_batch_wide_update(b, f_dev, ld, active_dev);
+  else if (b->lanes) nka_batch_lanes_update(b, f_dev, ld, active_dev);
+  else launch_flavor(b, f_dev, ld, active_dev);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -811,7 +834,8 @@ int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, doubl
     const uintptr_t t0 = reinterpret_cast<uintptr_t>(tol_dev), n0 = reinterpret_cast<uintptr_t>(fnorm_dev), len = sizeof(double) * (uintptr_t)b->k.nsys;
     if (t0 < n0 + len && n0 < t0 + len) return fail(NKA_HIP_EINVAL, "batch_accel_step: fnorm overlaps tol (a threshold would be overwritten while it is read)");
   }
-  launch_flavor(b, f_dev, ld, active_dev, StepArgs{x_dev, x_dev ? ldx : 0, tol_dev, fnorm_dev});
+  if (b->lanes) nka_batch_lanes_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
+  else launch_flavor(b, f_dev, ld, active_dev, StepArgs{x_dev, x_dev ? ldx : 0, tol_dev, fnorm_dev});
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -836,6 +860,9 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
   if (b->storage == NKA_HIP_BATCH_STORE_F32 && order == NKA_HIP_SUMS_REFERENCE_ORDER)
     return fail(NKA_HIP_EINVAL, "batch_set_sum_order: a batch with binary32 storage forms the rounded fast sums only (the reference order is "
                                 "there for the reference's bits, which this storage gives up): NKA_HIP_SUMS_BLOCKED_ROUNDED or _AUTO");
+  if (b->lanes && (order == NKA_HIP_SUMS_BLOCKED || order == NKA_HIP_SUMS_BLOCKED_ROUNDED))
+    return fail(NKA_HIP_EINVAL, "batch_set_sum_order: a lane batch forms every sum in the reference's order (one lane, element after "
+                                "element): NKA_HIP_SUMS_REFERENCE_ORDER or _AUTO; the fast sums: nka_hip_batch_create");
   if (order == NKA_HIP_SUMS_BLOCKED)
     return fail(NKA_HIP_EINVAL, "batch_set_sum_order: NKA_HIP_SUMS_BLOCKED is not offered by a batch (it has no exchange to save): "
                                 "NKA_HIP_SUMS_BLOCKED_ROUNDED, _REFERENCE_ORDER or _AUTO");
@@ -848,6 +875,7 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
 int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_t ldw) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: null handle");
   if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wide batch (nka_hip_batch_create_wide)");
+  if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_dot_weights")) return rc;
   if (!w_dev) {
@@ -863,6 +891,7 @@ int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_
 int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, int64_t ldw) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: null handle");
   if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wide batch (nka_hip_batch_create_wide)");
+  if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_dot_weights_host")) return rc;
   if (!w_host) {
@@ -926,6 +955,7 @@ static int clear_lengths(nka_hip_batch_t b) {
 
 int nka_hip_batch_set_lengths(nka_hip_batch_t b, const int32_t *len_dev) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_lengths: null handle");
+  if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_lengths: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_lengths")) return rc;
   if (!len_dev) return clear_lengths(b);
@@ -938,6 +968,7 @@ int nka_hip_batch_set_lengths(nka_hip_batch_t b, const int32_t *len_dev) {
 
 int nka_hip_batch_set_lengths_host(nka_hip_batch_t b, const int32_t *len_host) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: null handle");
+  if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_lengths_host")) return rc;
   if (!len_host) return clear_lengths(b);
@@ -1015,6 +1046,7 @@ static int batch_get_slot(nka_hip_batch_t b, bool v, int32_t sys, int32_t slot, 
   if (slot < 1 || slot > b->k.mvec + 1) return fail(NKA_HIP_EINVAL, "batch_get_w/v: slot out of range");
   if (!host_out) return fail(NKA_HIP_EINVAL, "batch_get_w/v: null argument");
   HIP_TRY(hipSetDevice(b->device));
+  if (b->lanes) return nka_batch_lanes_get_slot(b, v, sys, slot, host_out);      // (gathered from the interleaved slots)
   if (b->storage == NKA_HIP_BATCH_STORE_F32) {
     // the slot of the pending pair: its binary64 row of the pending buffers; any other slot: the stored floats, widened
     std::vector<int32_t> ic;

@@ -215,9 +215,21 @@ struct nka_hip_batch_state {
   double *part = nullptr;                   // partial sums, nka_host::wide_part_index: nsys x (2 + 2 mvec) x nchunk
   double *plan_c = nullptr;                 // the combine plan from the scalar kernel to the combine: nsys x (mvec + 1) coefficients
   int32_t *plan_s = nullptr;                //   ... and slots, in list order (the control block's comb_c / comb_slots stay zero)
+  // a LANE batch (nka_hip_batch_create_lanes, nka_batch_lanes.hip): one lane per system, lanes_group systems per workgroup; k.w
+  // and k.v then hold the interleaved slots of nka_host::lanes_slot_offset (k.stride and k.sys_stride are not used)
+  bool lanes = false;
+  int32_t lanes_group = 0;
 };
 
 // nka_batch_wide.hip: the buffers of a wide batch (b->k is complete), and one update of it -- four launches on b->stream
 int nka_batch_wide_alloc(nka_hip_batch_t b);
 void nka_batch_wide_free(nka_hip_batch_t b);
 void nka_batch_wide_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
+// nka_batch_lanes.hip: the slots of a lane batch (b->k.n, mvec, nsys are set; sets k.w, k.v, lanes_group and vector_bytes), one
+// update and one solve step of it -- one launch each on b->stream --, and slot `slot` of system `sys` gathered to the host
+int nka_batch_lanes_alloc(nka_hip_batch_t b);
+void nka_batch_lanes_free(nka_hip_batch_t b);
+void nka_batch_lanes_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
+void nka_batch_lanes_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
+                          double *fnorm);
+int nka_batch_lanes_get_slot(nka_hip_batch_t b, bool v, int32_t sys, int32_t slot, double *host_out);

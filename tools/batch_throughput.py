@@ -49,7 +49,12 @@ alternated in one process, the same windows:
 (b) and (c) twice: every length = vlen, and lengths from a fixed seed, uniform in [vlen / 4, vlen].  Narrow points nsys 256,4096 x
 vlen 1024,16384 x mvec 10,20; wide points, (a) and (c) only, (16, 65 536) and (64, 262 144) x mvec 10,20.  Two conditions, both
 against code that exists without (c): with every length = vlen (c) is not slower than (a) beyond the spread of the five windows;
-with ragged lengths (c) is not slower than (b) on the same lengths beyond that spread.  A point that misses is marked, not tuned."""
+with ragged lengths (c) is not slower than (b) on the same lengths beyond that spread.  A point that misses is marked, not tuned.
+
+--lanes measures the lane batch (nka_hip_batch_create_lanes: one lane per system) with the method of --store32:
+  (a) a narrow batch at SUMS_AUTO; (a') a second one, the control; (b) the lane batch;
+nsys 256,4096,65536 x vlen 8,32,64 x mvec 5,10,20 with accel_update, then accel_step with X, mask, tol and fnorm at vlen 32.  The
+condition at nsys >= 4096: (b) takes less time than (a) by more than the control's difference and the spread of the windows."""
 import argparse
 import ctypes as C
 import os
@@ -285,6 +290,105 @@ def store32_main(args, torch, nka_amd, L, emit):
              f"(spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
     emit(f"# condition: {', '.join(verdicts) if verdicts else 'not measured (no point at 4096 x 16384)'}; {len(points)} points in "
          f"{time.time() - t0:.0f} s")
+    return 0
+
+
+def measure_lanes(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, step):
+    """(a) a narrow batch at SUMS_AUTO (vlen <= 64: the reference order); (a') a second one, the control for what two batches
+    of equal work differ by; (b) the lane batch.  Same inputs, alternated, as measure_store32.  step: accel_step with X, mask,
+    tol (zero: nothing retires) and fnorm instead of accel_update."""
+    npool = mvec + 3
+    if 8.0 * nsys * ((vlen + 31) // 32 * 32) * (mvec + 1) * 2 * 3 + 8.0 * nsys * vlen * (npool + 8) > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    forms = {"a": False, "a2": False, "b": True}
+    Fs, Xs, hs, batches = {}, {}, {}, {}
+    mask = torch.ones(nsys, dtype=torch.int32, device="cuda")
+    tol, fnorm = torch.zeros(nsys, dtype=torch.float64, device="cuda"), torch.zeros(nsys, dtype=torch.float64, device="cuda")
+    for name, lanes in forms.items():
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+        Xs[name] = torch.zeros(nsys, vlen, dtype=torch.float64, device="cuda")
+        batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, lanes=lanes)
+        assert batches[name].kind() == (nka_amd.KIND_LANES if lanes else nka_amd.KIND_NARROW), name
+        hs[name] = batches[name]._handle()
+    ld = vlen
+    upd, stp = L.nka_hip_batch_accel_update, L.nka_hip_batch_accel_step
+    count = [0]
+
+    def run(name, reps):
+        F, h = Fs[name], hs[name]
+        p, px = C.c_void_p(F.data_ptr()), C.c_void_p(Xs[name].data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[count[0] % npool])
+            count[0] += 1
+            if step:
+                assert stp(h, p, ld, px, ld, C.c_void_p(mask.data_ptr()), C.c_void_p(tol.data_ptr()), C.c_void_p(fnorm.data_ptr())) == 0
+            else:
+                assert upd(h, p, ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in forms}
+    for name in forms:                             # warm: fill the lists (steady state), settle clocks and caches
+        count[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    nv = batches["a"].num_vec()                    # (vlen < mvec: a list holds at most vlen independent vectors, the same in all three)
+    for name in forms:
+        assert (batches[name].num_vec() == nv).all(), name
+    for name in forms:
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in forms:
+            ts[name].append(timed(name, reps[name]))
+    assert bool(mask.all()), "a system retired: the windows did not time equal work"
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    for name in forms:
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+    for name in forms:
+        batches[name].delete()
+    del pool, Fs, Xs
+    torch.cuda.empty_cache()
+    return out
+
+
+def lanes_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m, False) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    points += [(n, 32, m, True) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    emit(f"# one call of (a) a narrow batch at SUMS_AUTO (one workgroup of 256 threads per system; its kernels are the parent "
+         f"commit's), (a') a second narrow batch of the same shape -- the control -- and (b) the lane batch "
+         f"(nka_hip_batch_create_lanes: one lane per system); {torch.cuda.get_device_name(0)}; windows >= {args.window} s, median of "
+         f"{args.repeats}, the three alternated on the same inputs; flavour C, full list; the time includes the copy of the input "
+         f"into F (equal for the three)")
+    emit("# systems per workgroup of (b): " + ", ".join(f"mvec {m}: {nka_amd.batch_lanes_limits(m)[0]}" for m in ints(args.mvecs)))
+    emit("# CONDITION at nsys >= 4096: b/a below 1 by more than the larger of the window spreads and |a - a'| / a; nothing is expected at 256")
+    emit(f"{'call':>6} {'nsys':>6} {'vlen':>4} {'mvec':>4} {'a us':>10} {'a2 us':>10} {'b us':>10} {'b/a':>6} {'|a-a2|/a':>8}  condition")
+    t0 = time.time()
+    verdicts = []
+    for n, v, m, step in points:
+        r = measure_lanes(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9, step)
+        what = "step" if step else "update"
+        if r is None:
+            emit(f"{what:>6} {n:6d} {v:4d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        ratio, ctl = r["b"] / r["a"], abs(r["a"] - r["a2"]) / r["a"]
+        noise = max(ctl, r["spread_a"], r["spread_a2"], r["spread_b"])
+        cond = "-"
+        if n >= 4096:
+            cond = "HELD" if 1.0 - ratio > noise else "MISSED"
+            verdicts.append(cond)
+        emit(f"{what:>6} {n:6d} {v:4d} {m:4d} {r['a'] * 1e6:10.1f} {r['a2'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {ratio:6.3f} {ctl:8.3f}  {cond}   "
+             f"(spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
+    emit(f"# condition: {verdicts.count('HELD')} HELD, {verdicts.count('MISSED')} MISSED of {len(verdicts)} points at nsys >= 4096; "
+         f"{len(points)} points in {time.time() - t0:.0f} s")
     return 0
 
 
@@ -658,6 +762,9 @@ def main():
     ap.add_argument("--store32", action="store_true",
                     help="time a batch with binary32 storage beside two binary64 batches (the second: a control); without --nsys / "
                          "--vlens / --mvecs: nsys 256,4096 x vlen 1024,16384 x mvec 10,20, plus 4096 x 64 x 10")
+    ap.add_argument("--lanes", action="store_true",
+                    help="time the lane batch (one lane per system) beside two narrow batches (the second: a control); without "
+                         "--nsys / --vlens / --mvecs: nsys 256,4096,65536 x vlen 8,32,64 x mvec 5,10,20, then accel_step at vlen 32")
     ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
@@ -681,6 +788,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.lanes:
+        for name, grid_l in (("nsys", "256,4096,65536"), ("vlens", "8,32,64"), ("mvecs", "5,10,20")):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_l)
+        return lanes_main(args, torch, nka_amd, L, emit)
     if args.store32:
         for name, grid_s in (("nsys", "256,4096"), ("vlens", "1024,16384"), ("mvecs", "10,20")):
             if getattr(args, name) == ap.get_default(name):
