@@ -61,7 +61,10 @@ enum { NKA_HIP_FLAVOR_DEFAULT = -1 };
  *     sequence (none has ever differed).  With reference-order sums that holds by construction; with the fast passes a
  *     pivot within rounding distance of vtol^2 could in principle fall the other way.
  *  2. REFERENCE-ORDER SUMS (NKA_HIP_SUMS_REFERENCE_ORDER; the default up to n = 64): the returned f -- and h, c, every
- *     stored vector -- carry the BITS of the reference flavour the handle runs, at any n, on one rank or sharded.
+ *     stored vector -- carry the BITS of the reference flavour the handle runs, at any n, on one rank or sharded.  On one
+ *     rank that is held for inputs of magnitude 2^-540 ... 2^600 -- a subnormal or underflowed <d,d>, s == 0 from underflow
+ *     and s == Inf included -- against the oracle, and the fast passes as exact covariance under a scaling of the inputs by
+ *     2^+-400 (tests/test_scale_range_gpu.py).
  *  3. FAST PASSES (the default beyond n = 64, both forms): sums in blocks with fma -- other last bits than the reference's
  *     sequential sums, and closer to f_exact than those from n ~ 1e3 up.  Over a call sequence
  *         TYPICAL  max err(f_device) <= max(base, F * max err(f_reference)),  base = 1e-12 (1e-10 for n >= 1e7),

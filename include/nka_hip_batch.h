@@ -24,7 +24,10 @@
  *            restart (a lone handle: only once its list is full, nka_hip_capture_safe).
  *   BITS     Results are bitwise reproducible and do not depend on nsys, on a system's position in the batch, on ld or the
  *            alignment of its row, or on which other systems are active: no workgroup reads what another writes, there are
- *            no atomics, flags or cooperative launches.
+ *            no atomics, flags or cooperative launches.  The bits are held over the whole binary64 exponent range, inputs of
+ *            magnitude 2^-540 ... 2^600 -- subnormal and underflowed norms, s == 0 from underflow and s == Inf included -- against the
+ *            oracle for the reference order and the lane batch, and as exact covariance under 2^+-400 for the fast sums
+ *            (tests/test_scale_range_gpu.py).
  *   ERRORS   Status codes, nka_hip_last_error() and the resolution of NKA_HIP_FLAVOR_DEFAULT / NKA_HIP_FLAVOR are the core's.
  *            Storage is the lone handle's for the flavour: nka_hip_batch_get_w / _get_v return what nka_hip_get_w / _get_v
  *            return (compact storage in the C flavour: v holds fl(v' - w') of a normalised pair).
