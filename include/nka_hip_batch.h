@@ -232,6 +232,51 @@
  *            threads share, 48 ... 470 us whatever nsys is.  So: tens of thousands of systems of at most 64 unknowns with mvec up
  *            to about 10 -- this kind; fewer systems or mvec = 20 -- the batch above, which returns the same bits; systems
  *            beyond 16 384 unknowns -- WIDE.
+ *   WAVES    nka_hip_batch_create_waves: the same handle type for SHORT systems, 1 <= vlen <= NKA_HIP_BATCH_WAVES_MAX_VLEN, with ONE
+ *            WAVEFRONT PER SYSTEM (nka_amd/csrc/nka_batch_waves.hip).  The batch above gives a system a workgroup of 256 threads,
+ *            of which one runs the scalar step while 255 wait at a barrier, and a 512-element tile that a system of a few hundred
+ *            unknowns fills by a quarter; here a workgroup is four wavefronts that advance four systems -- wavefront w of
+ *            workgroup g owns system 4 g + w through every phase, the grid is ceil(nsys / 4) --, no wavefront ever waits for
+ *            another (no workgroup barrier in the kernel: a masked, retired or absent system's wavefront returns on its own), and a
+ *            tile is 128 elements.  One launch per call.  Storage, control blocks and every query are those of the batch above:
+ *            nothing further is allocated.  mvec, vtol, nsys >= 1 and all three flavours as above.
+ *            OFFERED with their signatures and guarantees (MASKS, ASYNC, GRAPHS from the first update, BITS, the span checks):
+ *            accel_update; accel_step with x, active, tol and fnorm each optional, and its refusals; restart, relax, set_vec_tol,
+ *            set_stream; num_vec, get_state, get_reductions, get_w, get_v, state_digest, storage (NKA_HIP_BATCH_STORE_F64),
+ *            vector_bytes (the formula of the batch above); set_sum_order with NKA_HIP_SUMS_AUTO and _BLOCKED_ROUNDED, which
+ *            both mean the rounded fast sums at EVERY vlen (also at vlen <= 64, where _AUTO of the batch above means the reference
+ *            order).  nka_hip_batch_is_wide returns 0, nka_hip_batch_kind 3.  REFUSED with NKA_HIP_EINVAL, the batch staying
+ *            usable: nka_hip_batch_set_dot_weights and _host (dot_weighted returns 0), nka_hip_batch_set_lengths and _host
+ *            (has_lengths returns 0), NKA_HIP_SUMS_REFERENCE_ORDER and _BLOCKED, binary32 storage (nka_hip_batch_create_stored
+ *            stays the batch above), and creation with vlen above the cap, mvec outside 1 ... 32, nsys < 1 or vtol <= 0; a caller
+ *            who needs one of these has the batch above.
+ *            THE CONTRACT is the NUMERICAL one of the batch above in NKA_HIP_SUMS_BLOCKED_ROUNDED, and the sums are NOT ITS BITS:
+ *            a sum here is two fma per lane and 128-element tile (lane l owns the pair 2l, 2l + 1 of every tile, in increasing
+ *            order) and then the six-level butterfly of one wavefront, where the batch above sums 512-element tiles over 256
+ *            threads and adds four wavefronts.  Every entry of red[] is within gamma(K) sum|x_i y_i| of the exact sum of its
+ *            operands, K = 2 ceil(vlen / 128) + 6 (derived from the kernel, held by tests/test_batch_waves_gpu.py), with the
+ *            zeros of the batch above; the sums on w1' are taken on the ROUNDED w1' the slot will hold; given its sums, the scalar
+ *            step is the reference's by construction (the same statements, run by lane 0 on the wavefront's working copy), and
+ *            the elementwise statements are the flavour's, bit for bit.  The bits of a system depend on its own values alone: not
+ *            on nsys, on the system's position or the wavefront it lands on, on the other systems' masks or values (NaN and Inf
+ *            included), on ld / ldx or on the alignment of a row.
+ *            WHICH KIND, MEASURED: (profiles/r15/batch_waves_throughput.txt, 1 x MI355X): time of a call / time of the batch above at
+ *            NKA_HIP_SUMS_BLOCKED_ROUNDED, default flavour, full lists, the two alternated with a second batch above as the
+ *            control (it differs by at most 3.8 %), mvec = 5 / 10 / 20.  NKA_HIP_BATCH_WAVES_MAX_VLEN = 1024 is MEASURED: the
+ *            largest power of two v such that at 4096 systems, at every vlen <= v of the grid (65, 128, 256, 512, 1024, 2048,
+ *            4096; a build with the cap at 4096 measured them) and at all three mvec, this kind is faster than the batch above by
+ *            more than the control's difference.  At 4096 systems it WINS up to the cap: 0.36 / 0.33 / 0.29 at vlen 65,
+ *            0.37 / 0.33 / 0.30 at 128, 0.44 / 0.39 / 0.31 at 256, 0.81 / 0.59 / 0.39 at 512, 0.93 / 0.73 / 0.52 at 1024; beyond it
+ *            the short lists lose -- 1.09 / 0.94 / 0.69 at 2048, 1.20 / 1.11 / 0.90 at 4096 --, which is why the cap is where it is.
+ *            At 65 536 systems: 0.28 / 0.26 / 0.25 at 65, 0.25 / 0.25 / 0.25 at 128, 0.36 / 0.29 / 0.26 at 256, 0.76 / 0.56 at 512
+ *            (mvec 5 / 10), and 1.01 at 1024 x 5 -- a LOSS inside the cap; a step with x, mask, tol and fnorm at vlen 256, mvec
+ *            10 / 20: 0.42 / 0.35 at 4096 systems, 0.36 / 0.31 at 65 536.  At 256 systems it LOSES EVERYWHERE, 1.04 ... 1.23 up to
+ *            vlen 256, 1.3 ... 1.4 at 512, 1.4 ... 1.8 at 1024 (1.6 ... 2.4 beyond the cap): 64 workgroups cannot fill 256 compute
+ *            units, and a call then costs the latency of one wavefront that sweeps alone what 256 threads share.  So: thousands of
+ *            systems of 65 ... 1024 unknowns -- this kind (the longer the list the larger the gain; at mvec = 5 and vlen 1024 it is
+ *            a draw); a few hundred systems or fewer, longer systems, or a caller who needs weights, lengths, the reference order
+ *            or binary32 storage -- the batch above; at most 64 unknowns and tens of thousands of systems with mvec up to about
+ *            10 -- LANES; beyond 16 384 unknowns -- WIDE.
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -283,7 +328,16 @@ int nka_hip_batch_create_lanes(nka_hip_batch_t *out, int32_t nsys, int64_t vlen,
                                int32_t flavor, int32_t device, void *stream);
 int nka_hip_batch_lanes_limits(int32_t mvec, int32_t *systems_per_group, int64_t *max_vlen);
 int nka_hip_batch_kind(nka_hip_batch_t b);
-int nka_hip_batch_is_wide(nka_hip_batch_t b);                    /* 1 = wide, 0 = narrow or lanes; < 0 on error */
+/* WAVES above: the same handle type with ONE WAVEFRONT PER SYSTEM, four systems per workgroup; 1 <= vlen <=
+ * NKA_HIP_BATCH_WAVES_MAX_VLEN, mvec, vtol and the three flavours as above, nsys >= 1.  Allocates what nka_hip_batch_create
+ * allocates and nothing more (binary64 only).  _waves_limits: the systems one workgroup advances (4) and the cap on vlen, as the
+ * library was built (either output may be NULL).  _kind returns 3 for such a batch. */
+enum { NKA_HIP_BATCH_WAVES_MAX_VLEN = 1024 };
+enum { NKA_HIP_BATCH_KIND_WAVES = 3 };
+int nka_hip_batch_create_waves(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                               int32_t flavor, int32_t device, void *stream);
+int nka_hip_batch_waves_limits(int32_t *systems_per_group, int64_t *max_vlen);
+int nka_hip_batch_is_wide(nka_hip_batch_t b);                    /* 1 = wide, 0 = narrow, lanes or waves; < 0 on error */
 int nka_hip_batch_wide_limits(int64_t *chunk, int64_t *max_vlen);  /* the two constants, as the library was built */
 int nka_hip_batch_destroy(nka_hip_batch_t b);
 

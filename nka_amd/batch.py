@@ -26,7 +26,7 @@ def batch_wide_limits():
 
 
 BATCH_LANES_MAX_VLEN = 64                       # NKA_HIP_BATCH_LANES_MAX_VLEN (include/nka_hip_batch.h, LANES)
-KIND_NARROW, KIND_WIDE, KIND_LANES = 0, 1, 2    # NKA_HIP_BATCH_KIND_*
+KIND_NARROW, KIND_WIDE, KIND_LANES, KIND_WAVES = 0, 1, 2, 3    # NKA_HIP_BATCH_KIND_*
 
 
 def batch_lanes_limits(mvec: int):
@@ -38,6 +38,15 @@ def batch_lanes_limits(mvec: int):
     return int(group.value), int(cap.value)
 
 
+def batch_waves_limits():
+    """(systems_per_group, max_vlen) of a wave batch -- the wavefronts of a workgroup, one system each (4), and
+    NKA_HIP_BATCH_WAVES_MAX_VLEN as the loaded library was built (nka_hip_batch_waves_limits)."""
+    group, cap = C.c_int32(), C.c_int64()
+    L = _lib.load()
+    _check(L.nka_hip_batch_waves_limits(C.byref(group), C.byref(cap)), "nka_hip_batch_waves_limits", L)
+    return int(group.value), int(cap.value)
+
+
 class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
     """A batch of MI355X accelerator objects; see the module docstring."""
 
@@ -46,7 +55,8 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         self._L = _lib.load()          # raises if the HIP library is missing: no CPU path
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
-             stream: int | None = None, wide: bool = False, storage: int = STORE_F64, lanes: bool = False):
+             stream: int | None = None, wide: bool = False, storage: int = STORE_F64, lanes: bool = False,
+             waves: bool = False):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
@@ -58,8 +68,19 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         lanes: ONE LANE PER SYSTEM (nka_hip_batch_create_lanes; include/nka_hip_batch.h, LANES) for very short systems, vlen up
         to batch_lanes_limits(mvec)[1] = 64: every sum in the reference's order, bit-equal to a narrow batch with
         SUMS_REFERENCE_ORDER; accel_update, accel_step, masks, restart / relax and graphs are offered, weights, lengths and the
-        fast sums refused.  Together with wide=True or storage != STORE_F64 it raises NKAError."""
+        fast sums refused.  Together with wide=True or storage != STORE_F64 it raises NKAError.
+        waves: ONE WAVEFRONT PER SYSTEM, four systems per workgroup (nka_hip_batch_create_waves; include/nka_hip_batch.h, WAVES),
+        vlen up to batch_waves_limits()[1] = 1024, on the storage of the default batch: the rounded fast sums at every vlen (their own
+        bits, the numerical contract of SUMS_BLOCKED_ROUNDED); accel_update, accel_step, masks, restart / relax and graphs are
+        offered, weights, lengths and the reference sum order refused.  Together with wide=True, lanes=True or
+        storage != STORE_F64 it raises NKAError."""
         import torch
+
+        if waves and (wide or lanes):
+            raise NKAError("nka_batch init: waves=True excludes wide=True and lanes=True (one wavefront per system, a system split "
+                           "across workgroups, or one lane per system)")
+        if waves and int(storage) != STORE_F64:
+            raise NKAError("nka_batch init: binary32 storage is not offered by a wave batch (storage=STORE_F64)")
 
         if lanes and wide:
             raise NKAError("nka_batch init: lanes=True and wide=True exclude each other (one lane per system, or a system split "
@@ -83,6 +104,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         elif lanes:
             _check(self._L.nka_hip_batch_create_lanes(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                       C.c_void_p(stream)), "nka_hip_batch_create_lanes", self._L)
+        elif waves:
+            _check(self._L.nka_hip_batch_create_waves(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                      C.c_void_p(stream)), "nka_hip_batch_create_waves", self._L)
         else:
             create = self._L.nka_hip_batch_create_wide if wide else self._L.nka_hip_batch_create
             _check(create(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device), C.c_void_p(stream)),
@@ -332,7 +356,7 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         return r == 1
 
     def kind(self) -> int:
-        """KIND_NARROW (one workgroup per system), KIND_WIDE or KIND_LANES (nka_hip_batch_kind)."""
+        """KIND_NARROW (one workgroup per system), KIND_WIDE, KIND_LANES or KIND_WAVES (nka_hip_batch_kind)."""
         r = self._L.nka_hip_batch_kind(self._handle())
         _check(min(r, 0), "batch_kind", self._L)
         return r

@@ -314,6 +314,29 @@ NKA_HOST_DEVICE constexpr int64_t lanes_vector_bytes(int64_t vlen, int mvec, int
   return 2 * 8 * lanes_slot_alloc_elems(vlen, mvec, G, nsys);
 }
 
+// THE WAVE BATCH (nka_hip_batch_create_waves, nka_batch_waves.hip): ONE WAVEFRONT PER SYSTEM.  A workgroup is kWavesGroup = 4
+// wavefronts, wavefront w of workgroup g owns system 4 g + w; the grid is waves_ngroup(nsys) workgroups.  The storage and the
+// control blocks are the narrow batch's (batch_layout).  tests/c/batch_waves_layout_check.cpp paints every piece below.
+//   LDS      four working copies, each in the layout of batch_lds(mvec) (sm and res stay unused: a wavefront's sums never leave
+//            its registers); the copy of wavefront w starts at w * copy_bytes, copy_bytes = batch_lds(mvec).bytes() rounded up to
+//            16 bytes.  22.2 KiB at mvec = 20, 46.1 KiB at 32: below the 64 KiB a launch may ask for without a function attribute.
+//   SUMS     a tile is kWavesTile = 128 elements, lane l owns the pair 2l, 2l + 1 of every tile: two fma per lane and tile,
+//            then the six-level butterfly of wave_sum -- waves_k(n) roundings on the longest path to the result.
+constexpr int kWavesGroup = 4;                          // systems (wavefronts) per workgroup, = kBatchWaves
+constexpr int kWavesTile = 128;                         // elements per sweep step of a wavefront
+struct WavesLds {
+  BatchLds copy;            // the pieces inside one working copy (doubles first, then int32 from the end of the doubles)
+  int64_t copy_bytes;       // bytes between the copies of two wavefronts: a multiple of 16
+  NKA_HOST_DEVICE constexpr int64_t base(int w) const { return (int64_t)w * copy_bytes; }      // bytes from the start of the LDS
+  NKA_HOST_DEVICE constexpr int64_t bytes() const { return kWavesGroup * copy_bytes; }
+};
+NKA_HOST_DEVICE constexpr WavesLds waves_lds(int mvec) {
+  const BatchLds b = batch_lds(mvec);
+  return WavesLds{b, ((int64_t)b.bytes() + 15) / 16 * 16};
+}
+NKA_HOST_DEVICE constexpr int64_t waves_ngroup(int64_t nsys) { return (nsys + kWavesGroup - 1) / kWavesGroup; }
+NKA_HOST_DEVICE constexpr int64_t waves_k(int64_t n) { return 2 * (((n < 1 ? 1 : n) + kWavesTile - 1) / kWavesTile) + 6; }
+
 // THE WIDE BATCH (nka_hip_batch_create_wide, nka_batch_wide.hip): a system is nchunk = ceil(vlen / kWideChunk) chunks, one
 // workgroup each, and an update is four launches: norm, sums, scalar, combine.  tests/c/batch_wide_layout_check.cpp paints
 // every piece below.  (NKA_BATCH_WIDE_CHUNK: the candidate builds that chose the constant, tools/batch_throughput.py --wide.)

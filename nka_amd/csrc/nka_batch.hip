@@ -641,10 +641,11 @@ int set_weights_from_device(nka_hip_batch_t b, const double *src, int64_t ldw, c
 extern "C" {
 
 // the three kinds of batch: `wide` = a system split across workgroups (nka_batch_wide.hip), `lanes` = one lane per system
-// (nka_batch_lanes.hip), neither = one workgroup per system (this file)
+// (nka_batch_lanes.hip), `waves` = one wavefront per system on the storage of this file (nka_batch_waves.hip), none = one workgroup
+// per system (this file)
 static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor, int32_t device,
                         void *stream, bool wide, int32_t storage = NKA_HIP_BATCH_STORE_F64, const char *entry = nullptr,
-                        bool lanes = false) {
+                        bool lanes = false, bool waves = false) {
   const std::string who = entry ? entry : wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
   const bool s32 = storage == NKA_HIP_BATCH_STORE_F32;
   if (!out) return fail(NKA_HIP_EINVAL, who + ": out is NULL");
@@ -663,6 +664,10 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
     if (vlen < 1 || vlen > NKA_HIP_BATCH_LANES_MAX_VLEN)
       return fail(NKA_HIP_EINVAL, who + ": vlen must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_LANES_MAX_VLEN) +
                                       " (one lane forms every sum of a system; longer systems: nka_hip_batch_create)");
+  } else if (waves) {
+    if (vlen < 1 || vlen > NKA_HIP_BATCH_WAVES_MAX_VLEN)
+      return fail(NKA_HIP_EINVAL, who + ": vlen must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_WAVES_MAX_VLEN) +
+                                      " (one wavefront sweeps a system; longer systems: nka_hip_batch_create)");
   } else if (vlen < 1 || vlen > NKA_HIP_BATCH_MAX_VLEN)
     return fail(NKA_HIP_EINVAL, "nka_hip_batch_create: vlen must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_VLEN) +
                                     " (longer systems: nka_hip_batch_create_wide, or lone handles, nka_hip_create)");
@@ -681,6 +686,7 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
   auto *b = new nka_hip_batch_state();
   b->wide = wide;
   b->lanes = lanes;
+  b->waves = waves;
   b->device = device;
   b->stream = (hipStream_t)stream;
   b->flavor = flavor;
@@ -768,8 +774,14 @@ int nka_hip_batch_create_lanes(nka_hip_batch_t *out, int32_t nsys, int64_t vlen,
                                int32_t device, void *stream) {
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_lanes", true);
 }
+int nka_hip_batch_create_waves(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                               int32_t device, void *stream) {
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_waves", false,
+                      true);
+}
 int nka_hip_batch_kind(nka_hip_batch_t b) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_kind: null handle");
+  if (b->waves) return NKA_HIP_BATCH_KIND_WAVES;
   return b->lanes ? NKA_HIP_BATCH_KIND_LANES : b->wide ? NKA_HIP_BATCH_KIND_WIDE : NKA_HIP_BATCH_KIND_NARROW;
 }
 int nka_hip_batch_storage(nka_hip_batch_t b) { return b ? b->storage : fail(NKA_HIP_EINVAL, "batch_storage: null handle"); }
@@ -805,6 +817,7 @@ int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, con
   if (int rc = check_mask(b, active_dev, "batch_accel_update: active")) return rc;
   if (b->wide) nka_batch_wide_update(b, f_dev, ld, active_dev);
   else if (b->lanes) nka_batch_lanes_update(b, f_dev, ld, active_dev);
+  else if (b->waves) nka_batch_waves_update(b, f_dev, ld, active_dev);
   else launch_flavor(b, f_dev, ld, active_dev);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -835,6 +848,7 @@ int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, doubl
     if (t0 < n0 + len && n0 < t0 + len) return fail(NKA_HIP_EINVAL, "batch_accel_step: fnorm overlaps tol (a threshold would be overwritten while it is read)");
   }
   if (b->lanes) nka_batch_lanes_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
+  else if (b->waves) nka_batch_waves_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else launch_flavor(b, f_dev, ld, active_dev, StepArgs{x_dev, x_dev ? ldx : 0, tol_dev, fnorm_dev});
   HIP_TRY(hipGetLastError());
   return 0;
@@ -863,6 +877,9 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
   if (b->lanes && (order == NKA_HIP_SUMS_BLOCKED || order == NKA_HIP_SUMS_BLOCKED_ROUNDED))
     return fail(NKA_HIP_EINVAL, "batch_set_sum_order: a lane batch forms every sum in the reference's order (one lane, element after "
                                 "element): NKA_HIP_SUMS_REFERENCE_ORDER or _AUTO; the fast sums: nka_hip_batch_create");
+  if (b->waves && order != NKA_HIP_SUMS_AUTO && order != NKA_HIP_SUMS_BLOCKED_ROUNDED)
+    return fail(NKA_HIP_EINVAL, "batch_set_sum_order: a wave batch forms the rounded fast sums only (one wavefront per system): "
+                                "NKA_HIP_SUMS_BLOCKED_ROUNDED or _AUTO; the reference order: nka_hip_batch_create");
   if (order == NKA_HIP_SUMS_BLOCKED)
     return fail(NKA_HIP_EINVAL, "batch_set_sum_order: NKA_HIP_SUMS_BLOCKED is not offered by a batch (it has no exchange to save): "
                                 "NKA_HIP_SUMS_BLOCKED_ROUNDED, _REFERENCE_ORDER or _AUTO");
@@ -876,6 +893,7 @@ int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: null handle");
   if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wide batch (nka_hip_batch_create_wide)");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
+  if (b->waves) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_dot_weights")) return rc;
   if (!w_dev) {
@@ -892,6 +910,7 @@ int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, 
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: null handle");
   if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wide batch (nka_hip_batch_create_wide)");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
+  if (b->waves) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_dot_weights_host")) return rc;
   if (!w_host) {
@@ -956,6 +975,7 @@ static int clear_lengths(nka_hip_batch_t b) {
 int nka_hip_batch_set_lengths(nka_hip_batch_t b, const int32_t *len_dev) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_lengths: null handle");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_lengths: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
+  if (b->waves) return fail(NKA_HIP_EINVAL, "batch_set_lengths: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_lengths")) return rc;
   if (!len_dev) return clear_lengths(b);
@@ -969,6 +989,7 @@ int nka_hip_batch_set_lengths(nka_hip_batch_t b, const int32_t *len_dev) {
 int nka_hip_batch_set_lengths_host(nka_hip_batch_t b, const int32_t *len_host) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: null handle");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
+  if (b->waves) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_lengths_host")) return rc;
   if (!len_host) return clear_lengths(b);

@@ -219,6 +219,9 @@ struct nka_hip_batch_state {
   // and k.v then hold the interleaved slots of nka_host::lanes_slot_offset (k.stride and k.sys_stride are not used)
   bool lanes = false;
   int32_t lanes_group = 0;
+  // a WAVE batch (nka_hip_batch_create_waves, nka_batch_waves.hip): one wavefront per system; storage and control blocks are the
+  // narrow batch's, nothing further is allocated
+  bool waves = false;
 };
 
 // nka_batch_wide.hip: the buffers of a wide batch (b->k is complete), and one update of it -- four launches on b->stream
@@ -233,3 +236,7 @@ void nka_batch_lanes_update(nka_hip_batch_t b, double *f, int64_t ld, const int3
 void nka_batch_lanes_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
                           double *fnorm);
 int nka_batch_lanes_get_slot(nka_hip_batch_t b, bool v, int32_t sys, int32_t slot, double *host_out);
+// nka_batch_waves.hip: one update and one solve step of a wave batch -- one launch each on b->stream
+void nka_batch_waves_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
+void nka_batch_waves_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
+                          double *fnorm);

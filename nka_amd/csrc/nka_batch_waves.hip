@@ -1,0 +1,351 @@
+// nka_batch_waves.hip -- the WAVE batch of include/nka_hip_batch.h (nka_hip_batch_create_waves): ONE WAVEFRONT PER SYSTEM, four
+// systems per workgroup, for systems between the lane batch (vlen <= 64) and the lengths at which the narrow batch
+// (nka_batch.hip: a workgroup of 256 threads per system) fills its tiles.  Wavefront w of workgroup g owns system 4 g + w through
+// every phase; the storage, the control blocks and every host entry are the narrow batch's.
+//   0 skip      sys >= nsys or active[sys] == 0: the wavefront returns before any byte of the system is read or written
+//   1 load      h, c and the links into the wavefront's working copy in LDS, all lanes; lane 0 lists the older entries (the list
+//               length is read HERE, on the device: graphs from the first update)
+//   2 norm      sum d^2, d = fl(w1 - f) [, sum f^2 in the same sweep: the step]; s = sqrt          -- a step may retire here
+//   3 sums      on the ROUNDED w1' = batch_nrm<RCP>(d, s, 1/s): <f,w1'>, <w1',w_p>, <f,w_p>, kBatchGroup older vectors per sweep,
+//               kBatchAcc accumulators; red[] zeros as in the narrow kernel
+//   4 scalar    lane 0: batch_scalar_step (nka_batch_dev.hpp) on the wavefront's copy
+//   5 store     the copy and red[] back to the control block, all lanes
+//   6 combine   normalise the pending pair, combine in list order with comb1<COMB> (compact storage in flavour C),
+//               w_new = f_in, v_new = f_out, f [, x = fl(x - f_out)]; four pairs' loads in flight
+// SYNCHRONISATION: design 1 of the two the kind allows -- NO __syncthreads() ANYWHERE.  A wavefront never touches another
+// wavefront's copy or another system's memory, so nothing orders wavefronts against each other, and a wavefront that is masked,
+// retired or absent returns on its own while its three neighbours go on.  Inside a wavefront the LDS serves the instructions of
+// the wavefront in the order they were issued; what is left is to keep the COMPILER from moving an LDS access of one lane across
+// the point where another lane's access must have been issued: wave_sync() below -- a release fence, wave_barrier, an acquire
+// fence, all at wavefront scope; no instruction beyond the waits the fences imply.  It stands wherever one lane writes LDS that
+// another lane of the same wavefront reads (after the load, after lane 0's list walk, around the scalar step).  Global memory:
+// every element of f, x and the slots is read and written by ONE lane in all phases (pair 2l, 2l + 1 of every tile), and the
+// control block is read before it is written.  No flags, no spinning, no atomics, no cooperative launch.
+// THE WAVE SUM.  A tile is kWavesTile = 128 elements; lane l owns the pair 2l, 2l + 1 of every tile and meets its pairs in
+// increasing order on every path (full tiles: straight-line code, every load of the tile issued before the first wait; the ragged
+// last tile: guarded).  A sum is two fma per lane and tile into the lane's accumulator, then the six-level butterfly of wave_sum
+// (nka_device.hpp: x += x[lane + off], off = 32, 16, 8, 4, 2, 1, through registers), valid in lane 0.  Hence the longest chain of
+// roundings that reaches the result:
+//       waves_k(n) = 2 * ceil(n / 128) + 6                                                     (nka_host::waves_k)
+// A row of f or x that is 16-byte aligned is read with 16-byte accesses, any other with two 8-byte accesses of the same pair;
+// stored vectors are always 16-byte accesses.  The bits therefore depend on the system's own values alone: not on nsys, on the
+// position or the wavefront the system lands on, on its neighbours, on ld / ldx or on the alignment of a row.  They are NOT the
+// narrow batch's bits (its tile is 512 elements over 256 threads, plus three cross-wavefront additions): the contract is the
+// numerical one of NKA_HIP_SUMS_BLOCKED_ROUNDED.
+#include "nka_batch_dev.hpp"
+
+#include <cstdint>
+#include <string>
+#include <type_traits>
+
+using namespace nka;
+
+namespace {
+
+using nka_host::kWavesGroup;
+using nka_host::kWavesTile;
+constexpr int kWavesThreads = 64 * kWavesGroup;
+
+static_assert(kWavesGroup == kBatchWaves && kWavesThreads == kBatchThreads, "a workgroup is four wavefronts");
+static_assert(kWavesTile == 2 * 64, "lane l owns the pair 2l, 2l + 1 of a tile");
+static_assert(nka_host::waves_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 64 * 1024, "dynamic LDS a launch may ask for without an attribute");
+static_assert(NKA_HIP_BATCH_WAVES_MAX_VLEN <= NKA_HIP_BATCH_MAX_VLEN && NKA_HIP_BATCH_WAVES_MAX_VLEN % kWavesTile == 0,
+              "the cap is whole tiles, inside the narrow batch's range (the storage is the narrow batch's)");
+
+// what a solve step takes beside the update's arguments (the StepArgs of nka_batch.hip); each pointer may be NULL
+struct StepArgs {
+  double *x;
+  int64_t ldx;
+  const double *tol;
+  double *fnorm;
+};
+
+// one lane's LDS traffic ordered against the other lanes' of the SAME wavefront (the head comment, SYNCHRONISATION)
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the sum over the wavefront, in every lane (wave_sum leaves it in lane 0)
+__device__ __forceinline__ double wave_sum_all(double x) { return readlane_f64(wave_sum(x), 0); }
+
+// One sweep over a system's elements at wavefront width: body(FULL, FVEC, i) for this lane's pair i = 2l, 2l + 128, ... -- the full
+// tiles first, then the ragged one with guards (batch_sweep of nka_batch_dev.hpp with a tile of 128).
+template <class Body>
+__device__ __forceinline__ void waves_sweep(int64_t n, bool fvec, int lane, Body body) {
+  using T = std::true_type;
+  using F = std::false_type;
+  int64_t base = 0;
+  if (fvec) for (; base + kWavesTile <= n; base += kWavesTile) body(T{}, T{}, base + 2 * lane);
+  else for (; base + kWavesTile <= n; base += kWavesTile) body(T{}, F{}, base + 2 * lane);
+  if (base < n) {
+    if (fvec) body(F{}, T{}, base + 2 * lane); else body(F{}, F{}, base + 2 * lane);
+  }
+}
+
+// Step...: nothing (the update) or one StepArgs (the solve step); a step writes active[sys] = 0 when the system retires.
+template <int COMB, class... Step>
+__global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, double *__restrict__ f_all, int64_t ld,
+                                                                const int32_t *__restrict__ active, Step... step) {
+#pragma clang fp contract(off)      // elementwise statements round like the reference; fma is explicit
+  constexpr bool STEP = sizeof...(Step) == 1;
+  static_assert(sizeof...(Step) <= 1, "nothing, or one StepArgs");
+  constexpr int NNRM = STEP ? 2 : 1;      // sums of phase 2: [<f,f>,] <d,d>
+  constexpr bool RCP = (COMB == 1);
+  constexpr bool COMPACT = (COMB == 2);
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (uniform: addresses of the system in scalar registers)
+  const int64_t sys = (int64_t)blockIdx.x * kWavesGroup + wv;
+  // ---- phase 0: an absent or a masked system; the wavefront leaves alone ----
+  if (sys >= a.nsys) return;
+  if (active != nullptr && active[sys] == 0) return;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int mvec = a.mvec, m1 = mvec + 1, nh = (m1 + 1) * (m1 + 1);
+  const int64_t n = a.n;
+  const Ctl ctl = batch_ctl(a, (int)sys);
+  double *const f = f_all + (size_t)sys * ld;
+  double *const W = a.w + (size_t)sys * a.sys_stride, *const V = a.v + (size_t)sys * a.sys_stride;
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;      // (stored vectors: always 16-byte aligned)
+
+  const nka_host::WavesLds wl = nka_host::waves_lds(mvec);
+  const nka_host::BatchLds &lds = wl.copy;
+  double *const shd = reinterpret_cast<double *>(smem + wl.base(wv));      // this wavefront's working copy
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  Lst L;
+  L.h = shd + lds.h;
+  L.c = shd + lds.c;
+  double *const red = shd + lds.red;
+  double *const cc = shd + lds.cc;           // combine plan: coefficients in list order (slots: cs)
+  L.next = shi + lds.next;
+  L.prev = shi + lds.prev;
+  int32_t *const ps = shi + lds.ps;          // older list entries at entry, in list order
+  int32_t *const cs = shi + lds.cs;
+  int32_t *const hdr = shi + lds.hdr;
+  L.m1 = m1;
+  L.mvec = mvec;
+
+  // ---- phase 1: the working copy ----
+  for (int i = lane; i < nh; i += 64) L.h[i] = ctl.h()[i];
+  for (int i = lane; i < m1 + 1; i += 64) {
+    L.c[i] = ctl.c()[i];
+    L.next[i] = ctl.next()[i];
+    L.prev[i] = ctl.prev()[i];
+  }
+  for (int i = lane; i < 2 + 2 * mvec; i += 64) red[i] = 0.0;      // an update rewrites every entry
+  L.subspace = L.pending = L.first = L.last = L.free_ = 0;
+  L.vtol = 0.0;
+  wave_sync();
+  if (lane == 0) {
+    lst_load_scalars(L, ctl);
+    L.vtol = ctl.dc[DC_VTOL];
+    int no = 0;
+    for (int k = L.pending ? L.next[L.first] : L.first; k != 0 && no < m1; k = L.next[k]) ps[no++] = k;
+    hdr[HDR_PENDING] = L.pending;
+    hdr[HDR_FIRST] = L.first;
+    hdr[HDR_NOLDER] = no;
+  }
+  wave_sync();
+  const int pending = hdr[HDR_PENDING], nolder = hdr[HDR_NOLDER];
+  const double *const w1 = pending ? W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride : W;      // (no pending pair: loaded, never used)
+
+  // ---- phase 2: the norm (F08:266-267), and the step's residual norm ----
+  double s = 0.0;
+  [[maybe_unused]] double ff = 0.0;
+  if (pending) {
+    double acc[NNRM] = {};
+    waves_sweep(n, fvec, lane, [&](auto full, auto fv_, int64_t i) {
+      constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+      const d2 fv = ld_tile<FULL, FV>(f, i, n), wv_ = ld_tile<FULL, true>(w1, i, n);
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+        if (FULL || i + q < n) {
+          const double d = wv_[q] - fv[q];
+          acc[NNRM - 1] = fma(d, d, acc[NNRM - 1]);
+          if constexpr (STEP) acc[0] = fma(fv[q], fv[q], acc[0]);
+        }
+    });
+    const double dd = wave_sum_all(acc[NNRM - 1]);
+    if constexpr (STEP) ff = wave_sum_all(acc[0]);
+    s = sqrt(dd);
+    if (lane == 0) red[0] = dd;
+  } else if constexpr (STEP) {      // no pending pair (first update, after a restart): f is swept alone, the same chain
+    double acc = 0.0;
+    waves_sweep(n, fvec, lane, [&](auto full, auto fv_, int64_t i) {
+      constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+      const d2 fv = ld_tile<FULL, FV>(f, i, n);
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+        if (FULL || i + q < n) acc = fma(fv[q], fv[q], acc);
+    });
+    ff = wave_sum_all(acc);
+  }
+  // ---- STEP: the residual norm and the stop rule.  r is the same value in every lane and tol[sys] is written by nobody, so the
+  // wavefront leaves as one; nothing but its own LDS has been written so far ----
+  [[maybe_unused]] double *xrow = nullptr;      // this system's row of the iterate, if there is one
+  [[maybe_unused]] bool xvec = false;
+  if constexpr (STEP) {
+    const StepArgs &st = (step, ...);
+    const double r = sqrt(ff);
+    if (lane == 0 && st.fnorm != nullptr) st.fnorm[sys] = r;
+    if (st.tol != nullptr && r <= st.tol[sys]) {      // (a NaN on either side: false, the system goes on)
+      if (lane == 0) const_cast<int32_t *>(active)[sys] = 0;
+      return;
+    }
+    if (st.x != nullptr) {
+      xrow = st.x + (size_t)sys * st.ldx;
+      xvec = (reinterpret_cast<uintptr_t>(xrow) % 16) == 0;
+    }
+  }
+  const bool normed = pending && s != 0.0;      // (s == 0: the scalar step relaxes, F08:275; NaN: goes on, like the reference)
+  const double rs = 1.0 / s;
+
+  // ---- phase 3: every other sum, on the rounded w1' (F08:286-290, 371) ----
+  const int ngroup = (nolder + kBatchGroup - 1) / kBatchGroup;
+  for (int g = 0; g < (ngroup > 0 ? ngroup : (normed ? 1 : 0)); g++) {
+    const double *wk[kBatchGroup];
+#pragma unroll
+    for (int j = 0; j < kBatchGroup; j++) {
+      const int p = g * kBatchGroup + j;
+      wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1;   // (beyond the list: a re-read, discarded)
+    }
+    double acc[kBatchAcc];
+#pragma unroll
+    for (int q = 0; q < kBatchAcc; q++) acc[q] = 0.0;
+    waves_sweep(n, fvec, lane, [&](auto full, auto fv_, int64_t i) {
+      constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+      const d2 fv = ld_tile<FULL, FV>(f, i, n);
+      const d2 dv = ld_tile<FULL, true>(w1, i, n);     // (no pending pair: a stored vector whose value is not used)
+      d2 wv_[kBatchGroup];
+#pragma unroll
+      for (int j = 0; j < kBatchGroup; j++) wv_[j] = ld_tile<FULL, true>(wk[j], i, n);
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+        if (FULL || i + q < n) {
+          const double fq = fv[q];
+          if (normed) {
+            const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
+            if (g == 0) acc[2 * kBatchGroup] = fma(fq, wn, acc[2 * kBatchGroup]);
+#pragma unroll
+            for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wn, wv_[j][q], acc[j]);
+          }
+#pragma unroll
+          for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fq, wv_[j][q], acc[kBatchGroup + j]);
+        }
+    });
+#pragma unroll
+    for (int q = 0; q < kBatchAcc; q++) acc[q] = wave_sum(acc[q]);      // (valid in lane 0, which alone uses them)
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < kBatchGroup; j++)
+        if (g * kBatchGroup + j < nolder) {
+          if (normed) red[2 + g * kBatchGroup + j] = acc[j];
+          red[2 + mvec + g * kBatchGroup + j] = acc[kBatchGroup + j];
+        }
+      if (g == 0 && normed) red[1] = acc[2 * kBatchGroup];
+    }
+  }
+
+  // ---- phase 4: the scalar step on this wavefront's working copy (red, ps: written by lane 0 itself) ----
+  if (lane == 0) batch_scalar_step(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr);
+  wave_sync();
+
+  // ---- phase 5: the working copy back ----
+  for (int i = lane; i < nh; i += 64) ctl.h()[i] = L.h[i];
+  for (int i = lane; i < m1 + 1; i += 64) {
+    ctl.c()[i] = L.c[i];
+    ctl.next()[i] = L.next[i];
+    ctl.prev()[i] = L.prev[i];
+  }
+  for (int i = lane; i < 2 + 2 * mvec; i += 64) ctl.red()[i] = red[i];
+
+  // ---- phase 6: normalise the pending pair, combine, ring stores (F08:282-283, 361, 395-404) ----
+  const int ncomb = hdr[HDR_NCOMB];
+  const bool norm0 = hdr[HDR_NORMED] != 0;      // pair 0 of the plan is the pending pair, still raw
+  double *const wnew = W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
+  waves_sweep(n, fvec, lane, [&](auto full, auto fv_, int64_t i) {
+    constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+    if (!FULL && i >= n) return;
+    const d2 fin = ld_tile<FULL, FV>(f, i, n);
+    d2 x = fin;
+    [[maybe_unused]] d2 xit = {0.0, 0.0};      // STEP: the iterate's pair, loaded with the other loads of the tile
+    if constexpr (STEP)
+      if (xrow != nullptr) xit = xvec ? ld_tile<FULL, true>(xrow, i, n) : ld_tile<FULL, false>(xrow, i, n);
+    int j0 = 0;
+    if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
+      double *const wk = W + (size_t)(cs[0] - 1) * a.stride, *const vk = V + (size_t)(cs[0] - 1) * a.stride;
+      d2 wv_ = ld_tile<FULL, true>(wk, i, n), vv = ld_tile<FULL, true>(vk, i, n);
+      const double c = cc[0];
+#pragma unroll
+      for (int q = 0; q < 2; q++) {
+        const double wn = batch_nrm<RCP>(wv_[q] - fin[q], s, rs);
+        const double vn = batch_nrm<RCP>(vv[q], s, rs);
+        wv_[q] = wn;
+        vv[q] = COMPACT ? vn - wn : vn;
+        x[q] = COMPACT ? x[q] + c * vv[q] : comb1<COMB>(x[q], c, wv_[q], vv[q]);
+      }
+      st_tile<FULL, true>(wk, i, n, wv_);
+      st_tile<FULL, true>(vk, i, n, vv);
+      j0 = 1;
+    }
+    constexpr int U = 4;      // pairs whose loads are in flight together (beyond the plan: the last pair again, not applied)
+    for (int j = j0; j < ncomb; j += U) {
+      d2 wv_[U], vv[U];
+      double c[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int jj = j + u < ncomb ? j + u : ncomb - 1;
+        const size_t off = (size_t)(cs[jj] - 1) * a.stride;
+        c[u] = cc[jj];
+        vv[u] = ld_tile<FULL, true>(V + off, i, n);
+        if (!COMPACT) wv_[u] = ld_tile<FULL, true>(W + off, i, n); else wv_[u] = vv[u];
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (j + u < ncomb) {
+#pragma unroll
+          for (int q = 0; q < 2; q++) x[q] = COMPACT ? x[q] + c[u] * vv[u][q] : comb1<COMB>(x[q], c[u], wv_[u][q], vv[u][q]);
+        }
+    }
+    st_tile<FULL, true>(wnew, i, n, fin);
+    st_tile<FULL, true>(vnew, i, n, x);
+    if (ncomb > 0) st_tile<FULL, FV>(f, i, n, x);      // (nothing to combine: f stays as it is)
+    if constexpr (STEP)
+      if (xrow != nullptr) {
+        xit[0] = xit[0] - x[0];
+        xit[1] = xit[1] - x[1];
+        if (xvec) st_tile<FULL, true>(xrow, i, n, xit); else st_tile<FULL, false>(xrow, i, n, xit);
+      }
+  });
+}
+
+template <int COMB, class... Step>
+void launch_waves_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+  const size_t lds = (size_t)nka_host::waves_lds(b->k.mvec).bytes();
+  hipLaunchKernelGGL((k_waves_update<COMB, Step...>), dim3((unsigned)nka_host::waves_ngroup(b->k.nsys)), dim3(kWavesThreads), lds,
+                     b->stream, b->k, f, ld, active, step...);
+}
+template <class... Step>
+void launch_waves(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+  switch (b->flavor) {
+    case NKA_HIP_FLAVOR_F08_VECTOR: launch_waves_as<1>(b, f, ld, active, step...); break;
+    case NKA_HIP_FLAVOR_C: launch_waves_as<2>(b, f, ld, active, step...); break;
+    default: launch_waves_as<0>(b, f, ld, active, step...);
+  }
+}
+
+}  // namespace
+
+void nka_batch_waves_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active) { launch_waves(b, f, ld, active); }
+
+void nka_batch_waves_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
+                          double *fnorm) {
+  launch_waves(b, f, ld, active, StepArgs{x, x ? ldx : 0, tol, fnorm});
+}
+
+extern "C" int nka_hip_batch_waves_limits(int32_t *systems_per_group, int64_t *max_vlen) {
+  if (systems_per_group) *systems_per_group = kWavesGroup;
+  if (max_vlen) *max_vlen = NKA_HIP_BATCH_WAVES_MAX_VLEN;
+  return 0;
+}

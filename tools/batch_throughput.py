@@ -54,7 +54,16 @@ with ragged lengths (c) is not slower than (b) on the same lengths beyond that s
 --lanes measures the lane batch (nka_hip_batch_create_lanes: one lane per system) with the method of --store32:
   (a) a narrow batch at SUMS_AUTO; (a') a second one, the control; (b) the lane batch;
 nsys 256,4096,65536 x vlen 8,32,64 x mvec 5,10,20 with accel_update, then accel_step with X, mask, tol and fnorm at vlen 32.  The
-condition at nsys >= 4096: (b) takes less time than (a) by more than the control's difference and the spread of the windows."""
+condition at nsys >= 4096: (b) takes less time than (a) by more than the control's difference and the spread of the windows.
+
+--waves measures the wave batch (nka_hip_batch_create_waves: one wavefront per system, four systems per workgroup) with the same
+method:
+  (a) a narrow batch at SUMS_BLOCKED_ROUNDED; (a') a second one, the control; (b) the wave batch;
+nsys 256,4096,65536 x vlen 65,128,256,512,1024,2048,4096 x mvec 5,10,20 with accel_update, then accel_step with X, mask, tol and
+fnorm at vlen 256 x mvec 10,20; a point that needs more than --mem-gb (here 40) is skipped and listed, and so is a vlen beyond
+the cap of the library loaded (a candidate build with a larger NKA_HIP_BATCH_WAVES_MAX_VLEN measures the lengths that decide
+the cap).  THE CAP RULE, evaluated at the end: the largest power of two v such that at nsys = 4096, at every vlen <= v of the grid
+and every mvec, (b) takes less time than (a) by more than |a - a'|; 128 if that holds nowhere."""
 import argparse
 import ctypes as C
 import os
@@ -293,10 +302,11 @@ def store32_main(args, torch, nka_amd, L, emit):
     return 0
 
 
-def measure_lanes(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, step):
+def measure_lanes(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, step, waves=False):
     """(a) a narrow batch at SUMS_AUTO (vlen <= 64: the reference order); (a') a second one, the control for what two batches
     of equal work differ by; (b) the lane batch.  Same inputs, alternated, as measure_store32.  step: accel_step with X, mask,
-    tol (zero: nothing retires) and fnorm instead of accel_update."""
+    tol (zero: nothing retires) and fnorm instead of accel_update.  waves: (b) is the wave batch, (a) and (a') run the rounded
+    fast sums."""
     npool = mvec + 3
     if 8.0 * nsys * ((vlen + 31) // 32 * 32) * (mvec + 1) * 2 * 3 + 8.0 * nsys * vlen * (npool + 8) > mem_budget:
         return None
@@ -308,8 +318,13 @@ def measure_lanes(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budg
     for name, lanes in forms.items():
         Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
         Xs[name] = torch.zeros(nsys, vlen, dtype=torch.float64, device="cuda")
-        batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, lanes=lanes)
-        assert batches[name].kind() == (nka_amd.KIND_LANES if lanes else nka_amd.KIND_NARROW), name
+        if waves:
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, waves=lanes)
+            batches[name].set_sum_order(nka_amd.SUMS_BLOCKED_ROUNDED)
+            assert batches[name].kind() == (nka_amd.KIND_WAVES if lanes else nka_amd.KIND_NARROW), name
+        else:
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, lanes=lanes)
+            assert batches[name].kind() == (nka_amd.KIND_LANES if lanes else nka_amd.KIND_NARROW), name
         hs[name] = batches[name]._handle()
     ld = vlen
     upd, stp = L.nka_hip_batch_accel_update, L.nka_hip_batch_accel_step
@@ -389,6 +404,58 @@ def lanes_main(args, torch, nka_amd, L, emit):
              f"(spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
     emit(f"# condition: {verdicts.count('HELD')} HELD, {verdicts.count('MISSED')} MISSED of {len(verdicts)} points at nsys >= 4096; "
          f"{len(points)} points in {time.time() - t0:.0f} s")
+    return 0
+
+
+def waves_cap(rows, vlens, mvecs):
+    """THE CAP RULE on the measured rows {(nsys, vlen, mvec): (a, a2, b)} of accel_update: the largest power of two v such that at
+    nsys = 4096 every vlen <= v of the grid, at every mvec, was measured and has a - b > |a - a2|; 128 if there is none."""
+    def won(v, m):
+        r = rows.get((4096, v, m))
+        return r is not None and r[0] - r[2] > abs(r[0] - r[1])
+    cap, v = 128, 128
+    while v <= max(vlens):
+        if all(won(u, m) for u in vlens if u <= v for m in mvecs):
+            cap = v
+        v *= 2
+    return cap
+
+
+def waves_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    per_group, cap = nka_amd.batch_waves_limits()
+    # the points that decide the cap first, the largest batches last
+    order = sorted(ints(args.nsys), key=lambda n: (n != 4096, n))
+    points = [(n, v, m, False) for n in order for v in ints(args.vlens) for m in ints(args.mvecs)]
+    points += [(n, 256, m, True) for n in order for m in ints(args.mvecs) if m != 5]
+    emit(f"# one call of (a) a narrow batch at SUMS_BLOCKED_ROUNDED (one workgroup of 256 threads per system; its kernels are the "
+         f"parent commit's), (a') a second narrow batch of the same shape -- the control -- and (b) the wave batch "
+         f"(nka_hip_batch_create_waves: one wavefront per system, {per_group} systems per workgroup); {torch.cuda.get_device_name(0)}; "
+         f"windows >= {args.window} s, median of {args.repeats}, the three alternated on the same inputs; flavour C, full list; the "
+         f"time includes the copy of the input into F (equal for the three)")
+    emit(f"# NKA_HIP_BATCH_WAVES_MAX_VLEN of the library loaded: {cap}")
+    emit("# won: a - b > |a - a'| (THE CAP RULE reads the rows of accel_update at nsys = 4096)")
+    emit(f"{'call':>6} {'nsys':>6} {'vlen':>4} {'mvec':>4} {'a us':>10} {'a2 us':>10} {'b us':>10} {'b/a':>6} {'|a-a2|/a':>8}  won")
+    t0 = time.time()
+    rows, nwon, nlost = {}, 0, 0
+    for n, v, m, step in points:
+        what = "step" if step else "update"
+        if v > cap:
+            emit(f"{what:>6} {n:6d} {v:4d} {m:4d}   EXCLUDED: beyond the cap of the library loaded")
+            continue
+        r = measure_lanes(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9, step, waves=True)
+        if r is None:
+            emit(f"{what:>6} {n:6d} {v:4d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        ratio, ctl = r["b"] / r["a"], abs(r["a"] - r["a2"]) / r["a"]
+        won = r["a"] - r["b"] > abs(r["a"] - r["a2"])
+        nwon, nlost = nwon + won, nlost + (not won)
+        if not step:
+            rows[(n, v, m)] = (r["a"], r["a2"], r["b"])
+        emit(f"{what:>6} {n:6d} {v:4d} {m:4d} {r['a'] * 1e6:10.1f} {r['a2'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {ratio:6.3f} {ctl:8.3f}  "
+             f"{'yes' if won else 'NO'}   (spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
+    emit(f"# won at {nwon} of {nwon + nlost} measured points; {len(points)} points in {time.time() - t0:.0f} s")
+    emit(f"# THE CAP RULE on the rows at nsys = 4096: NKA_HIP_BATCH_WAVES_MAX_VLEN = {waves_cap(rows, ints(args.vlens), ints(args.mvecs))}")
     return 0
 
 
@@ -765,6 +832,10 @@ def main():
     ap.add_argument("--lanes", action="store_true",
                     help="time the lane batch (one lane per system) beside two narrow batches (the second: a control); without "
                          "--nsys / --vlens / --mvecs: nsys 256,4096,65536 x vlen 8,32,64 x mvec 5,10,20, then accel_step at vlen 32")
+    ap.add_argument("--waves", action="store_true",
+                    help="time the wave batch (one wavefront per system) beside two narrow batches at the rounded fast sums (the second: "
+                         "a control); without --nsys / --vlens / --mvecs / --mem-gb: nsys 256,4096,65536 x vlen 65,128,256,512,1024,2048,"
+                         "4096 x mvec 5,10,20, 40 GB, then accel_step at vlen 256 x mvec 10,20; prints the cap its rule yields")
     ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
@@ -788,6 +859,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.waves:
+        for name, grid_w in (("nsys", "256,4096,65536"), ("vlens", "65,128,256,512,1024,2048,4096"), ("mvecs", "5,10,20"), ("mem_gb", 40.0)):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+        return waves_main(args, torch, nka_amd, L, emit)
     if args.lanes:
         for name, grid_l in (("nsys", "256,4096,65536"), ("vlens", "8,32,64"), ("mvecs", "5,10,20")):
             if getattr(args, name) == ap.get_default(name):
