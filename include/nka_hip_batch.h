@@ -116,9 +116,46 @@
  *            the second grid index).  Beside the slots it allocates nsys * (2 + 2 mvec) * nchunk doubles of partial sums and
  *            the combine plan (the control block's comb_slots / comb_c stay zero, so that its digest is the narrow batch's).
  *            NKA_HIP_SUMS_AUTO and _BLOCKED_ROUNDED both mean the rounded fast sums, at every vlen.  REFUSED with NKA_HIP_EINVAL,
- *            the batch staying usable: nka_hip_batch_accel_step; nka_hip_batch_set_dot_weights and _set_dot_weights_host
- *            (nka_hip_batch_dot_weighted returns 0); NKA_HIP_SUMS_REFERENCE_ORDER and _BLOCKED through _set_sum_order.  A caller who
- *            needs one of these has the batch above up to 16 384 elements and lone handles beyond.
+ *            the batch staying usable: nka_hip_batch_accel_step on a batch of nka_hip_batch_create_wide (a batch of
+ *            nka_hip_batch_create_wide_step offers it: STEP below); on every wide batch nka_hip_batch_set_dot_weights and
+ *            _set_dot_weights_host (nka_hip_batch_dot_weighted returns 0), NKA_HIP_SUMS_REFERENCE_ORDER and _BLOCKED through
+ *            _set_sum_order, and binary32 storage.  A caller who needs one of the last three has the batch above up to 16 384
+ *            elements and lone handles beyond.
+ *            STEP of a wide batch: nka_hip_batch_create_wide_step is nka_hip_batch_create_wide -- the same limits, refusals, kind
+ *            (nka_hip_batch_kind 1, _is_wide 1) and accel_update, bit for bit and launch for launch -- with ONE MORE BUFFER: nsys *
+ *            nchunk doubles, one partial of <f,f> per chunk and system, zero-initialised, freed at destroy, never moved.  That
+ *            buffer is why the step has a creation entry of its own: what nka_hip_batch_create_wide allocates stays what it
+ *            documents, and such a batch keeps refusing the step.  nka_hip_batch_offers_step tells the two apart.  On a batch of
+ *            the new entry nka_hip_batch_accel_step is FOUR launches in a line (nka_amd/csrc/nka_batch_wide_step.hip), per
+ *            system active on entry:
+ *              1  r = sqrt(sum_c q_c), q_c the fast-sum <f,f> of chunk c;
+ *              2  q_c = sum fma(f_i, f_i, .) in the chunk's element -> thread map and per-thread order, reduced over the
+ *                 workgroup like every other sum of the chunk (lanes by butterfly, then wavefronts 0, 1, 2, 3);
+ *              3  the partials are added in chunk order from chunk 0, by one thread: r depends on NKA_HIP_BATCH_WIDE_CHUNK and on
+ *                 nothing else, and at one chunk it is the r of the batch above in NKA_HIP_SUMS_BLOCKED_ROUNDED;
+ *              4  fnorm_dev[sys] = r if fnorm_dev is given;
+ *              5  if tol_dev is given and r <= tol_dev[sys] the system retires: active_dev[sys] = 0, and nothing else of it is
+ *                 written -- rows of f and x, control block, red[], slots and digest stay (its partial sums are scratch: no later
+ *                 call reads one it did not write itself).  A NaN on either side compares false;
+ *              6  otherwise the update is BIT-EQUAL to accel_update of a wide batch -- row of f, state, red[], slots --, and
+ *                 x_i = fl(x_i - f_out_i) if x_dev is given, with 16-byte accesses on a 16-byte-aligned row and element by element
+ *                 otherwise: the same bits;
+ *              7  a system inactive on entry has nothing read or written, fnorm_dev[sys] included;
+ *              8  every pointer but f may be NULL;
+ *              9  captured into a graph it is four kernel nodes in a line, from the first call on; nothing is allocated or
+ *                 synchronised.
+ *            tol is read by launches 2 and 3 and fnorm written by launch 3 (their overlap is refused, as above); active[sys] is
+ *            cleared by launch 3, in the one workgroup of that launch that reads the entry, and read again by launch 4: within a
+ *            launch no workgroup reads what another writes.  The host checks are those of STEP above.  LENGTHS below applies: a
+ *            system's r, update and x -= f_out cover len[sys] elements and its own chunks.
+ *            COST, MEASURED (profiles/r16/batch_wide_step_throughput.txt, 1 x MI355X; nsys 16 / 64 / 256 x vlen 32 768 / 65 536 /
+ *            262 144 x mvec 10 / 20; default flavour, full lists; the two points at 256 x 262 144 need more than 40 GB and were
+ *            not measured): a step with x, mask, tol and fnorm, no system retiring, takes 0.80 ... 0.99 x the time of the same
+ *            loop composed from accel_update of a wide batch and three kernels of the caller -- 0.81 / 0.80 / 0.80 at 16 systems
+ *            and mvec 10, 0.90 ... 0.96 at mvec 20 up to 64 systems -- and 0.98 ... 1.11 x the time of a plain wide update.  With
+ *            the composed loop run twice as its own control (it differs from itself by at most 3.0 %), the step is faster by
+ *            more than that difference at 15 of the 16 points and level at one (256 x 65 536 x 20: 0.987, control 3.0 %);
+ *            slower nowhere.  One measurement; no ratio was fixed beforehand.
  *            BOTH CONSTANTS ARE MEASURED (profiles/r11/batch_wide_throughput.txt, 1 x MI355X) and frozen.  CHUNK = 2048: of
  *            2048 / 4096 / 8192 the fastest at (nsys, vlen, mvec) = (16, 65 536, 20) and (64, 262 144, 10): 243.7 / 260.4 /
  *            320.6 us and 828.0 / 831.7 / 853.5 us per update, windows spread 0.1 %.  MAX_VLEN = 1 048 576: by the rule of
@@ -130,8 +167,8 @@
  *            systems: 15.2 / 8.15 x and 11.0 / 6.20 x, 0.50 ... 0.58 of 8 TB/s), at 262 144: 1.65 ... 3.03 x, at 1 048 576:
  *            1.18 ... 1.42 x.  Up to 16 384 elements take the batch above for few or very many short systems and the wide one in
  *            between: at 4096 elements the two are level (wide / narrow 0.90 ... 1.06), at 16 384 the wide batch is 1.04 ... 2.45 x
- *            faster (2.45 x at 16 systems, 1.14 / 1.04 x at 256), and only the batch above has the step, the weights and the
- *            reference order.  FOUR systems: the wide batch wins at mvec = 10 (1.05 ... 1.95 x) and LOSES to four lone handles at
+ *            faster (2.45 x at 16 systems, 1.14 / 1.04 x at 256); both have the step (the wide one through
+ *            nka_hip_batch_create_wide_step), and only the batch above has the weights and the reference order.  FOUR systems: the wide batch wins at mvec = 10 (1.05 ... 1.95 x) and LOSES to four lone handles at
  *            mvec = 20 at every length (0.67 ... 0.86 x): the scalar step of a system runs on one thread, 127 us at mvec = 20 (59 %
  *            of an update at 16 x 65 536), and a lone handle's does not.  A lone system stays with a lone handle.
  *   LENGTHS  nka_hip_batch_set_lengths: RAGGED BATCHES without padding weights, on both kinds of batch.  System `sys` is
@@ -306,6 +343,12 @@ int nka_hip_batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32
  * 1 <= vlen <= NKA_HIP_BATCH_WIDE_MAX_VLEN, nsys <= 65535, mvec and vtol as above.  Allocates the partial sums beside the slots. */
 int nka_hip_batch_create_wide(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
                               int32_t flavor, int32_t device, void *stream);
+/* WIDE above, STEP of a wide batch: nka_hip_batch_create_wide with one more buffer (nsys * nchunk doubles), the only wide batch
+ * that offers nka_hip_batch_accel_step.  _offers_step: 1 = accel_step is offered (narrow, lanes, waves, and a wide batch of
+ * this entry), 0 = refused (a wide batch of nka_hip_batch_create_wide); < 0 on error. */
+int nka_hip_batch_create_wide_step(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                                   int32_t flavor, int32_t device, void *stream);
+int nka_hip_batch_offers_step(nka_hip_batch_t b);
 /* STORAGE above: how the normalised subspace vectors are kept.  _create_stored with NKA_HIP_BATCH_STORE_F64 is
  * nka_hip_batch_create; with NKA_HIP_BATCH_STORE_F32 it allocates 2*nsys*(mvec+1) slot vectors of binary32 elements at the same
  * stride in elements and two pending buffers of nsys*stride doubles (zero-initialised, freed by destroy only, never moved), and
@@ -343,7 +386,8 @@ int nka_hip_batch_destroy(nka_hip_batch_t b);
 
 /* call a%accel_update(f) for every active system, one launch.  Rows of inactive systems are not touched. */
 int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, const int32_t *active_dev);
-/* STEP above: norm, stop rule, update and correction of every active system, one launch.  x_dev (iterate rows, ldx apart),
+/* STEP above: norm, stop rule, update and correction of every active system, one launch (a wide batch of
+ * nka_hip_batch_create_wide_step: four).  x_dev (iterate rows, ldx apart),
  * active_dev (READ AND WRITTEN), tol_dev (nsys thresholds) and fnorm_dev (nsys doubles out) may each be NULL. */
 int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, double *x_dev, int64_t ldx, int32_t *active_dev,
                              const double *tol_dev, double *fnorm_dev);

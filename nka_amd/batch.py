@@ -56,12 +56,12 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
              stream: int | None = None, wide: bool = False, storage: int = STORE_F64, lanes: bool = False,
-             waves: bool = False):
+             waves: bool = False, step: bool = False):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
-        restart / relax, graphs and per-system lengths -- set_lengths -- are offered; accel_step, weights and the reference
-        sum order are refused).  storage=STORE_F32 (nka_hip_batch_create_stored; include/nka_hip_batch.h, STORAGE): the
+        restart / relax, graphs and per-system lengths -- set_lengths -- are offered; accel_step -- without step=True, below --, weights and the
+        reference sum order are refused).  storage=STORE_F32 (nka_hip_batch_create_stored; include/nka_hip_batch.h, STORAGE): the
         normalised subspace vectors are kept in binary32 -- 0.55 of the slot memory at mvec = 20 --, every product and sum
         still binary64, the pending pair still binary64.  Such a batch runs the default flavour (FLAVOR_C) and the rounded fast
         sums only: the F08 flavours, set_sum_order(SUMS_REFERENCE_ORDER) and wide=True are refused (NKAError).
@@ -73,9 +73,15 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         vlen up to batch_waves_limits()[1] = 1024, on the storage of the default batch: the rounded fast sums at every vlen (their own
         bits, the numerical contract of SUMS_BLOCKED_ROUNDED); accel_update, accel_step, masks, restart / relax and graphs are
         offered, weights, lengths and the reference sum order refused.  Together with wide=True, lanes=True or
-        storage != STORE_F64 it raises NKAError."""
+        storage != STORE_F64 it raises NKAError.
+        step (with wide=True only): the wide batch WITH the solve step (nka_hip_batch_create_wide_step; include/nka_hip_batch.h,
+        WIDE: STEP of a wide batch) -- one more buffer of nsys x nchunk doubles, accel_step as four launches, everything else the
+        wide batch bit for bit.  Every other kind offers the step already: step=True without wide=True raises NKAError."""
         import torch
 
+        if step and not wide:
+            raise NKAError("nka_batch init: step=True selects the wide batch with the solve step and needs wide=True (every other "
+                           "kind offers accel_step already)")
         if waves and (wide or lanes):
             raise NKAError("nka_batch init: waves=True excludes wide=True and lanes=True (one wavefront per system, a system split "
                            "across workgroups, or one lane per system)")
@@ -107,6 +113,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         elif waves:
             _check(self._L.nka_hip_batch_create_waves(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                       C.c_void_p(stream)), "nka_hip_batch_create_waves", self._L)
+        elif wide and step:
+            _check(self._L.nka_hip_batch_create_wide_step(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                          C.c_void_p(stream)), "nka_hip_batch_create_wide_step", self._L)
         else:
             create = self._L.nka_hip_batch_create_wide if wide else self._L.nka_hip_batch_create
             _check(create(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device), C.c_void_p(stream)),
@@ -196,7 +205,8 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         nka_hip_batch.h, STEP): fnorm[sys] = sqrt(dp(f, f)) with the batch's own dot product; if that is <= tol[sys] the system
         retires itself -- active[sys] = 0, nothing else of it written --, otherwise F's row is updated as by accel_update and
         X's row becomes X - F.  X: like F, with its own row stride, not overlapping F.  active: as in accel_update, but WRITTEN.
-        tol, fnorm: contiguous 1-d float64 CUDA tensors of nsys entries; tol needs active.  Each may be None."""
+        tol, fnorm: contiguous 1-d float64 CUDA tensors of nsys entries; tol needs active.  Each may be None.  A wide batch
+        offers it only when created with step=True, and then as four launches in a line (offers_step())."""
         h = self._handle()
         what = "batch accel_step"
         ptr, ld = self._rows(F, what)
@@ -354,6 +364,12 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         r = self._L.nka_hip_batch_is_wide(self._handle())
         _check(min(r, 0), "batch_is_wide", self._L)
         return r == 1
+
+    def offers_step(self) -> bool:
+        """True where accel_step is offered: every kind but a wide batch created without step=True (nka_hip_batch_offers_step)."""
+        r = self._L.nka_hip_batch_offers_step(self._handle())
+        _check(min(r, 0), "batch_offers_step", self._L)
+        return bool(r)
 
     def kind(self) -> int:
         """KIND_NARROW (one workgroup per system), KIND_WIDE, KIND_LANES or KIND_WAVES (nka_hip_batch_kind)."""

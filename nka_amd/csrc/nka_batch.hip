@@ -645,7 +645,7 @@ extern "C" {
 // per system (this file)
 static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor, int32_t device,
                         void *stream, bool wide, int32_t storage = NKA_HIP_BATCH_STORE_F64, const char *entry = nullptr,
-                        bool lanes = false, bool waves = false) {
+                        bool lanes = false, bool waves = false, bool wide_step = false) {
   const std::string who = entry ? entry : wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
   const bool s32 = storage == NKA_HIP_BATCH_STORE_F32;
   if (!out) return fail(NKA_HIP_EINVAL, who + ": out is NULL");
@@ -742,6 +742,10 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
     rc = fail(NKA_HIP_EHIP, who + ": initialising the batch failed");
   }
   if (!rc && wide) rc = nka_batch_wide_alloc(b);
+  if (!rc && wide_step) {      // (one more buffer than a batch of nka_hip_batch_create_wide holds; nothing else differs)
+    b->wide_step = true;
+    rc = nka_batch_wide_step_alloc(b);
+  }
   if (!rc) {
     hipLaunchKernelGGL(k_batch_set_vtol, dim3((unsigned)((nsys + 63) / 64)), dim3(64), 0, b->stream, k, vtol);
     hipLaunchKernelGGL(k_batch_list_op, dim3((unsigned)((nsys + 63) / 64)), dim3(64), 0, b->stream, k, (int)kBatchOpRestart,
@@ -766,6 +770,11 @@ int nka_hip_batch_create_wide(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, 
                               int32_t device, void *stream) {
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, true);
 }
+int nka_hip_batch_create_wide_step(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                                   int32_t device, void *stream) {
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, true, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_wide_step", false,
+                      false, true);
+}
 int nka_hip_batch_create_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
                                 int32_t device, void *stream, int32_t storage) {
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, storage, "nka_hip_batch_create_stored");
@@ -787,6 +796,9 @@ int nka_hip_batch_kind(nka_hip_batch_t b) {
 int nka_hip_batch_storage(nka_hip_batch_t b) { return b ? b->storage : fail(NKA_HIP_EINVAL, "batch_storage: null handle"); }
 int64_t nka_hip_batch_vector_bytes(nka_hip_batch_t b) { return b ? b->vector_bytes : (int64_t)fail(NKA_HIP_EINVAL, "batch_vector_bytes: null handle"); }
 int nka_hip_batch_is_wide(nka_hip_batch_t b) { return b ? (b->wide ? 1 : 0) : fail(NKA_HIP_EINVAL, "batch_is_wide: null handle"); }
+int nka_hip_batch_offers_step(nka_hip_batch_t b) {
+  return b ? (b->wide && !b->wide_step ? 0 : 1) : fail(NKA_HIP_EINVAL, "batch_offers_step: null handle");
+}
 
 int nka_hip_batch_destroy(nka_hip_batch_t b) {
   if (!b) return 0;
@@ -804,6 +816,7 @@ int nka_hip_batch_destroy(nka_hip_batch_t b) {
   hipFree(b->pend_w);
   hipFree(b->pend_v);
   nka_batch_wide_free(b);
+  nka_batch_wide_step_free(b);
   nka_batch_lanes_free(b);
   delete b;
   return 0;
@@ -826,7 +839,9 @@ int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, con
 int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, double *x_dev, int64_t ldx, int32_t *active_dev,
                              const double *tol_dev, double *fnorm_dev) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_accel_step: null handle");
-  if (b->wide) return fail(NKA_HIP_EINVAL, "batch_accel_step: not offered by a wide batch (nka_hip_batch_create_wide): accel_update");
+  if (b->wide && !b->wide_step)
+    return fail(NKA_HIP_EINVAL, "batch_accel_step: not offered by a wide batch (nka_hip_batch_create_wide): accel_update, or a batch of "
+                                "nka_hip_batch_create_wide_step");
   if (!f_dev) return fail(NKA_HIP_EINVAL, "batch_accel_step: f is NULL");
   if (tol_dev && !active_dev) return fail(NKA_HIP_EINVAL, "batch_accel_step: tol needs a mask (a system retires by clearing its entry)");
   HIP_TRY(hipSetDevice(b->device));
@@ -847,7 +862,8 @@ int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, doubl
     const uintptr_t t0 = reinterpret_cast<uintptr_t>(tol_dev), n0 = reinterpret_cast<uintptr_t>(fnorm_dev), len = sizeof(double) * (uintptr_t)b->k.nsys;
     if (t0 < n0 + len && n0 < t0 + len) return fail(NKA_HIP_EINVAL, "batch_accel_step: fnorm overlaps tol (a threshold would be overwritten while it is read)");
   }
-  if (b->lanes) nka_batch_lanes_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
+  if (b->wide) nka_batch_wide_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
+  else if (b->lanes) nka_batch_lanes_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else if (b->waves) nka_batch_waves_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else launch_flavor(b, f_dev, ld, active_dev, StepArgs{x_dev, x_dev ? ldx : 0, tol_dev, fnorm_dev});
   HIP_TRY(hipGetLastError());

@@ -215,6 +215,10 @@ struct nka_hip_batch_state {
   double *part = nullptr;                   // partial sums, nka_host::wide_part_index: nsys x (2 + 2 mvec) x nchunk
   double *plan_c = nullptr;                 // the combine plan from the scalar kernel to the combine: nsys x (mvec + 1) coefficients
   int32_t *plan_s = nullptr;                //   ... and slots, in list order (the control block's comb_c / comb_slots stay zero)
+  // ... with the solve step (nka_hip_batch_create_wide_step, nka_batch_wide_step.hip): the partials of <f,f>,
+  // nka_host::wide_fpart_index: nsys x nchunk, allocated at creation, freed at destroy only and never moved
+  bool wide_step = false;
+  double *fpart = nullptr;
   // a LANE batch (nka_hip_batch_create_lanes, nka_batch_lanes.hip): one lane per system, lanes_group systems per workgroup; k.w
   // and k.v then hold the interleaved slots of nka_host::lanes_slot_offset (k.stride and k.sys_stride are not used)
   bool lanes = false;
@@ -228,6 +232,11 @@ struct nka_hip_batch_state {
 int nka_batch_wide_alloc(nka_hip_batch_t b);
 void nka_batch_wide_free(nka_hip_batch_t b);
 void nka_batch_wide_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
+// nka_batch_wide_step.hip: the one buffer the solve step of a wide batch adds (b->nchunk is set), and one step -- four launches
+int nka_batch_wide_step_alloc(nka_hip_batch_t b);
+void nka_batch_wide_step_free(nka_hip_batch_t b);
+void nka_batch_wide_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
+                         double *fnorm);
 // nka_batch_lanes.hip: the slots of a lane batch (b->k.n, mvec, nsys are set; sets k.w, k.v, lanes_group and vector_bytes), one
 // update and one solve step of it -- one launch each on b->stream --, and slot `slot` of system `sys` gathered to the host
 int nka_batch_lanes_alloc(nka_hip_batch_t b);

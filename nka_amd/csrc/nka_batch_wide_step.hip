@@ -1,0 +1,472 @@
+// nka_batch_wide_step.hip -- the SOLVE STEP of a wide batch (nka_hip_batch_create_wide_step, include/nka_hip_batch.h: WIDE, STEP):
+// the four launches of nka_batch_wide.hip with the residual norm, the stop rule and x -= f_out in them.
+//   k_wide_step_norm      one sweep of a chunk: <f,f> -> fpart[sys][chunk]; <d,d> rides along where there is a pending pair
+//                         -> part[sys][0][chunk], the bits of k_wide_norm
+//   k_wide_step_sums      r = sqrt(fpart[sys][0] + fpart[sys][1] + ...), the same bits in every workgroup of the system; r <= tol[sys]:
+//                         the workgroup returns, nothing written (NOT active[sys]: other workgroups of this launch read it); else
+//                         k_wide_sums
+//   k_wide_step_scalar    one workgroup per system: r again; fnorm[sys] = r; r <= tol[sys]: active[sys] = 0 and return -- the only
+//                         workgroup of its launch that reads or writes the entry; else k_wide_scalar
+//   k_wide_step_combine   active[sys], now 0 for a retired system; else k_wide_combine, and x = fl(x - f_out)
+// Within a launch no workgroup reads what another writes, as in nka_batch_wide.hip.  Each kernel is written ONCE, as a template on
+// LEN (per-system lengths, nka_hip_batch_set_lengths): these kernels have no earlier instruction stream to keep.  Where a kernel
+// overlaps its sibling of nka_batch_wide.hip it follows it statement for statement; a change to a phase is made there and here.
+// WideArgs, wide_list and wide_norm_sum are restated: sharing them through a header is not worth a second look at the machine code
+// of the kernels that unit holds still.
+#include "nka_batch_dev.hpp"
+
+using namespace nka;
+
+namespace {
+
+using nka_host::kWideChunk;
+
+struct WideArgs {       // (nka_batch_wide.hip)
+  double *part;         // nka_host::wide_part_index
+  double *plan_c;       // combine plan of system sys: plan_c + sys * (mvec + 1), plan_s likewise
+  int32_t *plan_s;
+  int32_t nchunk;
+};
+
+// what the step takes beside the update's arguments; every pointer but fpart (and len in a LEN instance) may be NULL
+struct WideStepArgs {
+  double *fpart;        // nka_host::wide_fpart_index: the partials of <f,f>
+  double *x;            // the iterate, nsys rows ldx apart
+  int64_t ldx;
+  const double *tol;    // per-system thresholds on r (read in launches 2 and 3)
+  double *fnorm;        // per-system r out (written in launch 3)
+  const int32_t *len;   // per-system lengths (LEN instances only)
+};
+
+// (nka_batch_wide.hip) pending, first and the links of the system into LDS with one coalesced load; thread 0 lists the older
+// entries.  hdr[HDR_PENDING, HDR_FIRST, HDR_NOLDER] and ps[] are valid after the trailing barrier.
+__device__ __forceinline__ void wide_list(const Ctl &ctl, int m1, int32_t *next, int32_t *ps, int32_t *hdr) {
+  const int t = threadIdx.x;
+  if (t < m1 + 1) next[t] = ctl.next()[t];
+  if (t == 64) hdr[HDR_PENDING] = ctl.ic[IC_PENDING];
+  if (t == 65) hdr[HDR_FIRST] = ctl.ic[IC_FIRST];
+  __syncthreads();
+  if (t == 0) {
+    const int pending = hdr[HDR_PENDING], first = hdr[HDR_FIRST];
+    int no = 0;
+    for (int k = pending ? next[first] : first; k != 0 && no < m1; k = next[k]) ps[no++] = k;
+    hdr[HDR_NOLDER] = no;
+  }
+  __syncthreads();
+}
+
+// (nka_batch_wide.hip) a sum of a system from its nchunk partials in CHUNK ORDER, starting from part0[0] -- staged into LDS by the
+// whole workgroup, added by one thread.  Every workgroup that calls this for a system forms the same bits.  *out is valid after
+// the trailing barrier; stage and *out may be reused behind it.
+__device__ __forceinline__ void wide_norm_sum(const double *__restrict__ part0, int nchunk, double *stage, double *out) {
+  for (int c = threadIdx.x; c < nchunk; c += kBatchThreads) stage[c] = part0[c];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = stage[0];
+    for (int c = 1; c < nchunk; c++) r += stage[c];
+    *out = r;
+  }
+  __syncthreads();
+}
+
+// ---- 1: <f,f> of a chunk, and the norm (F08:266-267) of the chunk beside it ----
+template <bool LEN>
+__global__ __launch_bounds__(kBatchThreads) void k_wide_step_norm(BatchArgs a, WideArgs wa, WideStepArgs st, const double *__restrict__ f_all,
+                                                                  int64_t ld, const int32_t *__restrict__ active) {
+#pragma clang fp contract(off)
+  const int sys = blockIdx.y;
+  if (active != nullptr && active[sys] == 0) return;
+  int64_t sn = a.n;
+  if constexpr (LEN) {
+    sn = st.len[sys];
+    if (!nka_host::wide_len_owns(sn, blockIdx.x)) return;      // (uniform: a chunk beyond the system's own; nothing was read)
+  }
+  const Ctl ctl = batch_ctl(a, sys);
+  __shared__ double sm[2 * kBatchWaves], res[2];
+  const int64_t lo = (int64_t)blockIdx.x * kWideChunk, n = nka_host::wide_chunk_len(sn, blockIdx.x);
+  const double *const f = f_all + (size_t)sys * ld + lo;
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
+  double *const fp = st.fpart + nka_host::wide_fpart_index(sys, blockIdx.x, wa.nchunk);
+  if (ctl.ic[IC_PENDING] != 0) {      // (uniform)
+    const double *const w1 = a.w + (size_t)sys * a.sys_stride + (size_t)(ctl.ic[IC_FIRST] - 1) * a.stride + lo;
+    double acc[2] = {};
+    batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+      constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+      const d2 fv = ld_tile<FULL, FV>(f, i, n), wv = ld_tile<FULL, true>(w1, i, n);
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+        if (FULL || i + q < n) {
+          const double d = wv[q] - fv[q];
+          acc[1] = fma(d, d, acc[1]);
+          acc[0] = fma(fv[q], fv[q], acc[0]);
+        }
+    });
+    batch_block_sum<2>(acc, sm, res);
+    if (threadIdx.x == 0) {
+      *fp = res[0];
+      wa.part[nka_host::wide_part_index(sys, 0, blockIdx.x, a.mvec, wa.nchunk)] = res[1];
+    }
+  } else {      // no pending pair (first update, after a restart): f is swept alone, and nobody reads the partial of <d,d>
+    double acc[1] = {};
+    batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+      constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+      const d2 fv = ld_tile<FULL, FV>(f, i, n);
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+        if (FULL || i + q < n) acc[0] = fma(fv[q], fv[q], acc[0]);
+    });
+    batch_block_sum<1>(acc, sm, res);
+    if (threadIdx.x == 0) *fp = res[0];
+  }
+}
+
+// ---- 2: the stop rule, read only; every other sum of a chunk, on the rounded w1' (F08:286-290, 371) ----
+template <int COMB, bool LEN>
+__global__ __launch_bounds__(kBatchThreads) void k_wide_step_sums(BatchArgs a, WideArgs wa, WideStepArgs st, const double *__restrict__ f_all,
+                                                                  int64_t ld, const int32_t *__restrict__ active) {
+#pragma clang fp contract(off)
+  constexpr bool RCP = (COMB == 1);
+  const int sys = blockIdx.y, chunk = blockIdx.x;
+  if (active != nullptr && active[sys] == 0) return;
+  int64_t sn = a.n;
+  if constexpr (LEN) {
+    sn = st.len[sys];
+    if (!nka_host::wide_len_owns(sn, chunk)) return;      // (uniform, before the first barrier)
+  }
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int mvec = a.mvec, m1 = mvec + 1, nchunk = wa.nchunk;
+  const int nown = LEN ? (int)nka_host::wide_len_nchunk(sn) : nchunk;      // the partials that are added
+  const Ctl ctl = batch_ctl(a, sys);
+  const nka_host::WideLds lds = nka_host::wide_sums_lds(mvec, nchunk);
+  double *const shd = reinterpret_cast<double *>(smem);
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  double *const stage = shd + lds.stage, *const sm = shd + lds.sm, *const res = shd + lds.res;
+  int32_t *const next = shi + lds.next, *const ps = shi + lds.ps, *const hdr = shi + lds.hdr;
+
+  // STEP: r from LDS behind a barrier, tol[sys] written by nobody during this launch: the return is uniform, and nothing has been
+  // written.  active[sys] stays as it is -- the other workgroups of the system read it --; k_wide_step_scalar clears it.
+  wide_norm_sum(st.fpart + nka_host::wide_fpart_index(sys, 0, nchunk), nown, stage, res + kBatchAcc);
+  {
+    const double r = sqrt(res[kBatchAcc]);
+    if (st.tol != nullptr && r <= st.tol[sys]) return;      // (a NaN on either side: false, the system goes on)
+  }
+
+  wide_list(ctl, m1, next, ps, hdr);      // (its barriers lie between the read of res above and the next write of it)
+  const int pending = hdr[HDR_PENDING], nolder = hdr[HDR_NOLDER];
+  double s = 0.0;
+  if (pending) {
+    wide_norm_sum(wa.part + nka_host::wide_part_index(sys, 0, 0, mvec, nchunk), nown, stage, res + kBatchAcc);
+    s = sqrt(res[kBatchAcc]);
+  }
+  const bool normed = pending && s != 0.0;
+  const double rs = 1.0 / s;
+
+  const int64_t lo = (int64_t)chunk * kWideChunk, n = nka_host::wide_chunk_len(sn, chunk);
+  const double *const f = f_all + (size_t)sys * ld + lo;
+  const double *const W = a.w + (size_t)sys * a.sys_stride + lo;
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
+  const double *const w1s = pending ? W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride : W;      // always a stored vector
+  auto out = [&](int entry) -> double & { return wa.part[nka_host::wide_part_index(sys, entry, chunk, mvec, nchunk)]; };
+
+  const int ngroup = (nolder + kBatchGroup - 1) / kBatchGroup;
+  for (int g = 0; g < (ngroup > 0 ? ngroup : (normed ? 1 : 0)); g++) {
+    const double *wk[kBatchGroup];
+#pragma unroll
+    for (int j = 0; j < kBatchGroup; j++) {
+      const int p = g * kBatchGroup + j;
+      wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1s;   // (beyond the list: a re-read, discarded)
+    }
+    double acc[kBatchAcc];
+#pragma unroll
+    for (int q = 0; q < kBatchAcc; q++) acc[q] = 0.0;
+    batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+      constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+      const d2 fv = ld_tile<FULL, FV>(f, i, n);
+      const d2 dv = ld_tile<FULL, true>(w1s, i, n);     // (no pending pair: a stored vector whose value is not used)
+      d2 wv[kBatchGroup];
+#pragma unroll
+      for (int j = 0; j < kBatchGroup; j++) wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+        if (FULL || i + q < n) {
+          const double fq = fv[q];
+          if (normed) {
+            const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
+            if (g == 0) acc[2 * kBatchGroup] = fma(fq, wn, acc[2 * kBatchGroup]);
+#pragma unroll
+            for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wn, wv[j][q], acc[j]);
+          }
+#pragma unroll
+          for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fq, wv[j][q], acc[kBatchGroup + j]);
+        }
+    });
+    batch_block_sum<kBatchAcc>(acc, sm, res);
+    if (t < kBatchGroup && g * kBatchGroup + t < nolder) {
+      if (normed) out(2 + g * kBatchGroup + t) = res[t];
+      out(2 + mvec + g * kBatchGroup + t) = res[kBatchGroup + t];
+    }
+    if (t == 0 && g == 0 && normed) out(1) = res[2 * kBatchGroup];
+    // (res is rewritten only behind the two barriers of the next batch_block_sum)
+  }
+}
+
+// ---- 3: fnorm, the stop rule and the mask; the sums of the system from its partials, the scalar step, the plan; one workgroup
+// per system ----
+template <bool LEN>
+__global__ __launch_bounds__(kBatchThreads) void k_wide_step_scalar(BatchArgs a, WideArgs wa, WideStepArgs st, int32_t *__restrict__ active) {
+#pragma clang fp contract(off)
+  const int sys = blockIdx.x;
+  if (active != nullptr && active[sys] == 0) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int mvec = a.mvec, m1 = mvec + 1, nh = (m1 + 1) * (m1 + 1), nchunk = wa.nchunk;
+  int nown = nchunk;      // the partials that are added
+  if constexpr (LEN) nown = (int)nka_host::wide_len_nchunk(st.len[sys]);
+  const Ctl ctl = batch_ctl(a, sys);
+  const nka_host::WideScalarLds wl = nka_host::wide_scalar_lds(mvec, nchunk);
+  const nka_host::BatchLds &lds = wl.b;
+  double *const shd = reinterpret_cast<double *>(smem);
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  Lst L;
+  L.h = shd + lds.h;
+  L.c = shd + lds.c;
+  double *const red = shd + lds.red;
+  double *const cc = shd + lds.cc;
+  double *const res = shd + lds.res;
+  double *const stage = shd + wl.stage;
+  L.next = shi + lds.next;
+  L.prev = shi + lds.prev;
+  int32_t *const ps = shi + lds.ps;
+  int32_t *const cs = shi + lds.cs;
+  int32_t *const hdr = shi + lds.hdr;
+  L.m1 = m1;
+  L.mvec = mvec;
+
+  // STEP: the same chunk-order sum as k_wide_step_sums, hence the same decision.  This workgroup is the only one of its launch that
+  // reads or writes active[sys]; the return is uniform, and of the system's state nothing has been written.
+  wide_norm_sum(st.fpart + nka_host::wide_fpart_index(sys, 0, nchunk), nown, stage, res + kBatchAcc);
+  {
+    const double r = sqrt(res[kBatchAcc]);
+    if (t == 0 && st.fnorm != nullptr) st.fnorm[sys] = r;
+    if (st.tol != nullptr && r <= st.tol[sys]) {      // (a NaN on either side: false, the system goes on)
+      if (t == 0) active[sys] = 0;
+      return;
+    }
+  }
+
+  // the working copy (phase 1 of k_batch_update)
+  for (int i = t; i < nh; i += kBatchThreads) L.h[i] = ctl.h()[i];
+  for (int i = t; i < m1 + 1; i += kBatchThreads) {
+    L.c[i] = ctl.c()[i];
+    L.next[i] = ctl.next()[i];
+    L.prev[i] = ctl.prev()[i];
+  }
+  L.subspace = L.pending = L.first = L.last = L.free_ = 0;
+  L.vtol = 0.0;
+  __syncthreads();
+  if (t == 0) {
+    lst_load_scalars(L, ctl);
+    L.vtol = ctl.dc[DC_VTOL];
+    int no = 0;
+    for (int k = L.pending ? L.next[L.first] : L.first; k != 0 && no < m1; k = L.next[k]) ps[no++] = k;
+    hdr[HDR_PENDING] = L.pending;
+    hdr[HDR_FIRST] = L.first;
+    hdr[HDR_NOLDER] = no;
+  }
+  __syncthreads();
+  const int pending = hdr[HDR_PENDING], nolder = hdr[HDR_NOLDER];
+  double s = 0.0;
+  if (pending) {      // the same chunk-order sum as k_wide_step_sums
+    wide_norm_sum(wa.part + nka_host::wide_part_index(sys, 0, 0, mvec, nchunk), nown, stage, res + kBatchAcc);
+    s = sqrt(res[kBatchAcc]);
+  }
+  const bool normed = pending && s != 0.0;
+  // red[j], one thread per entry: the chunk-order sum of the partials k_wide_step_sums wrote in this step, zero everywhere else
+  if (t < 2 + 2 * mvec) {
+    double r = 0.0;
+    if (t == 0) {
+      if (pending) r = res[kBatchAcc];
+    } else {
+      const bool formed = t == 1 ? normed : t < 2 + mvec ? (normed && t - 2 < nolder) : (t - 2 - mvec < nolder);
+      if (formed) {
+        const double *const p = wa.part + nka_host::wide_part_index(sys, t, 0, mvec, nchunk);
+        r = p[0];
+        int c = 1;
+        for (; c + 8 <= nown; c += 8) {      // (eight loads in flight; the additions stay one chain, in chunk order)
+          double x[8];
+#pragma unroll
+          for (int u = 0; u < 8; u++) x[u] = p[c + u];
+#pragma unroll
+          for (int u = 0; u < 8; u++) r += x[u];
+        }
+        for (; c < nown; c++) r += p[c];
+      }
+    }
+    red[t] = r;
+  }
+  __syncthreads();
+
+  // phase 4: the scalar step on the working copy
+  if (t == 0) batch_scalar_step(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr);
+  __syncthreads();
+
+  // phase 5: the working copy back; the plan to the combine
+  for (int i = t; i < nh; i += kBatchThreads) ctl.h()[i] = L.h[i];
+  for (int i = t; i < m1 + 1; i += kBatchThreads) {
+    ctl.c()[i] = L.c[i];
+    ctl.next()[i] = L.next[i];
+    ctl.prev()[i] = L.prev[i];
+  }
+  for (int i = t; i < 2 + 2 * mvec; i += kBatchThreads) ctl.red()[i] = red[i];
+  if (t < hdr[HDR_NCOMB]) {
+    wa.plan_c[(size_t)sys * m1 + t] = cc[t];
+    wa.plan_s[(size_t)sys * m1 + t] = cs[t];
+  }
+}
+
+// ---- 4: normalise the pending pair, combine, ring stores (F08:282-283, 361, 395-404) on a chunk; x = fl(x - f_out) ----
+template <int COMB, bool LEN>
+__global__ __launch_bounds__(kBatchThreads) void k_wide_step_combine(BatchArgs a, WideArgs wa, WideStepArgs st, double *__restrict__ f_all,
+                                                                     int64_t ld, const int32_t *__restrict__ active) {
+#pragma clang fp contract(off)
+  constexpr bool RCP = (COMB == 1);
+  constexpr bool COMPACT = (COMB == 2);
+  const int sys = blockIdx.y;
+  if (active != nullptr && active[sys] == 0) return;      // (a system that retired in this step: cleared by the launch before)
+  int64_t sn = a.n;
+  if constexpr (LEN) {
+    sn = st.len[sys];
+    if (!nka_host::wide_len_owns(sn, blockIdx.x)) return;      // (uniform, before the first barrier)
+  }
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int m1 = a.mvec + 1;
+  const Ctl ctl = batch_ctl(a, sys);
+  const nka_host::WideLds lds = nka_host::wide_combine_lds(a.mvec);
+  double *const shd = reinterpret_cast<double *>(smem);
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  double *const cc = shd + lds.cc;
+  int32_t *const cs = shi + lds.cs, *const hdr = shi + lds.hdr;
+  // the plan into LDS
+  if (t == 64) hdr[HDR_NCOMB] = ctl.ic[IC_NCOMB];
+  if (t == 65) hdr[HDR_NEW] = ctl.ic[IC_NEW];
+  if (t == 66) hdr[HDR_NORMED] = ctl.ic[IC_NORMED];
+  if (t < m1) {      // (entries beyond the plan are never applied)
+    cc[t] = wa.plan_c[(size_t)sys * m1 + t];
+    cs[t] = wa.plan_s[(size_t)sys * m1 + t];
+  }
+  __syncthreads();
+  const int ncomb = hdr[HDR_NCOMB];
+  const bool norm0 = hdr[HDR_NORMED] != 0;      // pair 0 of the plan is the pending pair, still raw
+  const double s = norm0 ? ctl.dc[DC_S] : 0.0;
+  const double rs = 1.0 / s;
+
+  const int64_t lo = (int64_t)blockIdx.x * kWideChunk, n = nka_host::wide_chunk_len(sn, blockIdx.x);
+  double *const f = f_all + (size_t)sys * ld + lo;
+  double *const W = a.w + (size_t)sys * a.sys_stride + lo, *const V = a.v + (size_t)sys * a.sys_stride + lo;
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
+  double *const wnew = W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
+  // STEP: this chunk of the system's row of the iterate, if there is one; a chunk starts on a multiple of 16 bytes of its row
+  double *const xrow = st.x != nullptr ? st.x + (size_t)sys * st.ldx + lo : nullptr;
+  const bool xvec = (reinterpret_cast<uintptr_t>(xrow) % 16) == 0;
+  batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+    constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+    if (!FULL && i >= n) return;
+    const d2 fin = ld_tile<FULL, FV>(f, i, n);
+    d2 x = fin;
+    d2 xit = {0.0, 0.0};      // STEP: the iterate's pair, loaded with the other loads of the tile
+    if (xrow != nullptr) xit = xvec ? ld_tile<FULL, true>(xrow, i, n) : ld_tile<FULL, false>(xrow, i, n);
+    int j0 = 0;
+    if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
+      double *const wk = W + (size_t)(cs[0] - 1) * a.stride, *const vk = V + (size_t)(cs[0] - 1) * a.stride;
+      d2 wv = ld_tile<FULL, true>(wk, i, n), vv = ld_tile<FULL, true>(vk, i, n);
+      const double c = cc[0];
+#pragma unroll
+      for (int q = 0; q < 2; q++) {
+        const double wn = batch_nrm<RCP>(wv[q] - fin[q], s, rs);
+        const double vn = batch_nrm<RCP>(vv[q], s, rs);
+        wv[q] = wn;
+        vv[q] = COMPACT ? vn - wn : vn;
+        x[q] = COMPACT ? x[q] + c * vv[q] : comb1<COMB>(x[q], c, wv[q], vv[q]);
+      }
+      st_tile<FULL, true>(wk, i, n, wv);
+      st_tile<FULL, true>(vk, i, n, vv);
+      j0 = 1;
+    }
+    constexpr int U = 4;      // pairs whose loads are in flight together (beyond the plan: the last pair again, not applied)
+    for (int j = j0; j < ncomb; j += U) {
+      d2 wv[U], vv[U];
+      double c[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int jj = j + u < ncomb ? j + u : ncomb - 1;
+        const size_t off = (size_t)(cs[jj] - 1) * a.stride;
+        c[u] = cc[jj];
+        vv[u] = ld_tile<FULL, true>(V + off, i, n);
+        if (!COMPACT) wv[u] = ld_tile<FULL, true>(W + off, i, n); else wv[u] = vv[u];
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (j + u < ncomb) {
+#pragma unroll
+          for (int q = 0; q < 2; q++) x[q] = COMPACT ? x[q] + c[u] * vv[u][q] : comb1<COMB>(x[q], c[u], wv[u][q], vv[u][q]);
+        }
+    }
+    st_tile<FULL, true>(wnew, i, n, fin);
+    st_tile<FULL, true>(vnew, i, n, x);
+    if (ncomb > 0) st_tile<FULL, FV>(f, i, n, x);      // (nothing to combine: f stays as it is)
+    if (xrow != nullptr) {
+      xit[0] = xit[0] - x[0];
+      xit[1] = xit[1] - x[1];
+      if (xvec) st_tile<FULL, true>(xrow, i, n, xit); else st_tile<FULL, false>(xrow, i, n, xit);
+    }
+  });
+}
+
+// (whether a step runs with per-system lengths, and every address, are fixed when it is enqueued or captured; the grid is
+// nchunk x nsys either way)
+template <int COMB, bool LEN>
+void launch_wide_step(nka_hip_batch_t b, const WideArgs &wa, const WideStepArgs &st, double *f, int64_t ld, int32_t *active) {
+  const int mvec = b->k.mvec, nchunk = b->nchunk;
+  const dim3 grid((unsigned)nchunk, (unsigned)b->k.nsys), block(kBatchThreads);
+  hipLaunchKernelGGL((k_wide_step_norm<LEN>), grid, block, 0, b->stream, b->k, wa, st, (const double *)f, ld, (const int32_t *)active);
+  hipLaunchKernelGGL((k_wide_step_sums<COMB, LEN>), grid, block, nka_host::wide_sums_lds(mvec, nchunk).bytes(), b->stream, b->k, wa, st,
+                     (const double *)f, ld, (const int32_t *)active);
+  hipLaunchKernelGGL((k_wide_step_scalar<LEN>), dim3((unsigned)b->k.nsys), block, nka_host::wide_scalar_lds(mvec, nchunk).b.bytes(), b->stream,
+                     b->k, wa, st, active);
+  hipLaunchKernelGGL((k_wide_step_combine<COMB, LEN>), grid, block, nka_host::wide_combine_lds(mvec).bytes(), b->stream, b->k, wa, st, f, ld,
+                     (const int32_t *)active);
+}
+template <int COMB>
+void launch_wide_step_flavor(nka_hip_batch_t b, const WideArgs &wa, WideStepArgs st, double *f, int64_t ld, int32_t *active) {
+  if (b->has_len) {
+    st.len = b->len;
+    launch_wide_step<COMB, true>(b, wa, st, f, ld, active);
+  } else launch_wide_step<COMB, false>(b, wa, st, f, ld, active);
+}
+
+}  // namespace
+
+int nka_batch_wide_step_alloc(nka_hip_batch_t b) {
+  const size_t nf = (size_t)nka_host::wide_fpart_count(b->k.nsys, b->nchunk);
+  HIP_TRY(hipMalloc((void **)&b->fpart, sizeof(double) * nf));
+  HIP_TRY(hipMemsetAsync(b->fpart, 0, sizeof(double) * nf, b->stream));
+  return 0;
+}
+
+void nka_batch_wide_step_free(nka_hip_batch_t b) {
+  hipFree(b->fpart);
+  b->fpart = nullptr;
+}
+
+void nka_batch_wide_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
+                         double *fnorm) {
+  const WideArgs wa{b->part, b->plan_c, b->plan_s, b->nchunk};
+  const WideStepArgs st{b->fpart, x, x ? ldx : 0, tol, fnorm, nullptr};
+  switch (b->flavor) {
+    case NKA_HIP_FLAVOR_F08_VECTOR: launch_wide_step_flavor<1>(b, wa, st, f, ld, active); break;
+    case NKA_HIP_FLAVOR_C: launch_wide_step_flavor<2>(b, wa, st, f, ld, active); break;
+    default: launch_wide_step_flavor<0>(b, wa, st, f, ld, active);
+  }
+}

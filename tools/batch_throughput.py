@@ -63,7 +63,15 @@ nsys 256,4096,65536 x vlen 65,128,256,512,1024,2048,4096 x mvec 5,10,20 with acc
 fnorm at vlen 256 x mvec 10,20; a point that needs more than --mem-gb (here 40) is skipped and listed, and so is a vlen beyond
 the cap of the library loaded (a candidate build with a larger NKA_HIP_BATCH_WAVES_MAX_VLEN measures the lengths that decide
 the cap).  THE CAP RULE, evaluated at the end: the largest power of two v such that at nsys = 4096, at every vlen <= v of the grid
-and every mvec, (b) takes less time than (a) by more than |a - a'|; 128 if that holds nowhere."""
+and every mvec, (b) takes less time than (a) by more than |a - a'|; 128 if that holds nowhere.
+
+--wide-step measures the solve step of a wide batch (nka_hip_batch_create_wide_step) with the method of --step on wide batches:
+  (a) accel_update of a plain wide batch;
+  (b) the loop a caller composes from it: vector_norm, the mask update, accel_update under the mask, the masked X -= F;
+  (b') the same loop a second time, on a batch of its own: the control;
+  (c) accel_step with X, the mask, tol and fnorm on a batch of the new entry, no system retiring.
+nsys 16,64,256 x vlen 32768,65536,262144 x mvec 10,20; a point that needs more than --mem-gb (here 40) is skipped and listed.  No
+ratio is fixed: a point counts as won when b - c > |b - b'|, as lost when c - b > |b - b'|, and is level otherwise."""
 import argparse
 import ctypes as C
 import os
@@ -638,6 +646,106 @@ def measure_step(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budge
     return out
 
 
+def measure_wide_step(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
+    """measure_step on wide batches, with the composed loop twice: (b') is the control that says what two runs of the SAME loop
+    differ by.  (a), (b) and (b') run plain wide batches -- the kernels of nka_batch_wide.hip --, (c) the batch with the step."""
+    npool = mvec + 3
+    need = 8.0 * nsys * vlen * (4 * 2 * (mvec + 1) + npool + 4 + 3)       # four batches' slots, the pool, four f, three x
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    names = ("a", "b", "b2", "c")
+    Fs = {v: torch.empty(nsys, vlen, dtype=torch.float64, device="cuda") for v in names}
+    Xs = {v: torch.zeros(nsys, vlen, dtype=torch.float64, device="cuda") for v in ("b", "b2", "c")}
+    masks = {v: torch.ones(nsys, dtype=torch.int32, device="cuda") for v in ("b", "b2", "c")}
+    tol = torch.zeros(nsys, dtype=torch.float64, device="cuda")
+    rs = {v: torch.zeros(nsys, dtype=torch.float64, device="cuda") for v in ("b", "b2", "c")}
+    batches = {v: nka_amd.nka_batch().init(nsys, vlen, mvec, wide=True, step=(v == "c")) for v in names}
+    assert batches["c"].offers_step() and not batches["a"].offers_step()
+    hs = {v: batches[v]._handle() for v in names}
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    P = lambda t: C.c_void_p(t.data_ptr())                                           # noqa: E731
+    upd, stp = L.nka_hip_batch_accel_update, L.nka_hip_batch_accel_step
+    step = [0]
+
+    def run(name, reps):
+        F, h = Fs[name], hs[name]
+        for _ in range(reps):
+            F.copy_(pool[step[0] % npool])
+            step[0] += 1
+            if name == "a":
+                assert upd(h, P(F), ld, None) == 0
+            elif name == "c":
+                assert stp(h, P(F), ld, P(Xs["c"]), ld, P(masks["c"]), P(tol), P(rs["c"])) == 0
+            else:
+                torch.linalg.vector_norm(F, dim=1, out=rs[name])
+                torch.gt(rs[name], tol, out=masks[name])
+                assert upd(h, P(F), ld, P(masks[name])) == 0
+                torch.addcmul(Xs[name], F, masks[name][:, None], value=-1.0, out=Xs[name])
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {v: [] for v in names}
+    for v in names:                                # warm: fill the lists (steady state), settle clocks and caches
+        step[0] = 0
+        run(v, mvec + 4)
+    torch.cuda.synchronize()
+    for v in ("a", "b", "b2"):                     # the same work
+        assert torch.equal(Fs[v], Fs["c"]), v
+    assert torch.equal(Xs["b"], Xs["c"]) and torch.equal(Xs["b2"], Xs["c"])
+    for v in names:
+        assert (batches[v].num_vec() == mvec).all(), v
+        reps[v] = max(3, int(window / timed(v, 3)) + 1)
+    for _ in range(repeats):                       # alternate the variants
+        for v in names:
+            ts[v].append(timed(v, reps[v]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    assert all(m.all() for m in masks.values())    # nothing retired
+    for v in names:
+        assert (batches[v].num_vec() == mvec).all(), v
+        med = statistics.median(ts[v])
+        out[v], out["spread_" + v] = med, (max(ts[v]) - min(ts[v])) / med
+        batches[v].delete()
+    del pool, Fs, Xs
+    torch.cuda.empty_cache()
+    return out
+
+
+def wide_step_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    emit(f"# one iteration on WIDE batches: (a) accel_update; (b) vector_norm + mask update + accel_update(mask) + masked X -= F; (b') "
+         f"the same loop a second time, the control; (c) accel_step of a batch of nka_hip_batch_create_wide_step with X, mask, tol, "
+         f"fnorm; {torch.cuda.get_device_name(0)}; windows >= {args.window} s, median of {args.repeats}, the four alternated on the "
+         f"same inputs; default flavour and sums, full list; tol = 0: no system retires; the time includes the copy of the input "
+         f"into F (equal for the four)")
+    emit("# (a), (b) and (b') run the kernels of nka_batch_wide.hip; a point is WON when b - c > |b - b'|, LOST when c - b > |b - b'|")
+    emit(f"{'nsys':>5} {'vlen':>7} {'mvec':>4} {'(a) us':>10} {'(b) us':>10} {'(b2) us':>10} {'(c) us':>10} {'c/b':>7} {'c/a':>7} "
+         f"{'|b-b2|/b':>8}  c vs b")
+    t0 = time.time()
+    tally = {"won": [], "lost": [], "level": []}
+    for n, v, m in points:
+        r = measure_wide_step(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9)
+        if r is None:
+            emit(f"{n:5d} {v:7d} {m:4d}   SKIPPED: the four batches and the inputs need more than {args.mem_gb:g} GB of device memory")
+            continue
+        noise = abs(r["b"] - r["b2"])
+        verdict = "won" if r["b"] - r["c"] > noise else "lost" if r["c"] - r["b"] > noise else "level"
+        tally[verdict].append((n, v, m, round(r["c"] / r["b"], 3)))
+        emit(f"{n:5d} {v:7d} {m:4d} {r['a'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {r['b2'] * 1e6:10.1f} {r['c'] * 1e6:10.1f} "
+             f"{r['c'] / r['b']:7.3f} {r['c'] / r['a']:7.3f} {noise / r['b']:8.4f}  {verdict.upper():5}   "
+             f"(spread a {100 * r['spread_a']:.1f} % b {100 * r['spread_b']:.1f} % b2 {100 * r['spread_b2']:.1f} % c {100 * r['spread_c']:.1f} %)")
+    emit(f"# {len(points)} points in {time.time() - t0:.0f} s; won {len(tally['won'])}, level {len(tally['level'])}, lost {len(tally['lost'])}"
+         f"{': ' + str(tally['lost']) if tally['lost'] else ''}")
+    return 0
+
+
 def measure_wide(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
     npool = mvec + 3
     narrow = vlen <= nka_amd.BATCH_MAX_VLEN
@@ -836,6 +944,10 @@ def main():
                     help="time the wave batch (one wavefront per system) beside two narrow batches at the rounded fast sums (the second: "
                          "a control); without --nsys / --vlens / --mvecs / --mem-gb: nsys 256,4096,65536 x vlen 65,128,256,512,1024,2048,"
                          "4096 x mvec 5,10,20, 40 GB, then accel_step at vlen 256 x mvec 10,20; prints the cap its rule yields")
+    ap.add_argument("--wide-step", action="store_true",
+                    help="time accel_step of a wide batch (nka_hip_batch_create_wide_step) against the wide accel_update and against "
+                         "the loop a caller composes from it, run twice (the second: a control); without --nsys / --vlens / --mvecs / "
+                         "--mem-gb: nsys 16,64,256 x vlen 32768,65536,262144 x mvec 10,20, 40 GB")
     ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
@@ -859,6 +971,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.wide_step:
+        for name, grid_w in (("nsys", "16,64,256"), ("vlens", "32768,65536,262144"), ("mvecs", "10,20"), ("mem_gb", 40.0)):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+        return wide_step_main(args, torch, nka_amd, L, emit)
     if args.waves:
         for name, grid_w in (("nsys", "256,4096,65536"), ("vlens", "65,128,256,512,1024,2048,4096"), ("mvecs", "5,10,20"), ("mem_gb", 40.0)):
             if getattr(args, name) == ap.get_default(name):
