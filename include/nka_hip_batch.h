@@ -311,9 +311,39 @@
  *            vlen 256, 1.3 ... 1.4 at 512, 1.4 ... 1.8 at 1024 (1.6 ... 2.4 beyond the cap): 64 workgroups cannot fill 256 compute
  *            units, and a call then costs the latency of one wavefront that sweeps alone what 256 threads share.  So: thousands of
  *            systems of 65 ... 1024 unknowns -- this kind (the longer the list the larger the gain; at mvec = 5 and vlen 1024 it is
- *            a draw); a few hundred systems or fewer, longer systems, or a caller who needs weights, lengths, the reference order
- *            or binary32 storage -- the batch above; at most 64 unknowns and tens of thousands of systems with mvec up to about
+ *            a draw); a few hundred systems or fewer, longer systems, or a caller who needs the reference order or binary32 storage
+ *            -- the batch above (weights and lengths: WAVES EXT below); at most 64 unknowns and tens of thousands of systems with mvec up to about
  *            10 -- LANES; beyond 16 384 unknowns -- WIDE.
+ *   WAVES EXT  nka_hip_batch_create_waves_ext: THE WAVE BATCH WITH LENGTHS AND WEIGHTS (nka_amd/csrc/nka_batch_waves_ext.hip).  Limits,
+ *            cap, flavours, storage and every guarantee of WAVES; nothing more is allocated at creation (the weight and the length
+ *            buffer come at the first set, as in the batch above), and nka_hip_batch_kind stays 3.  What it adds is exactly the two
+ *            entries WAVES refuses: nka_hip_batch_set_lengths / _host and nka_hip_batch_set_dot_weights / _host, with the host side,
+ *            the checks and the refusals of the batch above (values checked before they are copied, refused values leave the
+ *            previous ones in force, NKA_HIP_ESTATE while the stream is capturing, a row stride of 0 = one shared row).
+ *            set_sum_order and binary32 storage stay refused as in WAVES.  A batch of nka_hip_batch_create_waves keeps every
+ *            refusal it has; nka_hip_batch_offers_lengths / _offers_weights tell the two apart.
+ *            LENGTHS: system sys with len[sys] = L is BIT-EQUAL to the same system of a batch of nka_hip_batch_create_waves with
+ *            vlen = L -- f[0..L) and x[0..L), red[], state, num_vec and digest, fnorm and the retirement decision, [0..L) of every
+ *            slot --, and nothing at or beyond L is read or written in a row of f or x, in the weight row or in a slot.  Derived,
+ *            not fitted: lane l owns the pair 2l, 2l + 1 of every 128-element tile and meets its pairs in increasing order
+ *            whatever the length is, and the butterfly does not depend on it.
+ *            WEIGHTS: fl(w_i a_i) is the FIRST operand of every product, the table of the batch above: red[0] = sum fma(fl(w d), d, .),
+ *            red[1] = sum fma(fl(w f), w1', .), red[2+p] = sum fma(fl(w w1'), w_p, .), red[2+m+p] = sum fma(fl(w f), w_p, .), the
+ *            step's <f,f> = sum fma(fl(w f), f, .); fl(w f) is formed once per element and sweep, the combine does not read the
+ *            weights.  Every entry is within gamma(K) sum|fl(w x) y| of the exact sum of fl(w x) and y with the K of WAVES at the
+ *            system's length (the first operand is already rounded, so K does not change).
+ *            NEITHER SET: the batch runs the kernels of WAVES and is that batch bit for bit.  A captured call keeps whether it
+ *            was weighted, in which form, and whether it had lengths; it reads the VALUES at replay (GRAPHS from the first update).
+ *            WHICH KIND, MEASURED (profiles/r17/batch_waves_ext_throughput.txt, tools/batch_throughput.py --waves-ext, 1 x MI355X):
+ *            seven variants alternated in one process on the same inputs, default flavour, NKA_HIP_SUMS_BLOCKED_ROUNDED, full lists,
+ *            median of five windows; lengths uniform in [vlen / 4, vlen]; the control (a second batch above with the same lengths)
+ *            differs by at most 0.2 %.  RAGGED LENGTHS, time of an update / time of the batch above with the same lengths, mvec =
+ *            10 / 20: 0.33 / 0.29 at 4096 x 128, 0.36 / 0.30 at 4096 x 256, 0.63 / 0.43 at 4096 x 1024, 0.30 at 65 536 x 256 x 10.
+ *            ONE WEIGHT ROW PER SYSTEM, against the batch above with the same weights: 0.36 / 0.33 at 4096 x 128, 0.44 / 0.36 at
+ *            4096 x 256, 0.87 / 0.61 at 4096 x 1024, 0.37 at 65 536 x 256 x 10.  WHAT THE LENGTH ARGUMENT COSTS (every length = vlen
+ *            against a batch of nka_hip_batch_create_waves): 1.000 ... 1.014.  Won at 7 of 7 points in both comparisons.  So:
+ *            thousands of systems of up to 1024 unknowns that differ in length or in the scale of their unknowns -- this entry;
+ *            for every other case the sentences of WAVES stand (256 systems were not measured here: there WAVES loses).
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -380,6 +410,14 @@ enum { NKA_HIP_BATCH_KIND_WAVES = 3 };
 int nka_hip_batch_create_waves(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
                                int32_t flavor, int32_t device, void *stream);
 int nka_hip_batch_waves_limits(int32_t *systems_per_group, int64_t *max_vlen);
+/* WAVES EXT above: nka_hip_batch_create_waves with nka_hip_batch_set_lengths / _host and nka_hip_batch_set_dot_weights / _host
+ * offered; arguments, limits, allocations and _kind (3) as for nka_hip_batch_create_waves.
+ * _offers_lengths / _offers_weights: 1 = the setters are offered, 0 = refused; < 0 on error (a NULL handle).  Lengths: every kind
+ * but lanes and a batch of nka_hip_batch_create_waves; weights: narrow (either storage) and a batch of this entry. */
+int nka_hip_batch_create_waves_ext(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                                   int32_t flavor, int32_t device, void *stream);
+int nka_hip_batch_offers_lengths(nka_hip_batch_t b);
+int nka_hip_batch_offers_weights(nka_hip_batch_t b);
 int nka_hip_batch_is_wide(nka_hip_batch_t b);                    /* 1 = wide, 0 = narrow, lanes or waves; < 0 on error */
 int nka_hip_batch_wide_limits(int64_t *chunk, int64_t *max_vlen);  /* the two constants, as the library was built */
 int nka_hip_batch_destroy(nka_hip_batch_t b);

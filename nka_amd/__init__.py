@@ -7,7 +7,7 @@ include/nka_hip.h).  This package holds only what that path needs:
   nka.py     a Python mirror of the reference's `type nka` used by tests and bench.py
   batch.py   the same for a batch of systems advanced together (include/nka_hip_batch.h): one workgroup per system, or
              wide: a system split across workgroups (with step=True: its solve step too), or lanes: one lane per system (very short systems), or waves: one
-             wavefront per system (short systems)
+             wavefront per system (short systems; with ext=True: per-system lengths and dot weights too)
   dist.py    slicing + RCCL bootstrap for the sharded (one rank per GPU) run
 There is NO CPU fallback: without the HIP library every entry point raises.
 """

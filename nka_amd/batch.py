@@ -56,7 +56,7 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
              stream: int | None = None, wide: bool = False, storage: int = STORE_F64, lanes: bool = False,
-             waves: bool = False, step: bool = False):
+             waves: bool = False, step: bool = False, ext: bool = False):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
@@ -74,6 +74,10 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         bits, the numerical contract of SUMS_BLOCKED_ROUNDED); accel_update, accel_step, masks, restart / relax and graphs are
         offered, weights, lengths and the reference sum order refused.  Together with wide=True, lanes=True or
         storage != STORE_F64 it raises NKAError.
+        ext (with waves=True only): the wave batch WITH per-system lengths and diagonal dot weights (nka_hip_batch_create_waves_ext;
+        include/nka_hip_batch.h, WAVES EXT) -- set_lengths and set_dot_weights are offered with the contracts of the default batch,
+        a system of length L carries the bits of a wave batch of vlen = L, and with neither set the batch is the plain wave batch
+        bit for bit.  ext=True without waves=True raises NKAError.
         step (with wide=True only): the wide batch WITH the solve step (nka_hip_batch_create_wide_step; include/nka_hip_batch.h,
         WIDE: STEP of a wide batch) -- one more buffer of nsys x nchunk doubles, accel_step as four launches, everything else the
         wide batch bit for bit.  Every other kind offers the step already: step=True without wide=True raises NKAError."""
@@ -82,6 +86,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         if step and not wide:
             raise NKAError("nka_batch init: step=True selects the wide batch with the solve step and needs wide=True (every other "
                            "kind offers accel_step already)")
+        if ext and not waves:
+            raise NKAError("nka_batch init: ext=True selects the wave batch with lengths and weights and needs waves=True (the default "
+                           "batch offers both already)")
         if waves and (wide or lanes):
             raise NKAError("nka_batch init: waves=True excludes wide=True and lanes=True (one wavefront per system, a system split "
                            "across workgroups, or one lane per system)")
@@ -110,6 +117,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         elif lanes:
             _check(self._L.nka_hip_batch_create_lanes(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                       C.c_void_p(stream)), "nka_hip_batch_create_lanes", self._L)
+        elif waves and ext:
+            _check(self._L.nka_hip_batch_create_waves_ext(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                          C.c_void_p(stream)), "nka_hip_batch_create_waves_ext", self._L)
         elif waves:
             _check(self._L.nka_hip_batch_create_waves(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                       C.c_void_p(stream)), "nka_hip_batch_create_waves", self._L)
@@ -369,6 +379,20 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         """True where accel_step is offered: every kind but a wide batch created without step=True (nka_hip_batch_offers_step)."""
         r = self._L.nka_hip_batch_offers_step(self._handle())
         _check(min(r, 0), "batch_offers_step", self._L)
+        return bool(r)
+
+    def offers_lengths(self) -> bool:
+        """True where set_lengths is offered: every kind but a lane batch and a wave batch created without ext=True
+        (nka_hip_batch_offers_lengths)."""
+        r = self._L.nka_hip_batch_offers_lengths(self._handle())
+        _check(min(r, 0), "batch_offers_lengths", self._L)
+        return bool(r)
+
+    def offers_weights(self) -> bool:
+        """True where set_dot_weights is offered: the default batch (either storage) and a wave batch created with ext=True
+        (nka_hip_batch_offers_weights)."""
+        r = self._L.nka_hip_batch_offers_weights(self._handle())
+        _check(min(r, 0), "batch_offers_weights", self._L)
         return bool(r)
 
     def kind(self) -> int:

@@ -645,7 +645,7 @@ extern "C" {
 // per system (this file)
 static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor, int32_t device,
                         void *stream, bool wide, int32_t storage = NKA_HIP_BATCH_STORE_F64, const char *entry = nullptr,
-                        bool lanes = false, bool waves = false, bool wide_step = false) {
+                        bool lanes = false, bool waves = false, bool wide_step = false, bool waves_ext = false) {
   const std::string who = entry ? entry : wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
   const bool s32 = storage == NKA_HIP_BATCH_STORE_F32;
   if (!out) return fail(NKA_HIP_EINVAL, who + ": out is NULL");
@@ -687,6 +687,7 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
   b->wide = wide;
   b->lanes = lanes;
   b->waves = waves;
+  b->waves_ext = waves && waves_ext;
   b->device = device;
   b->stream = (hipStream_t)stream;
   b->flavor = flavor;
@@ -788,6 +789,11 @@ int nka_hip_batch_create_waves(nka_hip_batch_t *out, int32_t nsys, int64_t vlen,
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_waves", false,
                       true);
 }
+int nka_hip_batch_create_waves_ext(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                                   int32_t device, void *stream) {
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_waves_ext",
+                      false, true, false, true);
+}
 int nka_hip_batch_kind(nka_hip_batch_t b) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_kind: null handle");
   if (b->waves) return NKA_HIP_BATCH_KIND_WAVES;
@@ -798,6 +804,15 @@ int64_t nka_hip_batch_vector_bytes(nka_hip_batch_t b) { return b ? b->vector_byt
 int nka_hip_batch_is_wide(nka_hip_batch_t b) { return b ? (b->wide ? 1 : 0) : fail(NKA_HIP_EINVAL, "batch_is_wide: null handle"); }
 int nka_hip_batch_offers_step(nka_hip_batch_t b) {
   return b ? (b->wide && !b->wide_step ? 0 : 1) : fail(NKA_HIP_EINVAL, "batch_offers_step: null handle");
+}
+
+int nka_hip_batch_offers_lengths(nka_hip_batch_t b) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_offers_lengths: null handle");
+  return b->lanes || (b->waves && !b->waves_ext) ? 0 : 1;
+}
+int nka_hip_batch_offers_weights(nka_hip_batch_t b) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_offers_weights: null handle");
+  return b->wide || b->lanes || (b->waves && !b->waves_ext) ? 0 : 1;
 }
 
 int nka_hip_batch_destroy(nka_hip_batch_t b) {
@@ -830,6 +845,7 @@ int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, con
   if (int rc = check_mask(b, active_dev, "batch_accel_update: active")) return rc;
   if (b->wide) nka_batch_wide_update(b, f_dev, ld, active_dev);
   else if (b->lanes) nka_batch_lanes_update(b, f_dev, ld, active_dev);
+  else if (b->waves_ext && (b->weighted || b->has_len)) nka_batch_waves_ext_update(b, f_dev, ld, active_dev);
   else if (b->waves) nka_batch_waves_update(b, f_dev, ld, active_dev);
   else launch_flavor(b, f_dev, ld, active_dev);
   HIP_TRY(hipGetLastError());
@@ -864,6 +880,7 @@ int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, doubl
   }
   if (b->wide) nka_batch_wide_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else if (b->lanes) nka_batch_lanes_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
+  else if (b->waves_ext && (b->weighted || b->has_len)) nka_batch_waves_ext_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else if (b->waves) nka_batch_waves_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else launch_flavor(b, f_dev, ld, active_dev, StepArgs{x_dev, x_dev ? ldx : 0, tol_dev, fnorm_dev});
   HIP_TRY(hipGetLastError());
@@ -909,7 +926,7 @@ int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: null handle");
   if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wide batch (nka_hip_batch_create_wide)");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
-  if (b->waves) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
+  if (b->waves && !b->waves_ext) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_dot_weights")) return rc;
   if (!w_dev) {
@@ -926,7 +943,7 @@ int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, 
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: null handle");
   if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wide batch (nka_hip_batch_create_wide)");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
-  if (b->waves) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
+  if (b->waves && !b->waves_ext) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_dot_weights_host")) return rc;
   if (!w_host) {
@@ -991,7 +1008,7 @@ static int clear_lengths(nka_hip_batch_t b) {
 int nka_hip_batch_set_lengths(nka_hip_batch_t b, const int32_t *len_dev) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_lengths: null handle");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_lengths: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
-  if (b->waves) return fail(NKA_HIP_EINVAL, "batch_set_lengths: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
+  if (b->waves && !b->waves_ext) return fail(NKA_HIP_EINVAL, "batch_set_lengths: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_lengths")) return rc;
   if (!len_dev) return clear_lengths(b);
@@ -1005,7 +1022,7 @@ int nka_hip_batch_set_lengths(nka_hip_batch_t b, const int32_t *len_dev) {
 int nka_hip_batch_set_lengths_host(nka_hip_batch_t b, const int32_t *len_host) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: null handle");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
-  if (b->waves) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
+  if (b->waves && !b->waves_ext) return fail(NKA_HIP_EINVAL, "batch_set_lengths_host: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
   if (int rc = weights_settable(b, "batch_set_lengths_host")) return rc;
   if (!len_host) return clear_lengths(b);

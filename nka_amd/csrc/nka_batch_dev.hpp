@@ -226,6 +226,8 @@ struct nka_hip_batch_state {
   // a WAVE batch (nka_hip_batch_create_waves, nka_batch_waves.hip): one wavefront per system; storage and control blocks are the
   // narrow batch's, nothing further is allocated
   bool waves = false;
+  // ... of nka_hip_batch_create_waves_ext (nka_batch_waves_ext.hip): the same batch, which also takes lengths and weights
+  bool waves_ext = false;
 };
 
 // nka_batch_wide.hip: the buffers of a wide batch (b->k is complete), and one update of it -- four launches on b->stream
@@ -249,3 +251,7 @@ int nka_batch_lanes_get_slot(nka_hip_batch_t b, bool v, int32_t sys, int32_t slo
 void nka_batch_waves_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
 void nka_batch_waves_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
                           double *fnorm);
+// nka_batch_waves_ext.hip: the same of a wave batch with weights (b->weighted) or lengths (b->has_len) or both set
+void nka_batch_waves_ext_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
+void nka_batch_waves_ext_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
+                              double *fnorm);

@@ -65,6 +65,15 @@ the cap of the library loaded (a candidate build with a larger NKA_HIP_BATCH_WAV
 the cap).  THE CAP RULE, evaluated at the end: the largest power of two v such that at nsys = 4096, at every vlen <= v of the grid
 and every mvec, (b) takes less time than (a) by more than |a - a'|; 128 if that holds nowhere.
 
+--waves-ext measures the wave batch with lengths and weights (nka_hip_batch_create_waves_ext) with the method of --waves -- same
+inputs, the variants alternated in one process, flavour C, SUMS_BLOCKED_ROUNDED, full lists:
+  (a) a narrow batch with ragged lengths, uniform in [vlen / 4, vlen] from a fixed seed; (a') the same again, the control;
+  (b) an ext wave batch with the same lengths;
+  (c) a plain wave batch, without lengths; (d) an ext batch with every length = vlen: (d) against (c) is what the length argument costs;
+  (e) a narrow batch with one weight row per system; (f) an ext batch with the same weights.
+nsys 4096 x vlen 128,256,1024 x mvec 10,20, then 65 536 x 256 x 10; a point that needs more than --mem-gb (here 40) is skipped and
+listed.  (b) won against (a) when a - b > |a - a'|, and (f) against (e) by the same rule; every point is recorded, lost ones too.
+
 --wide-step measures the solve step of a wide batch (nka_hip_batch_create_wide_step) with the method of --step on wide batches:
   (a) accel_update of a plain wide batch;
   (b) the loop a caller composes from it: vector_norm, the mask update, accel_update under the mask, the masked X -= F;
@@ -464,6 +473,110 @@ def waves_main(args, torch, nka_amd, L, emit):
              f"{'yes' if won else 'NO'}   (spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
     emit(f"# won at {nwon} of {nwon + nlost} measured points; {len(points)} points in {time.time() - t0:.0f} s")
     emit(f"# THE CAP RULE on the rows at nsys = 4096: NKA_HIP_BATCH_WAVES_MAX_VLEN = {waves_cap(rows, ints(args.vlens), ints(args.mvecs))}")
+    return 0
+
+
+def measure_waves_ext(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
+    """--waves-ext: the seven variants of the module docstring on the same inputs, alternated.  The ragged lengths are
+    ragged_lengths (below); the weights 2^U(-1, 1) per system and element from a fixed seed."""
+    import numpy as np
+    names = ["a", "a2", "b", "c", "d", "e", "f"]
+    npool = mvec + 3
+    if 8.0 * nsys * ((vlen + 31) // 32 * 32) * ((mvec + 1) * 2 * len(names) + 3) + 8.0 * nsys * vlen * (npool + len(names)) > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    ragged, full = ragged_lengths(nsys, vlen), np.full(nsys, vlen, np.int32)
+    gen = torch.Generator(device="cuda").manual_seed(LENGTHS_SEED)
+    w = torch.exp2(2.0 * torch.rand(nsys, vlen, dtype=torch.float64, device="cuda", generator=gen) - 1.0)
+    Fs, hs, batches = {}, {}, {}
+    for name in names:
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+        waves = name in ("b", "c", "d", "f")
+        b = batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, waves=waves, ext=waves and name != "c")
+        b.set_sum_order(nka_amd.SUMS_BLOCKED_ROUNDED)
+        assert b.kind() == (nka_amd.KIND_WAVES if waves else nka_amd.KIND_NARROW), name
+        if name in ("a", "a2", "b"):
+            b.set_lengths(ragged)
+        if name == "d":
+            b.set_lengths(full)
+        if name in ("e", "f"):
+            b.set_dot_weights(w)
+        hs[name] = b._handle()
+    del w
+    upd = L.nka_hip_batch_accel_update
+    count = [0]
+
+    def run(name, reps):
+        F, h = Fs[name], hs[name]
+        p = C.c_void_p(F.data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[count[0] % npool])
+            count[0] += 1
+            assert upd(h, p, vlen, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in names}
+    for name in names:                             # warm: fill the lists (steady state), settle clocks and caches
+        count[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    for name in names:                             # (a system shorter than mvec holds at most that many independent vectors)
+        assert (batches[name].num_vec() == np.minimum(mvec, batches[name].lengths())).all(), name
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in names:
+            ts[name].append(timed(name, reps[name]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec, mean_len=float(ragged.mean()))
+    for name in names:
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+        batches[name].delete()
+    del pool, Fs
+    torch.cuda.empty_cache()
+    return out
+
+
+def waves_ext_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    per_group, cap = nka_amd.batch_waves_limits()
+    points = [(n, v, m) for n in ints(args.nsys) for v in ints(args.vlens) for m in ints(args.mvecs)] + [(65536, 256, 10)]
+    emit(f"# one update of (a) a narrow batch with ragged lengths (uniform in [vlen/4, vlen], seed {LENGTHS_SEED}; its kernels are the "
+         f"parent commit's), (a') the same again -- the control --, (b) an ext wave batch (nka_hip_batch_create_waves_ext) with the same "
+         f"lengths, (c) a plain wave batch without lengths (the parent commit's kernels), (d) an ext batch with every length = vlen, "
+         f"(e) a narrow batch with one weight row per system, (f) an ext batch with the same weights; {torch.cuda.get_device_name(0)}; "
+         f"windows >= {args.window} s, median of {args.repeats}, the seven alternated on the same inputs; flavour C, "
+         f"SUMS_BLOCKED_ROUNDED, full lists; the time includes the copy of the input into F (equal for all)")
+    emit(f"# NKA_HIP_BATCH_WAVES_MAX_VLEN of the library loaded: {cap}; {per_group} systems per workgroup")
+    emit("# b won: a - b > |a - a'|;  f won: e - f > |a - a'|;  d/c: what the length argument costs")
+    emit(f"{'nsys':>6} {'vlen':>4} {'mvec':>4} {'mean len':>8} {'a us':>9} {'a2 us':>9} {'b us':>9} {'c us':>9} {'d us':>9} {'e us':>9} {'f us':>9} "
+         f"{'b/a':>6} {'|a-a2|/a':>8} {'d/c':>6} {'f/e':>6}  b won  f won")
+    t0 = time.time()
+    tally = {"b": [0, 0], "f": [0, 0]}
+    for n, v, m in points:
+        if v > cap:
+            emit(f"{n:6d} {v:4d} {m:4d}   EXCLUDED: beyond the cap of the library loaded")
+            continue
+        r = measure_waves_ext(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9)
+        if r is None:
+            emit(f"{n:6d} {v:4d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        ctl = abs(r["a"] - r["a2"])
+        bwon, fwon = r["a"] - r["b"] > ctl, r["e"] - r["f"] > ctl
+        tally["b"][not bwon] += 1
+        tally["f"][not fwon] += 1
+        spreads = " ".join(f"{k} {100 * r['spread_' + k]:.1f} %" for k in ("a", "a2", "b", "c", "d", "e", "f"))
+        emit(f"{n:6d} {v:4d} {m:4d} {r['mean_len']:8.0f} " + " ".join(f"{r[k] * 1e6:9.1f}" for k in ("a", "a2", "b", "c", "d", "e", "f")) +
+             f" {r['b'] / r['a']:6.3f} {ctl / r['a']:8.3f} {r['d'] / r['c']:6.3f} {r['f'] / r['e']:6.3f}  {'yes' if bwon else 'NO':>5}  "
+             f"{'yes' if fwon else 'NO':>5}   (spread {spreads})")
+    emit(f"# (b) won at {tally['b'][0]} of {sum(tally['b'])} measured points, (f) at {tally['f'][0]} of {sum(tally['f'])}; "
+         f"{len(points)} points in {time.time() - t0:.0f} s")
     return 0
 
 
@@ -944,6 +1057,10 @@ def main():
                     help="time the wave batch (one wavefront per system) beside two narrow batches at the rounded fast sums (the second: "
                          "a control); without --nsys / --vlens / --mvecs / --mem-gb: nsys 256,4096,65536 x vlen 65,128,256,512,1024,2048,"
                          "4096 x mvec 5,10,20, 40 GB, then accel_step at vlen 256 x mvec 10,20; prints the cap its rule yields")
+    ap.add_argument("--waves-ext", action="store_true",
+                    help="time the wave batch with lengths and weights (nka_hip_batch_create_waves_ext) beside narrow batches with the "
+                         "same lengths and weights and beside the plain wave batch; without --nsys / --vlens / --mvecs / --mem-gb: nsys "
+                         "4096 x vlen 128,256,1024 x mvec 10,20, then 65536 x 256 x 10, 40 GB")
     ap.add_argument("--wide-step", action="store_true",
                     help="time accel_step of a wide batch (nka_hip_batch_create_wide_step) against the wide accel_update and against "
                          "the loop a caller composes from it, run twice (the second: a control); without --nsys / --vlens / --mvecs / "
@@ -976,6 +1093,11 @@ def main():
             if getattr(args, name) == ap.get_default(name):
                 setattr(args, name, grid_w)
         return wide_step_main(args, torch, nka_amd, L, emit)
+    if args.waves_ext:
+        for name, grid_w in (("nsys", "4096"), ("vlens", "128,256,1024"), ("mvecs", "10,20"), ("mem_gb", 40.0)):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+        return waves_ext_main(args, torch, nka_amd, L, emit)
     if args.waves:
         for name, grid_w in (("nsys", "256,4096,65536"), ("vlens", "65,128,256,512,1024,2048,4096"), ("mvecs", "5,10,20"), ("mem_gb", 40.0)):
             if getattr(args, name) == ap.get_default(name):
