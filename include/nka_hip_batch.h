@@ -314,7 +314,7 @@
  *            a draw); a few hundred systems or fewer, longer systems, or a caller who needs the reference order or binary32 storage
  *            -- the batch above (weights and lengths: WAVES EXT below); at most 64 unknowns and tens of thousands of systems with mvec up to about
  *            10 -- LANES; beyond 16 384 unknowns -- WIDE.
- *   WAVES EXT  nka_hip_batch_create_waves_ext: THE WAVE BATCH WITH LENGTHS AND WEIGHTS (nka_amd/csrc/nka_batch_waves_ext.hip).  Limits,
+ *   WAVES EXT  nka_hip_batch_create_waves_ext: THE WAVE BATCH WITH LENGTHS AND WEIGHTS (nka_amd/csrc/nka_batch_waves.hip).  Limits,
  *            cap, flavours, storage and every guarantee of WAVES; nothing more is allocated at creation (the weight and the length
  *            buffer come at the first set, as in the batch above), and nka_hip_batch_kind stays 3.  What it adds is exactly the two
  *            entries WAVES refuses: nka_hip_batch_set_lengths / _host and nka_hip_batch_set_dot_weights / _host, with the host side,

@@ -845,7 +845,6 @@ int nka_hip_batch_accel_update(nka_hip_batch_t b, double *f_dev, int64_t ld, con
   if (int rc = check_mask(b, active_dev, "batch_accel_update: active")) return rc;
   if (b->wide) nka_batch_wide_update(b, f_dev, ld, active_dev);
   else if (b->lanes) nka_batch_lanes_update(b, f_dev, ld, active_dev);
-  else if (b->waves_ext && (b->weighted || b->has_len)) nka_batch_waves_ext_update(b, f_dev, ld, active_dev);
   else if (b->waves) nka_batch_waves_update(b, f_dev, ld, active_dev);
   else launch_flavor(b, f_dev, ld, active_dev);
   HIP_TRY(hipGetLastError());
@@ -880,7 +879,6 @@ int nka_hip_batch_accel_step(nka_hip_batch_t b, double *f_dev, int64_t ld, doubl
   }
   if (b->wide) nka_batch_wide_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else if (b->lanes) nka_batch_lanes_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
-  else if (b->waves_ext && (b->weighted || b->has_len)) nka_batch_waves_ext_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else if (b->waves) nka_batch_waves_step(b, f_dev, ld, x_dev, ldx, active_dev, tol_dev, fnorm_dev);
   else launch_flavor(b, f_dev, ld, active_dev, StepArgs{x_dev, x_dev ? ldx : 0, tol_dev, fnorm_dev});
   HIP_TRY(hipGetLastError());

@@ -226,7 +226,7 @@ struct nka_hip_batch_state {
   // a WAVE batch (nka_hip_batch_create_waves, nka_batch_waves.hip): one wavefront per system; storage and control blocks are the
   // narrow batch's, nothing further is allocated
   bool waves = false;
-  // ... of nka_hip_batch_create_waves_ext (nka_batch_waves_ext.hip): the same batch, which also takes lengths and weights
+  // ... of nka_hip_batch_create_waves_ext: the same batch, which also takes lengths and weights (the same unit and kernel)
   bool waves_ext = false;
 };
 
@@ -247,11 +247,8 @@ void nka_batch_lanes_update(nka_hip_batch_t b, double *f, int64_t ld, const int3
 void nka_batch_lanes_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
                           double *fnorm);
 int nka_batch_lanes_get_slot(nka_hip_batch_t b, bool v, int32_t sys, int32_t slot, double *host_out);
-// nka_batch_waves.hip: one update and one solve step of a wave batch -- one launch each on b->stream
+// nka_batch_waves.hip: one update and one solve step of a wave batch -- one launch each on b->stream --, with the weights
+// (b->weighted) and the lengths (b->has_len) that a batch of nka_hip_batch_create_waves_ext (b->waves_ext) may have set
 void nka_batch_waves_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
 void nka_batch_waves_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
                           double *fnorm);
-// nka_batch_waves_ext.hip: the same of a wave batch with weights (b->weighted) or lengths (b->has_len) or both set
-void nka_batch_waves_ext_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
-void nka_batch_waves_ext_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
-                              double *fnorm);

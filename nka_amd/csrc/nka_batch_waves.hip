@@ -1,7 +1,7 @@
-// nka_batch_waves.hip -- the WAVE batch of include/nka_hip_batch.h (nka_hip_batch_create_waves): ONE WAVEFRONT PER SYSTEM, four
-// systems per workgroup, for systems between the lane batch (vlen <= 64) and the lengths at which the narrow batch
-// (nka_batch.hip: a workgroup of 256 threads per system) fills its tiles.  Wavefront w of workgroup g owns system 4 g + w through
-// every phase; the storage, the control blocks and every host entry are the narrow batch's.
+// nka_batch_waves.hip -- the WAVE batch of include/nka_hip_batch.h (nka_hip_batch_create_waves, nka_hip_batch_create_waves_ext):
+// ONE WAVEFRONT PER SYSTEM, four systems per workgroup, for systems between the lane batch (vlen <= 64) and the lengths at which
+// the narrow batch (nka_batch.hip: a workgroup of 256 threads per system) fills its tiles.  Wavefront w of workgroup g owns system
+// 4 g + w through every phase; the storage, the control blocks and every host entry are the narrow batch's.
 //   0 skip      sys >= nsys or active[sys] == 0: the wavefront returns before any byte of the system is read or written
 //   1 load      h, c and the links into the wavefront's working copy in LDS, all lanes; lane 0 lists the older entries (the list
 //               length is read HERE, on the device: graphs from the first update)
@@ -32,6 +32,20 @@
 // position or the wavefront the system lands on, on its neighbours, on ld / ldx or on the alignment of a row.  They are NOT the
 // narrow batch's bits (its tile is 512 elements over 256 threads, plus three cross-wavefront additions): the contract is the
 // numerical one of NKA_HIP_SUMS_BLOCKED_ROUNDED.
+// ONE KERNEL, 24 INSTANCES: 3 flavours x {update, step} x {plain, weights, lengths, both}.  What an instance takes beside the
+// update's arguments rides in the trailing pack (below), so an instance without a member keeps its arguments; a batch of
+// nka_hip_batch_create_waves can set neither lengths nor weights and runs the plain instances only.
+//   LENGTHS  A trailing LenArgs makes n = len[sys] -- one uniform load behind the `active` test -- the length of EVERY phase: the
+//            sweeps, the step's <f,f> and x -= f_out, the weight loads.  Lane l owns the pair 2l, 2l + 1 of every 128-element tile
+//            and meets its pairs in increasing order whatever n is, and the butterfly does not depend on n: the system carries the
+//            bits of a wave batch created with vlen = len[sys], and nothing at an index >= len[sys] of f, x, the weight row or a
+//            slot is read or written.
+//   WEIGHTS  A leading WgtRows, WgtStride: row `sys` of the batch's weight buffer -- rows + sys * stride, 0 for the form all
+//            systems share -- is read like a stored vector (16-byte aligned rows at the slot stride) in phases 2 and 3, and
+//            fl(w_i a_i) is the FIRST operand of every product, the narrow batch's table: red[0] fma(fl(w d), d, .), red[1]
+//            fma(fl(w f), w1', .), red[2+p] fma(fl(w w1'), w_p, .), red[2+m+p] fma(fl(w f), w_p, .), the step's <f,f>
+//            fma(fl(w f), f, .); fl(w f) is formed once per element and sweep.  Phase 6 does not read the weights.  The chain of
+//            roundings behind the first operand is the unweighted one: waves_k(n) stands.
 #include "nka_batch_dev.hpp"
 
 #include <cstdint>
@@ -52,6 +66,11 @@ static_assert(nka_host::waves_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 64 * 1024, 
 static_assert(NKA_HIP_BATCH_WAVES_MAX_VLEN <= NKA_HIP_BATCH_MAX_VLEN && NKA_HIP_BATCH_WAVES_MAX_VLEN % kWavesTile == 0,
               "the cap is whole tiles, inside the narrow batch's range (the storage is the narrow batch's)");
 
+// THE TRAILING PACK of k_waves_update: [WgtRows, WgtStride][, StepArgs][, LenArgs], each at most once, in this order.
+// the batch's weight buffer and its row stride (0: the form all systems share): the FIRST members, and two kernel arguments, not a
+// struct of two -- a pointer inside a struct cannot be __restrict__, and without it the weighted instances are scheduled differently
+using WgtRows = const double *__restrict__;
+enum class WgtStride : int64_t {};
 // what a solve step takes beside the update's arguments (the StepArgs of nka_batch.hip); each pointer may be NULL
 struct StepArgs {
   double *x;
@@ -59,6 +78,15 @@ struct StepArgs {
   const double *tol;
   double *fnorm;
 };
+// the batch's buffer of nsys validated lengths, 1 <= len[sys] <= vlen (the LenArgs of nka_batch.hip): the LAST member of the pack
+struct LenArgs {
+  const int32_t *len;
+};
+// the T of pack...
+template <class T, class First, class... Rest>
+__device__ __forceinline__ const T &pack_get(const First &first, const Rest &...rest) {
+  if constexpr (std::is_same<T, First>::value) return first; else return pack_get<T>(rest...);
+}
 
 // one lane's LDS traffic ordered against the other lanes' of the SAME wavefront (the head comment, SYNCHRONISATION)
 __device__ __forceinline__ void wave_sync() {
@@ -84,13 +112,16 @@ __device__ __forceinline__ void waves_sweep(int64_t n, bool fvec, int lane, Body
   }
 }
 
-// Step...: nothing (the update) or one StepArgs (the solve step); a step writes active[sys] = 0 when the system retires.
-template <int COMB, class... Step>
+// Pack...: the trailing pack above; a step writes active[sys] = 0 when the system retires.
+template <int COMB, class... Pack>
 __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, double *__restrict__ f_all, int64_t ld,
-                                                                const int32_t *__restrict__ active, Step... step) {
+                                                                const int32_t *__restrict__ active, Pack... pack) {
 #pragma clang fp contract(off)      // elementwise statements round like the reference; fma is explicit
-  constexpr bool STEP = sizeof...(Step) == 1;
-  static_assert(sizeof...(Step) <= 1, "nothing, or one StepArgs");
+  constexpr bool WGT = (std::is_same<Pack, WgtRows>::value || ...);
+  constexpr bool STEP = (std::is_same<Pack, StepArgs>::value || ...);
+  constexpr bool LEN = (std::is_same<Pack, LenArgs>::value || ...);
+  static_assert(WGT == (std::is_same<Pack, WgtStride>::value || ...) && sizeof...(Pack) == (WGT ? 2 : 0) + (STEP ? 1 : 0) + (LEN ? 1 : 0),
+                "at most one WgtRows with its WgtStride, then at most one StepArgs, then at most one LenArgs");
   constexpr int NNRM = STEP ? 2 : 1;      // sums of phase 2: [<f,f>,] <d,d>
   constexpr bool RCP = (COMB == 1);
   constexpr bool COMPACT = (COMB == 2);
@@ -103,11 +134,15 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int mvec = a.mvec, m1 = mvec + 1, nh = (m1 + 1) * (m1 + 1);
-  const int64_t n = a.n;
+  const int64_t n = [&]() -> int64_t {
+    if constexpr (LEN) return pack_get<LenArgs>(pack...).len[sys]; else return a.n;      // (validated when it was set: 1 <= len[sys] <= a.n)
+  }();
   const Ctl ctl = batch_ctl(a, (int)sys);
-  double *const f = f_all + (size_t)sys * ld;
-  double *const W = a.w + (size_t)sys * a.sys_stride, *const V = a.v + (size_t)sys * a.sys_stride;
+  double *const f = f_all + (size_t)sys * (size_t)ld;
+  double *const W = a.w + (size_t)sys * (size_t)a.sys_stride, *const V = a.v + (size_t)sys * (size_t)a.sys_stride;
   const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;      // (stored vectors: always 16-byte aligned)
+  [[maybe_unused]] const double *wg = nullptr;                       // this system's weights (rows: 16-byte aligned)
+  if constexpr (WGT) wg = pack_get<WgtRows>(pack...) + (size_t)sys * (size_t)pack_get<WgtStride>(pack...);
 
   const nka_host::WavesLds wl = nka_host::waves_lds(mvec);
   const nka_host::BatchLds &lds = wl.copy;
@@ -158,12 +193,16 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
     waves_sweep(n, fvec, lane, [&](auto full, auto fv_, int64_t i) {
       constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
       const d2 fv = ld_tile<FULL, FV>(f, i, n), wv_ = ld_tile<FULL, true>(w1, i, n);
+      [[maybe_unused]] d2 gv;
+      if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);
 #pragma unroll
       for (int q = 0; q < 2; q++)
         if (FULL || i + q < n) {
           const double d = wv_[q] - fv[q];
-          acc[NNRM - 1] = fma(d, d, acc[NNRM - 1]);
-          if constexpr (STEP) acc[0] = fma(fv[q], fv[q], acc[0]);
+          if constexpr (WGT) acc[NNRM - 1] = fma(gv[q] * d, d, acc[NNRM - 1]); else acc[NNRM - 1] = fma(d, d, acc[NNRM - 1]);
+          if constexpr (STEP) {
+            if constexpr (WGT) acc[0] = fma(gv[q] * fv[q], fv[q], acc[0]); else acc[0] = fma(fv[q], fv[q], acc[0]);
+          }
         }
     });
     const double dd = wave_sum_all(acc[NNRM - 1]);
@@ -175,9 +214,13 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
     waves_sweep(n, fvec, lane, [&](auto full, auto fv_, int64_t i) {
       constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
       const d2 fv = ld_tile<FULL, FV>(f, i, n);
+      [[maybe_unused]] d2 gv;
+      if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);      // (the weights ride along)
 #pragma unroll
       for (int q = 0; q < 2; q++)
-        if (FULL || i + q < n) acc = fma(fv[q], fv[q], acc);
+        if (FULL || i + q < n) {
+          if constexpr (WGT) acc = fma(gv[q] * fv[q], fv[q], acc); else acc = fma(fv[q], fv[q], acc);
+        }
     });
     ff = wave_sum_all(acc);
   }
@@ -186,7 +229,7 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
   [[maybe_unused]] double *xrow = nullptr;      // this system's row of the iterate, if there is one
   [[maybe_unused]] bool xvec = false;
   if constexpr (STEP) {
-    const StepArgs &st = (step, ...);
+    const StepArgs &st = pack_get<StepArgs>(pack...);
     const double r = sqrt(ff);
     if (lane == 0 && st.fnorm != nullptr) st.fnorm[sys] = r;
     if (st.tol != nullptr && r <= st.tol[sys]) {      // (a NaN on either side: false, the system goes on)
@@ -194,7 +237,7 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
       return;
     }
     if (st.x != nullptr) {
-      xrow = st.x + (size_t)sys * st.ldx;
+      xrow = st.x + (size_t)sys * (size_t)st.ldx;
       xvec = (reinterpret_cast<uintptr_t>(xrow) % 16) == 0;
     }
   }
@@ -220,18 +263,24 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
       d2 wv_[kBatchGroup];
 #pragma unroll
       for (int j = 0; j < kBatchGroup; j++) wv_[j] = ld_tile<FULL, true>(wk[j], i, n);
+      [[maybe_unused]] d2 gv;
+      if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);
 #pragma unroll
       for (int q = 0; q < 2; q++)
         if (FULL || i + q < n) {
           const double fq = fv[q];
+          double fa = fq;                                  // first operand of the products on f: fl(w f), formed once
+          if constexpr (WGT) fa = gv[q] * fq;
           if (normed) {
             const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
-            if (g == 0) acc[2 * kBatchGroup] = fma(fq, wn, acc[2 * kBatchGroup]);
+            double wa = wn;                                // first operand of the Gram row: fl(w w1')
+            if constexpr (WGT) wa = gv[q] * wn;
+            if (g == 0) acc[2 * kBatchGroup] = fma(fa, wn, acc[2 * kBatchGroup]);
 #pragma unroll
-            for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wn, wv_[j][q], acc[j]);
+            for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wa, wv_[j][q], acc[j]);
           }
 #pragma unroll
-          for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fq, wv_[j][q], acc[kBatchGroup + j]);
+          for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fa, wv_[j][q], acc[kBatchGroup + j]);
         }
     });
 #pragma unroll
@@ -260,7 +309,7 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
   }
   for (int i = lane; i < 2 + 2 * mvec; i += 64) ctl.red()[i] = red[i];
 
-  // ---- phase 6: normalise the pending pair, combine, ring stores (F08:282-283, 361, 395-404) ----
+  // ---- phase 6: normalise the pending pair, combine, ring stores (F08:282-283, 361, 395-404); the weights are not read ----
   const int ncomb = hdr[HDR_NCOMB];
   const bool norm0 = hdr[HDR_NORMED] != 0;      // pair 0 of the plan is the pending pair, still raw
   double *const wnew = W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
@@ -320,18 +369,33 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
   });
 }
 
-template <int COMB, class... Step>
-void launch_waves_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+// THE LAUNCH LADDER: flavour -> weighted? -> lengths? -> launch.  (Whether a call is weighted, in which form, and whether it has
+// lengths travels in the launch: the instance, the two buffers' addresses and the row stride are fixed when the call is enqueued
+// -- or captured --, the buffers' VALUES are read when it runs.)
+template <int COMB, class... Pack>
+void launch_waves_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Pack... pack) {
   const size_t lds = (size_t)nka_host::waves_lds(b->k.mvec).bytes();
-  hipLaunchKernelGGL((k_waves_update<COMB, Step...>), dim3((unsigned)nka_host::waves_ngroup(b->k.nsys)), dim3(kWavesThreads), lds,
-                     b->stream, b->k, f, ld, active, step...);
+  hipLaunchKernelGGL((k_waves_update<COMB, Pack...>), dim3((unsigned)nka_host::waves_ngroup(b->k.nsys)), dim3(kWavesThreads), lds,
+                     b->stream, b->k, f, ld, active, pack...);
 }
+template <int COMB, class... Pack>
+void launch_waves_len(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Pack... pack) {
+  if (b->waves_ext && b->has_len) launch_waves_as<COMB, Pack..., LenArgs>(b, f, ld, active, pack..., LenArgs{b->len});
+  else launch_waves_as<COMB, Pack...>(b, f, ld, active, pack...);
+}
+template <int COMB, class... Step>
+void launch_waves_wgt(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
+  if (b->waves_ext && b->weighted)      // (the pack is named throughout: deduction would drop the __restrict__ of WgtRows)
+    launch_waves_len<COMB, WgtRows, WgtStride, Step...>(b, f, ld, active, b->wgt, WgtStride(b->wgt_stride), step...);
+  else launch_waves_len<COMB, Step...>(b, f, ld, active, step...);
+}
+// `step`: nothing for the update, one StepArgs for the solve step
 template <class... Step>
 void launch_waves(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Step... step) {
   switch (b->flavor) {
-    case NKA_HIP_FLAVOR_F08_VECTOR: launch_waves_as<1>(b, f, ld, active, step...); break;
-    case NKA_HIP_FLAVOR_C: launch_waves_as<2>(b, f, ld, active, step...); break;
-    default: launch_waves_as<0>(b, f, ld, active, step...);
+    case NKA_HIP_FLAVOR_F08_VECTOR: launch_waves_wgt<1>(b, f, ld, active, step...); break;
+    case NKA_HIP_FLAVOR_C: launch_waves_wgt<2>(b, f, ld, active, step...); break;
+    default: launch_waves_wgt<0>(b, f, ld, active, step...);
   }
 }
 

@@ -1,5 +1,5 @@
 """The wave batch with per-system lengths and diagonal dot weights (nka_hip_batch_create_waves_ext; include/nka_hip_batch.h,
-WAVES EXT; nka_amd/csrc/nka_batch_waves_ext.hip) as far as the host can restate it: the shapes of
+WAVES EXT; nka_amd/csrc/nka_batch_waves.hip) as far as the host can restate it: the shapes of
 tests/test_batch_waves_ext_gpu.py, the weights, the call plan of the twin tests, the large shape, and the ragged weighted solve
 with its budget.  No GPU here: tests/test_batch_waves_ext_cpu.py holds all of it."""
 import numpy as np

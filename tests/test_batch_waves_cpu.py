@@ -61,7 +61,17 @@ def test_waves_k_is_what_the_kernel_does():
     # every accumulation is one fma per element (q = 0, 1) into one accumulator; nothing else adds into an accumulator
     kern = code[code.index("void k_waves_update"):code.index("void launch_waves_as")]
     fmas = re.findall(r"(acc(?:\[[^\]]+\])?) = fma\(([^;]+), \1\);", kern)
-    assert len(fmas) == 6, fmas                              # <d,d>, <f,f> (twice: with and without a pending pair), and the three of phase 3
+    first = sorted(f[1].split(",")[0].strip() for f in fmas)
+    # <d,d>, <f,f> (twice: with and without a pending pair), each weighted and plain, and the three of phase 3, whose first
+    # operands fa = fl(w f) and wa = fl(w w1') are formed once per element
+    assert first == sorted(["gv[q] * d", "d", "gv[q] * fv[q]", "fv[q]", "gv[q] * fv[q]", "fv[q]", "fa", "wa", "fa"]), first
+    # each weighted form stands in an `if constexpr (WGT)` whose `else` is the plain form
+    for wgt, plain in (("acc[NNRM - 1] = fma(gv[q] * d, d, acc[NNRM - 1]);", "acc[NNRM - 1] = fma(d, d, acc[NNRM - 1]);"),
+                       ("acc[0] = fma(gv[q] * fv[q], fv[q], acc[0]);", "acc[0] = fma(fv[q], fv[q], acc[0]);"),
+                       ("acc = fma(gv[q] * fv[q], fv[q], acc);", "acc = fma(fv[q], fv[q], acc);")):
+        assert kern.count(f"if constexpr (WGT) {wgt} else {plain}") == 1, wgt
+    assert kern.count("double fa = fq;") == 1 and kern.count("if constexpr (WGT) fa = gv[q] * fq;") == 1
+    assert kern.count("double wa = wn;") == 1 and kern.count("if constexpr (WGT) wa = gv[q] * wn;") == 1
     assert len(re.findall(r"acc(?:\[[^\]]+\])?\s*(?:\+=|= acc)", kern)) == 0
     assert kern.count("for (int q = 0; q < 2; q++)") >= 4
     # the butterfly: wave_sum, six levels, through registers

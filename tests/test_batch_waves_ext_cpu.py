@@ -49,22 +49,21 @@ def test_the_model_of_the_weighted_wave_sum_is_inside_the_bound_and_every_mutati
             assert not _inside(got, a, y, n), (n, i, name)
 
 
-def test_the_new_unit_restates_the_wave_kernel():
-    """nka_batch_waves_ext.hip follows nka_batch_waves.hip where they overlap: the same sweep, one fma per element and accumulator
-    (each weighted product beside its unweighted form), the butterfly of wave_sum, no workgroup barrier, no atomics; the weight
-    pair is loaded like a stored vector and phase 6 does not read it; every sys * stride product is in 64 bits."""
-    ext = open(os.path.join(CSRC, "nka_batch_waves_ext.hip")).read()
-    old = open(os.path.join(CSRC, "nka_batch_waves.hip")).read()
-    code = "\n".join(ln.split("//")[0] for ln in ext.splitlines())
-    ocode = "\n".join(ln.split("//")[0] for ln in old.splitlines())
-    sweep = code[code.index("void waves_sweep"):code.index("k_waves_ext_update")]
-    assert sweep.split("{", 1)[1].split("template")[0].strip() == \
-        ocode[ocode.index("void waves_sweep"):ocode.index("k_waves_update")].split("{", 1)[1].split("template")[0].strip()
-    kern = code[code.index("void k_waves_ext_update"):code.index("void launch_waves_ext_as")]
+def test_the_one_wave_unit_holds_the_weighted_and_the_ragged_kernel():
+    """nka_batch_waves.hip is the only wave unit and k_waves_update the only wave kernel: one sweep, one wave_sync, one fma per
+    element and accumulator (each weighted product beside its unweighted form), the butterfly of wave_sum, no workgroup barrier,
+    no atomics; the weight pair is loaded like a stored vector and phase 6 does not read it; every sys * stride product is in 64
+    bits."""
+    assert not os.path.exists(os.path.join(CSRC, "nka_batch_waves_ext.hip"))
+    assert "nka_batch_waves_ext" not in open(os.path.join(CSRC, "Makefile")).read()
+    unit = open(os.path.join(CSRC, "nka_batch_waves.hip")).read()
+    code = "\n".join(ln.split("//")[0] for ln in unit.splitlines())
+    assert code.count("void waves_sweep(") == 1 and code.count("void wave_sync()") == 1 and code.count("__global__") == 1
+    kern = code[code.index("void k_waves_update"):code.index("void launch_waves_as")]
     fmas = re.findall(r"(acc(?:\[[^\]]+\])?) = fma\(([^;]+), \1\);", kern)
     first = sorted(f[1].split(",")[0].strip() for f in fmas)
-    # phase 2: <d,d> and <f,f> (twice: with and without a pending pair), each weighted and plain; phase 3: the three of
-    # k_waves_update, whose first operands fa = fl(w f) and wa = fl(w w1') are formed once per element
+    # phase 2: <d,d> and <f,f> (twice: with and without a pending pair), each weighted and plain; phase 3: the three sums, whose
+    # first operands fa = fl(w f) and wa = fl(w w1') are formed once per element
     assert first == sorted(["gv[q] * d", "d", "gv[q] * fv[q]", "fv[q]", "gv[q] * fv[q]", "fv[q]", "fa", "wa", "fa"]), first
     assert kern.count("if constexpr (WGT) fa = gv[q] * fq;") == 1 and kern.count("if constexpr (WGT) wa = gv[q] * wn;") == 1
     assert len(re.findall(r"acc(?:\[[^\]]+\])?\s*(?:\+=|= acc)", kern)) == 0
@@ -74,12 +73,10 @@ def test_the_new_unit_restates_the_wave_kernel():
     phase6 = kern[kern.index("const int ncomb = hdr[HDR_NCOMB];"):]
     assert "gv" not in phase6 and "wg" not in phase6
     assert kern.count("gv = ld_tile<FULL, true>(wg, i, n);") == 3      # phase 2 (twice: with and without a pending pair) and phase 3
-    for prod in ("(size_t)sys * (size_t)ld", "(size_t)sys * (size_t)a.sys_stride", "(size_t)sys * (size_t)wgt_stride",
+    for prod in ("(size_t)sys * (size_t)ld", "(size_t)sys * (size_t)a.sys_stride", "(size_t)sys * (size_t)pack_get<WgtStride>(pack...)",
                  "(size_t)sys * (size_t)st.ldx"):
         assert prod in kern, prod
-    assert "len_args(pack...)[sys]" in kern[kern.index("active[sys] == 0"):]      # one load behind the `active` test
-    # 3 flavours x {weights, lengths, both} x {update, step}: the (none, none) instance is refused at compile time
-    assert 'static_assert(WGT || LEN' in kern
+    assert "pack_get<LenArgs>(pack...).len[sys]" in kern[kern.index("active[sys] == 0"):]      # one load behind the `active` test
 
 
 # ---- lengths and shapes -------------------------------------------------------------------------------------------------------------

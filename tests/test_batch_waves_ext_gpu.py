@@ -1,5 +1,5 @@
 """The wave batch with per-system lengths and diagonal dot weights (include/nka_hip_batch.h, WAVES EXT;
-nka_amd.nka_batch().init(..., waves=True, ext=True); nka_amd/csrc/nka_batch_waves_ext.hip).
+nka_amd.nka_batch().init(..., waves=True, ext=True); nka_amd/csrc/nka_batch_waves.hip).
   1 lengths: every system == its own plain wave twin of vlen = len, after every call, tails untouched
   2 lengths changed between calls, cleared, and new values between the replays of a graph captured before the first update
   3 weights: unit weights, powers of four, the three layers against exact sums, a zero-weight tail, the weighted fnorm and the stop
