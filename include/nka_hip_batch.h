@@ -117,9 +117,10 @@
  *            the combine plan (the control block's comb_slots / comb_c stay zero, so that its digest is the narrow batch's).
  *            NKA_HIP_SUMS_AUTO and _BLOCKED_ROUNDED both mean the rounded fast sums, at every vlen.  REFUSED with NKA_HIP_EINVAL,
  *            the batch staying usable: nka_hip_batch_accel_step on a batch of nka_hip_batch_create_wide (a batch of
- *            nka_hip_batch_create_wide_step offers it: STEP below); on every wide batch nka_hip_batch_set_dot_weights and
- *            _set_dot_weights_host (nka_hip_batch_dot_weighted returns 0), NKA_HIP_SUMS_REFERENCE_ORDER and _BLOCKED through
- *            _set_sum_order, and binary32 storage.  A caller who needs one of the last three has the batch above up to 16 384
+ *            nka_hip_batch_create_wide_step offers it: STEP below); on a batch of these two entries nka_hip_batch_set_dot_weights and
+ *            _set_dot_weights_host (nka_hip_batch_dot_weighted returns 0; a batch of nka_hip_batch_create_wide_ext offers them: WIDE
+ *            EXT below); on every wide batch NKA_HIP_SUMS_REFERENCE_ORDER and _BLOCKED through
+ *            _set_sum_order, and binary32 storage.  A caller who needs one of the last two has the batch above up to 16 384
  *            elements and lone handles beyond.
  *            STEP of a wide batch: nka_hip_batch_create_wide_step is nka_hip_batch_create_wide -- the same limits, refusals, kind
  *            (nka_hip_batch_kind 1, _is_wide 1) and accel_update, bit for bit and launch for launch -- with ONE MORE BUFFER: nsys *
@@ -168,7 +169,7 @@
  *            1.18 ... 1.42 x.  Up to 16 384 elements take the batch above for few or very many short systems and the wide one in
  *            between: at 4096 elements the two are level (wide / narrow 0.90 ... 1.06), at 16 384 the wide batch is 1.04 ... 2.45 x
  *            faster (2.45 x at 16 systems, 1.14 / 1.04 x at 256); both have the step (the wide one through
- *            nka_hip_batch_create_wide_step), and only the batch above has the weights and the reference order.  FOUR systems: the wide batch wins at mvec = 10 (1.05 ... 1.95 x) and LOSES to four lone handles at
+ *            nka_hip_batch_create_wide_step) and the weights (the wide one through nka_hip_batch_create_wide_ext: WIDE EXT below), and only the batch above has the reference order.  FOUR systems: the wide batch wins at mvec = 10 (1.05 ... 1.95 x) and LOSES to four lone handles at
  *            mvec = 20 at every length (0.67 ... 0.86 x): the scalar step of a system runs on one thread, 127 us at mvec = 20 (59 %
  *            of an update at 16 x 65 536), and a lone handle's does not.  A lone system stays with a lone handle.
  *   LENGTHS  nka_hip_batch_set_lengths: RAGGED BATCHES without padding weights, on both kinds of batch.  System `sys` is
@@ -344,6 +345,32 @@
  *            against a batch of nka_hip_batch_create_waves): 1.000 ... 1.014.  Won at 7 of 7 points in both comparisons.  So:
  *            thousands of systems of up to 1024 unknowns that differ in length or in the scale of their unknowns -- this entry;
  *            for every other case the sentences of WAVES stand (256 systems were not measured here: there WAVES loses).
+ *   WIDE EXT  nka_hip_batch_create_wide_ext: THE WIDE BATCH WITH WEIGHTS (nka_amd/csrc/nka_batch_wide.hip, nka_batch_wide_step.hip).
+ *            Limits, allocations and every guarantee of nka_hip_batch_create_wide for step == 0 and of nka_hip_batch_create_wide_step
+ *            for step == 1 (any other step: NKA_HIP_EINVAL); nka_hip_batch_kind stays 1, _is_wide 1, _offers_lengths 1, _offers_step
+ *            returns step, and the weight buffer comes at the first set, as in the batch above.  What it adds is exactly the entry
+ *            WIDE refuses: nka_hip_batch_set_dot_weights / _host, with the host side, the checks and the refusals of the batch
+ *            above (values checked before they are copied, refused values leave the previous weighting in force, NKA_HIP_ESTATE
+ *            while the stream is capturing, a row stride of 0 = one shared row).  set_sum_order and binary32 storage stay refused as
+ *            in WIDE; a batch of the two other wide entries keeps refusing the weights; nka_hip_batch_offers_weights tells them apart.
+ *            A weighted update, and a weighted step, is still FOUR launches in a line: the first two are the weighted kernels of a
+ *            chunk, the scalar step and the combine do not read the weights and are the launches of WIDE.  Within a launch no
+ *            workgroup reads what another writes: no flags, no spinning, no atomics, no cooperative launch.
+ *            WEIGHTS: fl(w_i a_i) is the FIRST operand of every product, the table of the batch above, per chunk:
+ *            part[0] = sum fma(fl(w d), d, .), red[1] = sum fma(fl(w f), w1', .), red[2+p] = sum fma(fl(w w1'), w_p, .), red[2+m+p] =
+ *            sum fma(fl(w f), w_p, .), the step's <f,f> = sum fma(fl(w f), f, .); fl(w f) is formed once per element and sweep.
+ *            NEITHER SET (weights nor lengths): the batch launches the kernels of WIDE and is a batch of nka_hip_batch_create_wide /
+ *            _create_wide_step bit for bit.  ONE CHUNK: a weighted wide batch of at most one chunk is the weighted batch above in
+ *            NKA_HIP_SUMS_BLOCKED_ROUNDED, bit for bit.  SEVERAL CHUNKS: every entry of red[] and the step's <f,f> lies within
+ *            gamma(K) sum|fl(w x) y| of the exact sum of fl(w x) and y, with the K of WIDE at the system's length (the first operand
+ *            is already rounded, so K does not change); red[0] is the chunk-order chain of the chunks' partials.  EXACT
+ *            CONSEQUENCES: w == 1 gives the plain wide batch's bits; w = 4^k is an exact rescaling, as under WEIGHTS.  LENGTHS: the
+ *            contract of LENGTHS holds with "the same weights on [0 .. L)", and nothing at or beyond len[sys] of the weight row is
+ *            read.  ZERO WEIGHTS: a zero weight does not shield a non-finite value, as in the batch above.  A captured call keeps
+ *            whether it was weighted and in which form, and reads the VALUES at replay (GRAPHS from the first update).
+ *            COST: the norm launch streams three vectors instead of two and each sweep of four of the sums launch seven instead of
+ *            six; the combine is unchanged.  What that costs is recorded in profiles/r19/batch_wide_weights_throughput.txt (tools/
+ *            batch_throughput.py --wide-weights) and read in docs/design/12_batched_systems.md, "Wide batch: weights".
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -413,11 +440,17 @@ int nka_hip_batch_waves_limits(int32_t *systems_per_group, int64_t *max_vlen);
 /* WAVES EXT above: nka_hip_batch_create_waves with nka_hip_batch_set_lengths / _host and nka_hip_batch_set_dot_weights / _host
  * offered; arguments, limits, allocations and _kind (3) as for nka_hip_batch_create_waves.
  * _offers_lengths / _offers_weights: 1 = the setters are offered, 0 = refused; < 0 on error (a NULL handle).  Lengths: every kind
- * but lanes and a batch of nka_hip_batch_create_waves; weights: narrow (either storage) and a batch of this entry. */
+ * but lanes and a batch of nka_hip_batch_create_waves; weights: narrow (either storage), a batch of this entry and a wide batch of
+ * nka_hip_batch_create_wide_ext. */
 int nka_hip_batch_create_waves_ext(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
                                    int32_t flavor, int32_t device, void *stream);
 int nka_hip_batch_offers_lengths(nka_hip_batch_t b);
 int nka_hip_batch_offers_weights(nka_hip_batch_t b);
+/* WIDE EXT above: the wide batch with nka_hip_batch_set_dot_weights / _host offered.  step == 0: arguments, limits, allocations and
+ * guarantees of nka_hip_batch_create_wide; step == 1: those of nka_hip_batch_create_wide_step; any other step: NKA_HIP_EINVAL.
+ * _kind 1, _is_wide 1, _offers_lengths 1, _offers_weights 1, _offers_step = step. */
+int nka_hip_batch_create_wide_ext(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                                  int32_t flavor, int32_t device, void *stream, int32_t step);
 int nka_hip_batch_is_wide(nka_hip_batch_t b);                    /* 1 = wide, 0 = narrow, lanes or waves; < 0 on error */
 int nka_hip_batch_wide_limits(int64_t *chunk, int64_t *max_vlen);  /* the two constants, as the library was built */
 int nka_hip_batch_destroy(nka_hip_batch_t b);

@@ -60,7 +60,7 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
-        restart / relax, graphs and per-system lengths -- set_lengths -- are offered; accel_step -- without step=True, below --, weights and the
+        restart / relax, graphs and per-system lengths -- set_lengths -- are offered; accel_step -- without step=True, below --, weights -- without ext=True, below -- and the
         reference sum order are refused).  storage=STORE_F32 (nka_hip_batch_create_stored; include/nka_hip_batch.h, STORAGE): the
         normalised subspace vectors are kept in binary32 -- 0.55 of the slot memory at mvec = 20 --, every product and sum
         still binary64, the pending pair still binary64.  Such a batch runs the default flavour (FLAVOR_C) and the rounded fast
@@ -77,7 +77,11 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         ext (with waves=True only): the wave batch WITH per-system lengths and diagonal dot weights (nka_hip_batch_create_waves_ext;
         include/nka_hip_batch.h, WAVES EXT) -- set_lengths and set_dot_weights are offered with the contracts of the default batch,
         a system of length L carries the bits of a wave batch of vlen = L, and with neither set the batch is the plain wave batch
-        bit for bit.  ext=True without waves=True raises NKAError.
+        bit for bit.  ext=True with neither waves=True nor wide=True raises NKAError.
+        ext (with wide=True, with or without step=True): the wide batch WITH diagonal dot weights (nka_hip_batch_create_wide_ext;
+        include/nka_hip_batch.h, WIDE EXT) -- set_dot_weights is offered in both forms, one shared row or one row per system, with
+        the contract of the default batch per chunk; at one chunk it is the weighted default batch bit for bit, with unit weights or
+        none set it is the plain wide batch bit for bit.  The reference sum order and binary32 storage stay refused.
         step (with wide=True only): the wide batch WITH the solve step (nka_hip_batch_create_wide_step; include/nka_hip_batch.h,
         WIDE: STEP of a wide batch) -- one more buffer of nsys x nchunk doubles, accel_step as four launches, everything else the
         wide batch bit for bit.  Every other kind offers the step already: step=True without wide=True raises NKAError."""
@@ -86,9 +90,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         if step and not wide:
             raise NKAError("nka_batch init: step=True selects the wide batch with the solve step and needs wide=True (every other "
                            "kind offers accel_step already)")
-        if ext and not waves:
-            raise NKAError("nka_batch init: ext=True selects the wave batch with lengths and weights and needs waves=True (the default "
-                           "batch offers both already)")
+        if ext and not (waves or wide):
+            raise NKAError("nka_batch init: ext=True selects the wave batch with lengths and weights and needs waves=True, or the wide "
+                           "batch with weights and needs wide=True (the default batch offers both already)")
         if waves and (wide or lanes):
             raise NKAError("nka_batch init: waves=True excludes wide=True and lanes=True (one wavefront per system, a system split "
                            "across workgroups, or one lane per system)")
@@ -123,6 +127,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         elif waves:
             _check(self._L.nka_hip_batch_create_waves(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                       C.c_void_p(stream)), "nka_hip_batch_create_waves", self._L)
+        elif wide and ext:
+            _check(self._L.nka_hip_batch_create_wide_ext(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                         C.c_void_p(stream), 1 if step else 0), "nka_hip_batch_create_wide_ext", self._L)
         elif wide and step:
             _check(self._L.nka_hip_batch_create_wide_step(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                           C.c_void_p(stream)), "nka_hip_batch_create_wide_step", self._L)
@@ -256,7 +263,8 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         float64 CUDA tensor on the batch's device or a numpy array, 1-d of vlen entries (one row shared by all systems) or 2-d
         nsys x vlen (row `sys` weights system `sys`; element stride 1, the row stride is `ldw`); None: plain sums again.
         Finite and >= 0; copied, so `w` is free again on return.  Synchronises; applies from the next update on -- follow it
-        with restart().  Returns self."""
+        with restart().  Offered by the default batch, by a wave batch created with ext=True and by a wide batch created with
+        ext=True (offers_weights()); every other kind raises NKAError and stays usable.  Returns self."""
         import torch
         h = self._handle()
         what = "batch set_dot_weights"
@@ -376,7 +384,8 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         return r == 1
 
     def offers_step(self) -> bool:
-        """True where accel_step is offered: every kind but a wide batch created without step=True (nka_hip_batch_offers_step)."""
+        """True where accel_step is offered: every kind but a wide batch created without step=True, with or without ext=True
+        (nka_hip_batch_offers_step)."""
         r = self._L.nka_hip_batch_offers_step(self._handle())
         _check(min(r, 0), "batch_offers_step", self._L)
         return bool(r)
@@ -389,8 +398,8 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         return bool(r)
 
     def offers_weights(self) -> bool:
-        """True where set_dot_weights is offered: the default batch (either storage) and a wave batch created with ext=True
-        (nka_hip_batch_offers_weights)."""
+        """True where set_dot_weights is offered: the default batch (either storage), a wave batch created with ext=True and a
+        wide batch created with ext=True (nka_hip_batch_offers_weights)."""
         r = self._L.nka_hip_batch_offers_weights(self._handle())
         _check(min(r, 0), "batch_offers_weights", self._L)
         return bool(r)

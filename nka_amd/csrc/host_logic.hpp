@@ -368,6 +368,12 @@ NKA_HOST_DEVICE constexpr bool batch_len_valid(int64_t len, int64_t vlen) { retu
 NKA_HOST_DEVICE constexpr int64_t wide_len_nchunk(int64_t len) { return wide_nchunk(len); }
 NKA_HOST_DEVICE constexpr bool wide_len_owns(int64_t len, int64_t c) { return c >= 0 && c < wide_len_nchunk(len); }
 NKA_HOST_DEVICE constexpr int64_t wide_len_chunk_len(int64_t len, int64_t c) { return wide_chunk_len(len, c); }      // (c owned)
+// DIAGONAL DOT WEIGHTS of a wide batch (nka_hip_batch_create_wide_ext): element 0 of chunk c of the weight row of system sys, in
+// doubles from the start of the batch's weight buffer -- rows lie wgt_stride apart, the slot stride (a multiple of 32 doubles),
+// or 0 apart in the form all systems share; a chunk starts on a multiple of kWideChunk elements, so the offset is a multiple of
+// 16 bytes in either form.  Every product is 64-bit.  tests/c/batch_wide_weights_check.cpp holds it against __int128 and walks
+// what a workgroup reads from there for every length.
+NKA_HOST_DEVICE constexpr int64_t wide_wgt_offset(int64_t sys, int64_t wgt_stride, int64_t c) { return sys * wgt_stride + c * kWideChunk; }
 // LDS of the sums and the combine kernel: doubles first, then int32 (a piece a kernel lacks has length 0; the norm kernel
 // holds sm [waves] and res [2] only, declared where it uses them)
 struct WideLds {

@@ -645,7 +645,7 @@ extern "C" {
 // per system (this file)
 static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor, int32_t device,
                         void *stream, bool wide, int32_t storage = NKA_HIP_BATCH_STORE_F64, const char *entry = nullptr,
-                        bool lanes = false, bool waves = false, bool wide_step = false, bool waves_ext = false) {
+                        bool lanes = false, bool waves = false, bool wide_step = false, bool waves_ext = false, bool wide_ext = false) {
   const std::string who = entry ? entry : wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
   const bool s32 = storage == NKA_HIP_BATCH_STORE_F32;
   if (!out) return fail(NKA_HIP_EINVAL, who + ": out is NULL");
@@ -688,6 +688,7 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
   b->lanes = lanes;
   b->waves = waves;
   b->waves_ext = waves && waves_ext;
+  b->wide_ext = wide && wide_ext;
   b->device = device;
   b->stream = (hipStream_t)stream;
   b->flavor = flavor;
@@ -776,6 +777,15 @@ int nka_hip_batch_create_wide_step(nka_hip_batch_t *out, int32_t nsys, int64_t v
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, true, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_wide_step", false,
                       false, true);
 }
+int nka_hip_batch_create_wide_ext(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                                  int32_t device, void *stream, int32_t step) {
+  if (step != 0 && step != 1) {
+    if (out) *out = nullptr;
+    return fail(NKA_HIP_EINVAL, "nka_hip_batch_create_wide_ext: step must be 0 (nka_hip_batch_create_wide) or 1 (nka_hip_batch_create_wide_step)");
+  }
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, true, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_wide_ext", false,
+                      false, step == 1, false, true);
+}
 int nka_hip_batch_create_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
                                 int32_t device, void *stream, int32_t storage) {
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, storage, "nka_hip_batch_create_stored");
@@ -812,7 +822,7 @@ int nka_hip_batch_offers_lengths(nka_hip_batch_t b) {
 }
 int nka_hip_batch_offers_weights(nka_hip_batch_t b) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_offers_weights: null handle");
-  return b->wide || b->lanes || (b->waves && !b->waves_ext) ? 0 : 1;
+  return (b->wide && !b->wide_ext) || b->lanes || (b->waves && !b->waves_ext) ? 0 : 1;
 }
 
 int nka_hip_batch_destroy(nka_hip_batch_t b) {
@@ -922,7 +932,7 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
 
 int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_t ldw) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: null handle");
-  if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wide batch (nka_hip_batch_create_wide)");
+  if (b->wide && !b->wide_ext) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wide batch (nka_hip_batch_create_wide)");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
   if (b->waves && !b->waves_ext) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));
@@ -939,7 +949,7 @@ int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_
 
 int nka_hip_batch_set_dot_weights_host(nka_hip_batch_t b, const double *w_host, int64_t ldw) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: null handle");
-  if (b->wide) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wide batch (nka_hip_batch_create_wide)");
+  if (b->wide && !b->wide_ext) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wide batch (nka_hip_batch_create_wide)");
   if (b->lanes) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a lane batch (nka_hip_batch_create_lanes): nka_hip_batch_create");
   if (b->waves && !b->waves_ext) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights_host: not offered by a wave batch (nka_hip_batch_create_waves): nka_hip_batch_create");
   HIP_TRY(hipSetDevice(b->device));

@@ -228,9 +228,13 @@ struct nka_hip_batch_state {
   bool waves = false;
   // ... of nka_hip_batch_create_waves_ext: the same batch, which also takes lengths and weights (the same unit and kernel)
   bool waves_ext = false;
+  // a WIDE batch of nka_hip_batch_create_wide_ext: the same batch, which also takes weights (the weighted norm and sums kernels of
+  // nka_batch_wide.hip and nka_batch_wide_step.hip); with wide_step as its `step` argument says
+  bool wide_ext = false;
 };
 
-// nka_batch_wide.hip: the buffers of a wide batch (b->k is complete), and one update of it -- four launches on b->stream
+// nka_batch_wide.hip: the buffers of a wide batch (b->k is complete), and one update of it -- four launches on b->stream, the first
+// two of them the weighted kernels where b->weighted (a batch of nka_hip_batch_create_wide_ext, b->wide_ext)
 int nka_batch_wide_alloc(nka_hip_batch_t b);
 void nka_batch_wide_free(nka_hip_batch_t b);
 void nka_batch_wide_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);

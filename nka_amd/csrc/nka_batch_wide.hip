@@ -12,6 +12,8 @@
 // the stored vectors and the parity of a row of f are those of the narrow kernel: a wide batch of ONE chunk returns the
 // narrow batch's bits.  Which partials a kernel reads is decided from the list (pending, normed, nolder), never from what the
 // buffer holds: a partial that this update did not write is not read.
+// With diagonal dot weights (a batch of nka_hip_batch_create_wide_ext) the first two launches are k_wide_norm_wgt and
+// k_wide_sums_wgt, further down; the last two do not read weights and stay the kernels above.
 #include "nka_batch_dev.hpp"
 
 #include <string>
@@ -656,12 +658,168 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_combine_len(BatchArgs a,
   });
 }
 
-// (whether an update runs with per-system lengths, and the buffer's address, are fixed when it is enqueued or captured; the grid
-// is nchunk x nsys either way, so the host needs no length to launch)
+// ---- THE FIRST TWO KERNELS WITH DIAGONAL DOT WEIGHTS (nka_hip_batch_create_wide_ext, nka_hip_batch_set_dot_weights) ----
+// Row `sys` of the batch's weight buffer -- wgt + sys * wgt_stride, wgt_stride = 0 for the form all systems share -- is read like a
+// stored vector: rows lie at the slot stride and a chunk starts on a multiple of 2048 elements, so every chunk of a weight row is
+// 16-byte aligned.  fl(w_i a_i) is the FIRST operand of every product, the table of k_batch_update<..., WGT = true> (nka_batch.hip):
+// <d,d> = sum fma(fl(w d), d, .), <f,w1'> = sum fma(fl(w f), w1', .), <w1',w_p> = sum fma(fl(w w1'), w_p, .), <f,w_p> = sum
+// fma(fl(w f), w_p, .).  The thread -> element map, the per-thread order, batch_block_sum, the chunk-order chains and which
+// partials are written are those of the kernels above.  The scalar step and the combine do not read weights: a weighted update
+// launches k_wide_scalar[_len] and k_wide_combine[_len].  Each body is written ONCE, as a template on LEN -- these kernels have no
+// earlier instruction stream to keep --; `len` is not read where LEN is false.  With LEN nothing at or beyond len[sys] of the weight
+// row is read: the weight pair is loaded under the guards of the pair of f.
+
+// ---- 1, weighted ----
+template <bool LEN>
+__global__ __launch_bounds__(kBatchThreads) void k_wide_norm_wgt(BatchArgs a, WideArgs wa, const double *__restrict__ f_all, int64_t ld,
+                                                                 const int32_t *__restrict__ active, const int32_t *__restrict__ len,
+                                                                 const double *__restrict__ wgt, int64_t wgt_stride) {
+#pragma clang fp contract(off)
+  const int sys = blockIdx.y;
+  if (active != nullptr && active[sys] == 0) return;
+  int64_t sn = a.n;
+  if constexpr (LEN) {
+    sn = len[sys];
+    if (!nka_host::wide_len_owns(sn, blockIdx.x)) return;      // (uniform: a chunk beyond the system's own; nothing was read)
+  }
+  const Ctl ctl = batch_ctl(a, sys);
+  if (ctl.ic[IC_PENDING] == 0) return;      // (uniform: no pending pair, no norm -- and nobody reads this partial)
+  __shared__ double sm[kBatchWaves], res[2];
+  const int64_t lo = (int64_t)blockIdx.x * kWideChunk, n = nka_host::wide_chunk_len(sn, blockIdx.x);
+  const double *const f = f_all + (size_t)sys * (size_t)ld + lo;
+  const double *const w1 = a.w + (size_t)sys * a.sys_stride + (size_t)(ctl.ic[IC_FIRST] - 1) * a.stride + lo;
+  const double *const wg = wgt + (size_t)nka_host::wide_wgt_offset(sys, wgt_stride, blockIdx.x);
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
+  double acc[1] = {};
+  batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+    constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+    const d2 fv = ld_tile<FULL, FV>(f, i, n), wv = ld_tile<FULL, true>(w1, i, n);
+    const d2 gv = ld_tile<FULL, true>(wg, i, n);
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+      if (FULL || i + q < n) {
+        const double d = wv[q] - fv[q];
+        acc[0] = fma(gv[q] * d, d, acc[0]);
+      }
+  });
+  batch_block_sum<1>(acc, sm, res);
+  if (threadIdx.x == 0) wa.part[nka_host::wide_part_index(sys, 0, blockIdx.x, a.mvec, wa.nchunk)] = res[0];
+}
+
+// ---- 2, weighted ----
+template <int COMB, bool LEN>
+__global__ __launch_bounds__(kBatchThreads) void k_wide_sums_wgt(BatchArgs a, WideArgs wa, const double *__restrict__ f_all, int64_t ld,
+                                                                 const int32_t *__restrict__ active, const int32_t *__restrict__ len,
+                                                                 const double *__restrict__ wgt, int64_t wgt_stride) {
+#pragma clang fp contract(off)
+  constexpr bool RCP = (COMB == 1);
+  const int sys = blockIdx.y, chunk = blockIdx.x;
+  if (active != nullptr && active[sys] == 0) return;
+  int64_t sn = a.n;
+  if constexpr (LEN) {
+    sn = len[sys];
+    if (!nka_host::wide_len_owns(sn, chunk)) return;      // (uniform, before the first barrier)
+  }
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int mvec = a.mvec, m1 = mvec + 1, nchunk = wa.nchunk;
+  const int nown = LEN ? (int)nka_host::wide_len_nchunk(sn) : nchunk;      // the partials of <d,d> that are added
+  const Ctl ctl = batch_ctl(a, sys);
+  const nka_host::WideLds lds = nka_host::wide_sums_lds(mvec, nchunk);
+  double *const shd = reinterpret_cast<double *>(smem);
+  int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
+  double *const stage = shd + lds.stage, *const sm = shd + lds.sm, *const res = shd + lds.res;
+  int32_t *const next = shi + lds.next, *const ps = shi + lds.ps, *const hdr = shi + lds.hdr;
+
+  wide_list(ctl, m1, next, ps, hdr);
+  const int pending = hdr[HDR_PENDING], nolder = hdr[HDR_NOLDER];
+  double s = 0.0;
+  if (pending) {
+    wide_norm_sum(wa.part + nka_host::wide_part_index(sys, 0, 0, mvec, nchunk), nown, stage, res + kBatchAcc);
+    s = sqrt(res[kBatchAcc]);
+  }
+  const bool normed = pending && s != 0.0;
+  const double rs = 1.0 / s;
+
+  const int64_t lo = (int64_t)chunk * kWideChunk, n = nka_host::wide_chunk_len(sn, chunk);
+  const double *const f = f_all + (size_t)sys * (size_t)ld + lo;
+  const double *const W = a.w + (size_t)sys * a.sys_stride + lo;
+  const double *const wg = wgt + (size_t)nka_host::wide_wgt_offset(sys, wgt_stride, blockIdx.x);
+  const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
+  const double *const w1s = pending ? W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride : W;      // always a stored vector
+  auto out = [&](int entry) -> double & { return wa.part[nka_host::wide_part_index(sys, entry, chunk, mvec, nchunk)]; };
+
+  const int ngroup = (nolder + kBatchGroup - 1) / kBatchGroup;
+  for (int g = 0; g < (ngroup > 0 ? ngroup : (normed ? 1 : 0)); g++) {
+    const double *wk[kBatchGroup];
+#pragma unroll
+    for (int j = 0; j < kBatchGroup; j++) {
+      const int p = g * kBatchGroup + j;
+      wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1s;   // (beyond the list: a re-read, discarded)
+    }
+    double acc[kBatchAcc];
+#pragma unroll
+    for (int q = 0; q < kBatchAcc; q++) acc[q] = 0.0;
+    batch_sweep(n, fvec, [&](auto full, auto fv_, int64_t i) {
+      constexpr bool FULL = decltype(full)::value, FV = decltype(fv_)::value;
+      const d2 fv = ld_tile<FULL, FV>(f, i, n);
+      const d2 dv = ld_tile<FULL, true>(w1s, i, n);     // (no pending pair: a stored vector whose value is not used)
+      d2 wv[kBatchGroup];
+#pragma unroll
+      for (int j = 0; j < kBatchGroup; j++) wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+      const d2 gv = ld_tile<FULL, true>(wg, i, n);
+#pragma unroll
+      for (int q = 0; q < 2; q++)
+        if (FULL || i + q < n) {
+          const double fq = fv[q];
+          const double fa = gv[q] * fq;                      // first operand of the products on f: fl(w f), formed once
+          if (normed) {
+            const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
+            const double wa_ = gv[q] * wn;                   // first operand of the Gram row: fl(w w1')
+            if (g == 0) acc[2 * kBatchGroup] = fma(fa, wn, acc[2 * kBatchGroup]);
+#pragma unroll
+            for (int j = 0; j < kBatchGroup; j++) acc[j] = fma(wa_, wv[j][q], acc[j]);
+          }
+#pragma unroll
+          for (int j = 0; j < kBatchGroup; j++) acc[kBatchGroup + j] = fma(fa, wv[j][q], acc[kBatchGroup + j]);
+        }
+    });
+    batch_block_sum<kBatchAcc>(acc, sm, res);
+    if (t < kBatchGroup && g * kBatchGroup + t < nolder) {
+      if (normed) out(2 + g * kBatchGroup + t) = res[t];
+      out(2 + mvec + g * kBatchGroup + t) = res[kBatchGroup + t];
+    }
+    if (t == 0 && g == 0 && normed) out(1) = res[2 * kBatchGroup];
+    // (res is rewritten only behind the two barriers of the next batch_block_sum)
+  }
+}
+
+// (whether an update runs with per-system lengths or weights, in which form, and the buffers' addresses are fixed when it is
+// enqueued or captured; the values are read when it runs.  The grid is nchunk x nsys either way, so the host needs no length to
+// launch)
 template <int COMB>
 void launch_wide(nka_hip_batch_t b, const WideArgs &wa, double *f, int64_t ld, const int32_t *active) {
   const int mvec = b->k.mvec, nchunk = b->nchunk;
   const dim3 grid((unsigned)nchunk, (unsigned)b->k.nsys), block(kBatchThreads);
+  if (b->weighted) {      // (only a batch of nka_hip_batch_create_wide_ext can be: every other wide batch refuses the setters)
+    const int32_t *const len = b->has_len ? b->len : nullptr;
+    const double *const wgt = b->wgt;
+    const int64_t ws = b->wgt_stride;
+    const size_t lsums = nka_host::wide_sums_lds(mvec, nchunk).bytes(), lscal = nka_host::wide_scalar_lds(mvec, nchunk).b.bytes(),
+                 lcomb = nka_host::wide_combine_lds(mvec).bytes();
+    if (len) {
+      hipLaunchKernelGGL(k_wide_norm_wgt<true>, grid, block, 0, b->stream, b->k, wa, (const double *)f, ld, active, len, wgt, ws);
+      hipLaunchKernelGGL((k_wide_sums_wgt<COMB, true>), grid, block, lsums, b->stream, b->k, wa, (const double *)f, ld, active, len, wgt, ws);
+      hipLaunchKernelGGL(k_wide_scalar_len, dim3((unsigned)b->k.nsys), block, lscal, b->stream, b->k, wa, active, len);
+      hipLaunchKernelGGL((k_wide_combine_len<COMB>), grid, block, lcomb, b->stream, b->k, wa, f, ld, active, len);
+    } else {
+      hipLaunchKernelGGL(k_wide_norm_wgt<false>, grid, block, 0, b->stream, b->k, wa, (const double *)f, ld, active, len, wgt, ws);
+      hipLaunchKernelGGL((k_wide_sums_wgt<COMB, false>), grid, block, lsums, b->stream, b->k, wa, (const double *)f, ld, active, len, wgt, ws);
+      hipLaunchKernelGGL(k_wide_scalar, dim3((unsigned)b->k.nsys), block, lscal, b->stream, b->k, wa, active);
+      hipLaunchKernelGGL((k_wide_combine<COMB>), grid, block, lcomb, b->stream, b->k, wa, f, ld, active);
+    }
+    return;
+  }
   if (b->has_len) {
     const int32_t *const len = b->len;
     hipLaunchKernelGGL(k_wide_norm_len, grid, block, 0, b->stream, b->k, wa, (const double *)f, ld, active, len);

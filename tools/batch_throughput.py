@@ -80,7 +80,17 @@ listed.  (b) won against (a) when a - b > |a - a'|, and (f) against (e) by the s
   (b') the same loop a second time, on a batch of its own: the control;
   (c) accel_step with X, the mask, tol and fnorm on a batch of the new entry, no system retiring.
 nsys 16,64,256 x vlen 32768,65536,262144 x mvec 10,20; a point that needs more than --mem-gb (here 40) is skipped and listed.  No
-ratio is fixed: a point counts as won when b - c > |b - b'|, as lost when c - b > |b - b'|, and is level otherwise."""
+ratio is fixed: a point counts as won when b - c > |b - b'|, as lost when c - b > |b - b'|, and is level otherwise.
+
+--wide-weights measures diagonal dot weights on wide batches (nka_hip_batch_create_wide_ext) with the method of --weights:
+  (a) a plain wide batch; (a') the same again, the control;
+  (b) an ext batch with one shared weight row; (c) an ext batch with one weight row per system;
+  (d) an ext batch with nothing set: it launches the kernels of (a), so (d)/(a) should lie within |a - a'| / a;
+  (e) a loop over lone handles with nka_hip_set_dot_weights, the only thing such a caller had before.
+nsys 16,64,256 x vlen 32768,262144 x mvec 10,20 with accel_update, then accel_step with X, mask, tol and fnorm at 64 x 65536 (no
+(e) there); a point that needs more than --mem-gb (here 40) is skipped and listed.  Beside b/a and c/a stands the stream model's
+prediction (norm 2 -> 3 streams, each sweep of four 6 -> 7, combine unchanged).  No ratio is fixed: (c) won against (e) when
+e - c > |a - a'|."""
 import argparse
 import ctypes as C
 import os
@@ -859,6 +869,133 @@ def wide_step_main(args, torch, nka_amd, L, emit):
     return 0
 
 
+def wide_weights_streams(mvec, weighted):
+    """Streams of vlen doubles an update of a wide batch reads or writes per element, full list, compact storage: the norm launch 2
+    (3 with weights), G = ceil(L / 4) sweeps of 6 (7 with weights) over L = mvec - 1 older vectors, the combine 7 + k, k = mvec."""
+    g = -(-(mvec - 1) // 4)
+    return (3 + 7 * g if weighted else 2 + 6 * g) + 7 + mvec
+
+
+def measure_wide_weights(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, step):
+    """Six variants on the same inputs, alternated: (a) a plain wide batch, (a2) the same again, the control, (b) an ext batch with
+    the shared row, (c) an ext batch with one row per system, (d) an ext batch with nothing set, (e) a loop over lone handles with
+    nka_hip_set_dot_weights (update only).  step: accel_step with X, the mask, tol = 0 and fnorm on batches that offer it."""
+    npool = mvec + 3
+    names = ("a", "a2", "b", "c", "d") + (() if step else ("e",))
+    need = 8.0 * nsys * vlen * (len(names) * 2 * (mvec + 1) + npool + len(names) * (2 if step else 1) + 3)
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    w = torch.exp2(6.0 * torch.rand(nsys, vlen, dtype=torch.float64, device="cuda") - 3.0)
+    Fs = {v: torch.empty(nsys, vlen, dtype=torch.float64, device="cuda") for v in names}
+    Xs = {v: torch.zeros(nsys, vlen, dtype=torch.float64, device="cuda") for v in names} if step else {}
+    masks = {v: torch.ones(nsys, dtype=torch.int32, device="cuda") for v in names}
+    tol = torch.zeros(nsys, dtype=torch.float64, device="cuda")
+    rs = {v: torch.zeros(nsys, dtype=torch.float64, device="cuda") for v in names}
+    batches = {v: nka_amd.nka_batch().init(nsys, vlen, mvec, wide=True, step=step, ext=v in ("b", "c", "d")) for v in names if v != "e"}
+    batches["b"].set_dot_weights(w[0])
+    batches["c"].set_dot_weights(w)
+    assert [batches[v].dot_weighted() for v in ("a", "a2", "b", "c", "d")] == [False, False, True, True, False]
+    assert batches["d"].offers_weights() and not batches["a"].offers_weights()
+    lones = []
+    if not step:
+        lones = [nka_amd.nka().init(vlen, mvec).set_dot_weights(w[k]) for k in range(nsys)]
+        hl = [x._handle() for x in lones]
+        pl = [C.c_void_p(Fs["e"][k].data_ptr()) for k in range(nsys)]
+    hs = {v: b._handle() for v, b in batches.items()}
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    P = lambda t: C.c_void_p(t.data_ptr())                                           # noqa: E731
+    upd, stp, upd_lone = L.nka_hip_batch_accel_update, L.nka_hip_batch_accel_step, L.nka_hip_accel_update
+    count = [0]
+
+    def run(name, reps):
+        F = Fs[name]
+        for _ in range(reps):
+            F.copy_(pool[count[0] % npool])
+            count[0] += 1
+            if name == "e":
+                for k in range(nsys):
+                    if upd_lone(hl[k], pl[k]) != 0:
+                        raise RuntimeError(L.nka_hip_last_error())
+            elif step:
+                assert stp(hs[name], P(F), ld, P(Xs[name]), ld, P(masks[name]), P(tol), P(rs[name])) == 0
+            else:
+                assert upd(hs[name], P(F), ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {v: [] for v in names}
+    for v in names:                                # warm: fill the lists (steady state), settle clocks and caches
+        count[0] = 0
+        run(v, mvec + 4)
+    torch.cuda.synchronize()
+    for v in ("a2", "d"):                          # the same kernels on the same inputs: the same bits
+        assert torch.equal(Fs[v], Fs["a"]), v
+    for v in names:
+        if v != "e":
+            assert (batches[v].num_vec() == mvec).all(), v
+        reps[v] = max(3, int(window / timed(v, 3)) + 1)
+    for _ in range(repeats):                       # alternate the variants
+        for v in names:
+            ts[v].append(timed(v, reps[v]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    assert all(m.all() for m in masks.values())    # nothing retired
+    for v in names:
+        med = statistics.median(ts[v])
+        out[v], out["spread_" + v] = med, (max(ts[v]) - min(ts[v])) / med
+    for b in list(batches.values()) + lones:
+        b.delete()
+    del pool, w, Fs, Xs
+    torch.cuda.empty_cache()
+    return out
+
+
+def wide_weights_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m, False) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    points += [(64, 65536, m, True) for m in ints(args.mvecs)]                       # the step variants at one point
+    chunk, cap = nka_amd.batch_wide_limits()
+    emit(f"# diagonal dot weights on WIDE batches (nka_hip_batch_create_wide_ext; chunk {chunk}, cap {cap}): (a) a plain wide batch; (a2) "
+         f"the same again, the control; (b) an ext batch, one shared weight row; (c) an ext batch, one weight row per system; (d) an ext "
+         f"batch with nothing set; (e) a loop over lone handles with nka_hip_set_dot_weights on one stream; {torch.cuda.get_device_name(0)}; "
+         f"windows >= {args.window} s, median of {args.repeats}, the variants alternated on the same inputs; default flavour, full "
+         f"list; weights 2^U(-3, 3); the time includes the copy of the input into F (equal for all)")
+    emit("# streams per element: norm 2 -> 3, each sweep of four 6 -> 7, combine 7 + k unchanged; (d) launches the kernels of (a); "
+         "(c) against (e): WON when e - c > |a - a2|, LOST when c - e > |a - a2|; `step`: accel_step with X, mask, tol = 0 and fnorm, no (e)")
+    emit(f"{'nsys':>5} {'vlen':>7} {'mvec':>4} {'call':>6} {'(a) us':>10} {'(a2) us':>10} {'(b) us':>10} {'(c) us':>10} {'(d) us':>10} {'(e) us':>11} "
+         f"{'b/a':>6} {'c/a':>6} {'model':>6} {'d/a':>6} {'|a-a2|/a':>8} {'e/c':>7}  c vs e")
+    t0 = time.time()
+    tally = {"won": [], "lost": [], "level": []}
+    for n, v, m, step in points:
+        r = measure_wide_weights(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9, step)
+        call = "step" if step else "update"
+        if r is None:
+            emit(f"{n:5d} {v:7d} {m:4d} {call:>6}   SKIPPED: the batches, the lone handles and the inputs need more than {args.mem_gb:g} GB of "
+                 f"device memory")
+            continue
+        noise = abs(r["a"] - r["a2"])
+        model = wide_weights_streams(m, True) / wide_weights_streams(m, False)
+        if step:
+            e_us, e_c, verdict = f"{'-':>11}", f"{'-':>7}", "-"
+        else:
+            verdict = "won" if r["e"] - r["c"] > noise else "lost" if r["c"] - r["e"] > noise else "level"
+            tally[verdict].append((n, v, m, round(r["e"] / r["c"], 2)))
+            e_us, e_c = f"{r['e'] * 1e6:11.1f}", f"{r['e'] / r['c']:7.2f}"
+        emit(f"{n:5d} {v:7d} {m:4d} {call:>6} {r['a'] * 1e6:10.1f} {r['a2'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {r['c'] * 1e6:10.1f} "
+             f"{r['d'] * 1e6:10.1f} {e_us} {r['b'] / r['a']:6.3f} {r['c'] / r['a']:6.3f} {model:6.3f} {r['d'] / r['a']:6.3f} "
+             f"{noise / r['a']:8.4f} {e_c}  {verdict.upper():5}   (spread " +
+             " ".join(f"{k} {100 * r['spread_' + k]:.1f} %" for k in ("a", "a2", "b", "c", "d") + (() if step else ("e",))) + ")")
+    emit(f"# {len(points)} points in {time.time() - t0:.0f} s; (c) against (e): won {len(tally['won'])}, level {len(tally['level'])}, "
+         f"lost {len(tally['lost'])}{': ' + str(tally['lost']) if tally['lost'] else ''}")
+    return 0
+
+
 def measure_wide(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
     npool = mvec + 3
     narrow = vlen <= nka_amd.BATCH_MAX_VLEN
@@ -1065,6 +1202,11 @@ def main():
                     help="time accel_step of a wide batch (nka_hip_batch_create_wide_step) against the wide accel_update and against "
                          "the loop a caller composes from it, run twice (the second: a control); without --nsys / --vlens / --mvecs / "
                          "--mem-gb: nsys 16,64,256 x vlen 32768,65536,262144 x mvec 10,20, 40 GB")
+    ap.add_argument("--wide-weights", action="store_true",
+                    help="time diagonal dot weights on wide batches (nka_hip_batch_create_wide_ext): a plain wide batch twice, ext "
+                         "batches with a shared row, with one row per system and with nothing set, and a loop over lone handles with "
+                         "weights; without --nsys / --vlens / --mvecs / --mem-gb: nsys 16,64,256 x vlen 32768,262144 x mvec 10,20, "
+                         "then accel_step at 64 x 65536, 40 GB")
     ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
@@ -1088,6 +1230,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.wide_weights:
+        for name, grid_w in (("nsys", "16,64,256"), ("vlens", "32768,262144"), ("mvecs", "10,20"), ("mem_gb", 40.0)):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+        return wide_weights_main(args, torch, nka_amd, L, emit)
     if args.wide_step:
         for name, grid_w in (("nsys", "16,64,256"), ("vlens", "32768,65536,262144"), ("mvecs", "10,20"), ("mem_gb", 40.0)):
             if getattr(args, name) == ap.get_default(name):
