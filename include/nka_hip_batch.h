@@ -127,7 +127,7 @@
  *            nchunk doubles, one partial of <f,f> per chunk and system, zero-initialised, freed at destroy, never moved.  That
  *            buffer is why the step has a creation entry of its own: what nka_hip_batch_create_wide allocates stays what it
  *            documents, and such a batch keeps refusing the step.  nka_hip_batch_offers_step tells the two apart.  On a batch of
- *            the new entry nka_hip_batch_accel_step is FOUR launches in a line (nka_amd/csrc/nka_batch_wide_step.hip), per
+ *            the new entry nka_hip_batch_accel_step is FOUR launches in a line (nka_amd/csrc/nka_batch_wide.hip), per
  *            system active on entry:
  *              1  r = sqrt(sum_c q_c), q_c the fast-sum <f,f> of chunk c;
  *              2  q_c = sum fma(f_i, f_i, .) in the chunk's element -> thread map and per-thread order, reduced over the
@@ -345,7 +345,7 @@
  *            against a batch of nka_hip_batch_create_waves): 1.000 ... 1.014.  Won at 7 of 7 points in both comparisons.  So:
  *            thousands of systems of up to 1024 unknowns that differ in length or in the scale of their unknowns -- this entry;
  *            for every other case the sentences of WAVES stand (256 systems were not measured here: there WAVES loses).
- *   WIDE EXT  nka_hip_batch_create_wide_ext: THE WIDE BATCH WITH WEIGHTS (nka_amd/csrc/nka_batch_wide.hip, nka_batch_wide_step.hip).
+ *   WIDE EXT  nka_hip_batch_create_wide_ext: THE WIDE BATCH WITH WEIGHTS (nka_amd/csrc/nka_batch_wide.hip).
  *            Limits, allocations and every guarantee of nka_hip_batch_create_wide for step == 0 and of nka_hip_batch_create_wide_step
  *            for step == 1 (any other step: NKA_HIP_EINVAL); nka_hip_batch_kind stays 1, _is_wide 1, _offers_lengths 1, _offers_step
  *            returns step, and the weight buffer comes at the first set, as in the batch above.  What it adds is exactly the entry

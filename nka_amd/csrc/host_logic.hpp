@@ -355,7 +355,7 @@ NKA_HOST_DEVICE constexpr int64_t wide_part_count(int64_t nsys, int mvec, int64_
 NKA_HOST_DEVICE constexpr int64_t wide_part_index(int64_t sys, int entry, int64_t c, int mvec, int64_t nchunk) {
   return (sys * (2 + 2 * mvec) + entry) * nchunk + c;
 }
-// THE SOLVE STEP of a wide batch (nka_hip_batch_create_wide_step, nka_batch_wide_step.hip): one partial of <f,f> per system and
+// THE SOLVE STEP of a wide batch (nka_hip_batch_create_wide_step, nka_batch_wide.hip): one partial of <f,f> per system and
 // chunk in a buffer of its own, the chunks of a system together and in order -- the partials above keep their cells.
 // tests/c/batch_wide_step_layout_check.cpp paints every cell.
 NKA_HOST_DEVICE constexpr int64_t wide_fpart_count(int64_t nsys, int64_t nchunk) { return nsys * nchunk; }

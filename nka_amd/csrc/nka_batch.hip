@@ -23,8 +23,8 @@
 // swept alone where there is no pending pair), the system may retire itself between phases 2 and 3 -- up to there a workgroup
 // has written LDS only --, and phase 6 also forms x = fl(x - f_out).  Without it every step statement is discarded at compile
 // time and the instance is the plain update, instruction for instruction.
-// A WIDE batch (nka_hip_batch_create_wide) shares the handle, the storage and every host entry of this file; its update -- a
-// system split across workgroups, four launches -- is nka_batch_wide.hip, and what the two units share nka_batch_dev.hpp.
+// A WIDE batch (nka_hip_batch_create_wide) shares the handle, the storage and every host entry of this file; its update and
+// its solve step -- a system split across workgroups, four launches each -- are nka_batch_wide.hip, what the units share nka_batch_dev.hpp.
 #include "nka_batch_dev.hpp"      // BatchArgs, the tile loads and stores, batch_sweep, batch_block_sum, the scalar step, the handle
 
 #include <algorithm>

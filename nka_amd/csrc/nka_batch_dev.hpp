@@ -136,6 +136,18 @@ __device__ __forceinline__ void batch_block_sum(const double (&acc)[NACC], doubl
   __syncthreads();
 }
 
+// MEMBERS OF A TRAILING PACK (k_waves_update of nka_batch_waves.hip, the four kernels of nka_batch_wide.hip: what an instance takes
+// beside the update's arguments, so that an instance without a member keeps its arguments).  The batch's weight buffer and its row
+// stride (0: the form all systems share): two kernel arguments, not a struct of two -- a pointer inside a struct cannot be
+// __restrict__, and without it the weighted instances are scheduled differently
+using WgtRows = const double *__restrict__;
+enum class WgtStride : int64_t {};
+// the T of pack...
+template <class T, class First, class... Rest>
+__host__ __device__ __forceinline__ const T &pack_get(const First &first, const Rest &...rest) {
+  if constexpr (std::is_same<T, First>::value) return first; else return pack_get<T>(rest...);
+}
+
 enum { HDR_PENDING = 0, HDR_FIRST = 1, HDR_NOLDER = 2, HDR_NCOMB = 3, HDR_NEW = 4, HDR_NORMED = 5 };
 
 // THE SCALAR STEP of one system, the statements of k_solve on the working copy L (one thread): s == 0 relaxes (F08:275), the
@@ -215,7 +227,7 @@ struct nka_hip_batch_state {
   double *part = nullptr;                   // partial sums, nka_host::wide_part_index: nsys x (2 + 2 mvec) x nchunk
   double *plan_c = nullptr;                 // the combine plan from the scalar kernel to the combine: nsys x (mvec + 1) coefficients
   int32_t *plan_s = nullptr;                //   ... and slots, in list order (the control block's comb_c / comb_slots stay zero)
-  // ... with the solve step (nka_hip_batch_create_wide_step, nka_batch_wide_step.hip): the partials of <f,f>,
+  // ... with the solve step (nka_hip_batch_create_wide_step, the same unit): the partials of <f,f>,
   // nka_host::wide_fpart_index: nsys x nchunk, allocated at creation, freed at destroy only and never moved
   bool wide_step = false;
   double *fpart = nullptr;
@@ -228,17 +240,17 @@ struct nka_hip_batch_state {
   bool waves = false;
   // ... of nka_hip_batch_create_waves_ext: the same batch, which also takes lengths and weights (the same unit and kernel)
   bool waves_ext = false;
-  // a WIDE batch of nka_hip_batch_create_wide_ext: the same batch, which also takes weights (the weighted norm and sums kernels of
-  // nka_batch_wide.hip and nka_batch_wide_step.hip); with wide_step as its `step` argument says
+  // a WIDE batch of nka_hip_batch_create_wide_ext: the same batch, which also takes weights (the weighted instances of the norm and
+  // the sums kernel of nka_batch_wide.hip); with wide_step as its `step` argument says
   bool wide_ext = false;
 };
 
 // nka_batch_wide.hip: the buffers of a wide batch (b->k is complete), and one update of it -- four launches on b->stream, the first
-// two of them the weighted kernels where b->weighted (a batch of nka_hip_batch_create_wide_ext, b->wide_ext)
+// two of them the weighted instances where b->weighted (a batch of nka_hip_batch_create_wide_ext, b->wide_ext)
 int nka_batch_wide_alloc(nka_hip_batch_t b);
 void nka_batch_wide_free(nka_hip_batch_t b);
 void nka_batch_wide_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
-// nka_batch_wide_step.hip: the one buffer the solve step of a wide batch adds (b->nchunk is set), and one step -- four launches
+// ... the same unit: the one buffer the solve step of a wide batch adds (b->nchunk is set), and one step -- the same four launches
 int nka_batch_wide_step_alloc(nka_hip_batch_t b);
 void nka_batch_wide_step_free(nka_hip_batch_t b);
 void nka_batch_wide_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,

@@ -67,10 +67,7 @@ static_assert(NKA_HIP_BATCH_WAVES_MAX_VLEN <= NKA_HIP_BATCH_MAX_VLEN && NKA_HIP_
               "the cap is whole tiles, inside the narrow batch's range (the storage is the narrow batch's)");
 
 // THE TRAILING PACK of k_waves_update: [WgtRows, WgtStride][, StepArgs][, LenArgs], each at most once, in this order.
-// the batch's weight buffer and its row stride (0: the form all systems share): the FIRST members, and two kernel arguments, not a
-// struct of two -- a pointer inside a struct cannot be __restrict__, and without it the weighted instances are scheduled differently
-using WgtRows = const double *__restrict__;
-enum class WgtStride : int64_t {};
+// WgtRows, WgtStride (nka_batch_dev.hpp): the batch's weight buffer and its row stride, the FIRST members
 // what a solve step takes beside the update's arguments (the StepArgs of nka_batch.hip); each pointer may be NULL
 struct StepArgs {
   double *x;
@@ -82,11 +79,6 @@ struct StepArgs {
 struct LenArgs {
   const int32_t *len;
 };
-// the T of pack...
-template <class T, class First, class... Rest>
-__device__ __forceinline__ const T &pack_get(const First &first, const Rest &...rest) {
-  if constexpr (std::is_same<T, First>::value) return first; else return pack_get<T>(rest...);
-}
 
 // one lane's LDS traffic ordered against the other lanes' of the SAME wavefront (the head comment, SYNCHRONISATION)
 __device__ __forceinline__ void wave_sync() {

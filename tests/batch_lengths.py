@@ -25,7 +25,7 @@ def wide_shape(c):
 
 def wide_medium_shape(c):
     """(vlen, lengths): 18 chunks, of which the systems add 1, 2, 9, 9, 10, 16, 17 and 18 partials at a stride of 18 -- the
-    eight-way chain over a system's own partials (k_wide_scalar_len) with no trip, one and two, and a remainder of none, one and
+    eight-way chain over a system's own partials (k_wide_scalar with lengths) with no trip, one and two, and a remainder of none, one and
     seven.  Every twin's vlen but 9 C, 1 and the full row is a shape that tests/test_batch_wide_gpu.py holds to the exact sums."""
     return 17 * c + 33, (1, c + 1, 8 * c + 1, 9 * c, 9 * c + 1, 15 * c + 513, 16 * c + 1, 17 * c + 33)
 

@@ -256,7 +256,7 @@ def test_wide_lengths_carry_the_bits_of_a_wide_batch_of_that_length(torch_cuda, 
 @pytest.mark.parametrize("flavor", [0, 2])
 def test_wide_lengths_where_the_chain_over_the_own_partials_takes_whole_trips(torch_cuda, CH, flavor):
     """Eight systems in one wide batch of 17 C + 33 (18 chunks) against eight wide batches of one system: the systems add 1, 2,
-    9, 9, 10, 16, 17 and 18 of their partials at a stride of 18, so the eight-way chain of k_wide_scalar_len runs no trip, one
+    9, 9, 10, 16, 17 and 18 of their partials at a stride of 18, so the eight-way chain of k_wide_scalar runs no trip, one
     and two over nown, with a remainder of none, one and seven.  mvec = 3 over 9 calls: the lists fill, the capacity drop runs.
     The twins at 9, 10, 16 and 17 chunks are shapes tests/test_batch_wide_gpu.py holds to the exact sums."""
     c = CH[0]

@@ -1,5 +1,5 @@
-"""The solve step of a WIDE batch (nka_hip_batch_create_wide_step, nka_batch().init(..., wide=True, step=True); nka_amd/csrc/
-nka_batch_wide_step.hip): residual norm, stop rule, update and x -= f of every system in four launches, no host in the loop.
+"""The solve step of a WIDE batch (nka_hip_batch_create_wide_step, nka_batch().init(..., wide=True, step=True); the step instances of
+nka_amd/csrc/nka_batch_wide.hip): residual norm, stop rule, update and x -= f of every system in four launches, no host in the loop.
 
   1 a step is the update: rows of F, state, red[], slots of a plain wide twin that runs accel_update under the mask the host
     predicts from the step's own fnorm and tol; the mask; X; 1 ... 17 chunks

@@ -130,40 +130,70 @@ def test_weight_addresses_of_a_wide_batch_against_a_brute_force_model_under_sani
     assert "wideweightscheck" in re.search(r"^hostcheck:(.*)$", open(os.path.join(CSRC, "Makefile")).read(), flags=re.M).group(1)
 
 
-def test_the_weighted_kernels_read_the_weights_like_a_stored_vector_and_launch_the_existing_scalar_and_combine():
-    """Both wide units: the weighted norm and sums kernels are templates on LEN written once, the weight pointer is __restrict__ on
-    the kernel argument itself and follows the existing arguments with its row stride, the weight pair is loaded with
-    ld_tile<FULL, true> from wide_wgt_offset, fl(w f) and fl(w w1') are formed once per element and sweep and stand FIRST in every
-    product, and a weighted call launches the existing scalar and combine kernels.  No atomics, no cooperative launch."""
-    for unit, norm, sums, tail in (("nka_batch_wide.hip", "k_wide_norm_wgt", "k_wide_sums_wgt", ("k_wide_scalar", "k_wide_combine")),
-                                   ("nka_batch_wide_step.hip", "k_wide_step_norm_wgt", "k_wide_step_sums_wgt",
-                                    ("k_wide_step_scalar", "k_wide_step_combine"))):
-        text = open(os.path.join(CSRC, unit)).read()
-        code = "\n".join(ln.split("//")[0] for ln in text.splitlines())
-        for word in ("atomic", "hipLaunchCooperativeKernel", "__threadfence"):
-            assert word not in code, (unit, word)
-        assert code.count(f"void {norm}(") == 1 and code.count(f"void {sums}(") == 1, unit
-        kn = code[code.index(f"void {norm}("):code.index(f"void {sums}(")]
-        ks = code[code.index(f"void {sums}("):code.index("void launch_wide")]
-        for kern in (kn, ks):
-            head = kern[:kern.index("{")]
-            assert re.search(r"const double \*__restrict__ wgt, int64_t wgt_stride\)\s*$", head), (unit, head)
-            assert kern.count("wgt + (size_t)nka_host::wide_wgt_offset(sys, wgt_stride, blockIdx.x)") == 1, unit
-            assert "if constexpr (LEN)" in kern and "active[sys] == 0) return;" in kern
-            assert kern.index("active[sys] == 0) return;") < kern.index("wide_wgt_offset"), "a masked system returns before it reads anything"
-            assert len(re.findall(r"acc(?:\[[^\]]+\])?\s*(?:\+=|= acc)", kern)) == 0
-        first = sorted(f.split(",")[0].strip() for f in re.findall(r"acc\[[^\]]+\] = fma\(([^;]+), acc\[[^\]]+\]\);", kn))
-        assert first == (["gv[q] * d"] if "step" not in unit else sorted(["gv[q] * d", "gv[q] * fv[q]", "gv[q] * fv[q]"])), (unit, first)
-        assert kn.count("gv = ld_tile<FULL, true>(wg, i, n);") == (1 if "step" not in unit else 2)
-        first = sorted(f.split(",")[0].strip() for f in re.findall(r"acc\[[^\]]+\] = fma\(([^;]+), acc\[[^\]]+\]\);", ks))
-        assert first == ["fa", "fa", "wa_"], (unit, first)
-        assert ks.count("const double fa = gv[q] * fq;") == 1 and ks.count("const double wa_ = gv[q] * wn;") == 1
-        assert ks.count("gv = ld_tile<FULL, true>(wg, i, n);") == 1
-        launch = code[code.index("void launch_wide"):]
-        weighted = launch[launch.index("if (b->weighted)"):]
-        for name in tail:
-            assert name in weighted, (unit, name)
-        assert code.count("__global__") == (6 if "step" in unit else 10), unit
+def test_the_one_wide_unit_holds_every_form_of_the_five_kernels():
+    """nka_batch_wide.hip is the only wide unit: five kernel templates -- the step's norm left the fold of four as a kernel of its
+    own, the layout its measurement asked for --, each body written once, what an instance takes in the trailing pack.  The norm and the sums read the weight pair like a stored vector -- ld_tile<FULL, true> from pack_get<WgtRows> +
+    wide_wgt_offset, inside if constexpr (WGT), behind the `active` and the length test --, fl(w f) and fl(w w1') are formed once per
+    element and sweep and stand FIRST in every product, each weighted product beside its plain form; the scalar kernel and the
+    combine never take the weights, and a weighted call launches them.  No atomics, no cooperative launch."""
+    assert not os.path.exists(os.path.join(CSRC, "nka_batch_wide_step.hip")), "the step lives in nka_batch_wide.hip"
+    assert "nka_batch_wide_step" not in open(os.path.join(CSRC, "Makefile")).read()
+    text = open(os.path.join(CSRC, "nka_batch_wide.hip")).read()
+    code = "\n".join(ln.split("//")[0] for ln in text.splitlines())
+    assert code.count("__global__") == 5      # (the four of the fold, and k_wide_step_norm: the one family its measurement took out)
+    for once in ("void wide_list(", "void wide_norm_sum(", "struct WideArgs {", "struct WideStepArgs {", "void k_wide_norm(", "void k_wide_step_norm(",
+                 "void k_wide_sums(", "void k_wide_scalar(", "void k_wide_combine("):
+        assert code.count(once) == 1, once
+    for word in ("atomic", "hipLaunchCooperativeKernel", "__threadfence"):
+        assert word not in code, word
+    kn = code[code.index("void k_wide_norm("):code.index("void k_wide_step_norm(")]
+    kp = code[code.index("void k_wide_step_norm("):code.index("void k_wide_sums(")]
+    ks = code[code.index("void k_wide_sums("):code.index("void k_wide_scalar(")]
+    tail = code[code.index("void k_wide_scalar("):code.index("void launch_wide(")]
+    fma = r"acc\[[^\]]+\] = fma\(([^;]+), acc\[[^\]]+\]\);"
+    for kern in (kn, kp, ks):
+        head = kern[:kern.index("{")]
+        pack = "wgt" if kern is kp else "pack"
+        assert re.search(r"const int32_t \*__restrict__ active, (Pack\.\.\. pack|Wgt\.\.\. wgt)\)\s*$", head), head
+        assert "static_assert(wide_pack_ok<Pack...>()" in kern or "static_assert(wide_pack_ok<Wgt...>()" in kern
+        # a masked system returns before anything of the pack is read; the length test comes before the weight row is addressed
+        assert kern.index("active[sys] == 0) return;") < kern.index("pack_get")
+        assert kern.index("if (!nka_host::wide_len_owns(sn, ") < kern.index("wide_wgt_offset")
+        assert kern.index("if constexpr (LEN)") < kern.index("wide_len_owns") < kern.index("__shared__")
+        assert kern.count(f"if constexpr (WGT) wg = pack_get<WgtRows>({pack}...) + (size_t)nka_host::wide_wgt_offset(sys, "
+                          f"(int64_t)pack_get<WgtStride>({pack}...), blockIdx.x);") == 1
+        assert len(re.findall(r"acc(?:\[[^\]]+\])?\s*(?:\+=|= acc)", kern)) == 0
+    # the update's norm: <d,d>; the step's: <d,d> and <f,f>, the latter twice (with and without a pending pair); each weighted form
+    # in an if constexpr (WGT) whose else is the plain form; one weight load per sweep body
+    first = sorted(f.split(",")[0].strip() for f in re.findall(fma, kn))
+    assert first == sorted(["gv[q] * d", "d"]), first
+    assert kn.count("if constexpr (WGT) acc[0] = fma(gv[q] * d, d, acc[0]); else acc[0] = fma(d, d, acc[0]);") == 1
+    assert kn.count("if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);") == 1 == kn.count("batch_sweep(") == kn.count("gv = ld_tile")
+    first = sorted(f.split(",")[0].strip() for f in re.findall(fma, kp))
+    assert first == sorted(["gv[q] * d", "gv[q] * fv[q]", "gv[q] * fv[q]", "d", "fv[q]", "fv[q]"]), first
+    assert kp.count("if constexpr (WGT) acc[1] = fma(gv[q] * d, d, acc[1]); else acc[1] = fma(d, d, acc[1]);") == 1
+    assert kp.count("if constexpr (WGT) acc[0] = fma(gv[q] * fv[q], fv[q], acc[0]); else acc[0] = fma(fv[q], fv[q], acc[0]);") == 2
+    assert kp.count("if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);") == 2 == kp.count("batch_sweep(") == kp.count("gv = ld_tile")
+    # the step's norm keeps the layout it had: the step's arguments, the lengths in them, in front of f_all; only the weights behind
+    assert re.search(r"void k_wide_step_norm\(BatchArgs a, WideArgs wa, WideStepLenArgs st, const double \*__restrict__ f_all,", kp)
+    assert "sn = st.len[sys];" in kp and "WideStepArgs" not in kn.split("static_assert")[0]
+    # the sums: the three products of today; their first operands are the plain ones unless WGT, formed once per element and sweep
+    first = sorted(f.split(",")[0].strip() for f in re.findall(fma, ks))
+    assert first == ["fa", "fa", "wa_"], first
+    assert ks.count("double fa = fq;") == 1 and ks.count("if constexpr (WGT) fa = gv[q] * fq;") == 1 == ks.count("gv[q] * fq")
+    assert ks.count("double wa_ = wn;") == 1 and ks.count("if constexpr (WGT) wa_ = gv[q] * wn;") == 1 == ks.count("gv[q] * wn")
+    assert ks.count("if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);") == 1 == ks.count("batch_sweep(") == ks.count("gv = ld_tile")
+    # the scalar kernel and the combine never take the weights, and a weighted call launches them
+    assert "WgtRows" not in tail and "WgtStride" not in tail and "wide_wgt_offset" not in tail and "gv" not in tail
+    assert tail.count("sizeof...(Pack) == (STEP ? 1 : 0) + (LEN ? 1 : 0)") == 2
+    launch = code[code.index("void launch_wide("):code.index("void launch_wide_len(")]
+    weighted = launch[launch.index("if (b->weighted)"):launch.index("} else {")]
+    assert "k_wide_norm<Pack..., WgtRows, WgtStride>" in weighted and "k_wide_sums<COMB, Pack..., WgtRows, WgtStride>" in weighted
+    assert "k_wide_step_norm<LEN, WgtRows, WgtStride>" in weighted
+    after = launch[launch.index("} else {"):]
+    assert "k_wide_scalar<Mask, Pack...>" in after[after.index("}", 1):] and "k_wide_combine<COMB, Pack...>" in after[after.index("}", 1):]
+    # four per call: the sums in two forms, the norm in two forms for the update and in two for the step
+    assert launch.count("hipLaunchKernelGGL(") == 8 and code.count("hipLaunchKernelGGL(") == 8
 
 
 # ---- prototypes, exports, refusals, text --------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """The WIDE batch with diagonal dot weights (nka_hip_batch_create_wide_ext, nka_batch().init(..., wide=True, ext=True[, step=True]);
-the weighted norm and sums kernels of nka_amd/csrc/nka_batch_wide.hip and nka_batch_wide_step.hip).  Shapes are given in units of
+the weighted instances of k_wide_norm, k_wide_step_norm and k_wide_sums of nka_amd/csrc/nka_batch_wide.hip).  Shapes are given in units of
 C = NKA_HIP_BATCH_WIDE_CHUNK, read from the library.
 
    1 one chunk            a weighted wide batch of at most C elements is the weighted narrow batch in SUMS_BLOCKED_ROUNDED, bit for bit

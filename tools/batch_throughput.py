@@ -771,7 +771,7 @@ def measure_step(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budge
 
 def measure_wide_step(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget):
     """measure_step on wide batches, with the composed loop twice: (b') is the control that says what two runs of the SAME loop
-    differ by.  (a), (b) and (b') run plain wide batches -- the kernels of nka_batch_wide.hip --, (c) the batch with the step."""
+    differ by.  (a), (b) and (b') run plain wide batches -- the update instances of nka_batch_wide.hip --, (c) the batch with the step."""
     npool = mvec + 3
     need = 8.0 * nsys * vlen * (4 * 2 * (mvec + 1) + npool + 4 + 3)       # four batches' slots, the pool, four f, three x
     if need > mem_budget:
@@ -848,7 +848,7 @@ def wide_step_main(args, torch, nka_amd, L, emit):
          f"fnorm; {torch.cuda.get_device_name(0)}; windows >= {args.window} s, median of {args.repeats}, the four alternated on the "
          f"same inputs; default flavour and sums, full list; tol = 0: no system retires; the time includes the copy of the input "
          f"into F (equal for the four)")
-    emit("# (a), (b) and (b') run the kernels of nka_batch_wide.hip; a point is WON when b - c > |b - b'|, LOST when c - b > |b - b'|")
+    emit("# (a), (b) and (b') run the update instances of nka_batch_wide.hip; a point is WON when b - c > |b - b'|, LOST when c - b > |b - b'|")
     emit(f"{'nsys':>5} {'vlen':>7} {'mvec':>4} {'(a) us':>10} {'(b) us':>10} {'(b2) us':>10} {'(c) us':>10} {'c/b':>7} {'c/a':>7} "
          f"{'|b-b2|/b':>8}  c vs b")
     t0 = time.time()
