@@ -120,8 +120,8 @@
  *            nka_hip_batch_create_wide_step offers it: STEP below); on a batch of these two entries nka_hip_batch_set_dot_weights and
  *            _set_dot_weights_host (nka_hip_batch_dot_weighted returns 0; a batch of nka_hip_batch_create_wide_ext offers them: WIDE
  *            EXT below); on every wide batch NKA_HIP_SUMS_REFERENCE_ORDER and _BLOCKED through
- *            _set_sum_order, and binary32 storage.  A caller who needs one of the last two has the batch above up to 16 384
- *            elements and lone handles beyond.
+ *            _set_sum_order, and binary32 storage (a batch of nka_hip_batch_create_wide_stored offers it: WIDE STORED below).  A
+ *            caller who needs the reference order has the batch above up to 16 384 elements and lone handles beyond.
  *            STEP of a wide batch: nka_hip_batch_create_wide_step is nka_hip_batch_create_wide -- the same limits, refusals, kind
  *            (nka_hip_batch_kind 1, _is_wide 1) and accel_update, bit for bit and launch for launch -- with ONE MORE BUFFER: nsys *
  *            nchunk doubles, one partial of <f,f> per chunk and system, zero-initialised, freed at destroy, never moved.  That
@@ -201,7 +201,8 @@
  *              1  it runs the default flavour (NKA_HIP_FLAVOR_C: compact storage) and NKA_HIP_SUMS_BLOCKED_ROUNDED only;
  *                 NKA_HIP_SUMS_AUTO resolves to _BLOCKED_ROUNDED at EVERY vlen, vlen <= 64 included.  REFUSED with NKA_HIP_EINVAL:
  *                 the two F08 flavours and NKA_HIP_SUMS_REFERENCE_ORDER (their point is the reference's bits, which this storage
- *                 gives up), and a WIDE batch with this storage (the follow-up: nka_hip_batch_create_wide stays binary64).
+ *                 gives up), and a WIDE batch with this storage through this entry and the three older wide entries, which stay
+ *                 binary64 (a batch of nka_hip_batch_create_wide_stored offers it: WIDE STORED below).
  *              2  THE PENDING PAIR STAYS binary64: the raw pair (w_new = f_in, v_new = f_out) lives in two buffers of the batch,
  *                 one row per system at the slot stride, not in the ring slot.  d = fl(w1 - f), red[0] and s = sqrt(red[0]) are
  *                 therefore exactly those of binary64 storage.
@@ -371,6 +372,45 @@
  *            COST: the norm launch streams three vectors instead of two and each sweep of four of the sums launch seven instead of
  *            six; the combine is unchanged.  What that costs is recorded in profiles/r19/batch_wide_weights_throughput.txt (tools/
  *            batch_throughput.py --wide-weights) and read in docs/design/12_batched_systems.md, "Wide batch: weights".
+ *   WIDE STORED  nka_hip_batch_create_wide_stored(..., step, storage): THE WIDE BATCH WITH BINARY32 STORAGE of the normalised subspace
+ *            vectors (nka_amd/csrc/nka_batch_wide.hip).  storage == NKA_HIP_BATCH_STORE_F64: the batch of
+ *            nka_hip_batch_create_wide_ext(..., step), bit for bit and launch for launch.  storage == NKA_HIP_BATCH_STORE_F32: the
+ *            limits of nka_hip_batch_create_wide, step 0 or 1 as in WIDE EXT (the buffer of the step only for 1), weights and
+ *            lengths offered; nka_hip_batch_kind 1, _is_wide 1, _offers_step = step, _offers_weights 1, _offers_lengths 1,
+ *            nka_hip_batch_storage NKA_HIP_BATCH_STORE_F32, nka_hip_batch_vector_bytes = 2 nsys stride (4 (mvec + 1) + 8), the
+ *            formula of STORAGE at the wide batch's slot stride: float slots and the two binary64 pending buffers of one row per
+ *            system, zero-initialised, freed at destroy, never moved.  REFUSED with NKA_HIP_EINVAL, nothing left allocated: the two
+ *            F08 flavours with binary32, an unknown storage, a step outside {0, 1}, the wide limits.  set_sum_order refuses
+ *            NKA_HIP_SUMS_REFERENCE_ORDER and _BLOCKED as on every wide batch; _AUTO and _BLOCKED_ROUNDED are the rounded fast
+ *            sums.  The four older entries (_create_wide, _create_wide_step, _create_wide_ext, _create_stored) allocate, refuse and
+ *            compute what they did.
+ *            THE CONTRACT is that of STORAGE, points 2 to 7, PER CHUNK: the pending pair stays binary64 in the pending rows, so d,
+ *            red[0] and s are exactly those of a binary64 wide batch; w1' = q(fl(d/s)) is the operand of every sum (fl(w w1') the
+ *            first operand under weights), the value stored and the value the compact difference is formed from; the slot's v
+ *            holds q(fl(fl(v1/s) - w1')) and the combine applies exactly that value; binary32 subnormals are kept, a value beyond
+ *            the binary32 range becomes +-Inf and stays in its own system; every product and accumulation is binary64;
+ *            nka_hip_batch_get_w / _get_v return binary64 (the pending rows for the slot of the pending pair, the widened floats
+ *            otherwise).  The two norm launches read binary64 data only, f and the raw w1 of the pending row.  WHAT THE WIDE BATCH
+ *            GUARANTEES HOLDS UNCHANGED: FOUR launches in a line; within a launch no workgroup reads what another writes, no flags,
+ *            no atomics, no spinning, no cooperative launch; capture from the first call; MASKS, LENGTHS (nothing at or beyond
+ *            len[sys] of a float slot or a pending row is read or written), WEIGHTS and STEP.  A chunk starts on a multiple of 2048
+ *            elements, so a float pair stays 8-byte aligned.
+ *            ONE CHUNK: a binary32 wide batch of at most one chunk is the binary32 batch of nka_hip_batch_create_stored, bit for
+ *            bit.  SEVERAL CHUNKS: every entry of red[] and the step's <f,f> lies within gamma(K) sum|xy| of the exact sum of the
+ *            operands actually used -- the widened stored values and q(w1') --, with the K of WIDE at the system's length: K is
+ *            unchanged, because widening is exact and the narrowing precedes the product; red[0] is the chunk-order chain of the
+ *            chunks' partials (tests/test_batch_wide_store32_gpu.py holds all of it).
+ *            MEMORY: 0.55 of the stored vectors of a binary64 wide batch at mvec = 20 and 0.59 at 10, as in STORAGE.
+ *            COST, MEASURED (profiles/r21/batch_wide_store32_throughput.txt, 1 x MI355X; a binary64 batch of
+ *            nka_hip_batch_create_wide, a second one as a control and the binary32 batch alternated on the same inputs; nsys 16 /
+ *            64 / 256 x vlen 32 768 / 65 536 / 262 144 x mvec 10 / 20, default flavour, full lists; 256 x 262 144 x 20 needs more
+ *            than 40 GB and was not measured).  THE CONDITION, fixed beforehand -- at 256 x 65 536, both mvec, a - b > |a - a'| plus
+ *            the largest window spread -- HELD: 0.674 (mvec 10) and 0.648 (mvec 20) of the time of the binary64 update, the two
+ *            binary64 batches differing by 2.3 % and 2.6 %; the byte model of STORAGE predicts 0.69 and 0.65.  From 64 systems on
+ *            0.65 ... 0.81 at every point (0.78 / 0.81 at 64 x 32 768, 0.69 / 0.65 at 64 x 262 144, 0.69 at 256 x 262 144 x 10); at
+ *            16 systems 0.99 / 0.98 at 32 768, 0.86 / 0.85 at 65 536 and 0.75 / 0.77 at 262 144 (there the scalar step on one thread
+ *            is a large share of a call); a step with x, mask, tol and fnorm at 64 x 65 536 x 20: 0.75.  Faster by more than the
+ *            control's difference and the window spread at all 18 points.  One measurement.
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -451,6 +491,14 @@ int nka_hip_batch_offers_weights(nka_hip_batch_t b);
  * _kind 1, _is_wide 1, _offers_lengths 1, _offers_weights 1, _offers_step = step. */
 int nka_hip_batch_create_wide_ext(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
                                   int32_t flavor, int32_t device, void *stream, int32_t step);
+/* WIDE STORED above: the wide batch with a choice of storage.  storage == NKA_HIP_BATCH_STORE_F64: nka_hip_batch_create_wide_ext(...,
+ * step), bit for bit and launch for launch.  storage == NKA_HIP_BATCH_STORE_F32: the limits of nka_hip_batch_create_wide, step 0 or 1
+ * as in nka_hip_batch_create_wide_ext, 2*nsys*(mvec+1) slot vectors of binary32 elements at the wide batch's slot stride and two
+ * pending buffers of nsys*stride doubles (zero-initialised, freed by destroy only, never moved); _kind 1, _is_wide 1, _offers_lengths
+ * 1, _offers_weights 1, _offers_step = step, _storage NKA_HIP_BATCH_STORE_F32.  NKA_HIP_EINVAL, nothing left allocated: every flavour
+ * but NKA_HIP_FLAVOR_C with binary32, any other storage, any other step, the wide limits. */
+int nka_hip_batch_create_wide_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                                     int32_t flavor, int32_t device, void *stream, int32_t step, int32_t storage);
 int nka_hip_batch_is_wide(nka_hip_batch_t b);                    /* 1 = wide, 0 = narrow, lanes or waves; < 0 on error */
 int nka_hip_batch_wide_limits(int64_t *chunk, int64_t *max_vlen);  /* the two constants, as the library was built */
 int nka_hip_batch_destroy(nka_hip_batch_t b);

@@ -134,6 +134,8 @@ BATCH_SIGNATURES = {
                                                  C.c_int32, C.c_void_p]),
     "nka_hip_batch_create_wide_ext": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32,
                                                 C.c_int32, C.c_void_p, C.c_int32]),
+    "nka_hip_batch_create_wide_stored": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32,
+                                                   C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "nka_hip_batch_offers_step": (C.c_int, [C.c_void_p]),
     "nka_hip_batch_create_stored": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32,
                                               C.c_int32, C.c_void_p, C.c_int32]),

@@ -56,7 +56,7 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
              stream: int | None = None, wide: bool = False, storage: int = STORE_F64, lanes: bool = False,
-             waves: bool = False, step: bool = False, ext: bool = False):
+             waves: bool = False, step: bool = False, ext: bool = False, wide_storage: int = STORE_F64):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
@@ -84,7 +84,13 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         none set it is the plain wide batch bit for bit.  The reference sum order and binary32 storage stay refused.
         step (with wide=True only): the wide batch WITH the solve step (nka_hip_batch_create_wide_step; include/nka_hip_batch.h,
         WIDE: STEP of a wide batch) -- one more buffer of nsys x nchunk doubles, accel_step as four launches, everything else the
-        wide batch bit for bit.  Every other kind offers the step already: step=True without wide=True raises NKAError."""
+        wide batch bit for bit.  Every other kind offers the step already: step=True without wide=True raises NKAError.
+        wide_storage (with wide=True only; with or without step=True, ext=True or not): wide_storage=STORE_F32 is the wide batch WITH
+        binary32 storage of the normalised subspace vectors (nka_hip_batch_create_wide_stored; include/nka_hip_batch.h, WIDE STORED)
+        -- the STORAGE contract per chunk, the pending pair and every product and sum still binary64; the default flavour and the
+        rounded fast sums only; weights and lengths are offered, accel_step with step=True; at one chunk it is the default batch with
+        storage=STORE_F32 bit for bit.  storage=STORE_F32 together with wide=True keeps raising: the keyword of the wide batch is
+        this one.  wide_storage != STORE_F64 without wide=True raises NKAError."""
         import torch
 
         if step and not wide:
@@ -93,6 +99,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         if ext and not (waves or wide):
             raise NKAError("nka_batch init: ext=True selects the wave batch with lengths and weights and needs waves=True, or the wide "
                            "batch with weights and needs wide=True (the default batch offers both already)")
+        if int(wide_storage) != STORE_F64 and not wide:
+            raise NKAError("nka_batch init: wide_storage selects the storage of a wide batch and needs wide=True (the default batch: "
+                           "storage=STORE_F32)")
         if waves and (wide or lanes):
             raise NKAError("nka_batch init: waves=True excludes wide=True and lanes=True (one wavefront per system, a system split "
                            "across workgroups, or one lane per system)")
@@ -115,9 +124,14 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         h = C.c_void_p()
         if int(storage) != STORE_F64:
             if wide:
-                raise NKAError("nka_batch init: binary32 storage is not offered by a wide batch (storage=STORE_F64)")
+                raise NKAError("nka_batch init: binary32 storage is not offered by a wide batch (storage=STORE_F64) through `storage`: "
+                               "wide_storage=STORE_F32 selects it")
             _check(self._L.nka_hip_batch_create_stored(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                        C.c_void_p(stream), int(storage)), "nka_hip_batch_create_stored", self._L)
+        elif wide and int(wide_storage) != STORE_F64:
+            _check(self._L.nka_hip_batch_create_wide_stored(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                            C.c_void_p(stream), 1 if step else 0, int(wide_storage)),
+                   "nka_hip_batch_create_wide_stored", self._L)
         elif lanes:
             _check(self._L.nka_hip_batch_create_lanes(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                       C.c_void_p(stream)), "nka_hip_batch_create_lanes", self._L)

@@ -55,11 +55,9 @@ struct LenArgs {
 __device__ __forceinline__ const StepArgs &step_args(const StepArgs &st, const LenArgs &) { return st; }
 __device__ __forceinline__ const int32_t *len_args(const LenArgs &l) { return l.len; }
 __device__ __forceinline__ const int32_t *len_args(const StepArgs &, const LenArgs &l) { return l.len; }
-// BINARY32 STORAGE (nka_hip_batch_create_stored): the two pending buffers, nsys binary64 rows at the slot stride.  It is the LAST
-// member of the trailing pack, behind the StepArgs and the LenArgs if there are any, so an instance without it keeps its arguments.
-struct Store32Args {
-  double *pw, *pv;
-};
+// BINARY32 STORAGE (nka_hip_batch_create_stored): the two pending buffers, nsys binary64 rows at the slot stride (Store32Args,
+// nka_batch_dev.hpp).  It is the LAST member of the trailing pack, behind the StepArgs and the LenArgs if there are any, so an
+// instance without it keeps its arguments.
 __device__ __forceinline__ const StepArgs &step_args(const StepArgs &st, const Store32Args &) { return st; }
 __device__ __forceinline__ const StepArgs &step_args(const StepArgs &st, const LenArgs &, const Store32Args &) { return st; }
 __device__ __forceinline__ const int32_t *len_args(const LenArgs &l, const Store32Args &) { return l.len; }
@@ -652,8 +650,6 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
   *out = nullptr;
   if (nsys < 1) return fail(NKA_HIP_EINVAL, who + ": nsys must be >= 1");
   if (storage != NKA_HIP_BATCH_STORE_F64 && !s32) return fail(NKA_HIP_EINVAL, who + ": unknown storage (NKA_HIP_BATCH_STORE_F64 or _F32)");
-  if (wide && s32)
-    return fail(NKA_HIP_EINVAL, who + ": binary32 storage is not offered by a wide batch yet (the follow-up): NKA_HIP_BATCH_STORE_F64");
   if (wide) {
     int64_t chunk = 0, cap = 0;
     nka_hip_batch_wide_limits(&chunk, &cap);
@@ -785,6 +781,17 @@ int nka_hip_batch_create_wide_ext(nka_hip_batch_t *out, int32_t nsys, int64_t vl
   }
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, true, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_wide_ext", false,
                       false, step == 1, false, true);
+}
+// (a wide batch with binary32 storage: the allocations of batch_create for that storage at the wide batch's stride, the binary32
+// instances of nka_batch_wide.hip; with binary64 storage every argument of the call above)
+int nka_hip_batch_create_wide_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                                     int32_t device, void *stream, int32_t step, int32_t storage) {
+  if (step != 0 && step != 1) {
+    if (out) *out = nullptr;
+    return fail(NKA_HIP_EINVAL, "nka_hip_batch_create_wide_stored: step must be 0 (no solve step) or 1 (nka_hip_batch_accel_step is offered)");
+  }
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, true, storage, "nka_hip_batch_create_wide_stored", false, false,
+                      step == 1, false, true);
 }
 int nka_hip_batch_create_stored(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
                                 int32_t device, void *stream, int32_t storage) {

@@ -142,6 +142,11 @@ __device__ __forceinline__ void batch_block_sum(const double (&acc)[NACC], doubl
 // __restrict__, and without it the weighted instances are scheduled differently
 using WgtRows = const double *__restrict__;
 enum class WgtStride : int64_t {};
+// BINARY32 STORAGE (nka_hip_batch_create_stored, nka_hip_batch_create_wide_stored): the two pending buffers, nsys binary64 rows at
+// the slot stride.  In k_batch_update (nka_batch.hip) the LAST member of the trailing pack; in the wide kernels ahead of the weights
+struct Store32Args {
+  double *pw, *pv;
+};
 // the T of pack...
 template <class T, class First, class... Rest>
 __host__ __device__ __forceinline__ const T &pack_get(const First &first, const Rest &...rest) {
@@ -241,7 +246,9 @@ struct nka_hip_batch_state {
   // ... of nka_hip_batch_create_waves_ext: the same batch, which also takes lengths and weights (the same unit and kernel)
   bool waves_ext = false;
   // a WIDE batch of nka_hip_batch_create_wide_ext: the same batch, which also takes weights (the weighted instances of the norm and
-  // the sums kernel of nka_batch_wide.hip); with wide_step as its `step` argument says
+  // the sums kernel of nka_batch_wide.hip); with wide_step as its `step` argument says.  A batch of
+  // nka_hip_batch_create_wide_stored is such a batch whose `storage` may be NKA_HIP_BATCH_STORE_F32 (the binary32 instances of the
+  // sums, the scalar and the combine kernel; the norm kernels read the pending rows through their BatchArgs)
   bool wide_ext = false;
 };
 

@@ -1,4 +1,4 @@
-// nka_batch_wide.hip -- the WIDE batched accelerator (nka_hip_batch_create_wide, _wide_step, _wide_ext; include/nka_hip_batch.h):
+// nka_batch_wide.hip -- the WIDE batched accelerator (nka_hip_batch_create_wide, _wide_step, _wide_ext, _wide_stored; include/nka_hip_batch.h):
 // nsys independent NKA states of equal shape, each split into nchunk chunks of NKA_HIP_BATCH_WIDE_CHUNK elements with ONE WORKGROUP
 // PER CHUNK (blockIdx.x = chunk, blockIdx.y = system).  The phases of k_batch_update (nka_batch.hip) that need a sum over the whole
 // system are separated by KERNEL BOUNDARIES instead of workgroup barriers -- an update is four launches in a line, a solve step
@@ -18,9 +18,9 @@
 // the stored vectors and the parity of a row of f are those of the narrow kernel: a wide batch of ONE chunk returns the
 // narrow batch's bits.  Which partials a kernel reads is decided from the list (pending, normed, nolder), never from what the
 // buffer holds: a partial that this update did not write is not read.
-// FIVE KERNEL TEMPLATES, 48 INSTANCES: norm 4 + 4, sums 24, scalar 4, combine 12.  What an instance takes beside the update's
-// arguments rides in THE TRAILING PACK [WideStepArgs][, LenRows][, WgtRows, WgtStride] (below), so an instance without a member
-// keeps its arguments.  The step's norm alone is a kernel of its own, k_wide_step_norm<LEN, [WgtRows, WgtStride]>: folded into
+// FIVE KERNEL TEMPLATES, 68 INSTANCES: norm 8 + 4, sums 32, scalar 8, combine 16 (20 of them with binary32 storage).  What an
+// instance takes beside the update's arguments rides in THE TRAILING PACK [WideStepArgs][, LenRows][, Store32Args][, WgtRows,
+// WgtStride] (below), so an instance without a member keeps its arguments.  The step's norm alone is a kernel of its own, k_wide_step_norm<LEN, [WgtRows, WgtStride]>: folded into
 // k_wide_norm it was measured slower than before.
 //   LENGTHS  (nka_hip_batch_set_lengths) The system is len[sys] elements long -- one uniform scalar load behind the `active` test,
 //            a value that was validated when it was set: 1 <= len[sys] <= a.n --, it owns the first wide_len_nchunk(len[sys])
@@ -35,6 +35,15 @@
 //            fma(fl(w w1'), w_p, .), <f,w_p> = sum fma(fl(w f), w_p, .).  The weight pair is loaded under the guards of the pair of
 //            f: with lengths nothing at or beyond len[sys] of the weight row is read.  The scalar kernel and the combine do not
 //            read weights and never take them.
+//   STORAGE  (nka_hip_batch_create_wide_stored with NKA_HIP_BATCH_STORE_F32; flavour C only) A Store32Args in the pack makes the
+//            instance one of BINARY32 STORAGE, the statements of k_batch_update<..., Store32Args> (nka_batch.hip) per chunk: a.w / a.v
+//            are float allocations of the same strides in elements, an older vector is one 8-byte load widened exactly (a chunk
+//            starts on a multiple of 2048 elements, so a float pair is 8-byte aligned), the raw pending pair is read from and written
+//            to the binary64 rows pw / pv + sys * stride, and the normalised pair is narrowed once -- w1' = q(fl(d/s)) in the sums and
+//            the combine alike, v = q(fl(fl(v1/s) - w1')) -- before it is used or stored.  The two norm kernels read binary64 data
+//            only: the launch gives them the pending buffer as a.w (launch_wide), the step's norm runs its binary64 instances, and
+//            k_wide_norm and k_wide_scalar take the member with the pack without reading it.  Without the member every such
+//            statement is discarded at compile time and the instance is the one it was, instruction for instruction.
 #include "nka_batch_dev.hpp"
 
 #include <string>
@@ -57,8 +66,9 @@ struct WideArgs {
   int32_t nchunk;
 };
 
-// THE TRAILING PACK of the kernels: [WideStepArgs][, LenRows][, WgtRows, WgtStride], each at most once, in this order (WgtRows
-// and WgtStride: nka_batch_dev.hpp; the scalar kernel and the combine take the first two only, k_wide_norm the last three).
+// THE TRAILING PACK of the kernels: [WideStepArgs][, LenRows][, Store32Args][, WgtRows, WgtStride], each at most once, in this order
+// (Store32Args, WgtRows and WgtStride: nka_batch_dev.hpp; the scalar kernel and the combine never take the weights, k_wide_norm
+// never the step's arguments).
 // what a solve step takes beside the update's arguments; every pointer but fpart may be NULL
 struct WideStepArgs {
   double *fpart;        // nka_host::wide_fpart_index: the partials of <f,f>
@@ -75,8 +85,8 @@ struct WideStepLenArgs : WideStepArgs {
 };
 template <class T, class... Pack> constexpr bool wide_has = (std::is_same<Pack, T>::value || ...);
 template <class T>
-constexpr int wide_pack_rank = std::is_same<T, WideStepArgs>::value ? 0 : std::is_same<T, LenRows>::value ? 1
-                               : std::is_same<T, WgtRows>::value ? 2 : std::is_same<T, WgtStride>::value ? 3 : -1;
+constexpr int wide_pack_rank = std::is_same<T, WideStepArgs>::value ? 0 : std::is_same<T, LenRows>::value ? 1 : std::is_same<T, Store32Args>::value ? 2
+                               : std::is_same<T, WgtRows>::value ? 3 : std::is_same<T, WgtStride>::value ? 4 : -1;
 template <class... Pack> constexpr bool wide_pack_ok() {      // known members only, ranks strictly increasing, the weights as a pair
   int prev = -1;
   bool ok = true;
@@ -121,7 +131,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_norm(BatchArgs a, WideAr
                                                              const int32_t *__restrict__ active, Pack... pack) {
 #pragma clang fp contract(off)
   constexpr bool LEN = wide_has<LenRows, Pack...>, WGT = wide_has<WgtRows, Pack...>;
-  static_assert(wide_pack_ok<Pack...>() && !wide_has<WideStepArgs, Pack...>, "[LenRows][, WgtRows, WgtStride]: a step's norm is k_wide_step_norm");
+  // (a Store32Args is taken and not read: the launch gives such an instance the pending rows as a.w, see launch_wide)
+  static_assert(wide_pack_ok<Pack...>() && !wide_has<WideStepArgs, Pack...>, "[LenRows][, Store32Args][, WgtRows, WgtStride]: a step's norm is k_wide_step_norm");
   const int sys = blockIdx.y;
   if (active != nullptr && active[sys] == 0) return;
   int64_t sn = a.n;
@@ -225,7 +236,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_sums(BatchArgs a, WideAr
                                                              const int32_t *__restrict__ active, Pack... pack) {
 #pragma clang fp contract(off)
   constexpr bool STEP = wide_has<WideStepArgs, Pack...>, LEN = wide_has<LenRows, Pack...>, WGT = wide_has<WgtRows, Pack...>;
-  static_assert(wide_pack_ok<Pack...>(), "[WideStepArgs][, LenRows][, WgtRows, WgtStride]");
+  constexpr bool S32 = wide_has<Store32Args, Pack...>;
+  static_assert(wide_pack_ok<Pack...>(), "[WideStepArgs][, LenRows][, Store32Args][, WgtRows, WgtStride]");
+  static_assert(!S32 || COMB == 2, "binary32 storage: the default flavour only");
   constexpr bool RCP = (COMB == 1);
   const int sys = blockIdx.y, chunk = blockIdx.x;
   if (active != nullptr && active[sys] == 0) return;
@@ -270,16 +283,25 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_sums(BatchArgs a, WideAr
   [[maybe_unused]] const double *wg = nullptr;      // this chunk of the system's weight row
   if constexpr (WGT) wg = pack_get<WgtRows>(pack...) + (size_t)nka_host::wide_wgt_offset(sys, (int64_t)pack_get<WgtStride>(pack...), blockIdx.x);
   const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
-  const double *const w1s = pending ? W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride : W;      // always a stored vector
+  // binary32 storage: this chunk of the system's float slots, and of its row of the pending buffer where the raw w1 lies
+  [[maybe_unused]] const float *W32 = nullptr;
+  [[maybe_unused]] const double *pw = nullptr;
+  if constexpr (S32) {
+    W32 = reinterpret_cast<const float *>(a.w) + (size_t)sys * a.sys_stride + lo;
+    pw = pack_get<Store32Args>(pack...).pw + (size_t)sys * a.stride + lo;
+  }
+  const double *const w1s = S32 ? pw : pending ? W + (size_t)(hdr[HDR_FIRST] - 1) * a.stride : W;      // always a stored vector
   auto out = [&](int entry) -> double & { return wa.part[nka_host::wide_part_index(sys, entry, chunk, mvec, nchunk)]; };
 
   const int ngroup = (nolder + kBatchGroup - 1) / kBatchGroup;
   for (int g = 0; g < (ngroup > 0 ? ngroup : (normed ? 1 : 0)); g++) {
     const double *wk[kBatchGroup];
+    [[maybe_unused]] const float *wk32[kBatchGroup];
 #pragma unroll
     for (int j = 0; j < kBatchGroup; j++) {
       const int p = g * kBatchGroup + j;
-      wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1s;   // (beyond the list: a re-read, discarded)
+      if constexpr (S32) wk32[j] = W32 + (nolder > 0 ? (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : (size_t)0);
+      else wk[j] = nolder > 0 ? W + (size_t)(ps[p < nolder ? p : nolder - 1] - 1) * a.stride : w1s;   // (beyond the list: a re-read, discarded)
     }
     double acc[kBatchAcc];
 #pragma unroll
@@ -290,7 +312,9 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_sums(BatchArgs a, WideAr
       const d2 dv = ld_tile<FULL, true>(w1s, i, n);     // (no pending pair: a stored vector whose value is not used)
       d2 wv[kBatchGroup];
 #pragma unroll
-      for (int j = 0; j < kBatchGroup; j++) wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+      for (int j = 0; j < kBatchGroup; j++) {
+        if constexpr (S32) wv[j] = ld_tile32<FULL>(wk32[j], i, n); else wv[j] = ld_tile<FULL, true>(wk[j], i, n);
+      }
       [[maybe_unused]] d2 gv;
       if constexpr (WGT) gv = ld_tile<FULL, true>(wg, i, n);
 #pragma unroll
@@ -300,7 +324,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_sums(BatchArgs a, WideAr
           double fa = fq;                                    // first operand of the products on f: fl(w f), formed once
           if constexpr (WGT) fa = gv[q] * fq;
           if (normed) {
-            const double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
+            double wn = batch_nrm<RCP>(dv[q] - fq, s, rs);
+            if constexpr (S32) wn = batch_q32(wn);           // (binary32 storage: the value the slot will hold)
             double wa_ = wn;                                 // first operand of the Gram row: fl(w w1')
             if constexpr (WGT) wa_ = gv[q] * wn;
             if (g == 0) acc[2 * kBatchGroup] = fma(fa, wn, acc[2 * kBatchGroup]);
@@ -327,8 +352,9 @@ template <class Mask, class... Pack>
 __global__ __launch_bounds__(kBatchThreads) void k_wide_scalar(BatchArgs a, WideArgs wa, Mask *__restrict__ active, Pack... pack) {
 #pragma clang fp contract(off)
   constexpr bool STEP = wide_has<WideStepArgs, Pack...>, LEN = wide_has<LenRows, Pack...>;
-  static_assert(wide_pack_ok<Pack...>() && sizeof...(Pack) == (STEP ? 1 : 0) + (LEN ? 1 : 0) && STEP == !std::is_const<Mask>::value,
-                "[WideStepArgs][, LenRows]: the weights are not taken; a step, and only a step, writes the mask");
+  constexpr bool S32 = wide_has<Store32Args, Pack...>;      // (taken with the pack and not read: this kernel touches no stored vector)
+  static_assert(wide_pack_ok<Pack...>() && sizeof...(Pack) == (STEP ? 1 : 0) + (LEN ? 1 : 0) + (S32 ? 1 : 0) && STEP == !std::is_const<Mask>::value,
+                "[WideStepArgs][, LenRows][, Store32Args]: the weights are not taken; a step, and only a step, writes the mask");
   const int sys = blockIdx.x;
   if (active != nullptr && active[sys] == 0) return;
   int nown = wa.nchunk;      // the partials that are added
@@ -445,7 +471,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_combine(BatchArgs a, Wid
                                                                 const int32_t *__restrict__ active, Pack... pack) {
 #pragma clang fp contract(off)
   constexpr bool STEP = wide_has<WideStepArgs, Pack...>, LEN = wide_has<LenRows, Pack...>;
-  static_assert(wide_pack_ok<Pack...>() && sizeof...(Pack) == (STEP ? 1 : 0) + (LEN ? 1 : 0), "[WideStepArgs][, LenRows]: the weights are not taken");
+  constexpr bool S32 = wide_has<Store32Args, Pack...>;
+  static_assert(wide_pack_ok<Pack...>() && sizeof...(Pack) == (STEP ? 1 : 0) + (LEN ? 1 : 0) + (S32 ? 1 : 0),
+                "[WideStepArgs][, LenRows][, Store32Args]: the weights are not taken");
+  static_assert(!S32 || COMB == 2, "binary32 storage: the default flavour only");
   constexpr bool RCP = (COMB == 1);
   constexpr bool COMPACT = (COMB == 2);
   const int sys = blockIdx.y;
@@ -482,7 +511,16 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_combine(BatchArgs a, Wid
   double *const f = f_all + (size_t)sys * ld + lo;
   double *const W = a.w + (size_t)sys * a.sys_stride + lo, *const V = a.v + (size_t)sys * a.sys_stride + lo;
   const bool fvec = (reinterpret_cast<uintptr_t>(f) % 16) == 0;
-  double *const wnew = W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
+  // binary32 storage: this chunk of the system's float slots and of its rows of the pending buffers, where the new raw pair goes
+  [[maybe_unused]] float *W32 = nullptr, *V32 = nullptr;
+  [[maybe_unused]] double *pw = nullptr, *pv = nullptr;
+  if constexpr (S32) {
+    W32 = reinterpret_cast<float *>(a.w) + (size_t)sys * a.sys_stride + lo;
+    V32 = reinterpret_cast<float *>(a.v) + (size_t)sys * a.sys_stride + lo;
+    pw = pack_get<Store32Args>(pack...).pw + (size_t)sys * a.stride + lo;
+    pv = pack_get<Store32Args>(pack...).pv + (size_t)sys * a.stride + lo;
+  }
+  double *const wnew = S32 ? pw : W + (size_t)(hdr[HDR_NEW] - 1) * a.stride, *const vnew = S32 ? pv : V + (size_t)(hdr[HDR_NEW] - 1) * a.stride;
   // STEP: this chunk of the system's row of the iterate, if there is one; a chunk starts on a multiple of 16 bytes of its row
   [[maybe_unused]] double *xrow = nullptr;
   if constexpr (STEP) {
@@ -499,7 +537,24 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_combine(BatchArgs a, Wid
     if constexpr (STEP)
       if (xrow != nullptr) xit = xvec ? ld_tile<FULL, true>(xrow, i, n) : ld_tile<FULL, false>(xrow, i, n);
     int j0 = 0;
-    if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
+    if constexpr (S32) {
+      if (norm0) {      // pair 0 of the plan: raw in the pending rows; narrowed once, applied and stored as narrowed
+        const size_t off = (size_t)(cs[0] - 1) * a.stride;
+        d2 wv = ld_tile<FULL, true>(pw, i, n), vv = ld_tile<FULL, true>(pv, i, n);
+        const double c = cc[0];
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+          const double wn = batch_q32(batch_nrm<RCP>(wv[q] - fin[q], s, rs));
+          const double vn = batch_nrm<RCP>(vv[q], s, rs);
+          wv[q] = wn;
+          vv[q] = batch_q32(vn - wn);
+          x[q] = x[q] + c * vv[q];
+        }
+        st_tile32<FULL>(W32 + off, i, n, wv);
+        st_tile32<FULL>(V32 + off, i, n, vv);
+        j0 = 1;
+      }
+    } else if (norm0) {      // pair 0 of the plan: the pending pair, still raw (F08:282-283)
       double *const wk = W + (size_t)(cs[0] - 1) * a.stride, *const vk = V + (size_t)(cs[0] - 1) * a.stride;
       d2 wv = ld_tile<FULL, true>(wk, i, n), vv = ld_tile<FULL, true>(vk, i, n);
       const double c = cc[0];
@@ -524,7 +579,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_combine(BatchArgs a, Wid
         const int jj = j + u < ncomb ? j + u : ncomb - 1;
         const size_t off = (size_t)(cs[jj] - 1) * a.stride;
         c[u] = cc[jj];
-        vv[u] = ld_tile<FULL, true>(V + off, i, n);
+        if constexpr (S32) vv[u] = ld_tile32<FULL>(V32 + off, i, n); else vv[u] = ld_tile<FULL, true>(V + off, i, n);
         if (!COMPACT) wv[u] = ld_tile<FULL, true>(W + off, i, n); else wv[u] = vv[u];
       }
 #pragma unroll
@@ -562,17 +617,25 @@ void launch_wide(nka_hip_batch_t b, double *f, int64_t ld, Mask *active, Pack...
   const double *const cf = f;
   const int32_t *const mask = active;
   constexpr bool STEP = wide_has<WideStepArgs, Pack...>, LEN = wide_has<LenRows, Pack...>;
+  // binary32 storage: both norm kernels read binary64 data only, f and the raw w1 of the system's pending row -- they get the
+  // pending buffer as `w`, its row stride as the stride between systems and 0 between slots, and form the address they always did
+  BatchArgs kn = b->k;
+  if constexpr (wide_has<Store32Args, Pack...>) {
+    kn.w = pack_get<Store32Args>(pack...).pw;
+    kn.sys_stride = b->k.stride;
+    kn.stride = 0;
+  }
   [[maybe_unused]] WideStepLenArgs sl{};      // STEP: what the step's norm takes in place of the pack
   if constexpr (STEP) sl = WideStepLenArgs{pack_get<WideStepArgs>(pack...), b->has_len ? b->len : nullptr};
   if (b->weighted) {
     const WgtRows wgt = b->wgt;
     const WgtStride ws = WgtStride(b->wgt_stride);
-    if constexpr (STEP) hipLaunchKernelGGL((k_wide_step_norm<LEN, WgtRows, WgtStride>), grid, block, 0, b->stream, b->k, wa, sl, cf, ld, mask, wgt, ws);
-    else hipLaunchKernelGGL((k_wide_norm<Pack..., WgtRows, WgtStride>), grid, block, 0, b->stream, b->k, wa, cf, ld, mask, pack..., wgt, ws);
+    if constexpr (STEP) hipLaunchKernelGGL((k_wide_step_norm<LEN, WgtRows, WgtStride>), grid, block, 0, b->stream, kn, wa, sl, cf, ld, mask, wgt, ws);
+    else hipLaunchKernelGGL((k_wide_norm<Pack..., WgtRows, WgtStride>), grid, block, 0, b->stream, kn, wa, cf, ld, mask, pack..., wgt, ws);
     hipLaunchKernelGGL((k_wide_sums<COMB, Pack..., WgtRows, WgtStride>), grid, block, lsums, b->stream, b->k, wa, cf, ld, mask, pack..., wgt, ws);
   } else {
-    if constexpr (STEP) hipLaunchKernelGGL((k_wide_step_norm<LEN>), grid, block, 0, b->stream, b->k, wa, sl, cf, ld, mask);
-    else hipLaunchKernelGGL((k_wide_norm<Pack...>), grid, block, 0, b->stream, b->k, wa, cf, ld, mask, pack...);
+    if constexpr (STEP) hipLaunchKernelGGL((k_wide_step_norm<LEN>), grid, block, 0, b->stream, kn, wa, sl, cf, ld, mask);
+    else hipLaunchKernelGGL((k_wide_norm<Pack...>), grid, block, 0, b->stream, kn, wa, cf, ld, mask, pack...);
     hipLaunchKernelGGL((k_wide_sums<COMB, Pack...>), grid, block, lsums, b->stream, b->k, wa, cf, ld, mask, pack...);
   }
   hipLaunchKernelGGL((k_wide_scalar<Mask, Pack...>), dim3((unsigned)b->k.nsys), block, lscal, b->stream, b->k, wa, active, pack...);
@@ -580,6 +643,14 @@ void launch_wide(nka_hip_batch_t b, double *f, int64_t ld, Mask *active, Pack...
 }
 template <int COMB, class Mask, class... Step>
 void launch_wide_len(nka_hip_batch_t b, double *f, int64_t ld, Mask *active, Step... step) {
+  if (b->storage == NKA_HIP_BATCH_STORE_F32) {      // (the default flavour only: every other one was refused at creation)
+    if constexpr (COMB == 2) {
+      const Store32Args s32{b->pend_w, b->pend_v};
+      if (b->has_len) launch_wide<COMB, Mask, Step..., LenRows, Store32Args>(b, f, ld, active, step..., b->len, s32);
+      else launch_wide<COMB, Mask, Step..., Store32Args>(b, f, ld, active, step..., s32);
+    }
+    return;
+  }
   if (b->has_len) launch_wide<COMB, Mask, Step..., LenRows>(b, f, ld, active, step..., b->len);
   else launch_wide<COMB, Mask, Step...>(b, f, ld, active, step...);
 }

@@ -90,7 +90,14 @@ ratio is fixed: a point counts as won when b - c > |b - b'|, as lost when c - b 
 nsys 16,64,256 x vlen 32768,262144 x mvec 10,20 with accel_update, then accel_step with X, mask, tol and fnorm at 64 x 65536 (no
 (e) there); a point that needs more than --mem-gb (here 40) is skipped and listed.  Beside b/a and c/a stands the stream model's
 prediction (norm 2 -> 3 streams, each sweep of four 6 -> 7, combine unchanged).  No ratio is fixed: (c) won against (e) when
-e - c > |a - a'|."""
+e - c > |a - a'|.
+
+--wide-store32 measures binary32 storage of a wide batch (nka_hip_batch_create_wide_stored) with the method of --store32:
+  (a) a binary64 wide batch of nka_hip_batch_create_wide; (a') the same again, the control; (b) the binary32 wide batch.
+nsys 16,64,256 x vlen 32768,65536,262144 x mvec 10,20 with accel_update, then accel_step with X, mask, tol and fnorm at 64 x 65536
+x 20; a point that needs more than --mem-gb (here 40) is skipped and listed; vector_bytes is held to the formula at every point.
+The condition, fixed before measuring: at 256 x 65536, both mvec, a - b > |a - a'| + the largest window spread of the point.  The
+byte model of --store32 stands beside b/a as a prediction."""
 import argparse
 import ctypes as C
 import os
@@ -325,6 +332,114 @@ def store32_main(args, torch, nka_amd, L, emit):
              f"{b32 / b64:6.3f} {r['bytes_a'] / 1e6:12.1f} {r['bytes_b'] / 1e6:12.1f} {r['bytes_b'] / r['bytes_a']:7.3f}  {cond}   "
              f"(spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
     emit(f"# condition: {', '.join(verdicts) if verdicts else 'not measured (no point at 4096 x 16384)'}; {len(points)} points in "
+         f"{time.time() - t0:.0f} s")
+    return 0
+
+
+def measure_wide_store32(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, step):
+    """(a) a binary64 wide batch of nka_hip_batch_create_wide (step: _create_wide_step), whose kernels are untouched by the binary32
+    instances; (a') a second one, the control; (b) the wide batch with binary32 storage (nka_hip_batch_create_wide_stored).  Same
+    inputs, alternated, as measure_store32.  step: accel_step with X, mask, tol (nobody retires) and fnorm."""
+    npool = mvec + 3
+    stride = (vlen + 31) // 32 * 32
+    vec = {s: 2 * nsys * stride * (8 * (mvec + 1) if s == nka_amd.STORE_F64 else 4 * (mvec + 1) + 8) for s in (nka_amd.STORE_F64, nka_amd.STORE_F32)}
+    need = 2 * vec[nka_amd.STORE_F64] + vec[nka_amd.STORE_F32] + 8.0 * nsys * vlen * (npool + 3 + (3 if step else 0))
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    forms = {"a": nka_amd.STORE_F64, "a2": nka_amd.STORE_F64, "b": nka_amd.STORE_F32}
+    Fs, Xs, hs, batches = {}, {}, {}, {}
+    for name, storage in forms.items():
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+        if storage == nka_amd.STORE_F32:
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, wide=True, wide_storage=storage, step=step)
+        else:
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, wide=True, step=step)
+        assert batches[name].is_wide() and batches[name].storage() == storage and batches[name].vector_bytes() == vec[storage], name
+        hs[name] = batches[name]._handle()
+        if step:
+            Xs[name] = torch.zeros(nsys, vlen, dtype=torch.float64, device="cuda")
+    mask = torch.ones(nsys, dtype=torch.int32, device="cuda")
+    tol = torch.full((nsys,), -1.0, dtype=torch.float64, device="cuda")
+    fnorm = torch.zeros(nsys, dtype=torch.float64, device="cuda")
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    upd, stp = L.nka_hip_batch_accel_update, L.nka_hip_batch_accel_step
+    it = [0]
+
+    def run(name, reps):
+        F, h = Fs[name], hs[name]
+        p = C.c_void_p(F.data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[it[0] % npool])
+            it[0] += 1
+            if step:
+                assert stp(h, p, ld, C.c_void_p(Xs[name].data_ptr()), ld, C.c_void_p(mask.data_ptr()), C.c_void_p(tol.data_ptr()),
+                           C.c_void_p(fnorm.data_ptr())) == 0
+            else:
+                assert upd(h, p, ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in forms}
+    for name in forms:                             # warm: fill the lists (steady state), settle clocks and caches
+        it[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    for name in forms:
+        assert (batches[name].num_vec() == mvec).all(), name
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in forms:
+            ts[name].append(timed(name, reps[name]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec, bytes_a=vec[nka_amd.STORE_F64], bytes_b=vec[nka_amd.STORE_F32])
+    for name in forms:
+        assert (batches[name].num_vec() == mvec).all() and bool(mask.all()), name
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+        batches[name].delete()
+    del pool, Fs, Xs
+    torch.cuda.empty_cache()
+    return out
+
+
+def wide_store32_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m, False) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    points.append((64, 65536, 20, True))
+    emit(f"# one update of (a) a binary64 wide batch (nka_hip_batch_create_wide), (a') a second one of the same shape -- the control -- "
+         f"and (b) a wide batch with binary32 storage (nka_hip_batch_create_wide_stored); {torch.cuda.get_device_name(0)}; windows >= "
+         f"{args.window} s, median of {args.repeats}, the three alternated on the same inputs; flavour C, full list; the last row: "
+         f"accel_step with X, mask, tol and fnorm (a, a': nka_hip_batch_create_wide_step)")
+    emit("# byte model per element: 16 + 48 G + 8 (7 + k) binary64, 16 + 32 G + 56 + 4 (k - 1) binary32, G = ceil((mvec - 1) / 4), "
+         "k = mvec: 308 / 472 = 0.65 at mvec 20, 204 / 296 = 0.69 at 10 (a prediction, not a bar)")
+    emit("# CONDITION at 256 x 65536, both mvec: a - b > |a - a'| + the largest window spread of the point (x a)")
+    emit(f"{'nsys':>5} {'vlen':>7} {'mvec':>4} {'call':>6} {'a us':>10} {'a2 us':>10} {'b us':>10} {'b/a':>6} {'|a-a2|/a':>8} {'model':>6} "
+         f"{'vectors a MB':>12} {'vectors b MB':>12} {'b/a mem':>7}  condition")
+    t0 = time.time()
+    verdicts = []
+    for n, v, m, step in points:
+        r = measure_wide_store32(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9, step)
+        if r is None:
+            emit(f"{n:5d} {v:7d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        b64, b32 = store32_bytes_model(m)
+        ratio, ctl = r["b"] / r["a"], abs(r["a"] - r["a2"]) / r["a"]
+        spread = max(r["spread_a"], r["spread_a2"], r["spread_b"])
+        won = r["a"] - r["b"] > abs(r["a"] - r["a2"]) + spread * r["a"]
+        cond = "-"
+        if (n, v) == (256, 65536) and not step:
+            cond = "HELD" if won else "MISSED"
+            verdicts.append(cond)
+        emit(f"{n:5d} {v:7d} {m:4d} {'step' if step else 'update':>6} {r['a'] * 1e6:10.1f} {r['a2'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {ratio:6.3f} "
+             f"{ctl:8.3f} {b32 / b64:6.3f} {r['bytes_a'] / 1e6:12.1f} {r['bytes_b'] / 1e6:12.1f} {r['bytes_b'] / r['bytes_a']:7.3f}  {cond}   "
+             f"({'won' if won else 'not won'}; spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
+    emit(f"# condition: {', '.join(verdicts) if verdicts else 'not measured (no point at 256 x 65536)'}; {len(points)} points in "
          f"{time.time() - t0:.0f} s")
     return 0
 
@@ -1207,6 +1322,10 @@ def main():
                          "batches with a shared row, with one row per system and with nothing set, and a loop over lone handles with "
                          "weights; without --nsys / --vlens / --mvecs / --mem-gb: nsys 16,64,256 x vlen 32768,262144 x mvec 10,20, "
                          "then accel_step at 64 x 65536, 40 GB")
+    ap.add_argument("--wide-store32", action="store_true",
+                    help="time binary32 storage of a wide batch (nka_hip_batch_create_wide_stored) against a binary64 wide batch and a "
+                         "second one as a control; without --nsys / --vlens / --mvecs / --mem-gb: nsys 16,64,256 x vlen "
+                         "32768,65536,262144 x mvec 10,20, then accel_step at 64 x 65536 x 20, 40 GB")
     ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
@@ -1230,6 +1349,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.wide_store32:
+        for name, grid_w in (("nsys", "16,64,256"), ("vlens", "32768,65536,262144"), ("mvecs", "10,20"), ("mem_gb", 40.0)):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+        return wide_store32_main(args, torch, nka_amd, L, emit)
     if args.wide_weights:
         for name, grid_w in (("nsys", "16,64,256"), ("vlens", "32768,262144"), ("mvecs", "10,20"), ("mem_gb", 40.0)):
             if getattr(args, name) == ap.get_default(name):
