@@ -45,12 +45,23 @@ extern "C" {
  * mvec + 2) and three guarded launches behind the scalar step repair the rare update that needs its sums after all: -1
  * automatic (from a vector length on, where the stream saved outweighs the launches), 0 never, 1 wherever the launch allows
  * it (fast sums, one rank, the library's own dot product, 2 <= mvec <= 32, f 16-byte aligned) at any length.  Same outputs,
- * lists, factor and stored vectors; nka_hip_get_reductions reads 0 in the two skipped entries (nka_hip_ext.h). */
+ * lists, factor and stored vectors; nka_hip_get_reductions reads 0 in the two skipped entries (nka_hip_ext.h).
+ * "defer_v" = -1/0/1: the combine of an in-place update of the compact flavour leaves the accelerated f unstored in the v buffer
+ * of the new pair -- it is read exactly once, by the next combine, which forms it again from the vectors it streams anyway (one
+ * store of 27 words less) -- and everything else that reads that buffer writes it first (a guarded launch): -1 automatic (from
+ * a vector length on and where the tiles are handed out by tickets), 0 never, 1 wherever the launch allows it (f 16-byte
+ * aligned, lists of <= 32, one rolling-window launch with tile tickets not switched off, the library's own dot product, no
+ * graph) at any length.  Same outputs, lists, factor and stored vectors. */
 int nka_hip_set_tuning(nka_hip_t a, const char *key, int32_t value);
 
 /* The skip of the last vector ("skip_last") as the device holds it: out4 = { the plan of the next update may skip (0/1),
  * updates still to run without the skip after a repair, a repair is pending (0 between updates), repairs so far }. */
 int nka_hip_get_skip_state(nka_hip_t a, int32_t out4[4]);
+
+/* The deferred v of the pending pair ("defer_v") as the device holds it: out2 = { the v buffer of the pending pair does not
+ * hold the accelerated f yet (0/1), entries of the replay plan the last combine formed it from (0: it read it from memory) }.
+ * Reads the two words only: nothing is materialised. */
+int nka_hip_get_defer_state(nka_hip_t a, int32_t out2[2]);
 
 /* Launch geometry knobs for tuning: blocks per CU of PA and PB (0 = automatic). */
 int nka_hip_set_grid(nka_hip_t a, int32_t pa_blocks_per_cu, int32_t pb_blocks_per_cu);

@@ -22,6 +22,12 @@
  *                                        N ranks gated on a multi-GPU box); refused with REFERENCE_ORDER and with the user dot
  *                                        product
  *   out-of-place entry            every row above except the user dot product; not capturable into a graph
+ *   deferred v of the pending     compact flavour, in place, from 2e6 elements on where the combine takes its tiles by tickets: the
+ *   pair (automatic)              combine leaves v of the new pair unstored and the next one forms it again.
+ *                                 With every sum order and transport of the rows above (the combine is the same kernel) and with
+ *                                 diagonal weights; NOT in an update with a user dot product, an unaligned f, mvec > 32, the
+ *                                 out-of-place entry or a capture -- those write the missing v first, as do nka_hip_get_v and
+ *                                 nka_hip_clone; relax and restart discard it.  No result, state or stored vector differs.
  *   batched (nka_hip_batch.h)     none of the transports: single device, no hooks.  AUTO (reference order up to 64 elements, else
  *                                 BLOCKED_ROUNDED), BLOCKED_ROUNDED and REFERENCE_ORDER (any vlen up to the cap, mvec <= 32); BLOCKED, the
  *                                 user dot product, diagonal weights and the out-of-place entry are refused or absent; capturable

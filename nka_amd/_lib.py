@@ -188,6 +188,7 @@ DIAG_SIGNATURES = {
                                           C.POINTER(C.c_double), C.POINTER(C.c_float)]),
     "nka_hip_get_stamps": (C.c_int, [C.c_void_p, _dp]),
     "nka_hip_get_skip_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "nka_hip_get_defer_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "nka_hip_vec_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
 }
 _DIAG = None

@@ -119,6 +119,13 @@ struct nka_hip_state {
                               // -12.7 % at m = 31, -3.4 % at 29, -0.3 % at 23 (compact); -11 / -4.4 / -2.9 % in the src-F08 rounding
   int skip_last = -1;         // PA leaves out the vector a full list drops for capacity (nka_hip.hip, skip_last_applies): -1 automatic
                               // (from a vector length on), 0 never, 1 wherever the launch allows it (diagnostic switch "skip_last")
+  int defer_v = -1;           // PB leaves the pending pair's v unstored and the next PB replays it (nka_hip.hip, defer_v_applies;
+                              // k_combine_win, DEFER): -1 automatic (from a vector length on), 0 never, 1 wherever the launch
+                              // allows it (diagnostic switch "defer_v")
+  bool v_deferred = false;    // an update of this handle passed "may defer" and nothing has materialised the slot since: the
+                              // device may hold PC_VDEFER (the host never reads the word: ensure_v launches guarded kernels)
+  bool pb_defer = false;      // the update being enqueued is one that may defer: its scalar step writes the replay plan, its
+                              // PB is the DEFER instantiation
   int pa_skip = 0;            // the PA / final sums being enqueued: kSkipMay, kSkipRepair (nka_device.hpp) or 0
   bool state_in_global = false;  // mvec > 140: h, c and the links no longer fit the LDS of one CU; the one-lane
                                  // scalar kernels then work on the control block in global memory (slow, unlimited)

@@ -31,6 +31,18 @@ int nka_hip_get_skip_state(nka_hip_t a, int32_t out4[4]) {
   return 0;
 }
 
+// The deferred v of the pending pair as the device sees it: the word, and how many entries the last PB replayed (0: none).
+int nka_hip_get_defer_state(nka_hip_t a, int32_t out2[2]) {
+  if (!a || !out2) return fail(NKA_HIP_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(a->device));
+  long long w[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(w, a->ctl.pc + PC_VDEFER, sizeof w, hipMemcpyDeviceToHost, a->stream));
+  HIP_TRY(hipStreamSynchronize(a->stream));
+  out2[0] = (int32_t)w[0];
+  out2[1] = (int32_t)w[1];
+  return 0;
+}
+
 int nka_hip_set_grid(nka_hip_t a, int32_t pa, int32_t pb) {
   if (!a) return fail(NKA_HIP_EINVAL, "null handle");
   const int32_t v[2] = {pa, pb};
@@ -134,7 +146,10 @@ int nka_hip_set_tuning(nka_hip_t a, const char *key, int32_t value) {
   } else if (k == "skip_last") {      // -1 automatic (from a vector length on), 0 never, 1 wherever the launch allows it, at any n
     if (value < -1 || value > 1) return fail(NKA_HIP_EINVAL, "skip_last: -1, 0, 1");
     a->skip_last = value;
-  } else if (k == "chain_many") {     // -1 automatic, 0: one compute unit per reference-order sum at every length, 1: many wherever blocks exist
+  } else if (k == "defer_v") {        // -1 automatic (from a vector length on), 0 never, 1 wherever the launch allows it, at any n
+    if (value < -1 || value > 1) return fail(NKA_HIP_EINVAL, "defer_v: -1, 0, 1");
+    a->defer_v = value;
+  } else if (k == "chain_many") {    // -1 automatic, 0: one compute unit per reference-order sum at every length, 1: many wherever blocks exist
     if (value < -1 || value > 1) return fail(NKA_HIP_EINVAL, "chain_many: -1, 0, 1");
     a->chain_many = value;
   } else if (k == "chain_walk") {     // 1: the per-sum reference-order kernel walks every block (no summaries): same bits, for A/B

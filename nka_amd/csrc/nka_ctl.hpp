@@ -48,6 +48,13 @@ enum {
   PC_OLD_W = 3,    // what an out-of-place update displaced from that slot: handed to the caller /
   PC_OLD_V = 4,    //   kept as the library's next spare
   PC_WGT = 5,      // the diagonal dot-product weights of nka_hip_set_dot_weights (read by the WGT = true passes only)
+  // DEFERRED v OF THE PENDING PAIR (k_combine_win<.., DEFER = true>, nka_kernels.hpp).  The two words live here and not in the
+  // int32 header: that header is full, its length is part of the batch layouts, and a word in ic / dc would show in the state
+  // digest, which a deferring handle must share with one that never defers.
+  PC_VDEFER = 6,   // != 0: the v buffer of the pending pair does NOT hold f_out yet; f_out = w + sum c_k u_k over the combine plan
+                   //   as it stands (comb_v / comb_c / IC_NCOMB: nothing rewrites them before the next scalar step)
+  PC_VREPLAY = 7,  // written by the scalar step for ITS PB: 0 = v of the pending pair is in memory, np > 0 = form it from the np
+                   //   entries of the replay plan below
   PC_HEADER = 8
 };
 
@@ -79,7 +86,15 @@ struct Ctl {
   NKA_HOST_DEVICE long long *comb_v() const { return comb_w() + m1p(); }        // v of PB's pairs [m1p]
   NKA_HOST_DEVICE long long *wtab() const { return comb_v() + m1p(); }          // slot -> w buffer [m1+1], 1-based
   NKA_HOST_DEVICE long long *vtab() const { return wtab() + (m1() + 1); }       // slot -> v buffer [m1+1]
-  NKA_HOST_DEVICE constexpr int pc_count() const { return PC_HEADER + 3 * m1p() + 2 * (m1() + 1); }
+  // REPLAY PLAN (PC_VREPLAY): the combine plan of the update that deferred, in its list order -- entry j: the buffer of u_j, the
+  // coefficient it had THEN, the coefficient it has NOW -- and one word whose bit j says that entry j is still on the list.  The
+  // new plan minus the pending pair is a subsequence of the old one (drops keep the order), so this is all PB needs; a dropped
+  // entry is skipped, never multiplied by zero (-0 and non-finite values would change).
+  NKA_HOST_DEVICE long long *rp_v() const { return vtab() + (m1() + 1); }                                   // [m1p]
+  NKA_HOST_DEVICE double *rp_cprev() const { return reinterpret_cast<double *>(rp_v() + m1p()); }           // [m1p]
+  NKA_HOST_DEVICE double *rp_cnew() const { return rp_cprev() + m1p(); }                                    // [m1p]
+  NKA_HOST_DEVICE long long *rp_keep() const { return rp_v() + 3 * m1p(); }                                 // [1]
+  NKA_HOST_DEVICE constexpr int pc_count() const { return PC_HEADER + 3 * m1p() + 2 * (m1() + 1) + 3 * m1p() + 1; }
   // plan_slots / comb_slots / comb_c are padded by one pass width: the unrolled
   // kernels read (and ignore) entries up to the end of their last pass.
   NKA_HOST_DEVICE constexpr int m1() const { return mvec + 1; }

@@ -336,6 +336,19 @@ int launch_combine_w(int maxk, const nka_hip_state *a, double *f, int pass, int 
 // T = 16-byte pieces per thread, stream and tile (2 only for short lists, see launch_combine_win_k)
 template <int MAXK, int COMB, int W, int T = 1>
 int launch_combine_win_1(const nka_hip_state *a, double *f, int bpc, int base) {
+  if constexpr (COMB == 2) {
+    // an update that may defer the pending pair's v (update_impl: defer_v_applies): the same launch rules on the DEFER instantiation
+    if (a->pb_defer) {
+      static const int occ_d = occupancy_of(k_combine_win<MAXK, COMB, W, T, true>);
+      const int64_t ntile = a->n / (kBlock * 2 * T);
+      const int g = persistent_grid(a->num_cu, std::min(occ_d, std::max(1, bpc)), ntile);
+      const int ng = nka_host::ticket_counters(a->pb_tickets, a->tickets != nullptr, ntile, T, g, (MAXK + 2 + 5) * T);
+      const int tail = (ntile * (kBlock * 2 * T) < a->n) ? 1 : 0;
+      hipLaunchKernelGGL((k_combine_win<MAXK, COMB, W, T, true>), dim3(g + tail), dim3(kBlock), 0, a->stream, a->ctl, a->vs, f,
+                         ng > 0 ? a->tickets : nullptr, std::max(ng, 1), a->pb_flags | kPbMayDefer, base);
+      return g;
+    }
+  }
   static const int occ = occupancy_of(k_combine_win<MAXK, COMB, W, T>);
   const int64_t ntile = a->n / (kBlock * 2 * T);
   const int g = persistent_grid(a->num_cu, std::min(occ, std::max(1, bpc)), ntile);
@@ -688,6 +701,8 @@ int nka_hip_destroy(nka_hip_t a) {
   return 0;
 }
 
+static int ensure_v(nka_hip_t a, bool clear_only = false);      // (the deferred v of the pending pair: defined at update_impl)
+
 // The slot -> buffer tables as they stand on the device (synchronises).  t.wtab()[k], t.vtab()[k] for k = 1..mvec+1.
 static int fetch_tables(nka_hip_t a, std::vector<long long> &pc, Ctl &t) {
   pc.assign((size_t)a->ctl.pc_count(), 0);
@@ -714,6 +729,8 @@ static __global__ void k_plan_pointers_from_slots(Ctl ctl) {
 int nka_hip_clone(nka_hip_t src, nka_hip_t *out) {
   if (!src || !out) return fail(NKA_HIP_EINVAL, "nka_hip_clone: null argument");
   *out = nullptr;
+  HIP_TRY(hipSetDevice(src->device));
+  if (int rc = ensure_v(src)) return rc;      // (the copy takes the vectors as they lie in memory)
   nka_hip_t b = nullptr;
   if (int rc = nka_hip_create(&b, src->n, src->mvec, src->vtol, src->flavor, src->device, (void *)src->stream)) return rc;
   // same storage geometry by construction (n and mvec decide it)
@@ -764,6 +781,7 @@ int nka_hip_clone(nka_hip_t src, nka_hip_t *out) {
   b->pb_tickets = src->pb_tickets;
   b->prime_pad = src->prime_pad;
   b->skip_last = src->skip_last;
+  b->defer_v = src->defer_v;
   b->chain_walk = src->chain_walk;
   b->chain_many = src->chain_many;      // (the copy allocates its own block arrays when it needs them)
   b->chain_pred = nullptr; b->chain_summ = nullptr; b->chain_cap = 0;
@@ -806,6 +824,7 @@ int nka_hip_restart(nka_hip_t a) {
   if (!a) return fail(NKA_HIP_EINVAL, "null handle");
   if (a->poisoned) return fail(NKA_HIP_ESTATE, "restart: an earlier update failed after its scalar step had been enqueued: destroy the handle");
   HIP_TRY(hipSetDevice(a->device));
+  if (int rc = ensure_v(a, true)) return rc;      // (a deferred v dies with the list: only the word is cleared)
   hipLaunchKernelGGL(k_restart, dim3(1), dim3(kSolveThreads), a->state_in_global ? 0 : lst_smem_bytes(a->mvec), a->stream,
                      a->ctl, a->state_in_global ? 1 : 0);
   HIP_TRY(hipGetLastError());
@@ -820,6 +839,7 @@ int nka_hip_relax(nka_hip_t a) {
   if (!a) return fail(NKA_HIP_EINVAL, "null handle");
   if (a->poisoned) return fail(NKA_HIP_ESTATE, "relax: an earlier update failed after its scalar step had been enqueued: destroy the handle");
   HIP_TRY(hipSetDevice(a->device));
+  if (int rc = ensure_v(a, true)) return rc;      // (a deferred v is the pending pair's, which this drops: only the word is cleared)
   hipLaunchKernelGGL(k_relax, dim3(1), dim3(kSolveThreads), a->state_in_global ? 0 : lst_smem_bytes(a->mvec), a->stream,
                      a->ctl, a->state_in_global ? 1 : 0);
   HIP_TRY(hipGetLastError());
@@ -857,7 +877,7 @@ static int enqueue_solve(nka_hip_t a, int mode, long long swap_w = kNoBuffer, lo
     const long long id_stride = (a->swapped || a->captured) ? 0 : (long long)a->vs.stride, id_vbase = buffer_offset(a, a->vs.v);
 #define ROWS(NL) \
   hipLaunchKernelGGL((k_solve_rows<NL>), dim3(1), dim3(kSolveThreads), sm, s, a->ctl, mode, swap_w, swap_v, id_stride, id_vbase, x, \
-                     skip)
+                     skip, a->pb_defer ? 1 : 0)
     if (nl <= 6) ROWS(6);
     else if (nl <= 11) ROWS(11);
     else if (nl <= 21) ROWS(21);
@@ -1381,6 +1401,44 @@ static bool skip_last_applies(const nka_hip_state *a, SumsStage stage, int vec, 
   return a->skip_last > 0 || 8.0 * (double)a->n >= kSkipLastMinBytes;
 }
 
+// DEFERRED v OF THE PENDING PAIR (k_combine_win, DEFER; nka_ctl.hpp: PC_VDEFER).  May PB of this update leave v_new unstored,
+// and must its scalar step therefore hand it a replay plan?  The device decides whether it does (a plan to combine); the host
+// says whether the update is one that can: compact storage, in place, f 16-byte aligned, lists of <= 32, ONE launch of the
+// rolling-window PB with its tile tickets not switched off (automatic: where the tickets' own rule takes them), the
+// one-wavefront scalar step (it writes the replay plan), the library's own dot product, and no graph -- a replay would run the
+// update of the capture on a slot whose state the capture did not see.  An update that cannot starts with ensure_v.
+// Automatic from kDeferVMinBytes per vector on, by the rule of kSkipLastMinBytes: twice the smallest length at which deferring
+// was not slower in the in-process A/B at m = 20 (update, deferring minus not: n = 1e6: -0.1 us = equal, 3e6: -2.0 us,
+// 1e7: -3.4 us, 3e7: -35 us, 1e8: -134 us = -2.1 %; profiles/r22/ab_inproc.txt) -- and, like every other condition here, only
+// where the tickets' own automatic rule hands out the tiles, which at one block per CU is the longer of the two lengths.
+constexpr double kDeferVMinBytes = 1.6e7;
+static bool defer_v_applies(const nka_hip_state *a, int vec, long long swap_w, int comb_ub) {
+  if (a->defer_v == 0) return false;
+  if (a->flavor != NKA_HIP_FLAVOR_C || swap_w != kNoBuffer || vec != 2) return false;
+  if (a->mvec > kMaxPerPass || comb_ub > kMaxPerPass) return false;
+  if (a->captured || a->host_dot || a->serial_solve) return false;
+  if (a->pb_pipe != -1 && !(a->pb_pipe > 200 && a->pb_pipe < 210)) return false;
+  if (a->pb_tickets == 0 || !a->tickets) return false;
+  if (a->defer_v > 0) return true;
+  return pb_tickets_apply(a) && 8.0 * (double)a->n >= kDeferVMinBytes;
+}
+
+// Everything that reads, copies or depends on the v buffer of the pending pair calls this first: if an update has deferred that
+// v, it is written now (two guarded launches on the handle's stream; the host never reads the word back).  While the stream is
+// being captured the launches only go into the graph, so the host goes on assuming a deferred v.
+static int ensure_v(nka_hip_t a, bool clear_only) {
+  if (!a->v_deferred) return 0;
+  const int64_t nb = (a->n + kBlock - 1) / kBlock;
+  const int g = (int)std::max<int64_t>(1, std::min<int64_t>(nb, (int64_t)a->num_cu * 8));
+  if (!clear_only) hipLaunchKernelGGL(k_materialise_v, dim3(g), dim3(kBlock), 0, a->stream, a->ctl, a->vs, 0);
+  hipLaunchKernelGGL(k_materialise_v, dim3(1), dim3(64), 0, a->stream, a->ctl, a->vs, 1);
+  HIP_TRY(hipGetLastError());
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(a->stream, &cs) != hipSuccess) (void)hipGetLastError();
+  else if (cs == hipStreamCaptureStatusNone) a->v_deferred = false;
+  return 0;
+}
+
 int nka_hip_accel_update(nka_hip_t a, double *f) { return update_impl(a, f, kNoBuffer, kNoBuffer); }
 
 // One update.  swap_w / swap_v != kNoBuffer (offsets from vs.w): out of place (nka_hip_accel_update_swap) -- f (== swap_w)
@@ -1439,6 +1497,16 @@ static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_
   if (int rc = record(a, 0)) return rc;
   a->list_ub = list_bound_now(a);
   const int older_ub = a->pending ? std::max(a->list_ub - 1, 0) : a->list_ub;
+  const int comb_ub = a->pending ? std::min(a->list_ub, (int)a->mvec) : a->list_ub;
+  // may PB leave v_new to the next PB (defer_v_applies)?  An update that may not must find the pending pair's v in memory.
+  const bool defer = defer_v_applies(a, vec, swap_w, comb_ub);
+  if (!defer)
+    if (int rc = ensure_v(a)) return rc;
+  struct DeferScope {      // (the scalar steps and PB of THIS update only, whatever path leaves it)
+    nka_hip_state *a;
+    ~DeferScope() { a->pb_defer = false; }
+  } defer_scope{a};
+  a->pb_defer = defer;
 
   // ---- the inner products (F08:266-267, 286-290, 371): ONE function per way of forming them (round 6: update_impl used to
   // branch over all of them in line); each leaves the reduced sums in red[] -- or, with a user dot product, the whole scalar
@@ -1489,7 +1557,6 @@ static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_
   }
   if (int rc = record(a, 2)) return rc;
 
-  const int comb_ub = a->pending ? std::min(a->list_ub, (int)a->mvec) : a->list_ub;
   a->ctl.seq = (unsigned long long)(a->seq + 1);       // PB publishes (this number, list length at exit)
   {
     Ctl &c = a->ctl;
@@ -1501,6 +1568,7 @@ static int update_impl(nka_hip_t a, double *f, long long swap_w, long long swap_
     c.hw = hw;
     if (rc) return rc;
   }
+  if (defer) a->v_deferred = true;
   a->seq++;
   if (int rc = record(a, 3)) return rc;
 
@@ -1582,6 +1650,7 @@ int nka_hip_accel_update_swap(nka_hip_t a, double **f_io, const double **f_acc) 
   if (hipStreamIsCapturing(a->stream, &cs) != hipSuccess) (void)hipGetLastError();
   else if (cs != hipStreamCaptureStatusNone)
     return fail(NKA_HIP_ESTATE, "accel_update_swap: cannot be captured into a graph (the host chooses buffers per call)");
+  if (int rc = ensure_v(a)) return rc;
   if (int rc = collect_spares(a)) return rc;
   double *const in = *f_io, *const give_w = a->spare_w, *const vnew = a->spare_v;
   if (in && (in == give_w || in == vnew)) return fail(NKA_HIP_EINVAL, "accel_update_swap: that buffer is the library's own spare");
@@ -1721,6 +1790,13 @@ static int get_slot(nka_hip_t a, bool v, int32_t slot, double *host_out) {
   if (!a) return fail(NKA_HIP_EINVAL, "null handle");
   if (slot < 1 || slot > a->mvec + 1) return fail(NKA_HIP_EINVAL, "slot out of range");
   HIP_TRY(hipSetDevice(a->device));
+  if (v && a->v_deferred) {      // only the pending pair's v can be a deferred one (this entry synchronises anyway)
+    int32_t first = 0;
+    HIP_TRY(hipMemcpyAsync(&first, a->ctl.ic + IC_FIRST, sizeof first, hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    if (slot == first)
+      if (int rc = ensure_v(a)) return rc;
+  }
   std::vector<long long> pc;
   Ctl t{};
   if (a->swapped)

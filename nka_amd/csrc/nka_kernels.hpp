@@ -774,8 +774,9 @@ __global__ __launch_bounds__(64) void k_chain_apply(Ctl ctl, Vecs vs, const doub
 // w1' = (w1-f)/s, v1' = v1/s formed in registers and stored back.  The last pass
 // stores v_new = f_out.
 enum { kPbNoStoreW = 1, kPbNoStoreF = 2,     // `flags` of PB in an out-of-place update (nka_hip_accel_update_swap)
-       kPbNotFirst = 8, kPbNotLast = 16 };    // rolling-window PB over a list longer than kMaxPerPass: not the first / not the
+       kPbNotFirst = 8, kPbNotLast = 16,      // rolling-window PB over a list longer than kMaxPerPass: not the first / not the
                                               // last of its passes (enqueue_pb; in place only)
+       kPbMayDefer = 32 };                    // k_combine_win<.., DEFER = true> may leave v_new unstored (see there)
 
 template <int MAXK, int VEC, int COMB>
 __global__ __launch_bounds__(kBlock) void k_combine(Ctl ctl, Vecs vs, double *f, int pass, int last_pass, int flags) {
@@ -891,7 +892,202 @@ __global__ __launch_bounds__(kBlock) void k_combine(Ctl ctl, Vecs vs, double *f,
 // the pairs [base, base + MAXK) of the plan, f carrying the running value in between (the k loop of F08:395-399 cut into
 // consecutive pieces: same statements in the same order, same bits).  The FIRST pass (no kPbNotFirst) normalises the pending
 // pair -- pair 0 of the plan -- and stores w_new = f_in; the LAST (no kPbNotLast) stores v_new = f_out; every pass stores f.
-template <int MAXK, int COMB, int W, int T = 1>
+//
+// DEFERRED v OF THE PENDING PAIR (DEFER = true: compact storage, in place, one pass; chosen by the host, update_impl).  PB stores
+// the accelerated f twice, into the caller's f and into v_new, and v_new is read exactly once: by the next PB, to form
+// u1' = fl(v1/s) - w1'.  With kPbMayDefer in `flags` and a plan to combine, this instantiation leaves v_new UNSTORED and raises
+// PC_VDEFER.  The next update's scalar step then hands its PB -- this instantiation again, the host sees to that -- a replay
+// plan (Ctl::rp_v ...): the vectors and coefficients the missing v was combined from,
+//     v1 = w1 + c_prev,0 u_0 + c_prev,1 u_1 + ...     (w1 raw = the f_in of that update; list order; separate mul and add:
+//                                                      the statements that formed f_out, hence its bits)
+// and combine_win_replay below forms it while it streams the u_j -- the same vectors this update combines, plus those it has
+// just dropped, read in place of v1: one store less, no load more.  Everything that reads the slot otherwise first runs
+// k_materialise_v (host: ensure_v).  The other instantiations contain nothing of this.
+template <int MAXK, int W, int T>
+__device__ __forceinline__ void combine_win_replay(const Ctl &ctl, const Vecs &vs, double *f, unsigned *tickets, int ng, int flags,
+                                                   int np, unsigned *s_next) {
+  constexpr int VEC = 2;
+  using V = typename VecT<VEC>::type;
+  constexpr int TILE = kBlock * VEC * T;
+  const int64_t ntile = vs.n / TILE;
+  const bool has_tail = ntile * TILE < vs.n;
+  const int G = (int)gridDim.x - (has_tail ? 1 : 0);
+  const bool tail_block = has_tail && (int)blockIdx.x == G;
+  const int ncomb = ctl.ic[IC_NCOMB];                      // >= 1: entry 0 is the pending pair, normalised now
+  double *wnew = vs.w + ctl.pc[PC_NEW_W], *vnew = vs.w + ctl.pc[PC_NEW_V];
+  double *w1 = vs.w + ctl.comb_w()[0], *u1 = vs.w + ctl.comb_v()[0];
+  const double c0 = ctl.comb_c()[0];
+  const unsigned keep = (unsigned)ctl.rp_keep()[0];        // bit j: entry j of the replay plan is combined into f as well
+  const bool store_w = !(flags & kPbNoStoreW), store_f = !(flags & kPbNoStoreF);
+  const bool store_v = !((flags & kPbMayDefer) && ncomb > 0);
+  const double s = ctl.dc[DC_S];
+  // Both coefficient sets go through LDS into VGPRs: as uniform values they would want 4 MAXK SGPRs on top of the addresses.
+  __shared__ double s_cf[2 * MAXK];
+  for (int j = threadIdx.x; j < 2 * MAXK; j += kBlock) {
+    const int k = j < MAXK ? j : j - MAXK;
+    s_cf[j] = k < np ? (j < MAXK ? ctl.rp_cprev()[k] : ctl.rp_cnew()[k]) : 0.0;
+  }
+  __syncthreads();
+  double cp[MAXK], cn[MAXK];
+  const double *uk[MAXK];
+  long long slv[MAXK];
+#pragma unroll
+  for (int j = 0; j < MAXK; j++) {
+    cp[j] = s_cf[j];
+    cn[j] = s_cf[MAXK + j];
+    slv[j] = ctl.rp_v()[j];
+  }
+#pragma unroll
+  for (int j = 0; j < MAXK; j++) uk[j] = j < np ? vs.w + slv[j] : f;
+
+  const int lane_off = threadIdx.x * VEC;
+#define DEAD_OFF(live, off) ((live) ? (off) : (int64_t)lane_off)      // (dead ring slots: see k_combine_win)
+  V finv[T], w0v[T], rv[W][T];
+  int64_t t = tail_block ? ntile : (int64_t)blockIdx.x;
+  if (t < ntile) {
+    const int64_t e = t * TILE + lane_off;
+#pragma unroll
+    for (int q = 0; q < T; q++) {
+      finv[q] = ld<VEC>(f + e + q * (kBlock * VEC));
+      w0v[q] = ld<VEC>(w1 + e + q * (kBlock * VEC));
+    }
+#pragma unroll
+    for (int j = 0; j < W; j++)
+#pragma unroll
+      for (int q = 0; q < T; q++) rv[j][q] = ld<VEC>(uk[j] + DEAD_OFF(j < np, e) + q * (kBlock * VEC));
+  }
+  list_word_publish(ctl, ncomb, flags & kPbNoStoreW);
+  const unsigned grp = tickets ? blockIdx.x % (unsigned)ng : 0u;
+  unsigned *const my_ticket = tickets ? tickets + grp * kTicketStride : nullptr;
+  const unsigned ticket_base = tickets ? 2u * (unsigned)G / (unsigned)ng : 0u;
+  int64_t tnext = t + G;
+  unsigned par = 0;
+  while (t < ntile) {
+    const int64_t e = t * TILE + lane_off;
+    const bool more = tnext < ntile;
+    unsigned claimed = kNoTicket;
+    if (tickets && more && threadIdx.x == 0) claimed = ticket_request(my_ticket, ticket_base, (unsigned)ng, grp);
+    const int64_t tn = more ? tnext : t;
+    const int64_t en = tn * TILE + lane_off;
+    V fin[T], w0[T], v1[T], x[T], kept[MAXK][T];
+#pragma unroll
+    for (int q = 0; q < T; q++) {
+      fin[q] = finv[q];
+      w0[q] = w0v[q];
+      v1[q] = w0[q];
+      if (store_w) st(wnew + e + q * (kBlock * VEC), fin[q]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < T; q++) {
+      finv[q] = ld<VEC>(f + en + q * (kBlock * VEC));
+      w0v[q] = ld<VEC>(w1 + en + q * (kBlock * VEC));
+    }
+#pragma unroll
+    for (int j = 0; j < MAXK; j++) {
+#pragma unroll
+      for (int q = 0; q < T; q++) kept[j][q] = rv[j % W][q];
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int q = 0; q < T; q++) {
+        if (j + W < MAXK) rv[j % W][q] = ld<VEC>(uk[j + W] + DEAD_OFF(j + W < np, e) + q * (kBlock * VEC));
+        else rv[j % W][q] = ld<VEC>(uk[j + W - MAXK] + DEAD_OFF(j + W - MAXK < np, en) + q * (kBlock * VEC));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (j < np) {
+#pragma unroll
+        for (int q = 0; q < T; q++)
+#pragma unroll
+          for (int c = 0; c < VEC; c++) setc(v1[q], c, ex(v1[q], c) + cp[j] * ex(kept[j][q], c));
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < T; q++) {
+      V wn, un;
+#pragma unroll
+      for (int c = 0; c < VEC; c++) {
+        const double d = ex(w0[q], c) - ex(fin[q], c);
+        const double wq = d / s;
+        const double vq = ex(v1[q], c) / s;
+        setc(wn, c, wq);
+        setc(un, c, vq - wq);
+        setc(x[q], c, ex(fin[q], c) + c0 * (vq - wq));
+      }
+      st(w1 + e + q * (kBlock * VEC), wn);
+      st(u1 + e + q * (kBlock * VEC), un);
+    }
+#pragma unroll
+    for (int j = 0; j < MAXK; j++) {
+      if (j < np && ((keep >> j) & 1u)) {
+#pragma unroll
+        for (int q = 0; q < T; q++)
+#pragma unroll
+          for (int c = 0; c < VEC; c++) setc(x[q], c, ex(x[q], c) + cn[j] * ex(kept[j][q], c));
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < T; q++) {
+      if (store_v) st(vnew + e + q * (kBlock * VEC), x[q]);
+      if (store_f) st(f + e + q * (kBlock * VEC), x[q]);
+    }
+    const int64_t t2 = tickets ? ticket_publish(s_next, par, claimed, ntile) : tnext + G;
+    t = tnext;
+    tnext = t2;
+  }
+  if (tickets && !tail_block) ticket_finish(tickets, ng, G);
+  if (tail_block) {  // ragged tail, scalar
+    for (int64_t i = ntile * TILE + threadIdx.x; i < vs.n; i += kBlock) {
+      const double fin = f[i], w0 = w1[i];
+      double v1 = w0, kept[MAXK];
+#pragma unroll
+      for (int j = 0; j < MAXK; j++) {
+        kept[j] = 0.0;
+        if (j < np) {
+          kept[j] = uk[j][i];
+          v1 = v1 + cp[j] * kept[j];
+        }
+      }
+      const double d = w0 - fin;
+      const double wq = d / s;
+      const double vq = v1 / s;
+      const double un = vq - wq;
+      w1[i] = wq;
+      u1[i] = un;
+      double x = fin + c0 * un;
+#pragma unroll
+      for (int j = 0; j < MAXK; j++)
+        if (j < np && ((keep >> j) & 1u)) x = x + cn[j] * kept[j];
+      if (store_w) wnew[i] = fin;
+      if (store_v) vnew[i] = x;
+      if (store_f) f[i] = x;
+    }
+  }
+#undef DEAD_OFF
+}
+
+// v of the pending pair where an update has deferred it (PC_VDEFER; returns at once where none has, like the repair launches
+// of the skipped last vector): f_out = f_in + c_0 u_0 + c_1 u_1 + ... with the statements of PB in PB's order, from the
+// combine plan as that update left it.  `clear` != 0: a second launch behind the first that only clears the word (no block of
+// the first may find it clear while another still streams); relax and restart launch that one alone.
+__global__ __launch_bounds__(kBlock) void k_materialise_v(Ctl ctl, Vecs vs, int clear) {
+  if (ctl.pc[PC_VDEFER] == 0) return;
+  if (clear) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl.pc[PC_VDEFER] = 0;
+    return;
+  }
+  const int ncomb = ctl.ic[IC_NCOMB];
+  const double *w = vs.w + ctl.pc[PC_NEW_W];
+  double *v = vs.w + ctl.pc[PC_NEW_V];
+  const long long *cv = ctl.comb_v();
+  const double *cc = ctl.comb_c();
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < vs.n; i += (int64_t)gridDim.x * kBlock) {
+    double x = w[i];
+    for (int j = 0; j < ncomb; j++) x = x + cc[j] * (vs.w + cv[j])[i];
+    v[i] = x;
+  }
+}
+
+template <int MAXK, int COMB, int W, int T = 1, bool DEFER = false>
 __global__ __launch_bounds__(kBlock) void k_combine_win(Ctl ctl, Vecs vs, double *f, unsigned *tickets, int ng, int flags,
                                                         int base) {
   // T = 16-byte pieces per thread, stream and tile (tile = 512*T elements, 4*T KiB per stream and
@@ -921,8 +1117,18 @@ __global__ __launch_bounds__(kBlock) void k_combine_win(Ctl ctl, Vecs vs, double
   // (uniform: out-of-place update.  The two scalar branches around the stores cost the in-place path nothing measurable:
   //  interleaved A/B against a build with unconditional stores, profiles/r04/ab_pb_flags.txt)
   const bool first_pass = !(flags & kPbNotFirst), last_pass = !(flags & kPbNotLast);
-  const bool store_w = !(flags & kPbNoStoreW) && first_pass, store_f = !(flags & kPbNoStoreF), store_v = last_pass;
+  const bool store_w = !(flags & kPbNoStoreW) && first_pass, store_f = !(flags & kPbNoStoreF);
+  const bool store_v = last_pass && !(DEFER && (flags & kPbMayDefer) && ncomb_all > 0);
   const bool norm0 = first_pass && ctl.ic[IC_NORMED] != 0;
+  if constexpr (DEFER) {
+    static_assert(COMPACT, "the deferred v exists for compact storage only");
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl.pc[PC_VDEFER] = store_v ? 0 : 1;      // (nothing in this launch reads the word)
+    const int np = norm0 ? (int)ctl.pc[PC_VREPLAY] : 0;
+    if (np > 0) {                                // (uniform) the pending pair's v was deferred: form it on the way
+      combine_win_replay<MAXK, W, T>(ctl, vs, f, tickets, ng, flags, np, s_next);
+      return;
+    }
+  }
   const double s = ctl.dc[DC_S];
   const double rs = 1.0 / s;
 
@@ -1214,10 +1420,20 @@ __host__ __device__ inline size_t solve_wave_smem_bytes(int mvec) {
 // l_q = readlane(l, q) -- lanes p <= q update entries nobody reads.
 template <int NLMAX>
 __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode, long long swap_w, long long swap_v,
-                                                              long long id_stride, long long id_vbase, P2P x, int skip) {
+                                                              long long id_stride, long long id_vbase, P2P x, int skip, int vd) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x;
   if (skip_repair_idle(ctl, skip)) return;     // (the second scalar step of an update that skipped: nothing to repair)
+  // `vd`: the PB behind this step is the instantiation that can replay a deferred v (k_combine_win, DEFER): this step tells it
+  // whether to (PC_VREPLAY) and writes the replay plan.  Lane p holds what entry p - 1 of the OLD combine plan was combined
+  // with -- the old plan IS this update's list of older entries, position p -- before the new plan overwrites it.
+  const bool vd_in = vd != 0 && ctl.pc[PC_VDEFER] != 0;
+  double vd_cprev = 0.0;
+  long long vd_v = 0;
+  if (vd != 0 && lane >= 1 && lane <= ctl.mvec) {
+    vd_cprev = ctl.comb_c()[lane - 1];
+    vd_v = ctl.comb_v()[lane - 1];
+  }
   // peer-to-peer exchange: wait for the rows of all ranks and add them in rank order (P2P above); red[] then holds the
   // global sums like after an all-reduce (lane e reads back below what it has just written itself)
   if (x.base != nullptr) p2p_gather_block(x, ctl.red(), ctl.red_count());
@@ -1485,6 +1701,11 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
       ctl.plan_w()[r] = wb;
       L.c[myord] = yr;
     }
+    if (vd_in && lane >= 1 && lane < nl) {      // the replay plan: position `lane` of this list was entry lane - 1 of the old plan
+      ctl.rp_v()[lane - 1] = vd_v;
+      ctl.rp_cprev()[lane - 1] = vd_cprev;
+      ctl.rp_cnew()[lane - 1] = yr;             // (of a dropped position: never read, rp_keep)
+    }
   } else if (L.subspace) {
     // no new pair this call (after relax / s == 0): substitute on the stored factor
     for (int k = L.first; k != 0; k = L.next[k]) ord[nk++] = k;
@@ -1545,6 +1766,13 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_rows(Ctl ctl, int mode,
     }
     ctl.ic[IC_SKIP_HOLD] = hold;
     ctl.ic[IC_PLAN_SKIP] = hold == 0 ? 1 : 0;
+    if (vd != 0) {
+      // a deferred v is replayed by the PB behind this step when the pending pair is normalised now; where s == 0 has dropped
+      // the pair (F08:275) nobody needs its v any more.  Either way the word is clear until that PB defers again.
+      ctl.pc[PC_VREPLAY] = (vd_in && normed) ? nl - 1 : 0;
+      ctl.rp_keep()[0] = (long long)((alive & listmask) >> 1);
+      ctl.pc[PC_VDEFER] = 0;
+    }
   }
   NKA_STAMP(ctl, 9);
 }

@@ -490,6 +490,14 @@ class nka:  # noqa: N801  (the reference's type name)
         _check(self._L.nka_hip_get_skip_state(self._handle(), out), "get_skip_state", self._L)
         return tuple(out)
 
+    def defer_state(self):
+        """The deferred v of the pending pair as the device holds it (nka_hip_get_defer_state, include/nka_hip_diag.h):
+        (the pending pair's v is not in memory, entries the last combine replayed to form it).  Materialises nothing."""
+        self._need_diag("defer_state")
+        out = (C.c_int32 * 2)()
+        _check(self._L.nka_hip_get_defer_state(self._handle(), out), "get_defer_state", self._L)
+        return tuple(out)
+
     def debug_chain_sum(self, x, y, start: float = 0.0, walk: bool = False, many: bool = False):
         """start + x[0]*y[0] + x[1]*y[1] + ... formed by the reference-order kernel of long vectors over two device
         tensors (nka_hip_debug_chain_sum, include/nka_hip_diag.h); many: through the many-compute-unit kernels.  Returns
