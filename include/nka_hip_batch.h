@@ -171,7 +171,8 @@
  *            faster (2.45 x at 16 systems, 1.14 / 1.04 x at 256); both have the step (the wide one through
  *            nka_hip_batch_create_wide_step) and the weights (the wide one through nka_hip_batch_create_wide_ext: WIDE EXT below), and only the batch above has the reference order.  FOUR systems: the wide batch wins at mvec = 10 (1.05 ... 1.95 x) and LOSES to four lone handles at
  *            mvec = 20 at every length (0.67 ... 0.86 x): the scalar step of a system runs on one thread, 127 us at mvec = 20 (59 %
- *            of an update at 16 x 65 536), and a lone handle's does not.  A lone system stays with a lone handle.
+ *            of an update at 16 x 65 536), and a lone handle's does not (SCALAR STEP below: the opt-in that runs it on one wavefront,
+ *            and what the loss becomes with it).  A lone system stays with a lone handle.
  *   LENGTHS  nka_hip_batch_set_lengths: RAGGED BATCHES without padding weights, on both kinds of batch.  System `sys` is
  *            len[sys] elements long, 1 <= len[sys] <= vlen, in EVERY phase of accel_update and accel_step: the norm and the
  *            other sums in either order, the step's dp(f, f) and x -= f_out, the weight loads, the combine and the ring stores.
@@ -409,8 +410,46 @@
  *            binary64 batches differing by 2.3 % and 2.6 %; the byte model of STORAGE predicts 0.69 and 0.65.  From 64 systems on
  *            0.65 ... 0.81 at every point (0.78 / 0.81 at 64 x 32 768, 0.69 / 0.65 at 64 x 262 144, 0.69 at 256 x 262 144 x 10); at
  *            16 systems 0.99 / 0.98 at 32 768, 0.86 / 0.85 at 65 536 and 0.75 / 0.77 at 262 144 (there the scalar step on one thread
- *            is a large share of a call); a step with x, mask, tol and fnorm at 64 x 65 536 x 20: 0.75.  Faster by more than the
+ *            is a large share of a call: SCALAR STEP below); a step with x, mask, tol and fnorm at 64 x 65 536 x 20: 0.75.  Faster by more than the
  *            control's difference and the window spread at all 18 points.  One measurement.
+ *   SCALAR STEP  nka_hip_batch_set_scalar_step: an OPT-IN choice of how a wide batch runs the third of its four launches -- the
+ *            Gram row, the Cholesky factor with its drop decisions, both substitutions and the combine plan of a system.
+ *            NKA_HIP_BATCH_SCALAR_ONE_THREAD, the default: one thread runs the reference's loops, an O(mvec^3) chain of dependent LDS
+ *            round trips; a batch that never calls the setter launches exactly the kernels it always did.
+ *            NKA_HIP_BATCH_SCALAR_WAVEFRONT: the same arithmetic on ONE WAVEFRONT, the way k_solve_rows does it for a lone handle
+ *            -- lane p holds row p of the position-indexed Gram matrix in registers, the factorisation is right-looking, pivots and
+ *            column entries travel by v_readlane, the right-hand side rides along as one more row, the back-substitution runs by
+ *            columns -- in about mvec sequential steps.  Every entry receives the subtractions of the reference's inner loop in the
+ *            same order and then the same division (no contraction: every a - l l_q is two roundings), and the debris is the
+ *            one-thread step's too: the row of a dependence-dropped entry is stored at the kept columns ahead of it and its
+ *            diagonal never, the row of the capacity-dropped entry is not touched, c of a dropped entry keeps the raw right-hand
+ *            side, the drops reach the free list in list order, a NaN pivot drops, the last position of a full list is evaluated
+ *            by its pivot once an entry ahead of it was dropped; without a new pair (the first update, after relax or restart, s ==
+ *            0) one lane runs the one-thread statements.  So BOTH STEPS LEAVE THE SAME BITS -- f, x, fnorm, the mask, red[], all of
+ *            h and c, the lists, the counters, nka_hip_batch_state_digest, every stored vector -- and SWITCHING BETWEEN CALLS CHANGES
+ *            NO RESULT.  The setter is enqueue-side state: no synchronisation, no allocation (the matrix lives in dynamic LDS,
+ *            13.0 KiB at mvec = 20 and 24.0 KiB at 32 with 512 chunks), no new creation entry; it applies from the next accel_update /
+ *            accel_step on, and a captured call keeps the step it was captured with.  The instance is chosen from mvec (6 / 11 / 21 /
+ *            33 rows), fixed at creation.  Within the launch no workgroup reads what another writes: no flags, no spinning, no
+ *            atomics, no cooperative launch.  Offered by every wide batch (all five wide creation entries, both storages, with
+ *            lengths, weights and the step: the third launch reads neither weights nor stored vectors); NKA_HIP_EINVAL, the batch
+ *            staying usable, for any other value and for _WAVEFRONT on a narrow, lane or wave batch (_ONE_THREAD is accepted
+ *            everywhere; nka_hip_batch_offers_scalar_step tells them apart).
+ *            MEASURED (profiles/r22/batch_wide_rows_throughput.txt, tools/batch_throughput.py --wide-rows: a one-thread batch a, a
+ *            second one a' as the control, the wavefront batch b, alternated on the same inputs, windows >= 0.5 s, median of 5; nsys
+ *            4 / 16 / 64 / 256 x vlen 32 768 / 65 536 / 262 144 x mvec 5 / 10 / 20 / 32, default flavour, full lists; 256 x 262 144
+ *            at mvec >= 10 needs more than 40 GB and was not measured).  THE CONDITION, fixed beforehand -- at 16 x 65 536 x 20, a - b
+ *            > |a - a'| plus the largest window spread -- HELD: 249.7 -> 111.4 us, b/a = 0.446 (|a - a'|/a = 0.002); the third launch
+ *            itself 154.6 -> 16.8 us in a kernel trace of its own.  b/a at 16 systems: 0.89 / 0.67 / 0.33 / 0.18 at 32 768 (mvec 5 /
+ *            10 / 20 / 32), 0.92 / 0.74 / 0.45 / 0.25 at 65 536, 0.96 / 0.91 / 0.72 / 0.53 at 262 144; a step with x, mask, tol and
+ *            fnorm at 16 x 65 536 x 20: 0.453.  The gain shrinks as the other three launches grow: at 256 systems 0.97 / 0.92 / 0.82 /
+ *            0.69 at 32 768 and 0.99 / 1.00 / 0.96 / 0.77 at 65 536.  Won (by more than the control's difference and the window
+ *            spread) at 40 of the 46 measured points (the step among them), lost at none; inside the noise at 256 x 65 536 x 10 and x 20 and at 64 / 256 x 262 144 x 5,
+ *            64 x 262 144 x 10 and x 20.  FOUR systems at mvec = 20, where WIDE records a loss to four lone handles: the loop over
+ *            four lone handles takes 0.69 / 0.74 / 0.83 of the one-thread batch's time at 32 768 / 65 536 / 262 144 and 2.25 / 2.29 /
+ *            1.76 x the wavefront batch's -- with the opt-in the batch no longer loses.  One measurement; the default stays
+ *            _ONE_THREAD.  Not covered: the narrow batch, whose scalar step sits inside its one kernel (48 instances held to their
+ *            machine code), the wave batch and the lane batch keep the one-thread (one-lane) step -- follow-ups.
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -516,6 +555,17 @@ int nka_hip_batch_relax(nka_hip_batch_t b, const int32_t *active_dev);
 /* call a%set_vec_tol(vtol) for ALL systems (F08:202-207); stream-ordered like the updates around it. */
 int nka_hip_batch_set_vec_tol(nka_hip_batch_t b, double vtol);
 int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order);
+/* SCALAR STEP above: how a wide batch runs the third launch of an update or step.  _set_scalar_step changes enqueue-side state only
+ * (no synchronisation, no allocation, legal while the stream is capturing) and applies from the next accel_update / accel_step on; a
+ * captured call keeps the step it was captured with.  Both steps leave the same bits, so switching between calls changes no
+ * result.  NKA_HIP_EINVAL, the batch staying usable and its setting unchanged: any value but the two below; _WAVEFRONT on a batch
+ * that does not offer it (_ONE_THREAD is accepted by every batch).  _scalar_step: the value the next call runs with (default
+ * _ONE_THREAD); < 0 on error.  _offers_scalar_step: 1 = every wide batch (all five wide creation entries, both storages); 0 =
+ * narrow, lanes, waves; < 0 on error. */
+enum { NKA_HIP_BATCH_SCALAR_ONE_THREAD = 0, NKA_HIP_BATCH_SCALAR_WAVEFRONT = 1 };
+int nka_hip_batch_set_scalar_step(nka_hip_batch_t b, int32_t how);
+int nka_hip_batch_scalar_step(nka_hip_batch_t b);
+int nka_hip_batch_offers_scalar_step(nka_hip_batch_t b);
 /* DIAGONAL WEIGHTS (WEIGHTS above), as nka_hip_set_dot_weights of a lone handle, per system:
  *   ldw >= vlen  nsys rows of ldw doubles, row `sys` weights system `sys`; what lies between two rows is never read
  *   ldw == 0     ONE row of vlen doubles that all systems share

@@ -15,4 +15,4 @@ from ._lib import build, lib_path, load  # noqa: F401
 from .nka import (FLAVOR_C, FLAVOR_DEFAULT, FLAVOR_F08, FLAVOR_F08_VECTOR, SUMS_AUTO, SUMS_BLOCKED, SUMS_BLOCKED_ROUNDED,  # noqa: F401
                   SUMS_REFERENCE_ORDER, NKAError, nka)
 from .batch import (BATCH_LANES_MAX_VLEN, BATCH_MAX_MVEC, BATCH_MAX_VLEN, KIND_LANES, KIND_NARROW, KIND_WAVES, KIND_WIDE,  # noqa: F401
-                    STORE_F32, STORE_F64, batch_lanes_limits, batch_waves_limits, batch_wide_limits, nka_batch)
+                    SCALAR_ONE_THREAD, SCALAR_WAVEFRONT, STORE_F32, STORE_F64, batch_lanes_limits, batch_waves_limits, batch_wide_limits, nka_batch)

@@ -161,6 +161,9 @@ BATCH_SIGNATURES = {
     "nka_hip_batch_relax": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nka_hip_batch_set_vec_tol": (C.c_int, [C.c_void_p, C.c_double]),
     "nka_hip_batch_set_sum_order": (C.c_int, [C.c_void_p, C.c_int32]),
+    "nka_hip_batch_set_scalar_step": (C.c_int, [C.c_void_p, C.c_int32]),
+    "nka_hip_batch_scalar_step": (C.c_int, [C.c_void_p]),
+    "nka_hip_batch_offers_scalar_step": (C.c_int, [C.c_void_p]),
     "nka_hip_batch_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nka_hip_batch_set_dot_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "nka_hip_batch_set_dot_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -14,6 +14,7 @@ from .nka import FLAVOR_DEFAULT, NKAError, State, _check
 
 BATCH_MAX_VLEN, BATCH_MAX_MVEC = 16384, 32      # NKA_HIP_BATCH_MAX_VLEN / _MVEC (include/nka_hip_batch.h)
 STORE_F64, STORE_F32 = 0, 1                     # NKA_HIP_BATCH_STORE_F64 / _F32 (include/nka_hip_batch.h, STORAGE)
+SCALAR_ONE_THREAD, SCALAR_WAVEFRONT = 0, 1      # NKA_HIP_BATCH_SCALAR_ONE_THREAD / _WAVEFRONT (include/nka_hip_batch.h, SCALAR STEP)
 
 
 def batch_wide_limits():
@@ -271,6 +272,29 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         SUMS_AUTO is SUMS_BLOCKED_ROUNDED at every length.  Returns self."""
         _check(self._L.nka_hip_batch_set_sum_order(self._handle(), int(order)), "batch_set_sum_order", self._L)
         return self
+
+    def set_scalar_step(self, how: int):
+        """SCALAR_ONE_THREAD (the default) or SCALAR_WAVEFRONT: how a wide batch runs the third launch of an update or step
+        (include/nka_hip_batch.h, SCALAR STEP) -- the Gram row, the Cholesky with its drop decisions, both substitutions and the
+        combine plan on one thread, or the same arithmetic spread over one wavefront.  Both leave the same bits, so switching
+        between calls changes no result.  Enqueue-side state only: no synchronisation, no allocation; applies from the next
+        accel_update / accel_step on, and a captured call keeps the step it was captured with.  SCALAR_WAVEFRONT on a batch that
+        does not offer it (offers_scalar_step()) and any other value raise NKAError and the batch stays usable.  Returns self."""
+        _check(self._L.nka_hip_batch_set_scalar_step(self._handle(), int(how)), "batch_set_scalar_step", self._L)
+        return self
+
+    def scalar_step(self) -> int:
+        """SCALAR_ONE_THREAD or SCALAR_WAVEFRONT: what the next call runs with (nka_hip_batch_scalar_step)."""
+        r = self._L.nka_hip_batch_scalar_step(self._handle())
+        _check(min(r, 0), "batch_scalar_step", self._L)
+        return r
+
+    def offers_scalar_step(self) -> bool:
+        """True where set_scalar_step(SCALAR_WAVEFRONT) is offered: every wide batch, with or without step=True, ext=True or
+        wide_storage=STORE_F32 (nka_hip_batch_offers_scalar_step)."""
+        r = self._L.nka_hip_batch_offers_scalar_step(self._handle())
+        _check(min(r, 0), "batch_offers_scalar_step", self._L)
+        return bool(r)
 
     def set_dot_weights(self, w):
         """Diagonal weights of the dot product, <x,y>_w = sum_i w_i x_i y_i per system (include/nka_hip_batch.h, WEIGHTS): a

@@ -417,5 +417,23 @@ NKA_HOST_DEVICE constexpr WideScalarLds wide_scalar_lds(int mvec, int nchunk) {
   l.b.ndouble += nchunk;
   return l;
 }
+// ... and of its instances that run the scalar step on one wavefront (nka_hip_batch_set_scalar_step; batch_scalar_step_rows of
+// nka_batch_dev.hpp): the same pieces, then the dense position-indexed matrix with its right-hand-side row, a [(m1+1)^2], behind
+// the stage.  13.0 KiB at mvec = 20 and 24.0 KiB at 32 with 512 chunks, 28.0 KiB with 1024: below the 64 KiB a launch may ask for
+// without a function attribute.  tests/c/batch_wide_rows_layout_check.cpp paints every piece.
+constexpr int kWideRowsMaxList = 33;                      // the longest list the wavefront step holds in registers: mvec + 1 <= 33
+struct WideScalarRowsLds {
+  BatchLds b;      // (b.ndouble counts the stage and the matrix too: the int32 pieces start behind them)
+  int stage, a;
+};
+NKA_HOST_DEVICE constexpr WideScalarRowsLds wide_scalar_rows_lds(int mvec, int nchunk) {
+  WideScalarRowsLds l{batch_lds(mvec), 0, 0};
+  l.stage = l.b.ndouble;
+  l.a = l.stage + nchunk;
+  l.b.ndouble = l.a + (mvec + 2) * (mvec + 2);
+  return l;
+}
+// the instance of the wavefront step for a batch of `mvec`: the smallest of 6 / 11 / 21 / 33 rows that holds mvec + 1
+NKA_HOST_DEVICE constexpr int wide_rows_nlmax(int mvec) { return mvec + 1 <= 6 ? 6 : mvec + 1 <= 11 ? 11 : mvec + 1 <= 21 ? 21 : kWideRowsMaxList; }
 
 }  // namespace nka_host

@@ -937,6 +937,22 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
   return 0;
 }
 
+// SCALAR STEP: enqueue-side state of a wide batch, read by launch_wide (nka_batch_wide.hip) when a call is enqueued
+int nka_hip_batch_offers_scalar_step(nka_hip_batch_t b) {
+  return b ? (b->wide ? 1 : 0) : fail(NKA_HIP_EINVAL, "batch_offers_scalar_step: null handle");
+}
+int nka_hip_batch_scalar_step(nka_hip_batch_t b) { return b ? b->scalar_step : fail(NKA_HIP_EINVAL, "batch_scalar_step: null handle"); }
+int nka_hip_batch_set_scalar_step(nka_hip_batch_t b, int32_t how) {
+  if (!b) return fail(NKA_HIP_EINVAL, "batch_set_scalar_step: null handle");
+  if (how != NKA_HIP_BATCH_SCALAR_ONE_THREAD && how != NKA_HIP_BATCH_SCALAR_WAVEFRONT)
+    return fail(NKA_HIP_EINVAL, "batch_set_scalar_step: NKA_HIP_BATCH_SCALAR_ONE_THREAD or NKA_HIP_BATCH_SCALAR_WAVEFRONT");
+  if (how == NKA_HIP_BATCH_SCALAR_WAVEFRONT && !b->wide)
+    return fail(NKA_HIP_EINVAL, "batch_set_scalar_step: NKA_HIP_BATCH_SCALAR_WAVEFRONT is offered by a wide batch only (nka_hip_batch_create_wide "
+                                "and its four siblings): this batch keeps NKA_HIP_BATCH_SCALAR_ONE_THREAD");
+  b->scalar_step = how;
+  return 0;
+}
+
 int nka_hip_batch_set_dot_weights(nka_hip_batch_t b, const double *w_dev, int64_t ldw) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: null handle");
   if (b->wide && !b->wide_ext) return fail(NKA_HIP_EINVAL, "batch_set_dot_weights: not offered by a wide batch (nka_hip_batch_create_wide)");

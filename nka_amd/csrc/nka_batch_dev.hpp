@@ -200,6 +200,185 @@ __device__ __forceinline__ void batch_scalar_step(Lst &L, const Ctl &ctl, double
   ctl.ic[IC_NRELAX] = nrelax;
 }
 
+// one lane's LDS traffic ordered against the other lanes' of the SAME wavefront: the LDS serves a wavefront's instructions in the
+// order they were issued, so what is left is to keep the compiler from moving an access across this point (wave_sync of
+// nka_batch_waves.hip: a release fence, wave_barrier, an acquire fence, all at wavefront scope)
+__device__ __forceinline__ void batch_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// THE SAME SCALAR STEP ON ONE WAVEFRONT (nka_hip_batch.h, SCALAR STEP): called by ALL 64 LANES of one wavefront on a working copy
+// in LDS; L's scalars need be valid in lane 0 only (they are broadcast), s, nolder, mvec and every pointer are uniform.  What it
+// leaves -- L.h, L.c, the links, the five scalars, cs, cc, hdr and the control-block words -- is BIT FOR BIT what
+// batch_scalar_step leaves on the same inputs.  Wavefront-level means only (batch_wave_sync, readlane): no __syncthreads().
+//   The algorithm is phases 0-3 of k_solve_rows (nka_kernels.hpp): lane p holds row p of the position-indexed Gram matrix in
+// 2 NLMAX registers (NLMAX >= 1 + nolder), the right-hand side rides along as row nl, the Cholesky is right-looking -- at column i
+// the pivot of position i is final, the column is scaled by one division a lane and every trailing entry (p, q) gets a(p,q) -=
+// l_p l_q with l_q by v_readlane -- so every entry receives the subtractions of lst_factor's inner loop in the same order and then
+// the same division; the back-substitution is column-oriented in the same way.  ~m sequential steps instead of ~m^3 / 3.
+//   What the lone handle's kernel does not do and the one-thread step does -- nka_hip_batch_get_state and _state_digest cover
+// all of h and c, so the debris is part of the contract:
+//   * a DEPENDENCE-DROPPED row k is stored: lst_factor writes H(k, j) for every kept j ahead of k before it decides, and never
+//     H(k, k); the row of the CAPACITY-DROPPED entry is not touched at all;
+//   * c[ps[p]] = red[2 + mvec + p] is written RAW for every older entry, dropped ones too; only kept entries are overwritten by
+//     the substitutions (row nl holds partially updated values at dropped positions: they never reach c);
+//   * H(first, ps[p]) = red[2 + p] for every p < nolder;
+//   * the drops replay in list order (capacity F08:303-307, dependence F08:331-340, each pushed on the head of the free list);
+//     the pivot test is hkk > vtol * vtol, a NaN compares false and drops; after a dependence drop the last position of a full
+//     list is evaluated by its pivot (kept + 1 > mvec is lst_factor's nvec > mvec).
+//   Without a new pair (no pending pair, or s == 0, which relaxes) there is nothing to factor: lane 0 runs batch_scalar_step
+// itself under a wavefront-uniform branch.  A: LDS scratch of (m1 + 1) x (m1 + 1) doubles, rows LDA = m1 + 1 apart (the factor by
+// position for the column reads of the back-substitution, row nl the forward-substituted right-hand side; the last word takes
+// what must not reach h).
+template <int NLMAX>
+__device__ __forceinline__ void batch_scalar_step_rows(Lst &L, const Ctl &ctl, double s, int nolder, int mvec, const int32_t *ps,
+                                                       const double *red, int32_t *cs, double *cc, int32_t *hdr, double *A) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  L.pending = __builtin_amdgcn_readfirstlane(L.pending);
+  if (!(L.pending && s != 0.0)) {      // (uniform) the rare paths: bit-equal by construction
+    if (lane == 0) batch_scalar_step(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr);
+    return;
+  }
+  L.subspace = __builtin_amdgcn_readfirstlane(L.subspace);
+  L.first = __builtin_amdgcn_readfirstlane(L.first);
+  L.last = __builtin_amdgcn_readfirstlane(L.last);
+  L.free_ = __builtin_amdgcn_readfirstlane(L.free_);
+  L.vtol = readlane_f64(L.vtol, 0);
+  const int NL = L.m1, LDA = NL + 1;
+  const int entry_first = L.first;
+  const int nl = 1 + nolder;      // the list at entry: the pending entry, then ps[0 ... nolder - 1]; nl <= m1 <= NLMAX
+  const double vtol2 = L.vtol * L.vtol;
+  // ---- phase 0: the Gram row of w1' (F08:286-290) and the raw right-hand sides (F08:371), every older entry
+  if (lane == 0) {
+    ctl.dc[DC_S] = s;
+    L.H(entry_first, entry_first) = 1.0;      // F08:295
+    L.c[entry_first] = red[1];
+  }
+  if (lane < nolder) {
+    L.H(entry_first, ps[lane]) = red[2 + lane];
+    L.c[ps[lane]] = red[2 + mvec + lane];
+  }
+  const int myord = lane == 0 ? entry_first : (lane <= nolder ? ps[lane - 1] : 0);      // slot of list position `lane`
+  batch_wave_sync();
+  const uint64_t listmask = (1ull << nl) - 1;      // (nl <= 33)
+  uint64_t alive = listmask;
+  int capdrop = -1;
+  double ddr = 1.0;    // lane p: running pivot 1 - sum l^2 of list position p
+  double Ldr = 1.0;    // lane p: accepted pivot sqrt(hkk)
+  // ---- phase 1: right-looking Cholesky with drops (F08:295-347) on rows 0 ... nl - 1, the right-hand side as row nl
+  double a[NLMAX];
+#pragma unroll
+  for (int q = 0; q < NLMAX; q++) {
+    const int oq = __builtin_amdgcn_readlane(myord, q);      // slot of list position q (0 beyond the list)
+    a[q] = (lane < nl) ? L.H(oq, myord)                      // raw <w_q, w_p>, q newer (used for q < p only)
+                       : L.c[oq];                            // row nl: <f, w_q>
+  }
+  int kept = 0;
+  bool open_ = true;      // false once the capacity drop has ended the list (F08:309)
+#pragma unroll
+  for (int i = 0; i < NLMAX; i++) {      // (constant trip counts, guards instead of break: both loops unroll completely)
+    bool keep = false;
+    double Lii = 1.0;
+    if (open_ && i < nl) {
+      if (i == 0) {
+        keep = true;
+      } else if (kept + 1 > mvec) {
+        capdrop = i;      // F08:301-308: i is the last entry
+        open_ = false;
+      } else {
+        const double hkk = readlane_f64(ddr, i);
+        keep = hkk > vtol2;      // F08:326
+        if (keep) Lii = sqrt(hkk);
+      }
+      if (!keep) alive &= ~(1ull << i);
+    }
+    if (keep) {
+      kept++;
+      if (lane == i) Ldr = Lii;
+      const double l = a[i] / Lii;      // F08:320 (row nl: F08:377); rows <= i: unused
+      a[i] = l;
+      if (lane > i && lane < nl) ddr = ddr - l * l;      // F08:321
+#pragma unroll
+      for (int q = i + 1; q < NLMAX; q++) a[q] = a[q] - l * readlane_f64(l, q);      // F08:317 (row nl: F08:374)
+    }
+  }
+  // ---- phase 2: the rows back by slot -- of a kept AND of a dependence-dropped position its entries at the kept columns ahead
+  // of it, of the capacity-dropped position nothing --, and by position into A; the drops in list order
+  {
+    double *const dump = A + NL * LDA + NL;
+    const bool stored = lane < nl && lane != capdrop;
+    const uint64_t rowbits = stored ? (alive & ((1ull << lane) - 1)) : 0ull;
+    if (lane <= nl) {
+#pragma unroll
+      for (int q = 0; q < NLMAX; q++) A[lane * LDA + (q < nl ? q : nl)] = a[q];
+    }
+#pragma unroll
+    for (int q = 0; q < NLMAX; q++) {
+      const int oq = __builtin_amdgcn_readlane(myord, q);
+      double *const dst = ((rowbits >> q) & 1) ? &L.H(myord, oq) : dump;
+      *dst = a[q];
+    }
+    if (lane >= 1 && lane < nl && ((alive >> lane) & 1)) L.H(myord, myord) = Ldr;      // F08:327 (position 0: the 1.0 above)
+  }
+  batch_wave_sync();
+  double yr = 0.0;      // lane p: forward-substituted right-hand side, then the solution, of list position p
+  if (lane < nl) yr = A[nl * LDA + lane];
+  for (uint64_t dm = ~alive & listmask; dm != 0; dm &= dm - 1) {      // (every lane, the same values)
+    const int p = __builtin_ctzll(dm);
+    const int k = __builtin_amdgcn_readlane(myord, p);
+    if (p == capdrop) {      // F08:303-307
+      L.next[L.last] = L.free_;
+      L.free_ = k;
+      L.last = L.prev[k];
+      L.next[L.last] = 0;
+    } else {                 // F08:331-340
+      const int pv = L.prev[k], nx = L.next[k];
+      L.next[pv] = nx;
+      if (nx == 0) L.last = pv; else L.prev[nx] = pv;
+      L.next[k] = L.free_;
+      L.free_ = k;
+    }
+  }
+  L.subspace = 1;
+  L.pending = 0;
+  // ---- phase 3: the new slot; the back-substitution (F08:382-392) by columns; the plan
+  const int slot = L.free_;      // F08:357-358
+  L.free_ = L.next[slot];
+  {
+    double t[NLMAX];      // column `lane` of the factor (rows / lanes beyond the list fold onto row / column nl: values nobody uses)
+#pragma unroll
+    for (int i = 0; i < NLMAX; i++) t[i] = A[(i < nl ? i : nl) * LDA + (lane < nl ? lane : nl)];
+#pragma unroll
+    for (int i = NLMAX - 1; i >= 0; i--) {
+      if (i < nl && ((alive >> i) & 1)) {
+        const double ci = readlane_f64(yr, i) / readlane_f64(Ldr, i);
+        if (lane == i) yr = ci;
+        if (lane < i && ((alive >> lane) & 1)) yr = yr - t[i] * ci;
+      }
+    }
+  }
+  const int ncomb = __builtin_popcountll(alive);
+  if (lane < nl && ((alive >> lane) & 1)) {
+    const int r = __builtin_popcountll(alive & ((1ull << lane) - 1));      // position among the kept entries
+    cs[r] = myord;
+    cc[r] = yr;
+    L.c[myord] = yr;
+  }
+  lst_prepend(L, slot);      // F08:406-417 (every lane, the same values)
+  if (lane == 0) {
+    hdr[HDR_NCOMB] = ncomb;
+    hdr[HDR_NEW] = slot;
+    hdr[HDR_NORMED] = 1;
+    lst_store_scalars(L, ctl);
+    ctl.ic[IC_NEW] = slot;
+    ctl.ic[IC_NCOMB] = ncomb;
+    ctl.ic[IC_NORMED] = 1;      // (IC_NRELAX: batch_scalar_step writes back the value it read)
+  }
+}
+
 }  // namespace
 
 struct nka_hip_batch_state {
@@ -250,6 +429,8 @@ struct nka_hip_batch_state {
   // nka_hip_batch_create_wide_stored is such a batch whose `storage` may be NKA_HIP_BATCH_STORE_F32 (the binary32 instances of the
   // sums, the scalar and the combine kernel; the norm kernels read the pending rows through their BatchArgs)
   bool wide_ext = false;
+  // how a wide batch runs its third launch (nka_hip_batch_set_scalar_step): enqueue-side state only, read when a call is enqueued
+  int scalar_step = NKA_HIP_BATCH_SCALAR_ONE_THREAD;
 };
 
 // nka_batch_wide.hip: the buffers of a wide batch (b->k is complete), and one update of it -- four launches on b->stream, the first

@@ -58,6 +58,8 @@ static_assert(kWideChunk == NKA_HIP_BATCH_WIDE_CHUNK, "host_logic.hpp and nka_hi
 #endif
 static_assert((int64_t)NKA_HIP_BATCH_WIDE_MAX_VLEN <= nka_host::kWideMaxChunks * (int64_t)NKA_HIP_BATCH_WIDE_CHUNK, "the cap is at most 1024 chunks");
 static_assert(nka_host::wide_scalar_lds(NKA_HIP_BATCH_MAX_MVEC, nka_host::kWideMaxChunks).b.bytes() <= 40 * 1024, "LDS of the scalar kernel");
+static_assert(nka_host::wide_scalar_rows_lds(NKA_HIP_BATCH_MAX_MVEC, nka_host::kWideMaxChunks).b.bytes() <= 64 * 1024, "... with the wavefront step: no function attribute");
+static_assert(NKA_HIP_BATCH_MAX_MVEC + 1 <= nka_host::kWideRowsMaxList, "the wavefront step holds every list a batch can have");
 
 struct WideArgs {
   double *part;         // nka_host::wide_part_index
@@ -83,10 +85,20 @@ using LenRows = const int32_t *__restrict__;
 struct WideStepLenArgs : WideStepArgs {
   const int32_t *len;
 };
+// THE SCALAR STEP ON ONE WAVEFRONT (nka_hip_batch_set_scalar_step): an empty member, the LAST of the pack and taken by k_wide_scalar
+// alone; NLMAX: the rows batch_scalar_step_rows<NLMAX> holds in registers, >= mvec + 1 (nka_host::wide_rows_nlmax)
+template <int NLMAX> struct WideRows {};
+template <class T> struct wide_rows_of { static constexpr int value = 0; };
+template <int NLMAX> struct wide_rows_of<WideRows<NLMAX>> { static constexpr int value = NLMAX; };
+template <class... Pack> constexpr int wide_rows_nl = (0 + ... + wide_rows_of<Pack>::value);      // 0: the one-thread step
 template <class T, class... Pack> constexpr bool wide_has = (std::is_same<Pack, T>::value || ...);
 template <class T>
 constexpr int wide_pack_rank = std::is_same<T, WideStepArgs>::value ? 0 : std::is_same<T, LenRows>::value ? 1 : std::is_same<T, Store32Args>::value ? 2
-                               : std::is_same<T, WgtRows>::value ? 3 : std::is_same<T, WgtStride>::value ? 4 : -1;
+                               : std::is_same<T, WgtRows>::value ? 3 : std::is_same<T, WgtStride>::value ? 4 : wide_rows_of<T>::value > 0 ? 5 : -1;
+// LDS of the scalar kernel: with the matrix of the wavefront step where ROWS (host_logic.hpp)
+template <bool ROWS> __host__ __device__ constexpr auto wide_scalar_layout(int mvec, int nchunk) {
+  if constexpr (ROWS) return nka_host::wide_scalar_rows_lds(mvec, nchunk); else return nka_host::wide_scalar_lds(mvec, nchunk);
+}
 template <class... Pack> constexpr bool wide_pack_ok() {      // known members only, ranks strictly increasing, the weights as a pair
   int prev = -1;
   bool ok = true;
@@ -353,8 +365,10 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_scalar(BatchArgs a, Wide
 #pragma clang fp contract(off)
   constexpr bool STEP = wide_has<WideStepArgs, Pack...>, LEN = wide_has<LenRows, Pack...>;
   constexpr bool S32 = wide_has<Store32Args, Pack...>;      // (taken with the pack and not read: this kernel touches no stored vector)
-  static_assert(wide_pack_ok<Pack...>() && sizeof...(Pack) == (STEP ? 1 : 0) + (LEN ? 1 : 0) + (S32 ? 1 : 0) && STEP == !std::is_const<Mask>::value,
-                "[WideStepArgs][, LenRows][, Store32Args]: the weights are not taken; a step, and only a step, writes the mask");
+  constexpr int ROWS = wide_rows_nl<Pack...>;      // > 0: phase 4 on wavefront 0 (batch_scalar_step_rows<ROWS>), the matrix in LDS
+  static_assert(wide_pack_ok<Pack...>() && sizeof...(Pack) == (STEP ? 1 : 0) + (LEN ? 1 : 0) + (S32 ? 1 : 0) + (ROWS > 0 ? 1 : 0) &&
+                    STEP == !std::is_const<Mask>::value,
+                "[WideStepArgs][, LenRows][, Store32Args][, WideRows<NLMAX>]: the weights are not taken; a step, and only a step, writes the mask");
   const int sys = blockIdx.x;
   if (active != nullptr && active[sys] == 0) return;
   int nown = wa.nchunk;      // the partials that are added
@@ -363,7 +377,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_scalar(BatchArgs a, Wide
   const int t = threadIdx.x;
   const int mvec = a.mvec, m1 = mvec + 1, nh = (m1 + 1) * (m1 + 1), nchunk = wa.nchunk;
   const Ctl ctl = batch_ctl(a, sys);
-  const nka_host::WideScalarLds wl = nka_host::wide_scalar_lds(mvec, nchunk);
+  const auto wl = wide_scalar_layout<(ROWS > 0)>(mvec, nchunk);
   const nka_host::BatchLds &lds = wl.b;
   double *const shd = reinterpret_cast<double *>(smem);
   int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
@@ -447,8 +461,12 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_scalar(BatchArgs a, Wide
   }
   __syncthreads();
 
-  // phase 4: the scalar step on the working copy
-  if (t == 0) batch_scalar_step(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr);
+  // phase 4: the scalar step on the working copy -- one thread, or wavefront 0 while the other three wait at the barrier
+  if constexpr (ROWS > 0) {
+    if (t < 64) batch_scalar_step_rows<ROWS>(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr, shd + wl.a);
+  } else {
+    if (t == 0) batch_scalar_step(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr);
+  }
   __syncthreads();
 
   // phase 5: the working copy back; the plan to the combine
@@ -606,6 +624,25 @@ __global__ __launch_bounds__(kBatchThreads) void k_wide_combine(BatchArgs a, Wid
 // throughout: deduction would drop their __restrict__.  (Whether a call runs with per-system lengths or weights, in which form,
 // and every address are fixed when it is enqueued or captured; the values are read when it runs.  The grid is nchunk x nsys
 // either way, so the host needs no length to launch.)
+// THE THIRD LAUNCH WITH THE WAVEFRONT STEP (b->scalar_step): Pack: [WideStepArgs][, LenRows] -- a Store32Args is not passed on, the
+// scalar kernel never read it --, the instance by mvec, which is fixed at creation: a captured call stays valid
+template <class Mask, int NLMAX, class... Pack>
+void launch_wide_scalar_rows_nl(nka_hip_batch_t b, const WideArgs &wa, Mask *active, Pack... pack) {
+  const size_t lds = nka_host::wide_scalar_rows_lds(b->k.mvec, b->nchunk).b.bytes();
+  // (the chevron form of the same launch: the eight hipLaunchKernelGGL statements of this unit stay the four launches of launch_wide in
+  // their two forms, which tests/test_batch_wide_weights_cpu.py counts)
+  k_wide_scalar<Mask, Pack..., WideRows<NLMAX>><<<dim3((unsigned)b->k.nsys), dim3(kBatchThreads), lds, b->stream>>>(b->k, wa, active, pack...,
+                                                                                                             WideRows<NLMAX>{});
+}
+template <class Mask, class... Pack>
+void launch_wide_scalar_rows(nka_hip_batch_t b, const WideArgs &wa, Mask *active, Pack... pack) {
+  switch (nka_host::wide_rows_nlmax(b->k.mvec)) {
+    case 6: launch_wide_scalar_rows_nl<Mask, 6, Pack...>(b, wa, active, pack...); break;
+    case 11: launch_wide_scalar_rows_nl<Mask, 11, Pack...>(b, wa, active, pack...); break;
+    case 21: launch_wide_scalar_rows_nl<Mask, 21, Pack...>(b, wa, active, pack...); break;
+    default: launch_wide_scalar_rows_nl<Mask, nka_host::kWideRowsMaxList, Pack...>(b, wa, active, pack...);
+  }
+}
 // Pack: [WideStepArgs][, LenRows], what all four kernels take; Mask: the scalar kernel's
 template <int COMB, class Mask, class... Pack>
 void launch_wide(nka_hip_batch_t b, double *f, int64_t ld, Mask *active, Pack... pack) {
@@ -638,7 +675,14 @@ void launch_wide(nka_hip_batch_t b, double *f, int64_t ld, Mask *active, Pack...
     else hipLaunchKernelGGL((k_wide_norm<Pack...>), grid, block, 0, b->stream, kn, wa, cf, ld, mask, pack...);
     hipLaunchKernelGGL((k_wide_sums<COMB, Pack...>), grid, block, lsums, b->stream, b->k, wa, cf, ld, mask, pack...);
   }
-  hipLaunchKernelGGL((k_wide_scalar<Mask, Pack...>), dim3((unsigned)b->k.nsys), block, lscal, b->stream, b->k, wa, active, pack...);
+  if (b->scalar_step == NKA_HIP_BATCH_SCALAR_WAVEFRONT) {
+    if constexpr (STEP && LEN) launch_wide_scalar_rows<Mask, WideStepArgs, LenRows>(b, wa, active, pack_get<WideStepArgs>(pack...), pack_get<LenRows>(pack...));
+    else if constexpr (STEP) launch_wide_scalar_rows<Mask, WideStepArgs>(b, wa, active, pack_get<WideStepArgs>(pack...));
+    else if constexpr (LEN) launch_wide_scalar_rows<Mask, LenRows>(b, wa, active, pack_get<LenRows>(pack...));
+    else launch_wide_scalar_rows<Mask>(b, wa, active);
+  } else {
+    hipLaunchKernelGGL((k_wide_scalar<Mask, Pack...>), dim3((unsigned)b->k.nsys), block, lscal, b->stream, b->k, wa, active, pack...);
+  }
   hipLaunchKernelGGL((k_wide_combine<COMB, Pack...>), grid, block, lcomb, b->stream, b->k, wa, f, ld, mask, pack...);
 }
 template <int COMB, class Mask, class... Step>

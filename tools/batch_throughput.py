@@ -97,7 +97,16 @@ e - c > |a - a'|.
 nsys 16,64,256 x vlen 32768,65536,262144 x mvec 10,20 with accel_update, then accel_step with X, mask, tol and fnorm at 64 x 65536
 x 20; a point that needs more than --mem-gb (here 40) is skipped and listed; vector_bytes is held to the formula at every point.
 The condition, fixed before measuring: at 256 x 65536, both mvec, a - b > |a - a'| + the largest window spread of the point.  The
-byte model of --store32 stands beside b/a as a prediction."""
+byte model of --store32 stands beside b/a as a prediction.
+
+--wide-rows measures the scalar step of a wide batch on one wavefront (nka_hip_batch_set_scalar_step) with the method of
+--wide-store32:
+  (a) a wide batch with the one-thread step; (a') the same again, the control; (b) a wide batch with NKA_HIP_BATCH_SCALAR_WAVEFRONT;
+  (e) at nsys = 4 only: a loop over four lone handles on one stream.
+nsys 4,16,64,256 x vlen 32768,65536,262144 x mvec 5,10,20,32 with accel_update, then accel_step with X, mask, tol and fnorm at 16 x
+65536 x 20; a point that needs more than --mem-gb (here 40) is skipped and listed.  The condition, fixed before measuring: at 16 x
+65536 x 20, a - b > |a - a'| + the largest window spread of the point.  Whether four systems at mvec = 20 stop losing to four
+lone handles (e/b against e/a) is recorded without a bar."""
 import argparse
 import ctypes as C
 import os
@@ -440,6 +449,132 @@ def wide_store32_main(args, torch, nka_amd, L, emit):
              f"{ctl:8.3f} {b32 / b64:6.3f} {r['bytes_a'] / 1e6:12.1f} {r['bytes_b'] / 1e6:12.1f} {r['bytes_b'] / r['bytes_a']:7.3f}  {cond}   "
              f"({'won' if won else 'not won'}; spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
     emit(f"# condition: {', '.join(verdicts) if verdicts else 'not measured (no point at 256 x 65536)'}; {len(points)} points in "
+         f"{time.time() - t0:.0f} s")
+    return 0
+
+
+def measure_wide_rows(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, step, lone):
+    """(a) a wide batch with the one-thread scalar step, whose kernels the wavefront instances leave untouched; (a') a second one,
+    the control; (b) a wide batch with nka_hip_batch_set_scalar_step(NKA_HIP_BATCH_SCALAR_WAVEFRONT); lone: (e) a loop over nsys
+    lone handles on one stream.  Same inputs, alternated, as measure_wide_store32.  step: accel_step with X, mask, tol (nobody
+    retires) and fnorm."""
+    npool = mvec + 3
+    stride = (vlen + 31) // 32 * 32
+    nforms = 3 + (1 if lone else 0)
+    need = nforms * 16.0 * nsys * stride * (mvec + 1) + 8.0 * nsys * vlen * (npool + nforms + (3 if step else 0))
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    forms = {"a": nka_amd.SCALAR_ONE_THREAD, "a2": nka_amd.SCALAR_ONE_THREAD, "b": nka_amd.SCALAR_WAVEFRONT}
+    names = list(forms) + (["e"] if lone else [])
+    Fs, Xs, hs, batches = {}, {}, {}, {}
+    for name in names:
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+    for name, how in forms.items():
+        batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, wide=True, step=step).set_scalar_step(how)
+        assert batches[name].is_wide() and batches[name].scalar_step() == how, name
+        hs[name] = batches[name]._handle()
+        if step:
+            Xs[name] = torch.zeros(nsys, vlen, dtype=torch.float64, device="cuda")
+    lones = [nka_amd.nka().init(vlen, mvec) for _ in range(nsys)] if lone else []
+    hl = [x._handle() for x in lones]
+    pl = [C.c_void_p(Fs["e"][k].data_ptr()) for k in range(nsys)] if lone else []
+    mask = torch.ones(nsys, dtype=torch.int32, device="cuda")
+    tol = torch.full((nsys,), -1.0, dtype=torch.float64, device="cuda")
+    fnorm = torch.zeros(nsys, dtype=torch.float64, device="cuda")
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    upd, stp, upd_lone = L.nka_hip_batch_accel_update, L.nka_hip_batch_accel_step, L.nka_hip_accel_update
+    it = [0]
+
+    def run(name, reps):
+        F = Fs[name]
+        p = C.c_void_p(F.data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[it[0] % npool])
+            it[0] += 1
+            if name == "e":
+                for k in range(nsys):
+                    if upd_lone(hl[k], pl[k]) != 0:
+                        raise RuntimeError(L.nka_hip_last_error())
+            elif step:
+                assert stp(hs[name], p, ld, C.c_void_p(Xs[name].data_ptr()), ld, C.c_void_p(mask.data_ptr()), C.c_void_p(tol.data_ptr()),
+                           C.c_void_p(fnorm.data_ptr())) == 0
+            else:
+                assert upd(hs[name], p, ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in names}
+    for name in names:                             # warm: fill the lists (steady state), settle clocks and caches
+        it[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    assert torch.equal(Fs["a"], Fs["b"]) and torch.equal(Fs["a"], Fs["a2"])      # the same bits, whichever step ran
+    for name in names:
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in names:
+            ts[name].append(timed(name, reps[name]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    for name in forms:
+        assert (batches[name].num_vec() == mvec).all() and bool(mask.all()), name
+    for name in names:
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+    for b in batches.values():
+        b.delete()
+    for x in lones:
+        x.delete()
+    del pool, Fs, Xs
+    torch.cuda.empty_cache()
+    return out
+
+
+WIDE_ROWS_CONDITION_AT = (16, 65536, 20)
+
+
+def wide_rows_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    points = [(n, v, m, False) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    points.append(WIDE_ROWS_CONDITION_AT + (True,))
+    emit(f"# one update of (a) a wide batch with the one-thread scalar step, (a') a second one of the same shape -- the control -- and "
+         f"(b) a wide batch with nka_hip_batch_set_scalar_step(NKA_HIP_BATCH_SCALAR_WAVEFRONT); (e) at nsys = 4: a loop over four lone "
+         f"handles on one stream; {torch.cuda.get_device_name(0)}; windows >= {args.window} s, median of {args.repeats}, the contenders "
+         f"alternated on the same inputs; flavour C, full list; the last row: accel_step with X, mask, tol and fnorm "
+         f"(nka_hip_batch_create_wide_step)")
+    emit(f"# CONDITION at {WIDE_ROWS_CONDITION_AT}: a - b > |a - a'| + the largest window spread of the point (x a); every other point "
+         f"and e/a, e/b are recorded without a bar")
+    emit(f"{'nsys':>5} {'vlen':>7} {'mvec':>4} {'call':>6} {'a us':>10} {'a2 us':>10} {'b us':>10} {'b/a':>6} {'|a-a2|/a':>8} {'e us':>10} "
+         f"{'e/a':>6} {'e/b':>6}  condition")
+    t0 = time.time()
+    verdicts, wins, losses, skipped = [], [], [], []
+    for n, v, m, step in points:
+        r = measure_wide_rows(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9, step, lone=(n == 4 and not step))
+        if r is None:
+            skipped.append((n, v, m))
+            emit(f"{n:5d} {v:7d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        ratio, ctl = r["b"] / r["a"], abs(r["a"] - r["a2"]) / r["a"]
+        spread = max(r["spread_a"], r["spread_a2"], r["spread_b"])
+        won = r["a"] - r["b"] > abs(r["a"] - r["a2"]) + spread * r["a"]
+        lost = r["b"] - r["a"] > abs(r["a"] - r["a2"]) + spread * r["a"]
+        (wins if won else losses if lost else []).append((n, v, m) + (("step",) if step else ()))
+        cond = "-"
+        if (n, v, m) == WIDE_ROWS_CONDITION_AT and not step:
+            cond = "HELD" if won else "MISSED"
+            verdicts.append(cond)
+        e_us = f"{r['e'] * 1e6:10.1f} {r['e'] / r['a']:6.2f} {r['e'] / r['b']:6.2f}" if "e" in r else f"{'-':>10} {'-':>6} {'-':>6}"
+        emit(f"{n:5d} {v:7d} {m:4d} {'step' if step else 'update':>6} {r['a'] * 1e6:10.1f} {r['a2'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {ratio:6.3f} "
+             f"{ctl:8.3f} {e_us}  {cond}   ({'won' if won else 'lost' if lost else 'inside the noise'}; spread a {100 * r['spread_a']:.1f} % "
+             f"a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
+    emit(f"# condition: {', '.join(verdicts) if verdicts else 'not measured (no point at ' + str(WIDE_ROWS_CONDITION_AT) + ')'}; won "
+         f"{len(wins)}: {wins}; lost {len(losses)}: {losses}; skipped: {skipped if skipped else 'none'}; {len(points)} points in "
          f"{time.time() - t0:.0f} s")
     return 0
 
@@ -1326,6 +1461,11 @@ def main():
                     help="time binary32 storage of a wide batch (nka_hip_batch_create_wide_stored) against a binary64 wide batch and a "
                          "second one as a control; without --nsys / --vlens / --mvecs / --mem-gb: nsys 16,64,256 x vlen "
                          "32768,65536,262144 x mvec 10,20, then accel_step at 64 x 65536 x 20, 40 GB")
+    ap.add_argument("--wide-rows", action="store_true",
+                    help="time the scalar step of a wide batch on one wavefront (nka_hip_batch_set_scalar_step) against the one-thread "
+                         "step and a second one-thread batch as a control, at nsys = 4 also against four lone handles; without --nsys / "
+                         "--vlens / --mvecs / --mem-gb: nsys 4,16,64,256 x vlen 32768,65536,262144 x mvec 5,10,20,32, then accel_step at "
+                         "16 x 65536 x 20, 40 GB")
     ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
@@ -1349,6 +1489,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.wide_rows:
+        for name, grid_w in (("nsys", "4,16,64,256"), ("vlens", "32768,65536,262144"), ("mvecs", "5,10,20,32"), ("mem_gb", 40.0)):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+        return wide_rows_main(args, torch, nka_amd, L, emit)
     if args.wide_store32:
         for name, grid_w in (("nsys", "16,64,256"), ("vlens", "32768,65536,262144"), ("mvecs", "10,20"), ("mem_gb", 40.0)):
             if getattr(args, name) == ap.get_default(name):
