@@ -433,8 +433,9 @@
  *            33 rows), fixed at creation.  Within the launch no workgroup reads what another writes: no flags, no spinning, no
  *            atomics, no cooperative launch.  Offered by every wide batch (all five wide creation entries, both storages, with
  *            lengths, weights and the step: the third launch reads neither weights nor stored vectors); NKA_HIP_EINVAL, the batch
- *            staying usable, for any other value and for _WAVEFRONT on a narrow, lane or wave batch (_ONE_THREAD is accepted
- *            everywhere; nka_hip_batch_offers_scalar_step tells them apart).
+ *            staying usable, for any other value and for _WAVEFRONT on a narrow or lane batch and on a wave batch of
+ *            nka_hip_batch_create_waves / _create_waves_ext (_ONE_THREAD is accepted everywhere; a wave batch of
+ *            nka_hip_batch_create_waves_rows accepts both, WAVES ROWS below; nka_hip_batch_offers_scalar_step tells them apart).
  *            MEASURED (profiles/r22/batch_wide_rows_throughput.txt, tools/batch_throughput.py --wide-rows: a one-thread batch a, a
  *            second one a' as the control, the wavefront batch b, alternated on the same inputs, windows >= 0.5 s, median of 5; nsys
  *            4 / 16 / 64 / 256 x vlen 32 768 / 65 536 / 262 144 x mvec 5 / 10 / 20 / 32, default flavour, full lists; 256 x 262 144
@@ -448,8 +449,60 @@
  *            64 x 262 144 x 10 and x 20.  FOUR systems at mvec = 20, where WIDE records a loss to four lone handles: the loop over
  *            four lone handles takes 0.69 / 0.74 / 0.83 of the one-thread batch's time at 32 768 / 65 536 / 262 144 and 2.25 / 2.29 /
  *            1.76 x the wavefront batch's -- with the opt-in the batch no longer loses.  One measurement; the default stays
- *            _ONE_THREAD.  Not covered: the narrow batch, whose scalar step sits inside its one kernel (48 instances held to their
- *            machine code), the wave batch and the lane batch keep the one-thread (one-lane) step -- follow-ups.
+ *            _ONE_THREAD.  The wave batch offers the same choice through an entry of its own: WAVES ROWS below.  Not covered: the
+ *            narrow batch, whose scalar step sits inside its one kernel (48 instances held to their machine code), and the lane
+ *            batch keep the one-thread (one-lane) step -- follow-ups.
+ *   WAVES ROWS  nka_hip_batch_create_waves_rows: THE WAVE BATCH THAT OFFERS THE SCALAR STEP ON THE WHOLE WAVEFRONT
+ *            (nka_amd/csrc/nka_batch_waves.hip).  In WAVES lane 0 of a system's wavefront runs the scalar step while 63 lanes wait, and
+ *            from mvec = 10 on that step, not the memory traffic, is what an update costs (profiles/r15/batch_waves_throughput.txt:
+ *            about 20 / 50 / 210 us at mvec 5 / 10 / 20 whatever nsys and vlen are).  A batch of this entry accepts
+ *            nka_hip_batch_set_scalar_step(b, NKA_HIP_BATCH_SCALAR_WAVEFRONT): phase 4 of the one kernel then runs the device function
+ *            of SCALAR STEP on all 64 lanes of the system's own wavefront, in about mvec sequential steps.  ext == 0: limits,
+ *            allocations, refusals and guarantees of nka_hip_batch_create_waves; ext == 1: those of nka_hip_batch_create_waves_ext
+ *            (nka_hip_batch_offers_lengths / _offers_weights return ext); any other ext: NKA_HIP_EINVAL.  nka_hip_batch_kind is 3,
+ *            nka_hip_batch_offers_scalar_step 1, and nothing further is allocated: the matrix of the step lives in dynamic LDS.  The
+ *            default is NKA_HIP_BATCH_SCALAR_ONE_THREAD, which here means one lane; until the setter is called with _WAVEFRONT the batch
+ *            launches the kernels of the corresponding entry and is that batch bit for bit and launch for launch.  The setter is
+ *            enqueue-side state only (no synchronisation, no allocation, legal while the stream is capturing), applies from the next
+ *            accel_update / accel_step on, and a captured call keeps the step it was captured with -- the instance and the LDS size
+ *            it asks for are chosen together when the call is enqueued.  A new entry, because the old ones must not change: a batch
+ *            of nka_hip_batch_create_waves or _create_waves_ext, and every narrow and lane batch, keeps refusing _WAVEFRONT.
+ *            THE CONTRACT: BOTH STEPS LEAVE THE SAME BITS, so switching between calls changes no result.  For every system, after
+ *            every call: the rows of f and x, fnorm, the mask and the retirement decision, red[], all of h and c (the debris of
+ *            dropped rows included), the links, the five list scalars and the counters, nka_hip_batch_state_digest, w and v of every
+ *            slot are those of a one-lane wave batch of the same entry kind on the same inputs -- in all three flavours, with and
+ *            without lengths and weights, on the paths without a new pair (first update, after relax or restart, s == 0), and when
+ *            the system is fed NaN and Inf (tests/test_batch_waves_rows_gpu.py).  Everything WAVES guarantees stays: no workgroup barrier,
+ *            no atomics, flags or spinning (the step is built from wavefront-level means only; one more wavefront-scope fence stands
+ *            between lane 0's stores of the sums and the step); a masked, retired or absent system's wavefront returns on its own,
+ *            before it touches LDS; graphs from the first call; a system's bits depend on its own values alone.
+ *            THE CAP ON mvec IS DERIVED, NOT MEASURED: beside the working copy a system needs a matrix of (mvec + 2)^2 doubles, rounded
+ *            up to 16 bytes, and four copies plus four matrices must fit the 64 KiB of dynamic LDS a launch may ask for without a
+ *            function attribute: 36 672 bytes per workgroup at mvec = 20, 64 832 at 28 (fits), 68 992 at 29 (does not).  Creation with
+ *            mvec above the cap is NKA_HIP_EINVAL with the cap named and nothing left allocated; nka_hip_batch_waves_rows_limits
+ *            returns the cap and the bytes at an mvec, as the library was built (nka_host::waves_rows_max_mvec, a constexpr search;
+ *            tests/c/batch_waves_rows_layout_check.cpp paints the layout).  mvec 29 ... 32: nka_hip_batch_create_waves.  The instance
+ *            is chosen from mvec (6 / 11 / 21 / cap + 1 rows): 96 more instances of the one kernel, none with scratch or a spill, none
+ *            with more registers than its one-lane twin; 1.7 x the LDS per workgroup lowers the resident wavefronts of the sweeps,
+ *            which is the price the measurement weighs.
+ *            MEASURED (profiles/r23/batch_waves_rows_throughput.txt, tools/batch_throughput.py --waves-rows, 1 x MI355X: a one-lane
+ *            wave batch a of nka_hip_batch_create_waves, a second one a' as the control, the wavefront batch b, alternated on the
+ *            same inputs, windows >= 0.5 s, median of 5; nsys 256 / 4096 / 65 536 x vlen 65 / 256 / 1024 x mvec 5 / 10 / 20 / 28,
+ *            default flavour, full lists; 65 536 x 1024 at mvec >= 10 needs more than 40 GB and was not measured).  THE CONDITION,
+ *            fixed beforehand -- at 4096 x 256 x 20 and at 256 x 256 x 20, a - b > |a - a'| plus the largest window spread of the
+ *            three -- HELD at both: 244.1 -> 93.8 us (b/a = 0.384) and 211.1 -> 30.6 us (0.145), the two one-lane batches differing
+ *            by 0.0 % and 0.3 %.  b/a at mvec 5 / 10 / 20 / 28 -- 256 systems: 0.67 / 0.39 / 0.15 / 0.09 at vlen 65, 0.64 / 0.38 /
+ *            0.15 / 0.10 at 256, 0.81 / 0.61 / 0.30 / 0.19 at 1024; 4096 systems: 0.82 / 0.55 / 0.26 / 0.25 at 65, 0.90 / 0.69 / 0.38 /
+ *            0.31 at 256, 0.99 / 0.98 / 0.84 / 0.67 at 1024; 65 536 systems: 0.85 / 0.62 / 0.34 / 0.31 at 65, 1.11 / 0.92 / 0.48 / 0.32
+ *            at 256, 0.92 at 1024 x 5; a step with x, mask, tol and fnorm at 4096 x 256 x 10 / 20: 0.72 / 0.40.  By the same rule WON
+ *            at 34 of the 35 measured points (the two steps among them), LOST at none, INSIDE THE NOISE at 65 536 x 256 x 5 (b/a =
+ *            1.11 where the two one-lane batches themselves differ by 10.5 %).  The gain shrinks where the sweeps, not the step, fill
+ *            the time: 4096 x 1024 at mvec 5 / 10 (0.99 / 0.98) -- there the larger LDS footprint costs what the step saves.  AGAINST
+ *            THE NARROW BATCH AT 256 SYSTEMS, where WAVES records a loss everywhere (here 1.10 ... 1.81 x the narrow batch's time):
+ *            with the wavefront step the wave batch takes 0.74 / 0.47 / 0.18 / 0.11 of it at vlen 65, 0.73 / 0.46 / 0.18 / 0.11 at
+ *            256, and 1.47 / 1.05 / 0.42 / 0.25 at 1024 -- it no longer loses except at 256 x 1024 with mvec 5 and 10.  So: a wave
+ *            batch with mvec from about 10 on, at any nsys, or with any mvec at a few hundred systems up to vlen 256 -- this entry
+ *            with _WAVEFRONT; mvec 29 ... 32 -- nka_hip_batch_create_waves.  One measurement; the default stays _ONE_THREAD.
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -525,6 +578,16 @@ int nka_hip_batch_create_waves_ext(nka_hip_batch_t *out, int32_t nsys, int64_t v
                                    int32_t flavor, int32_t device, void *stream);
 int nka_hip_batch_offers_lengths(nka_hip_batch_t b);
 int nka_hip_batch_offers_weights(nka_hip_batch_t b);
+/* WAVES ROWS above: a wave batch that offers nka_hip_batch_set_scalar_step(b, NKA_HIP_BATCH_SCALAR_WAVEFRONT).  ext == 0: arguments,
+ * limits, allocations, refusals and guarantees of nka_hip_batch_create_waves; ext == 1: those of nka_hip_batch_create_waves_ext
+ * (_offers_lengths and _offers_weights return ext); any other ext: NKA_HIP_EINVAL.  mvec above the cap of _waves_rows_limits:
+ * NKA_HIP_EINVAL, nothing left allocated.  _kind 3; nothing further is allocated.  Until the setter is called with _WAVEFRONT the
+ * batch launches the kernels of the corresponding entry and is that batch bit for bit and launch for launch.
+ * _waves_rows_limits: the cap on mvec -- the largest whose four working copies and four matrices fit 64 KiB of LDS, as the library
+ * was built -- and the LDS bytes of one workgroup at `mvec` (either output may be NULL); NKA_HIP_EINVAL for an mvec outside 1 ... cap. */
+int nka_hip_batch_create_waves_rows(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                                    int32_t flavor, int32_t device, void *stream, int32_t ext);
+int nka_hip_batch_waves_rows_limits(int32_t *max_mvec, int32_t mvec, int64_t *lds_bytes);
 /* WIDE EXT above: the wide batch with nka_hip_batch_set_dot_weights / _host offered.  step == 0: arguments, limits, allocations and
  * guarantees of nka_hip_batch_create_wide; step == 1: those of nka_hip_batch_create_wide_step; any other step: NKA_HIP_EINVAL.
  * _kind 1, _is_wide 1, _offers_lengths 1, _offers_weights 1, _offers_step = step. */
@@ -555,13 +618,15 @@ int nka_hip_batch_relax(nka_hip_batch_t b, const int32_t *active_dev);
 /* call a%set_vec_tol(vtol) for ALL systems (F08:202-207); stream-ordered like the updates around it. */
 int nka_hip_batch_set_vec_tol(nka_hip_batch_t b, double vtol);
 int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order);
-/* SCALAR STEP above: how a wide batch runs the third launch of an update or step.  _set_scalar_step changes enqueue-side state only
+/* SCALAR STEP and WAVES ROWS above: how a wide batch runs the third launch of an update or step, and a wave batch of
+ * nka_hip_batch_create_waves_rows phase 4 of its one launch.  _set_scalar_step changes enqueue-side state only
  * (no synchronisation, no allocation, legal while the stream is capturing) and applies from the next accel_update / accel_step on; a
  * captured call keeps the step it was captured with.  Both steps leave the same bits, so switching between calls changes no
  * result.  NKA_HIP_EINVAL, the batch staying usable and its setting unchanged: any value but the two below; _WAVEFRONT on a batch
  * that does not offer it (_ONE_THREAD is accepted by every batch).  _scalar_step: the value the next call runs with (default
- * _ONE_THREAD); < 0 on error.  _offers_scalar_step: 1 = every wide batch (all five wide creation entries, both storages); 0 =
- * narrow, lanes, waves; < 0 on error. */
+ * _ONE_THREAD); < 0 on error.  _offers_scalar_step: 1 = every wide batch (all five wide creation entries, both storages) and a wave
+ * batch of nka_hip_batch_create_waves_rows (ext 0 or 1); 0 = narrow, lanes, and a wave batch of nka_hip_batch_create_waves or
+ * _create_waves_ext; < 0 on error. */
 enum { NKA_HIP_BATCH_SCALAR_ONE_THREAD = 0, NKA_HIP_BATCH_SCALAR_WAVEFRONT = 1 };
 int nka_hip_batch_set_scalar_step(nka_hip_batch_t b, int32_t how);
 int nka_hip_batch_scalar_step(nka_hip_batch_t b);

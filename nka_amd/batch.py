@@ -48,6 +48,18 @@ def batch_waves_limits():
     return int(group.value), int(cap.value)
 
 
+def batch_waves_rows_limits(mvec: int | None = None):
+    """(max_mvec, lds_bytes) of a wave batch that offers the scalar step on the wavefront (init(..., waves=True, rows=True);
+    nka_hip_batch_waves_rows_limits): the largest mvec whose four working copies and four matrices fit the 64 KiB of dynamic LDS
+    a launch may ask for, as the loaded library was built, and the LDS of one workgroup at `mvec` (default: at that cap)."""
+    cap, lds = C.c_int32(), C.c_int64()
+    L = _lib.load()
+    _check(L.nka_hip_batch_waves_rows_limits(C.byref(cap), 1, None), "nka_hip_batch_waves_rows_limits", L)
+    _check(L.nka_hip_batch_waves_rows_limits(None, int(cap.value if mvec is None else mvec), C.byref(lds)),
+           "nka_hip_batch_waves_rows_limits", L)
+    return int(cap.value), int(lds.value)
+
+
 class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
     """A batch of MI355X accelerator objects; see the module docstring."""
 
@@ -57,7 +69,7 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
              stream: int | None = None, wide: bool = False, storage: int = STORE_F64, lanes: bool = False,
-             waves: bool = False, step: bool = False, ext: bool = False, wide_storage: int = STORE_F64):
+             waves: bool = False, step: bool = False, ext: bool = False, wide_storage: int = STORE_F64, rows: bool = False):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
@@ -79,6 +91,10 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         include/nka_hip_batch.h, WAVES EXT) -- set_lengths and set_dot_weights are offered with the contracts of the default batch,
         a system of length L carries the bits of a wave batch of vlen = L, and with neither set the batch is the plain wave batch
         bit for bit.  ext=True with neither waves=True nor wide=True raises NKAError.
+        rows (with waves=True only, with or without ext=True): the wave batch that OFFERS THE SCALAR STEP ON THE WHOLE WAVEFRONT
+        (nka_hip_batch_create_waves_rows; include/nka_hip_batch.h, WAVES ROWS) -- set_scalar_step(SCALAR_WAVEFRONT) is accepted, and
+        both steps leave the same bits; until it is called the batch is the wave batch (ext=True: with lengths and weights) bit for
+        bit and launch for launch.  mvec is at most batch_waves_rows_limits()[0] = 28.  rows=True without waves=True raises NKAError.
         ext (with wide=True, with or without step=True): the wide batch WITH diagonal dot weights (nka_hip_batch_create_wide_ext;
         include/nka_hip_batch.h, WIDE EXT) -- set_dot_weights is offered in both forms, one shared row or one row per system, with
         the contract of the default batch per chunk; at one chunk it is the weighted default batch bit for bit, with unit weights or
@@ -100,6 +116,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         if ext and not (waves or wide):
             raise NKAError("nka_batch init: ext=True selects the wave batch with lengths and weights and needs waves=True, or the wide "
                            "batch with weights and needs wide=True (the default batch offers both already)")
+        if rows and not waves:
+            raise NKAError("nka_batch init: rows=True selects the wave batch that offers the scalar step on the wavefront and needs "
+                           "waves=True (a wide batch offers set_scalar_step already)")
         if int(wide_storage) != STORE_F64 and not wide:
             raise NKAError("nka_batch init: wide_storage selects the storage of a wide batch and needs wide=True (the default batch: "
                            "storage=STORE_F32)")
@@ -136,6 +155,9 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         elif lanes:
             _check(self._L.nka_hip_batch_create_lanes(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                       C.c_void_p(stream)), "nka_hip_batch_create_lanes", self._L)
+        elif waves and rows:
+            _check(self._L.nka_hip_batch_create_waves_rows(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                           C.c_void_p(stream), 1 if ext else 0), "nka_hip_batch_create_waves_rows", self._L)
         elif waves and ext:
             _check(self._L.nka_hip_batch_create_waves_ext(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
                                                           C.c_void_p(stream)), "nka_hip_batch_create_waves_ext", self._L)
@@ -291,7 +313,7 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def offers_scalar_step(self) -> bool:
         """True where set_scalar_step(SCALAR_WAVEFRONT) is offered: every wide batch, with or without step=True, ext=True or
-        wide_storage=STORE_F32 (nka_hip_batch_offers_scalar_step)."""
+        wide_storage=STORE_F32, and a wave batch of init(..., waves=True, rows=True) (nka_hip_batch_offers_scalar_step)."""
         r = self._L.nka_hip_batch_offers_scalar_step(self._handle())
         _check(min(r, 0), "batch_offers_scalar_step", self._L)
         return bool(r)

@@ -334,6 +334,36 @@ NKA_HOST_DEVICE constexpr WavesLds waves_lds(int mvec) {
   const BatchLds b = batch_lds(mvec);
   return WavesLds{b, ((int64_t)b.bytes() + 15) / 16 * 16};
 }
+// ... and of the instances that run the scalar step on the whole wavefront (nka_hip_batch_create_waves_rows with
+// nka_hip_batch_set_scalar_step; batch_scalar_step_rows of nka_batch_dev.hpp): behind the working copy of wavefront w, the copy of
+// waves_lds at the same offsets, lies that wavefront's dense position-indexed matrix with its right-hand-side row, (mvec + 2)^2
+// doubles rounded up to 16 bytes; wavefront w starts at w * stride_bytes.  36 672 bytes at mvec = 20.  THE CAP ON mvec IS DERIVED:
+// waves_rows_max_mvec() is the largest mvec whose four copies and four matrices fit kWavesRowsLdsLimit = 64 KiB, the dynamic LDS
+// a launch may ask for without a function attribute -- 28 (64 832 bytes; 29 needs 68 992).
+// tests/c/batch_waves_rows_layout_check.cpp paints every piece.
+constexpr int64_t kWavesRowsLdsLimit = 64 * 1024;
+struct WavesRowsLds {
+  BatchLds copy;            // the pieces inside one working copy, as in WavesLds
+  int64_t copy_bytes;       // = waves_lds(mvec).copy_bytes: where the matrix starts behind the start of the copy
+  int64_t a_bytes;          // bytes of one matrix: a multiple of 16
+  NKA_HOST_DEVICE constexpr int64_t stride_bytes() const { return copy_bytes + a_bytes; }
+  NKA_HOST_DEVICE constexpr int64_t base(int w) const { return (int64_t)w * stride_bytes(); }      // the copy of wavefront w
+  NKA_HOST_DEVICE constexpr int64_t a_base(int w) const { return base(w) + copy_bytes; }           // its matrix
+  NKA_HOST_DEVICE constexpr int64_t bytes() const { return kWavesGroup * stride_bytes(); }
+};
+NKA_HOST_DEVICE constexpr WavesRowsLds waves_rows_lds(int mvec) {
+  const WavesLds w = waves_lds(mvec);
+  return WavesRowsLds{w.copy, w.copy_bytes, ((int64_t)sizeof(double) * (mvec + 2) * (mvec + 2) + 15) / 16 * 16};
+}
+NKA_HOST_DEVICE constexpr int waves_rows_max_mvec() {
+  int m = 0;
+  while (waves_rows_lds(m + 1).bytes() <= kWavesRowsLdsLimit) m++;      // (the size grows with mvec)
+  return m;
+}
+// the instance of the wavefront step for a wave batch of `mvec`: the classes of the wide batch, the last one holding the cap's list
+NKA_HOST_DEVICE constexpr int waves_rows_nlmax(int mvec) {
+  return mvec + 1 <= 6 ? 6 : mvec + 1 <= 11 ? 11 : mvec + 1 <= 21 ? 21 : waves_rows_max_mvec() + 1;
+}
 NKA_HOST_DEVICE constexpr int64_t waves_ngroup(int64_t nsys) { return (nsys + kWavesGroup - 1) / kWavesGroup; }
 NKA_HOST_DEVICE constexpr int64_t waves_k(int64_t n) { return 2 * (((n < 1 ? 1 : n) + kWavesTile - 1) / kWavesTile) + 6; }
 

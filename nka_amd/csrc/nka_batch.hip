@@ -643,7 +643,8 @@ extern "C" {
 // per system (this file)
 static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor, int32_t device,
                         void *stream, bool wide, int32_t storage = NKA_HIP_BATCH_STORE_F64, const char *entry = nullptr,
-                        bool lanes = false, bool waves = false, bool wide_step = false, bool waves_ext = false, bool wide_ext = false) {
+                        bool lanes = false, bool waves = false, bool wide_step = false, bool waves_ext = false, bool wide_ext = false,
+                        bool waves_rows = false) {
   const std::string who = entry ? entry : wide ? "nka_hip_batch_create_wide" : "nka_hip_batch_create";
   const bool s32 = storage == NKA_HIP_BATCH_STORE_F32;
   if (!out) return fail(NKA_HIP_EINVAL, who + ": out is NULL");
@@ -669,6 +670,10 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
                                     " (longer systems: nka_hip_batch_create_wide, or lone handles, nka_hip_create)");
   if (mvec < 1 || mvec > NKA_HIP_BATCH_MAX_MVEC)
     return fail(NKA_HIP_EINVAL, who + ": mvec must be 1 ... " + std::to_string((int)NKA_HIP_BATCH_MAX_MVEC));
+  if (waves && waves_rows && mvec > nka_host::waves_rows_max_mvec())      // (derived: four working copies and four matrices in 64 KiB)
+    return fail(NKA_HIP_EINVAL, who + ": mvec must be 1 ... " + std::to_string(nka_host::waves_rows_max_mvec()) +
+                                    " (the wavefront step keeps a matrix of (mvec + 2)^2 doubles per system in LDS beside the working copy; "
+                                    "longer lists: nka_hip_batch_create_waves, which keeps the one-lane step)");
   if (!(vtol > 0.0)) return fail(NKA_HIP_EINVAL, who + ": vtol must be > 0");
   if (int rc = nka_detail::resolve_flavor(&flavor, who.c_str())) return rc;
   if (s32 && flavor != NKA_HIP_FLAVOR_C)
@@ -684,6 +689,7 @@ static int batch_create(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_
   b->lanes = lanes;
   b->waves = waves;
   b->waves_ext = waves && waves_ext;
+  b->waves_rows = waves && waves_rows;
   b->wide_ext = wide && wide_ext;
   b->device = device;
   b->stream = (hipStream_t)stream;
@@ -811,6 +817,16 @@ int nka_hip_batch_create_waves_ext(nka_hip_batch_t *out, int32_t nsys, int64_t v
   return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_waves_ext",
                       false, true, false, true);
 }
+// (a wave batch that offers the scalar step on the wavefront: the batch of one of the two entries above, with the cap on mvec)
+int nka_hip_batch_create_waves_rows(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol, int32_t flavor,
+                                    int32_t device, void *stream, int32_t ext) {
+  if (ext != 0 && ext != 1) {
+    if (out) *out = nullptr;
+    return fail(NKA_HIP_EINVAL, "nka_hip_batch_create_waves_rows: ext must be 0 (nka_hip_batch_create_waves) or 1 (nka_hip_batch_create_waves_ext)");
+  }
+  return batch_create(out, nsys, vlen, mvec, vtol, flavor, device, stream, false, NKA_HIP_BATCH_STORE_F64, "nka_hip_batch_create_waves_rows",
+                      false, true, false, ext == 1, false, true);
+}
 int nka_hip_batch_kind(nka_hip_batch_t b) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_kind: null handle");
   if (b->waves) return NKA_HIP_BATCH_KIND_WAVES;
@@ -937,18 +953,20 @@ int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order) {
   return 0;
 }
 
-// SCALAR STEP: enqueue-side state of a wide batch, read by launch_wide (nka_batch_wide.hip) when a call is enqueued
+// SCALAR STEP: enqueue-side state of a wide batch, read by launch_wide (nka_batch_wide.hip) when a call is enqueued, and of a wave
+// batch of nka_hip_batch_create_waves_rows, read by launch_waves_as (nka_batch_waves.hip)
 int nka_hip_batch_offers_scalar_step(nka_hip_batch_t b) {
-  return b ? (b->wide ? 1 : 0) : fail(NKA_HIP_EINVAL, "batch_offers_scalar_step: null handle");
+  return b ? (b->wide || b->waves_rows ? 1 : 0) : fail(NKA_HIP_EINVAL, "batch_offers_scalar_step: null handle");
 }
 int nka_hip_batch_scalar_step(nka_hip_batch_t b) { return b ? b->scalar_step : fail(NKA_HIP_EINVAL, "batch_scalar_step: null handle"); }
 int nka_hip_batch_set_scalar_step(nka_hip_batch_t b, int32_t how) {
   if (!b) return fail(NKA_HIP_EINVAL, "batch_set_scalar_step: null handle");
   if (how != NKA_HIP_BATCH_SCALAR_ONE_THREAD && how != NKA_HIP_BATCH_SCALAR_WAVEFRONT)
     return fail(NKA_HIP_EINVAL, "batch_set_scalar_step: NKA_HIP_BATCH_SCALAR_ONE_THREAD or NKA_HIP_BATCH_SCALAR_WAVEFRONT");
-  if (how == NKA_HIP_BATCH_SCALAR_WAVEFRONT && !b->wide)
-    return fail(NKA_HIP_EINVAL, "batch_set_scalar_step: NKA_HIP_BATCH_SCALAR_WAVEFRONT is offered by a wide batch only (nka_hip_batch_create_wide "
-                                "and its four siblings): this batch keeps NKA_HIP_BATCH_SCALAR_ONE_THREAD");
+  if (how == NKA_HIP_BATCH_SCALAR_WAVEFRONT && !b->wide && !b->waves_rows)
+    return fail(NKA_HIP_EINVAL, "batch_set_scalar_step: NKA_HIP_BATCH_SCALAR_WAVEFRONT is offered by a wide batch (nka_hip_batch_create_wide "
+                                "and its four siblings) and by a wave batch of nka_hip_batch_create_waves_rows only: this batch keeps "
+                                "NKA_HIP_BATCH_SCALAR_ONE_THREAD");
   b->scalar_step = how;
   return 0;
 }

@@ -424,12 +424,16 @@ struct nka_hip_batch_state {
   bool waves = false;
   // ... of nka_hip_batch_create_waves_ext: the same batch, which also takes lengths and weights (the same unit and kernel)
   bool waves_ext = false;
+  // ... of nka_hip_batch_create_waves_rows: a batch of either entry above (waves_ext = its `ext`) that offers the scalar step on the
+  // whole wavefront; mvec is at most nka_host::waves_rows_max_mvec().  Until scalar_step below says so it launches what they launch
+  bool waves_rows = false;
   // a WIDE batch of nka_hip_batch_create_wide_ext: the same batch, which also takes weights (the weighted instances of the norm and
   // the sums kernel of nka_batch_wide.hip); with wide_step as its `step` argument says.  A batch of
   // nka_hip_batch_create_wide_stored is such a batch whose `storage` may be NKA_HIP_BATCH_STORE_F32 (the binary32 instances of the
   // sums, the scalar and the combine kernel; the norm kernels read the pending rows through their BatchArgs)
   bool wide_ext = false;
-  // how a wide batch runs its third launch (nka_hip_batch_set_scalar_step): enqueue-side state only, read when a call is enqueued
+  // how a wide batch runs its third launch, and a wave batch of nka_hip_batch_create_waves_rows phase 4 of its one launch
+  // (nka_hip_batch_set_scalar_step): enqueue-side state only, read when a call is enqueued
   int scalar_step = NKA_HIP_BATCH_SCALAR_ONE_THREAD;
 };
 

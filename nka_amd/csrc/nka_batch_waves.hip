@@ -8,7 +8,8 @@
 //   2 norm      sum d^2, d = fl(w1 - f) [, sum f^2 in the same sweep: the step]; s = sqrt          -- a step may retire here
 //   3 sums      on the ROUNDED w1' = batch_nrm<RCP>(d, s, 1/s): <f,w1'>, <w1',w_p>, <f,w_p>, kBatchGroup older vectors per sweep,
 //               kBatchAcc accumulators; red[] zeros as in the narrow kernel
-//   4 scalar    lane 0: batch_scalar_step (nka_batch_dev.hpp) on the wavefront's copy
+//   4 scalar    lane 0: batch_scalar_step (nka_batch_dev.hpp) on the wavefront's copy -- or, in the instances with a WavesRows
+//               member (THE SCALAR STEP ON THE WAVEFRONT below), all 64 lanes: batch_scalar_step_rows, the same bits
 //   5 store     the copy and red[] back to the control block, all lanes
 //   6 combine   normalise the pending pair, combine in list order with comb1<COMB> (compact storage in flavour C),
 //               w_new = f_in, v_new = f_out, f [, x = fl(x - f_out)]; four pairs' loads in flight
@@ -32,7 +33,7 @@
 // position or the wavefront the system lands on, on its neighbours, on ld / ldx or on the alignment of a row.  They are NOT the
 // narrow batch's bits (its tile is 512 elements over 256 threads, plus three cross-wavefront additions): the contract is the
 // numerical one of NKA_HIP_SUMS_BLOCKED_ROUNDED.
-// ONE KERNEL, 24 INSTANCES: 3 flavours x {update, step} x {plain, weights, lengths, both}.  What an instance takes beside the
+// ONE KERNEL, 24 INSTANCES (and 4 x 24 more with the scalar step on the wavefront, below): 3 flavours x {update, step} x {plain, weights, lengths, both}.  What an instance takes beside the
 // update's arguments rides in the trailing pack (below), so an instance without a member keeps its arguments; a batch of
 // nka_hip_batch_create_waves can set neither lengths nor weights and runs the plain instances only.
 //   LENGTHS  A trailing LenArgs makes n = len[sys] -- one uniform load behind the `active` test -- the length of EVERY phase: the
@@ -46,6 +47,16 @@
 //            fma(fl(w f), w1', .), red[2+p] fma(fl(w w1'), w_p, .), red[2+m+p] fma(fl(w f), w_p, .), the step's <f,f>
 //            fma(fl(w f), f, .); fl(w f) is formed once per element and sweep.  Phase 6 does not read the weights.  The chain of
 //            roundings behind the first operand is the unweighted one: waves_k(n) stands.
+// THE SCALAR STEP ON THE WAVEFRONT (nka_hip_batch_create_waves_rows, nka_hip_batch_set_scalar_step).  A trailing, empty
+// WavesRows<NLMAX> -- the LAST member of the pack -- makes phase 4 batch_scalar_step_rows<NLMAX> (nka_batch_dev.hpp) on all 64
+// lanes of the system's own wavefront: about mvec sequential steps instead of lane 0's O(mvec^3) chain, and bit for bit what lane
+// 0 leaves, debris included.  It is built from wavefront-level means only, so nothing of SYNCHRONISATION changes: no workgroup
+// barrier, a masked, retired or absent system's wavefront still returns before it touches LDS.  One more wave_sync() stands
+// AHEAD of phase 4: in phase 3 lane 0 alone writes red[], and the rows step reads red[2 + lane] and ps[lane] in the other lanes.
+// The LDS is nka_host::waves_rows_lds: the same copy, then the wavefront's matrix of (mvec + 2)^2 doubles, four times; the launch
+// asks for that size and every other launch for exactly what it asked before.  Instance and size are chosen when a call is
+// enqueued, so a captured call keeps both.  NLMAX by classes of mvec, 6 / 11 / 21 / cap + 1 rows (nka_host::waves_rows_nlmax); the
+// cap on mvec, nka_host::waves_rows_max_mvec(), is where four copies and four matrices still fit 64 KiB.
 #include "nka_batch_dev.hpp"
 
 #include <cstdint>
@@ -63,10 +74,16 @@ constexpr int kWavesThreads = 64 * kWavesGroup;
 static_assert(kWavesGroup == kBatchWaves && kWavesThreads == kBatchThreads, "a workgroup is four wavefronts");
 static_assert(kWavesTile == 2 * 64, "lane l owns the pair 2l, 2l + 1 of a tile");
 static_assert(nka_host::waves_lds(NKA_HIP_BATCH_MAX_MVEC).bytes() <= 64 * 1024, "dynamic LDS a launch may ask for without an attribute");
+static_assert(nka_host::waves_rows_lds(nka_host::waves_rows_max_mvec()).bytes() <= nka_host::kWavesRowsLdsLimit &&
+                  nka_host::waves_rows_lds(nka_host::waves_rows_max_mvec() + 1).bytes() > nka_host::kWavesRowsLdsLimit &&
+                  nka_host::waves_rows_max_mvec() >= 1 && nka_host::waves_rows_max_mvec() <= NKA_HIP_BATCH_MAX_MVEC,
+              "... with the wavefront step: the cap on mvec is the last that fits without a function attribute");
+static_assert(nka_host::waves_rows_max_mvec() + 1 <= nka_host::kWideRowsMaxList && nka_host::waves_rows_max_mvec() + 1 > 21,
+              "the wavefront step holds every list such a batch can have (its masks are 64 bits, its lists at most 33 long)");
 static_assert(NKA_HIP_BATCH_WAVES_MAX_VLEN <= NKA_HIP_BATCH_MAX_VLEN && NKA_HIP_BATCH_WAVES_MAX_VLEN % kWavesTile == 0,
               "the cap is whole tiles, inside the narrow batch's range (the storage is the narrow batch's)");
 
-// THE TRAILING PACK of k_waves_update: [WgtRows, WgtStride][, StepArgs][, LenArgs], each at most once, in this order.
+// THE TRAILING PACK of k_waves_update: [WgtRows, WgtStride][, StepArgs][, LenArgs][, WavesRows<NLMAX>], each at most once, in this order.
 // WgtRows, WgtStride (nka_batch_dev.hpp): the batch's weight buffer and its row stride, the FIRST members
 // what a solve step takes beside the update's arguments (the StepArgs of nka_batch.hip); each pointer may be NULL
 struct StepArgs {
@@ -76,9 +93,20 @@ struct StepArgs {
   double *fnorm;
 };
 // the batch's buffer of nsys validated lengths, 1 <= len[sys] <= vlen (the LenArgs of nka_batch.hip): the LAST member of the pack
+// but for a WavesRows
 struct LenArgs {
   const int32_t *len;
 };
+// THE SCALAR STEP ON THE WAVEFRONT (the head comment): an empty member, the LAST of the pack; NLMAX: the rows
+// batch_scalar_step_rows<NLMAX> holds in registers, >= mvec + 1 (nka_host::waves_rows_nlmax)
+template <int NLMAX> struct WavesRows {};
+template <class T> struct waves_rows_of { static constexpr int value = 0; };
+template <int NLMAX> struct waves_rows_of<WavesRows<NLMAX>> { static constexpr int value = NLMAX; };
+template <class... Pack> constexpr int waves_rows_nl = (0 + ... + waves_rows_of<Pack>::value);      // 0: lane 0 alone
+// LDS of an instance: with the matrices of the wavefront step where ROWS (host_logic.hpp)
+template <bool ROWS> __host__ __device__ constexpr auto waves_layout(int mvec) {
+  if constexpr (ROWS) return nka_host::waves_rows_lds(mvec); else return nka_host::waves_lds(mvec);
+}
 
 // one lane's LDS traffic ordered against the other lanes' of the SAME wavefront (the head comment, SYNCHRONISATION)
 __device__ __forceinline__ void wave_sync() {
@@ -112,8 +140,10 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
   constexpr bool WGT = (std::is_same<Pack, WgtRows>::value || ...);
   constexpr bool STEP = (std::is_same<Pack, StepArgs>::value || ...);
   constexpr bool LEN = (std::is_same<Pack, LenArgs>::value || ...);
-  static_assert(WGT == (std::is_same<Pack, WgtStride>::value || ...) && sizeof...(Pack) == (WGT ? 2 : 0) + (STEP ? 1 : 0) + (LEN ? 1 : 0),
-                "at most one WgtRows with its WgtStride, then at most one StepArgs, then at most one LenArgs");
+  constexpr int ROWS = waves_rows_nl<Pack...>;      // > 0: phase 4 on all 64 lanes (batch_scalar_step_rows<ROWS>), the matrix in LDS
+  static_assert(WGT == (std::is_same<Pack, WgtStride>::value || ...) &&
+                    sizeof...(Pack) == (WGT ? 2 : 0) + (STEP ? 1 : 0) + (LEN ? 1 : 0) + (ROWS > 0 ? 1 : 0),
+                "at most one WgtRows with its WgtStride, then at most one StepArgs, then at most one LenArgs, then at most one WavesRows");
   constexpr int NNRM = STEP ? 2 : 1;      // sums of phase 2: [<f,f>,] <d,d>
   constexpr bool RCP = (COMB == 1);
   constexpr bool COMPACT = (COMB == 2);
@@ -136,7 +166,7 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
   [[maybe_unused]] const double *wg = nullptr;                       // this system's weights (rows: 16-byte aligned)
   if constexpr (WGT) wg = pack_get<WgtRows>(pack...) + (size_t)sys * (size_t)pack_get<WgtStride>(pack...);
 
-  const nka_host::WavesLds wl = nka_host::waves_lds(mvec);
+  const auto wl = waves_layout<(ROWS > 0)>(mvec);
   const nka_host::BatchLds &lds = wl.copy;
   double *const shd = reinterpret_cast<double *>(smem + wl.base(wv));      // this wavefront's working copy
   int32_t *const shi = reinterpret_cast<int32_t *>(shd + lds.ndouble);
@@ -288,8 +318,14 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
     }
   }
 
-  // ---- phase 4: the scalar step on this wavefront's working copy (red, ps: written by lane 0 itself) ----
-  if (lane == 0) batch_scalar_step(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr);
+  // ---- phase 4: the scalar step on this wavefront's working copy.  red and ps were written by lane 0: it runs the step itself,
+  // or, with ROWS, all 64 lanes run it and read them behind a wave_sync ----
+  if constexpr (ROWS > 0) {
+    wave_sync();
+    batch_scalar_step_rows<ROWS>(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr, reinterpret_cast<double *>(smem + wl.a_base(wv)));
+  } else {
+    if (lane == 0) batch_scalar_step(L, ctl, s, nolder, mvec, ps, red, cs, cc, hdr);
+  }
   wave_sync();
 
   // ---- phase 5: the working copy back ----
@@ -364,8 +400,25 @@ __global__ __launch_bounds__(kWavesThreads) void k_waves_update(BatchArgs a, dou
 // THE LAUNCH LADDER: flavour -> weighted? -> lengths? -> launch.  (Whether a call is weighted, in which form, and whether it has
 // lengths travels in the launch: the instance, the two buffers' addresses and the row stride are fixed when the call is enqueued
 // -- or captured --, the buffers' VALUES are read when it runs.)
+// ... -> the scalar step: a batch of nka_hip_batch_create_waves_rows whose setting is NKA_HIP_BATCH_SCALAR_WAVEFRONT launches the
+// instance with a WavesRows<NLMAX> behind the pack and asks for the LDS of waves_rows_lds; every other call is the launch it was
+template <int COMB, int NLMAX, class... Pack>
+void launch_waves_rows_nl(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Pack... pack) {
+  const size_t lds = (size_t)nka_host::waves_rows_lds(b->k.mvec).bytes();
+  hipLaunchKernelGGL((k_waves_update<COMB, Pack..., WavesRows<NLMAX>>), dim3((unsigned)nka_host::waves_ngroup(b->k.nsys)), dim3(kWavesThreads),
+                     lds, b->stream, b->k, f, ld, active, pack..., WavesRows<NLMAX>{});
+}
 template <int COMB, class... Pack>
 void launch_waves_as(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active, Pack... pack) {
+  if (b->waves_rows && b->scalar_step == NKA_HIP_BATCH_SCALAR_WAVEFRONT) {
+    switch (nka_host::waves_rows_nlmax(b->k.mvec)) {
+      case 6: launch_waves_rows_nl<COMB, 6, Pack...>(b, f, ld, active, pack...); break;
+      case 11: launch_waves_rows_nl<COMB, 11, Pack...>(b, f, ld, active, pack...); break;
+      case 21: launch_waves_rows_nl<COMB, 21, Pack...>(b, f, ld, active, pack...); break;
+      default: launch_waves_rows_nl<COMB, nka_host::waves_rows_max_mvec() + 1, Pack...>(b, f, ld, active, pack...);
+    }
+    return;
+  }
   const size_t lds = (size_t)nka_host::waves_lds(b->k.mvec).bytes();
   hipLaunchKernelGGL((k_waves_update<COMB, Pack...>), dim3((unsigned)nka_host::waves_ngroup(b->k.nsys)), dim3(kWavesThreads), lds,
                      b->stream, b->k, f, ld, active, pack...);
@@ -398,6 +451,16 @@ void nka_batch_waves_update(nka_hip_batch_t b, double *f, int64_t ld, const int3
 void nka_batch_waves_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
                           double *fnorm) {
   launch_waves(b, f, ld, active, StepArgs{x, x ? ldx : 0, tol, fnorm});
+}
+
+extern "C" int nka_hip_batch_waves_rows_limits(int32_t *max_mvec, int32_t mvec, int64_t *lds_bytes) {
+  constexpr int cap = nka_host::waves_rows_max_mvec();
+  if (mvec < 1 || mvec > cap)
+    return fail(NKA_HIP_EINVAL, "nka_hip_batch_waves_rows_limits: mvec must be 1 ... " + std::to_string(cap) +
+                                    " (four working copies and four matrices in 64 KiB of LDS)");
+  if (max_mvec) *max_mvec = cap;
+  if (lds_bytes) *lds_bytes = nka_host::waves_rows_lds(mvec).bytes();
+  return 0;
 }
 
 extern "C" int nka_hip_batch_waves_limits(int32_t *systems_per_group, int64_t *max_vlen) {

@@ -106,7 +106,17 @@ byte model of --store32 stands beside b/a as a prediction.
 nsys 4,16,64,256 x vlen 32768,65536,262144 x mvec 5,10,20,32 with accel_update, then accel_step with X, mask, tol and fnorm at 16 x
 65536 x 20; a point that needs more than --mem-gb (here 40) is skipped and listed.  The condition, fixed before measuring: at 16 x
 65536 x 20, a - b > |a - a'| + the largest window spread of the point.  Whether four systems at mvec = 20 stop losing to four
-lone handles (e/b against e/a) is recorded without a bar."""
+lone handles (e/b against e/a) is recorded without a bar.
+
+--waves-rows measures the scalar step of a wave batch on the whole wavefront (nka_hip_batch_create_waves_rows with
+nka_hip_batch_set_scalar_step) with the method of --wide-rows:
+  (a) a wave batch of nka_hip_batch_create_waves, one lane runs the step; (a') the same again, the control; (b) a wave batch of
+  the new entry with NKA_HIP_BATCH_SCALAR_WAVEFRONT; (n) at nsys = 256 only: a narrow batch at NKA_HIP_SUMS_BLOCKED_ROUNDED.
+nsys 256,4096,65536 x vlen 65,256,1024 x mvec 5,10,20 and the cap of nka_hip_batch_waves_rows_limits with accel_update, then
+accel_step with X, mask, tol and fnorm at 4096 x 256 x 10 and x 20; a point that needs more than --mem-gb (here 40) is skipped and
+listed.  The condition, fixed before measuring: at 4096 x 256 x 20 and at 256 x 256 x 20, a - b > |a - a'| + the largest window
+spread of the three.  Every point is judged won / lost / inside the noise by that rule; whether the wave batch still loses to the
+narrow batch at 256 systems is recorded without a bar."""
 import argparse
 import ctypes as C
 import os
@@ -576,6 +586,148 @@ def wide_rows_main(args, torch, nka_amd, L, emit):
     emit(f"# condition: {', '.join(verdicts) if verdicts else 'not measured (no point at ' + str(WIDE_ROWS_CONDITION_AT) + ')'}; won "
          f"{len(wins)}: {wins}; lost {len(losses)}: {losses}; skipped: {skipped if skipped else 'none'}; {len(points)} points in "
          f"{time.time() - t0:.0f} s")
+    return 0
+
+
+def measure_waves_rows(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, step, narrow):
+    """(a) a wave batch of nka_hip_batch_create_waves with the one-lane scalar step, whose kernels the wavefront instances leave
+    untouched; (a') a second one, the control; (b) a wave batch of nka_hip_batch_create_waves_rows with
+    nka_hip_batch_set_scalar_step(NKA_HIP_BATCH_SCALAR_WAVEFRONT); narrow: (n) a narrow batch at the rounded fast sums.  Same
+    inputs, alternated, as measure_wide_rows.  step: accel_step with X, mask, tol (nobody retires) and fnorm."""
+    npool = mvec + 3
+    stride = (vlen + 31) // 32 * 32
+    nforms = 3 + (1 if narrow else 0)
+    need = nforms * 16.0 * nsys * stride * (mvec + 1) + 8.0 * nsys * vlen * (npool + nforms + (3 if step else 0))
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    names = ["a", "a2", "b"] + (["n"] if narrow else [])
+    Fs, Xs, hs, batches = {}, {}, {}, {}
+    for name in names:
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+        if name == "b":
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, waves=True, rows=True)
+            batches[name].set_scalar_step(nka_amd.SCALAR_WAVEFRONT)
+            assert batches[name].scalar_step() == nka_amd.SCALAR_WAVEFRONT
+        elif name == "n":
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C).set_sum_order(nka_amd.SUMS_BLOCKED_ROUNDED)
+        else:
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, waves=True)
+            assert not batches[name].offers_scalar_step()
+        assert batches[name].kind() == (nka_amd.KIND_NARROW if name == "n" else nka_amd.KIND_WAVES), name
+        hs[name] = batches[name]._handle()
+        if step:
+            Xs[name] = torch.zeros(nsys, vlen, dtype=torch.float64, device="cuda")
+    mask = torch.ones(nsys, dtype=torch.int32, device="cuda")
+    tol = torch.full((nsys,), -1.0, dtype=torch.float64, device="cuda")
+    fnorm = torch.zeros(nsys, dtype=torch.float64, device="cuda")
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    upd, stp = L.nka_hip_batch_accel_update, L.nka_hip_batch_accel_step
+    it = [0]
+
+    def run(name, reps):
+        F = Fs[name]
+        p = C.c_void_p(F.data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[it[0] % npool])
+            it[0] += 1
+            if step:
+                assert stp(hs[name], p, ld, C.c_void_p(Xs[name].data_ptr()), ld, C.c_void_p(mask.data_ptr()), C.c_void_p(tol.data_ptr()),
+                           C.c_void_p(fnorm.data_ptr())) == 0
+            else:
+                assert upd(hs[name], p, ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in names}
+    for name in names:                             # warm: fill the lists (steady state), settle clocks and caches
+        it[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    assert torch.equal(Fs["a"], Fs["b"]) and torch.equal(Fs["a"], Fs["a2"])      # the same bits, whichever step ran
+    for name in names:
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in names:
+            ts[name].append(timed(name, reps[name]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    for name in names:
+        assert (batches[name].num_vec() == mvec).all() and bool(mask.all()), name
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+    for b in batches.values():
+        b.delete()
+    del pool, Fs, Xs
+    torch.cuda.empty_cache()
+    return out
+
+
+WAVES_ROWS_CONDITION_AT = ((4096, 256, 20), (256, 256, 20))
+WAVES_ROWS_STEP_AT = ((4096, 256, 10), (4096, 256, 20))
+WAVES_ROWS_NARROW_NSYS = 256
+
+
+def waves_rows_points(nsys, vlens, mvecs, step=True):
+    """The grid of --waves-rows: every update point, then the steps (x, mask, tol, fnorm) where the grid is the default one."""
+    points = [(n, v, m, False) for v in vlens for m in mvecs for n in nsys]
+    return points + ([p + (True,) for p in WAVES_ROWS_STEP_AT] if step else [])
+
+
+def waves_rows_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    cap, _ = nka_amd.batch_waves_rows_limits()
+    points = waves_rows_points(ints(args.nsys), ints(args.vlens), ints(args.mvecs), step=args.waves_rows_steps)
+    # (the condition stands at the head of the record)
+    emit(f"# CONDITION, fixed before the run, at {WAVES_ROWS_CONDITION_AT[0]} and at {WAVES_ROWS_CONDITION_AT[1]}: a - b > |a - a'| + the "
+         f"largest window spread of the three (x a); every other point is recorded and judged won / lost / inside the noise by the same "
+         f"rule, n/a and n/b without a bar")
+    emit(f"# one update of (a) a wave batch with the one-lane scalar step (nka_hip_batch_create_waves), (a') a second one of the same "
+         f"shape -- the control -- and (b) a wave batch of nka_hip_batch_create_waves_rows with nka_hip_batch_set_scalar_step("
+         f"NKA_HIP_BATCH_SCALAR_WAVEFRONT); (n) at nsys = {WAVES_ROWS_NARROW_NSYS}: a narrow batch at NKA_HIP_SUMS_BLOCKED_ROUNDED; "
+         f"{torch.cuda.get_device_name(0)}; windows >= {args.window} s, median of {args.repeats}, the contenders alternated on the same "
+         f"inputs; flavour C, full lists; the cap on mvec is {cap} ({nka_amd.batch_waves_rows_limits()[1]} bytes of LDS per workgroup; "
+         f"{nka_amd.batch_waves_rows_limits(20)[1]} at mvec 20); rows marked step: accel_step with X, mask, tol and fnorm")
+    emit(f"{'nsys':>6} {'vlen':>5} {'mvec':>4} {'call':>6} {'a us':>10} {'a2 us':>10} {'b us':>10} {'b/a':>6} {'|a-a2|/a':>8} {'n us':>10} "
+         f"{'a/n':>6} {'b/n':>6}  condition")
+    t0 = time.time()
+    verdicts, wins, losses, noise, skipped, narrow = [], [], [], [], [], []
+    for n, v, m, step in points:
+        r = measure_waves_rows(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9, step,
+                               narrow=(n == WAVES_ROWS_NARROW_NSYS and not step))
+        if r is None:
+            skipped.append((n, v, m))
+            emit(f"{n:6d} {v:5d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        ratio, ctl = r["b"] / r["a"], abs(r["a"] - r["a2"]) / r["a"]
+        spread = max(r["spread_a"], r["spread_a2"], r["spread_b"])
+        won = r["a"] - r["b"] > abs(r["a"] - r["a2"]) + spread * r["a"]
+        lost = r["b"] - r["a"] > abs(r["a"] - r["a2"]) + spread * r["a"]
+        (wins if won else losses if lost else noise).append((n, v, m) + (("step",) if step else ()))
+        cond = "-"
+        if (n, v, m) in WAVES_ROWS_CONDITION_AT and not step:
+            cond = "HELD" if won else "MISSED"
+            verdicts.append(f"{cond} at {(n, v, m)}")
+        if "n" in r:
+            narrow.append(((n, v, m), r["a"] / r["n"], r["b"] / r["n"]))
+            n_us = f"{r['n'] * 1e6:10.1f} {r['a'] / r['n']:6.2f} {r['b'] / r['n']:6.2f}"
+        else:
+            n_us = f"{'-':>10} {'-':>6} {'-':>6}"
+        emit(f"{n:6d} {v:5d} {m:4d} {'step' if step else 'update':>6} {r['a'] * 1e6:10.1f} {r['a2'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {ratio:6.3f} "
+             f"{ctl:8.3f} {n_us}  {cond}   ({'won' if won else 'lost' if lost else 'inside the noise'}; spread a {100 * r['spread_a']:.1f} % "
+             f"a' {100 * r['spread_a2']:.1f} % b {100 * r['spread_b']:.1f} %)")
+    emit(f"# condition: {'; '.join(verdicts) if verdicts else 'not measured (no point at ' + str(WAVES_ROWS_CONDITION_AT) + ')'}; won "
+         f"{len(wins)}: {wins}; lost {len(losses)}: {losses}; inside the noise {len(noise)}: {noise}; skipped: {skipped if skipped else 'none'}; "
+         f"{len(points)} points in {time.time() - t0:.0f} s")
+    if narrow:
+        emit(f"# against the narrow batch at {WAVES_ROWS_NARROW_NSYS} systems (time / narrow's time): the one-lane wave batch "
+             f"{min(x[1] for x in narrow):.2f} ... {max(x[1] for x in narrow):.2f}, with the wavefront step {min(x[2] for x in narrow):.2f} ... "
+             f"{max(x[2] for x in narrow):.2f}; still slower than the narrow batch at {[x[0] for x in narrow if x[2] > 1.0]}")
     return 0
 
 
@@ -1466,6 +1618,12 @@ def main():
                          "step and a second one-thread batch as a control, at nsys = 4 also against four lone handles; without --nsys / "
                          "--vlens / --mvecs / --mem-gb: nsys 4,16,64,256 x vlen 32768,65536,262144 x mvec 5,10,20,32, then accel_step at "
                          "16 x 65536 x 20, 40 GB")
+    ap.add_argument("--waves-rows", action="store_true",
+                    help="time the scalar step of a wave batch on the whole wavefront (nka_hip_batch_create_waves_rows, "
+                         "nka_hip_batch_set_scalar_step) against the one-lane wave batch and a second one as a control, at nsys = 256 also "
+                         "against the narrow batch; without --nsys / --vlens / --mvecs / --mem-gb: nsys 256,4096,65536 x vlen 65,256,1024 x "
+                         "mvec 5,10,20,cap, then accel_step at 4096 x 256 x 10,20, 40 GB")
+    ap.add_argument("--no-waves-rows-steps", dest="waves_rows_steps", action="store_false", help="--waves-rows: leave the two steps out")
     ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
     args = ap.parse_args()
@@ -1474,6 +1632,11 @@ def main():
     assert torch.cuda.is_available(), "needs the MI355X"
     torch.cuda.set_device(0)
     L = nka_amd.load()
+    if args.waves_rows:      # (ahead of the grid below: the last mvec of this mode is the library's cap)
+        for name, grid_w in (("nsys", "256,4096,65536"), ("vlens", "65,256,1024"), ("mvecs", f"5,10,20,{nka_amd.batch_waves_rows_limits()[0]}"),
+                             ("mem_gb", 40.0)):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
     cap = nka_amd.BATCH_MAX_VLEN
     vl = lambda s: list(dict.fromkeys(cap if v == "cap" else int(v) for v in s.split(",") if v))      # noqa: E731  (cap may be in the list already)
     ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
@@ -1489,6 +1652,8 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if args.waves_rows:
+        return waves_rows_main(args, torch, nka_amd, L, emit)
     if args.wide_rows:
         for name, grid_w in (("nsys", "4,16,64,256"), ("vlens", "32768,65536,262144"), ("mvecs", "5,10,20,32"), ("mem_gb", 40.0)):
             if getattr(args, name) == ap.get_default(name):
