@@ -433,9 +433,10 @@
  *            33 rows), fixed at creation.  Within the launch no workgroup reads what another writes: no flags, no spinning, no
  *            atomics, no cooperative launch.  Offered by every wide batch (all five wide creation entries, both storages, with
  *            lengths, weights and the step: the third launch reads neither weights nor stored vectors); NKA_HIP_EINVAL, the batch
- *            staying usable, for any other value and for _WAVEFRONT on a narrow or lane batch and on a wave batch of
- *            nka_hip_batch_create_waves / _create_waves_ext (_ONE_THREAD is accepted everywhere; a wave batch of
- *            nka_hip_batch_create_waves_rows accepts both, WAVES ROWS below; nka_hip_batch_offers_scalar_step tells them apart).
+ *            staying usable, for any other value and for _WAVEFRONT on a narrow batch of nka_hip_batch_create / _create_stored, on a
+ *            lane batch and on a wave batch of nka_hip_batch_create_waves / _create_waves_ext (_ONE_THREAD is accepted everywhere; a
+ *            wave batch of nka_hip_batch_create_waves_rows accepts both, WAVES ROWS below, and so does a narrow batch of
+ *            nka_hip_batch_create_rows, NARROW ROWS below; nka_hip_batch_offers_scalar_step tells them apart).
  *            MEASURED (profiles/r22/batch_wide_rows_throughput.txt, tools/batch_throughput.py --wide-rows: a one-thread batch a, a
  *            second one a' as the control, the wavefront batch b, alternated on the same inputs, windows >= 0.5 s, median of 5; nsys
  *            4 / 16 / 64 / 256 x vlen 32 768 / 65 536 / 262 144 x mvec 5 / 10 / 20 / 32, default flavour, full lists; 256 x 262 144
@@ -449,9 +450,9 @@
  *            64 x 262 144 x 10 and x 20.  FOUR systems at mvec = 20, where WIDE records a loss to four lone handles: the loop over
  *            four lone handles takes 0.69 / 0.74 / 0.83 of the one-thread batch's time at 32 768 / 65 536 / 262 144 and 2.25 / 2.29 /
  *            1.76 x the wavefront batch's -- with the opt-in the batch no longer loses.  One measurement; the default stays
- *            _ONE_THREAD.  The wave batch offers the same choice through an entry of its own: WAVES ROWS below.  Not covered: the
- *            narrow batch, whose scalar step sits inside its one kernel (48 instances held to their machine code), and the lane
- *            batch keep the one-thread (one-lane) step -- follow-ups.
+ *            _ONE_THREAD.  The wave batch offers the same choice through an entry of its own, WAVES ROWS below, and so
+ *            does the narrow batch, whose scalar step sits inside its one kernel (its older instances held to their machine code):
+ *            NARROW ROWS below.  Not covered: the lane batch keeps the one-lane step -- a follow-up.
  *   WAVES ROWS  nka_hip_batch_create_waves_rows: THE WAVE BATCH THAT OFFERS THE SCALAR STEP ON THE WHOLE WAVEFRONT
  *            (nka_amd/csrc/nka_batch_waves.hip).  In WAVES lane 0 of a system's wavefront runs the scalar step while 63 lanes wait, and
  *            from mvec = 10 on that step, not the memory traffic, is what an update costs (profiles/r15/batch_waves_throughput.txt:
@@ -466,7 +467,8 @@
  *            enqueue-side state only (no synchronisation, no allocation, legal while the stream is capturing), applies from the next
  *            accel_update / accel_step on, and a captured call keeps the step it was captured with -- the instance and the LDS size
  *            it asks for are chosen together when the call is enqueued.  A new entry, because the old ones must not change: a batch
- *            of nka_hip_batch_create_waves or _create_waves_ext, and every narrow and lane batch, keeps refusing _WAVEFRONT.
+ *            of nka_hip_batch_create_waves or _create_waves_ext, every lane batch and every narrow batch but one of
+ *            nka_hip_batch_create_rows (NARROW ROWS below) keeps refusing _WAVEFRONT.
  *            THE CONTRACT: BOTH STEPS LEAVE THE SAME BITS, so switching between calls changes no result.  For every system, after
  *            every call: the rows of f and x, fnorm, the mask and the retirement decision, red[], all of h and c (the debris of
  *            dropped rows included), the links, the five list scalars and the counters, nka_hip_batch_state_digest, w and v of every
@@ -503,6 +505,69 @@
  *            256, and 1.47 / 1.05 / 0.42 / 0.25 at 1024 -- it no longer loses except at 256 x 1024 with mvec 5 and 10.  So: a wave
  *            batch with mvec from about 10 on, at any nsys, or with any mvec at a few hundred systems up to vlen 256 -- this entry
  *            with _WAVEFRONT; mvec 29 ... 32 -- nka_hip_batch_create_waves.  One measurement; the default stays _ONE_THREAD.
+ *   NARROW ROWS  nka_hip_batch_create_rows: THE NARROW BATCH THAT OFFERS THE SCALAR STEP ON ONE WAVEFRONT (nka_amd/csrc/
+ *            nka_batch_kernel.hpp, the instances of nka_amd/csrc/nka_batch_rows.hip).  The batch at the head of this file -- one
+ *            workgroup per system, vlen up to 16 384, all three flavours, weights, lengths, accel_step, either storage -- runs
+ *            phase 4 of its one kernel on thread 0 while 255 threads wait at a barrier: 22 / 42 / 151 us per update at mvec 5 / 10 / 20,
+ *            whatever nsys is (profiles/r08/batch_throughput.txt).  A batch of this entry accepts nka_hip_batch_set_scalar_step(b,
+ *            NKA_HIP_BATCH_SCALAR_WAVEFRONT): phase 4 then runs the device function of SCALAR STEP on the 64 lanes of wavefront 0 of
+ *            the system's workgroup, between the same two barriers, in about mvec sequential steps; wavefronts 1 to 3 go on to the
+ *            second barrier.  storage == NKA_HIP_BATCH_STORE_F64: arguments, limits, allocations, refusals and guarantees of
+ *            nka_hip_batch_create; NKA_HIP_BATCH_STORE_F32: those of nka_hip_batch_create_stored (the default flavour only); any
+ *            other storage: NKA_HIP_EINVAL, with this entry's name in every message.  nka_hip_batch_kind is 0,
+ *            nka_hip_batch_offers_scalar_step 1, _offers_lengths, _offers_weights and _offers_step 1, and nothing further is
+ *            allocated: one host flag, and the matrix of the step lives in dynamic LDS.  mvec up to NKA_HIP_BATCH_MAX_MVEC: there is
+ *            no new cap.  The default is NKA_HIP_BATCH_SCALAR_ONE_THREAD; until the setter is called with _WAVEFRONT the batch
+ *            launches the kernels of the corresponding entry and is that batch bit for bit and launch for launch.  The setter is
+ *            enqueue-side state only (no synchronisation, no allocation, legal while the stream is capturing), applies from the next
+ *            accel_update / accel_step on, and a captured call keeps the step it was captured with -- the instance and the LDS size
+ *            it asks for are chosen together when the call is enqueued.  A new entry, because the old ones must not change: a batch
+ *            of nka_hip_batch_create or _create_stored keeps refusing _WAVEFRONT and keeps returning 0 from _offers_scalar_step.
+ *            FAST SUMS ONLY: the wavefront instances exist for the rounded fast sums.  The reference order is validation speed --
+ *            n dependent additions per sum --, and systems of at most 1024 elements have nka_hip_batch_create_waves_rows.
+ *            nka_hip_batch_set_scalar_step(b, _WAVEFRONT) is therefore refused with NKA_HIP_ESTATE while the batch forms its sums in
+ *            the reference order (NKA_HIP_SUMS_REFERENCE_ORDER, or NKA_HIP_SUMS_AUTO at vlen <= 64), and nka_hip_batch_set_sum_order
+ *            with an order that would mean the reference order is refused with NKA_HIP_ESTATE while _WAVEFRONT is set; each message
+ *            names the other setter and nka_hip_batch_create_waves_rows, the batch stays usable and both settings stay as they were.
+ *            A binary32 batch always runs the fast sums, at every vlen.  So nothing is silently downgraded: a call runs the step
+ *            and the sum order the two getters report.
+ *            THE CONTRACT: BOTH STEPS LEAVE THE SAME BITS, so switching between calls changes no result.  For every system, after
+ *            every call: the rows of f and x, fnorm, the mask and the retirement decision, red[], all of h and c (the debris of
+ *            dropped rows included), the links, the five list scalars and the counters, nka_hip_batch_state_digest, w and v of every
+ *            slot are those of the one-thread step on the same inputs -- in all three flavours, with weights (a row per system or
+ *            the shared row), lengths, accel_step and binary32 storage in any combination, on the paths without a new pair (first
+ *            update, after relax or restart, s == 0), and when the system is fed NaN and Inf (tests/test_batch_rows_gpu.py).
+ *            Everything the batch guarantees stays: within the launch no workgroup reads what another writes, no flags, no
+ *            spinning, no atomics, no cooperative launch (the step is built from wavefront-level means only, and the two workgroup
+ *            barriers around phase 4 are the ones that were there); MASKS, ASYNC, GRAPHS from the first call, BITS.
+ *            LDS: the working copy at the offsets it has in every other instance, and behind it, on the next multiple of 16 bytes,
+ *            the matrix of (mvec + 2)^2 doubles -- 9 168 bytes per workgroup at mvec = 20 (5 296 without the matrix), 20 496 at 32
+ *            (11 248): at most 40 KiB, so four workgroups still share a CU by LDS, and no function attribute is needed.
+ *            nka_hip_batch_rows_limits returns the bytes at an mvec, as the library was built (nka_host::batch_rows_lds;
+ *            tests/c/batch_rows_layout_check.cpp paints the layout).  The instance is chosen from mvec (11 / 21 / 33 rows; the
+ *            11-row instance serves the short lists, where a 6-row instance gave the wide and the wave batch 0.86 ... 0.99): 96 more
+ *            instances of the one kernel body -- 32 fast packs x 3, a unit of their own --, none with scratch or a vector-register
+ *            spill, 90 to 99 VGPR each, the 33-row instances included (at least four wavefronts per SIMD, as their one-thread
+ *            twins have), every older instance unchanged instruction for instruction.
+ *            MEASURED (profiles/r24/batch_rows_throughput.txt, tools/batch_throughput.py --rows, 1 x MI355X: a one-thread batch a of
+ *            this entry, a second one a' as the control, the wavefront batch b, alternated on the same inputs, windows >= 0.5 s,
+ *            median of 5; nsys 16 / 256 / 4096 x vlen 256 / 1024 / 4096 / 16 384 x mvec 5 / 10 / 20 / 32, default flavour, full lists;
+ *            4096 x 16 384 at mvec >= 10 needs more than 40 GB and was not measured).  THE CONDITION, fixed beforehand -- at 256 x
+ *            4096 x 20, a - b > |a - a'| plus the largest window spread of the three -- HELD: 238.8 -> 106.2 us, b/a = 0.445 (|a -
+ *            a'|/a = 0.001); the kernel itself 234.0 -> 100.9 us in a kernel trace of its own.  b/a at mvec 5 / 10 / 20 / 32 -- 16
+ *            systems: 0.80 / 0.45 / 0.18 / 0.08 at vlen 256, 0.80 / 0.47 / 0.18 / 0.09 at 1024, 0.89 / 0.62 / 0.29 / 0.17 at 4096,
+ *            0.96 / 0.87 / 0.62 / 0.39 at 16 384; 256 systems: 0.80 / 0.46 / 0.18 / 0.09, 0.87 / 0.52 / 0.21 / 0.10, 0.92 / 0.74 /
+ *            0.45 / 0.24, 0.95 / 0.91 / 0.72 / 0.54; 4096 systems, sixteen workgroups to a CU: 0.84 / 0.51 / 0.24 / 0.12, 0.90 /
+ *            0.70 / 0.40 / 0.20, 0.98 / 0.94 / 0.82 / 0.59, and 0.92 at 16 384 x 5.  By the same rule WON at all 45 measured
+ *            points, LOST at none, none inside the noise (the two one-thread batches differ by at most 4.0 %).  At 16 systems of 256
+ *            unknowns 17.8 / 40.9 / 163.1 / 525.4 us per update become 14.2 / 18.6 / 28.9 / 44.3.  The gain shrinks where the sweeps, not the step, fill the time -- 4096 x 4096 x 5: 0.98 -- and was not known
+ *            beforehand for launches in which several workgroups share a CU: at 4096 systems it is 0.12 ... 0.98.  AGAINST THE
+ *            WAVE BATCH of nka_hip_batch_create_waves_rows with _WAVEFRONT (b/w, vlen <= 1024, mvec <= 28, recorded without a bar):
+ *            at vlen 256 level at 16 and 256 systems from mvec 10 on (0.98 ... 1.01; 1.12 / 1.13 at mvec 5) and 1.9 ... 2.1 at 4096
+ *            systems, where four systems share a workgroup there; at vlen 1024 0.50 ... 0.62 at 16 and 256 systems and level (0.99 ...
+ *            1.01) at 4096.  So: mvec from about 10 on, or a few hundred systems and fewer at any mvec -- this entry with
+ *            _WAVEFRONT, at every vlen up to 16 384; thousands of systems of at most 256 unknowns -- WAVES ROWS.  One measurement;
+ *            the default stays _ONE_THREAD.
  *   OUT OF SCOPE  per-system mvec or vtol, an automatic restart on a length change, sharding and all-reduce hooks, the user dot product, a per-call weight argument, the out-of-place entry,
  *            the abstract-vector path and Fortran bindings: the reference has no batched type to mirror.  A caller who needs
  *            any of these uses lone handles.
@@ -588,6 +653,18 @@ int nka_hip_batch_offers_weights(nka_hip_batch_t b);
 int nka_hip_batch_create_waves_rows(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
                                     int32_t flavor, int32_t device, void *stream, int32_t ext);
 int nka_hip_batch_waves_rows_limits(int32_t *max_mvec, int32_t mvec, int64_t *lds_bytes);
+/* NARROW ROWS above: a narrow batch (one workgroup per system) that offers nka_hip_batch_set_scalar_step(b,
+ * NKA_HIP_BATCH_SCALAR_WAVEFRONT).  storage == NKA_HIP_BATCH_STORE_F64: arguments, limits, allocations, refusals and guarantees of
+ * nka_hip_batch_create; NKA_HIP_BATCH_STORE_F32: those of nka_hip_batch_create_stored; any other storage: NKA_HIP_EINVAL.  _kind 0;
+ * nothing further is allocated; mvec up to NKA_HIP_BATCH_MAX_MVEC.  Until the setter is called with _WAVEFRONT the batch launches the
+ * kernels of the corresponding entry and is that batch bit for bit and launch for launch.  The wavefront step runs with the fast sums
+ * only: NKA_HIP_ESTATE from the setter while the batch forms its sums in the reference order, and from nka_hip_batch_set_sum_order
+ * for such an order while _WAVEFRONT is set.
+ * _rows_limits: the dynamic LDS of a wavefront-step launch at `mvec`, as the library was built (lds_bytes may be NULL);
+ * NKA_HIP_EINVAL for an mvec outside 1 ... NKA_HIP_BATCH_MAX_MVEC. */
+int nka_hip_batch_create_rows(nka_hip_batch_t *out, int32_t nsys, int64_t vlen, int32_t mvec, double vtol,
+                              int32_t flavor, int32_t device, void *stream, int32_t storage);
+int nka_hip_batch_rows_limits(int32_t mvec, int64_t *lds_bytes);
 /* WIDE EXT above: the wide batch with nka_hip_batch_set_dot_weights / _host offered.  step == 0: arguments, limits, allocations and
  * guarantees of nka_hip_batch_create_wide; step == 1: those of nka_hip_batch_create_wide_step; any other step: NKA_HIP_EINVAL.
  * _kind 1, _is_wide 1, _offers_lengths 1, _offers_weights 1, _offers_step = step. */
@@ -618,15 +695,17 @@ int nka_hip_batch_relax(nka_hip_batch_t b, const int32_t *active_dev);
 /* call a%set_vec_tol(vtol) for ALL systems (F08:202-207); stream-ordered like the updates around it. */
 int nka_hip_batch_set_vec_tol(nka_hip_batch_t b, double vtol);
 int nka_hip_batch_set_sum_order(nka_hip_batch_t b, int32_t order);
-/* SCALAR STEP and WAVES ROWS above: how a wide batch runs the third launch of an update or step, and a wave batch of
- * nka_hip_batch_create_waves_rows phase 4 of its one launch.  _set_scalar_step changes enqueue-side state only
+/* SCALAR STEP, WAVES ROWS and NARROW ROWS above: how a wide batch runs the third launch of an update or step, and a wave batch of
+ * nka_hip_batch_create_waves_rows and a narrow batch of nka_hip_batch_create_rows phase 4 of their one launch.  _set_scalar_step changes enqueue-side state only
  * (no synchronisation, no allocation, legal while the stream is capturing) and applies from the next accel_update / accel_step on; a
  * captured call keeps the step it was captured with.  Both steps leave the same bits, so switching between calls changes no
  * result.  NKA_HIP_EINVAL, the batch staying usable and its setting unchanged: any value but the two below; _WAVEFRONT on a batch
- * that does not offer it (_ONE_THREAD is accepted by every batch).  _scalar_step: the value the next call runs with (default
- * _ONE_THREAD); < 0 on error.  _offers_scalar_step: 1 = every wide batch (all five wide creation entries, both storages) and a wave
- * batch of nka_hip_batch_create_waves_rows (ext 0 or 1); 0 = narrow, lanes, and a wave batch of nka_hip_batch_create_waves or
- * _create_waves_ext; < 0 on error. */
+ * that does not offer it (_ONE_THREAD is accepted by every batch).  NKA_HIP_ESTATE, likewise: _WAVEFRONT on a narrow batch of
+ * nka_hip_batch_create_rows while it forms its sums in the reference order (NARROW ROWS above).  _scalar_step: the value the next
+ * call runs with (default _ONE_THREAD); < 0 on error.  _offers_scalar_step: 1 = every wide batch (all five wide creation entries,
+ * both storages), a wave batch of nka_hip_batch_create_waves_rows (ext 0 or 1) and a narrow batch of nka_hip_batch_create_rows
+ * (either storage); 0 = a narrow batch of nka_hip_batch_create or _create_stored, lanes, and a wave batch of
+ * nka_hip_batch_create_waves or _create_waves_ext; < 0 on error. */
 enum { NKA_HIP_BATCH_SCALAR_ONE_THREAD = 0, NKA_HIP_BATCH_SCALAR_WAVEFRONT = 1 };
 int nka_hip_batch_set_scalar_step(nka_hip_batch_t b, int32_t how);
 int nka_hip_batch_scalar_step(nka_hip_batch_t b);

@@ -150,6 +150,9 @@ BATCH_SIGNATURES = {
     "nka_hip_batch_create_waves_rows": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32,
                                                   C.c_int32, C.c_void_p, C.c_int32]),
     "nka_hip_batch_waves_rows_limits": (C.c_int, [_i32p, C.c_int32, C.POINTER(C.c_int64)]),
+    "nka_hip_batch_create_rows": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32,
+                                            C.c_int32, C.c_void_p, C.c_int32]),
+    "nka_hip_batch_rows_limits": (C.c_int, [C.c_int32, C.POINTER(C.c_int64)]),
     "nka_hip_batch_offers_lengths": (C.c_int, [C.c_void_p]),
     "nka_hip_batch_offers_weights": (C.c_int, [C.c_void_p]),
     "nka_hip_batch_kind": (C.c_int, [C.c_void_p]),

@@ -60,6 +60,16 @@ def batch_waves_rows_limits(mvec: int | None = None):
     return int(cap.value), int(lds.value)
 
 
+def batch_rows_limits(mvec: int):
+    """lds_bytes of one workgroup of a narrow batch that runs the scalar step on wavefront 0 (init(..., narrow_rows=True) with
+    set_scalar_step(SCALAR_WAVEFRONT); nka_hip_batch_rows_limits): the working copy and, behind it, the matrix of (mvec + 2)^2
+    doubles, as the loaded library was built.  mvec outside 1 ... BATCH_MAX_MVEC raises NKAError."""
+    lds = C.c_int64()
+    L = _lib.load()
+    _check(L.nka_hip_batch_rows_limits(int(mvec), C.byref(lds)), "nka_hip_batch_rows_limits", L)
+    return int(lds.value)
+
+
 class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
     """A batch of MI355X accelerator objects; see the module docstring."""
 
@@ -69,7 +79,8 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def init(self, nsys: int, vlen: int, mvec: int, *, flavor: int = FLAVOR_DEFAULT, device: int | None = None,
              stream: int | None = None, wide: bool = False, storage: int = STORE_F64, lanes: bool = False,
-             waves: bool = False, step: bool = False, ext: bool = False, wide_storage: int = STORE_F64, rows: bool = False):
+             waves: bool = False, step: bool = False, ext: bool = False, wide_storage: int = STORE_F64, rows: bool = False,
+             narrow_rows: bool = False):
         """nsys systems of vlen elements, at most mvec vectors each, vtol = 0.01, all restarted.  `stream` is a raw
         hipStream_t (default: torch's current stream on `device`, followed from call to call like `nka`).  wide: every
         system split across workgroups (nka_hip_batch_create_wide: vlen up to batch_wide_limits()[1]; accel_update, masks,
@@ -107,7 +118,12 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         -- the STORAGE contract per chunk, the pending pair and every product and sum still binary64; the default flavour and the
         rounded fast sums only; weights and lengths are offered, accel_step with step=True; at one chunk it is the default batch with
         storage=STORE_F32 bit for bit.  storage=STORE_F32 together with wide=True keeps raising: the keyword of the wide batch is
-        this one.  wide_storage != STORE_F64 without wide=True raises NKAError."""
+        this one.  wide_storage != STORE_F64 without wide=True raises NKAError.
+        narrow_rows: the default batch -- one workgroup per system, vlen up to 16 384, every flavour, weights, lengths, accel_step,
+        storage=STORE_F32 or not -- that OFFERS THE SCALAR STEP ON ONE WAVEFRONT (nka_hip_batch_create_rows; include/nka_hip_batch.h,
+        NARROW ROWS): set_scalar_step(SCALAR_WAVEFRONT) is accepted while the batch runs the fast sums, and both steps leave the
+        same bits; until it is called the batch is the default batch bit for bit and launch for launch.  Together with wide=True,
+        lanes=True or waves=True it raises NKAError."""
         import torch
 
         if step and not wide:
@@ -119,6 +135,10 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         if rows and not waves:
             raise NKAError("nka_batch init: rows=True selects the wave batch that offers the scalar step on the wavefront and needs "
                            "waves=True (a wide batch offers set_scalar_step already)")
+        if narrow_rows and (wide or lanes or waves):
+            raise NKAError("nka_batch init: narrow_rows=True selects the default batch (one workgroup per system) that offers the scalar "
+                           "step on one wavefront and excludes wide=True, lanes=True and waves=True (a wide batch offers "
+                           "set_scalar_step already; a wave batch: waves=True, rows=True)")
         if int(wide_storage) != STORE_F64 and not wide:
             raise NKAError("nka_batch init: wide_storage selects the storage of a wide batch and needs wide=True (the default batch: "
                            "storage=STORE_F32)")
@@ -142,7 +162,10 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
         if stream is None:
             stream = torch.cuda.current_stream(device).cuda_stream
         h = C.c_void_p()
-        if int(storage) != STORE_F64:
+        if narrow_rows:
+            _check(self._L.nka_hip_batch_create_rows(C.byref(h), int(nsys), int(vlen), int(mvec), 0.01, int(flavor), int(device),
+                                                     C.c_void_p(stream), int(storage)), "nka_hip_batch_create_rows", self._L)
+        elif int(storage) != STORE_F64:
             if wide:
                 raise NKAError("nka_batch init: binary32 storage is not offered by a wide batch (storage=STORE_F64) through `storage`: "
                                "wide_storage=STORE_F32 selects it")
@@ -297,23 +320,29 @@ class nka_batch:  # noqa: N801  (beside the reference's type name `nka`)
 
     def set_scalar_step(self, how: int):
         """SCALAR_ONE_THREAD (the default) or SCALAR_WAVEFRONT: how a wide batch runs the third launch of an update or step
-        (include/nka_hip_batch.h, SCALAR STEP) -- the Gram row, the Cholesky with its drop decisions, both substitutions and the
+        (include/nka_hip_batch.h, SCALAR STEP), and a wave batch of rows=True and a default batch of narrow_rows=True phase 4 of
+        their one launch (WAVES ROWS, NARROW ROWS) -- the Gram row, the Cholesky with its drop decisions, both substitutions and the
         combine plan on one thread, or the same arithmetic spread over one wavefront.  Both leave the same bits, so switching
         between calls changes no result.  Enqueue-side state only: no synchronisation, no allocation; applies from the next
         accel_update / accel_step on, and a captured call keeps the step it was captured with.  SCALAR_WAVEFRONT on a batch that
-        does not offer it (offers_scalar_step()) and any other value raise NKAError and the batch stays usable.  Returns self."""
+        does not offer it (offers_scalar_step()) and any other value raise NKAError and the batch stays usable.  A batch of
+        narrow_rows=True has the wavefront step for the fast sums only: SCALAR_WAVEFRONT while it forms its sums in the reference
+        order (explicitly, or SUMS_AUTO at vlen <= 64), and set_sum_order to such an order while SCALAR_WAVEFRONT is set, raise
+        NKAError (NKA_HIP_ESTATE) -- nothing is silently downgraded.  Returns self."""
         _check(self._L.nka_hip_batch_set_scalar_step(self._handle(), int(how)), "batch_set_scalar_step", self._L)
         return self
 
     def scalar_step(self) -> int:
-        """SCALAR_ONE_THREAD or SCALAR_WAVEFRONT: what the next call runs with (nka_hip_batch_scalar_step)."""
+        """SCALAR_ONE_THREAD or SCALAR_WAVEFRONT: what the next call of a wide batch, a wave batch of rows=True or a default batch of
+        narrow_rows=True runs with (nka_hip_batch_scalar_step); every other batch: SCALAR_ONE_THREAD."""
         r = self._L.nka_hip_batch_scalar_step(self._handle())
         _check(min(r, 0), "batch_scalar_step", self._L)
         return r
 
     def offers_scalar_step(self) -> bool:
         """True where set_scalar_step(SCALAR_WAVEFRONT) is offered: every wide batch, with or without step=True, ext=True or
-        wide_storage=STORE_F32, and a wave batch of init(..., waves=True, rows=True) (nka_hip_batch_offers_scalar_step)."""
+        wide_storage=STORE_F32, a wave batch of init(..., waves=True, rows=True) and a default batch of init(..., narrow_rows=True),
+        either storage (nka_hip_batch_offers_scalar_step)."""
         r = self._L.nka_hip_batch_offers_scalar_step(self._handle())
         _check(min(r, 0), "batch_offers_scalar_step", self._L)
         return bool(r)

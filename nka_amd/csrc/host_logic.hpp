@@ -248,6 +248,24 @@ NKA_HOST_DEVICE constexpr BatchLds batch_lds(int mvec) {
   l.nint = l.hdr + 8;
   return l;
 }
+// ... and of the instances of k_batch_update that run the scalar step on wavefront 0 (nka_hip_batch_create_rows with
+// nka_hip_batch_set_scalar_step; batch_scalar_step_rows of nka_batch_dev.hpp): every piece of batch_lds(mvec) AT THE SAME OFFSET,
+// and behind the int32 pieces, on the next multiple of 16 bytes, the dense position-indexed matrix with its right-hand-side row,
+// (mvec + 2)^2 doubles.  9 168 bytes at mvec = 20, 20 496 at 32: at most 40 KiB, four workgroups per CU by LDS, and far below the
+// 64 KiB a launch may ask for without a function attribute.  tests/c/batch_rows_layout_check.cpp paints every piece.
+struct BatchRowsLds {
+  BatchLds b;               // the working copy, as in batch_lds
+  int64_t a_off;            // bytes from the start of the LDS to the matrix: b.bytes() rounded up to 16
+  int64_t a_bytes;          // bytes of the matrix
+  NKA_HOST_DEVICE constexpr int64_t bytes() const { return a_off + a_bytes; }
+};
+NKA_HOST_DEVICE constexpr BatchRowsLds batch_rows_lds(int mvec) {
+  const BatchLds b = batch_lds(mvec);
+  return BatchRowsLds{b, ((int64_t)b.bytes() + 15) / 16 * 16, (int64_t)sizeof(double) * (mvec + 2) * (mvec + 2)};
+}
+// the instance of that step for a narrow batch of `mvec`: the smallest of 11 / 21 / 33 rows that holds mvec + 1 (no 6-row
+// instance: the wide and the wave batch gain 0.86 ... 0.99 at mvec = 5, the 11-row instance serves those lists)
+NKA_HOST_DEVICE constexpr int batch_rows_nlmax(int mvec) { return mvec + 1 <= 11 ? 11 : mvec + 1 <= 21 ? 21 : 33; }
 
 // THE LANE BATCH (nka_hip_batch_create_lanes, nka_batch_lanes.hip): ONE LANE PER SYSTEM.  A workgroup is one wavefront and
 // advances G = lanes_group(mvec) systems, lane l system g * G + l of group g; the grid is lanes_ngroup(nsys, G) workgroups.

@@ -432,7 +432,12 @@ struct nka_hip_batch_state {
   // nka_hip_batch_create_wide_stored is such a batch whose `storage` may be NKA_HIP_BATCH_STORE_F32 (the binary32 instances of the
   // sums, the scalar and the combine kernel; the norm kernels read the pending rows through their BatchArgs)
   bool wide_ext = false;
-  // how a wide batch runs its third launch, and a wave batch of nka_hip_batch_create_waves_rows phase 4 of its one launch
+  // a NARROW batch of nka_hip_batch_create_rows: the batch of nka_hip_batch_create / _create_stored (as `storage` says) that offers
+  // the scalar step on wavefront 0 of a system's workgroup; nothing further is allocated.  Until scalar_step below says so it
+  // launches what they launch
+  bool narrow_rows = false;
+  // how a wide batch runs its third launch, and a wave batch of nka_hip_batch_create_waves_rows and a narrow batch of
+  // nka_hip_batch_create_rows phase 4 of their one launch
   // (nka_hip_batch_set_scalar_step): enqueue-side state only, read when a call is enqueued
   int scalar_step = NKA_HIP_BATCH_SCALAR_ONE_THREAD;
 };
@@ -460,3 +465,9 @@ int nka_batch_lanes_get_slot(nka_hip_batch_t b, bool v, int32_t sys, int32_t slo
 void nka_batch_waves_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
 void nka_batch_waves_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
                           double *fnorm);
+// nka_batch_rows.hip: one update and one solve step of a narrow batch of nka_hip_batch_create_rows (b->narrow_rows) while
+// b->scalar_step is NKA_HIP_BATCH_SCALAR_WAVEFRONT -- one launch each on b->stream, the instance of k_batch_update (nka_batch_kernel.hpp)
+// with the scalar step on wavefront 0, with the flavour, the storage, the weights and the lengths the batch has; fast sums only
+void nka_batch_rows_update(nka_hip_batch_t b, double *f, int64_t ld, const int32_t *active);
+void nka_batch_rows_step(nka_hip_batch_t b, double *f, int64_t ld, double *x, int64_t ldx, int32_t *active, const double *tol,
+                         double *fnorm);

@@ -116,7 +116,17 @@ nsys 256,4096,65536 x vlen 65,256,1024 x mvec 5,10,20 and the cap of nka_hip_bat
 accel_step with X, mask, tol and fnorm at 4096 x 256 x 10 and x 20; a point that needs more than --mem-gb (here 40) is skipped and
 listed.  The condition, fixed before measuring: at 4096 x 256 x 20 and at 256 x 256 x 20, a - b > |a - a'| + the largest window
 spread of the three.  Every point is judged won / lost / inside the noise by that rule; whether the wave batch still loses to the
-narrow batch at 256 systems is recorded without a bar."""
+narrow batch at 256 systems is recorded without a bar.
+
+--rows measures the scalar step of a narrow batch on one wavefront (nka_hip_batch_create_rows with nka_hip_batch_set_scalar_step)
+with the method of --wide-rows:
+  (a) a narrow batch of nka_hip_batch_create_rows left at the one-thread step; (a') the same again, the control; (b) a narrow batch of
+  the same entry with NKA_HIP_BATCH_SCALAR_WAVEFRONT; (w) at vlen <= 1024 only: a wave batch of nka_hip_batch_create_waves_rows with
+  NKA_HIP_BATCH_SCALAR_WAVEFRONT.
+nsys 16,256,4096 x vlen 256,1024,4096,16384 x mvec 5,10,20,32 with accel_update (the wave batch stops at its cap on mvec); a point
+that needs more than --mem-gb (here 40) is skipped and listed.  The condition, fixed before measuring: at 256 x 4096 x 20, a - b >
+|a - a'| + the largest window spread of the three.  Every point is judged won / lost / inside the noise by that rule; b/w is
+recorded without a bar."""
 import argparse
 import ctypes as C
 import os
@@ -728,6 +738,119 @@ def waves_rows_main(args, torch, nka_amd, L, emit):
         emit(f"# against the narrow batch at {WAVES_ROWS_NARROW_NSYS} systems (time / narrow's time): the one-lane wave batch "
              f"{min(x[1] for x in narrow):.2f} ... {max(x[1] for x in narrow):.2f}, with the wavefront step {min(x[2] for x in narrow):.2f} ... "
              f"{max(x[2] for x in narrow):.2f}; still slower than the narrow batch at {[x[0] for x in narrow if x[2] > 1.0]}")
+    return 0
+
+
+def measure_rows(torch, nka_amd, L, nsys, vlen, mvec, window, repeats, mem_budget, waves):
+    """(a) a narrow batch of nka_hip_batch_create_rows left at the one-thread scalar step, which launches the instances every
+    narrow batch launches; (a') a second one, the control; (b) a third with nka_hip_batch_set_scalar_step(
+    NKA_HIP_BATCH_SCALAR_WAVEFRONT); waves: (w) a wave batch of nka_hip_batch_create_waves_rows with the wavefront step.  Same inputs,
+    alternated, as measure_wide_rows; the fast sums (NKA_HIP_SUMS_AUTO beyond 64 elements)."""
+    npool = mvec + 3
+    stride = (vlen + 31) // 32 * 32
+    names = ["a", "a2", "b"] + (["w"] if waves else [])
+    need = len(names) * 16.0 * nsys * stride * (mvec + 1) + 8.0 * nsys * vlen * (npool + len(names))
+    if need > mem_budget:
+        return None
+    pool = torch.randn(npool, nsys, vlen, dtype=torch.float64, device="cuda")
+    Fs, hs, batches = {}, {}, {}
+    for name in names:
+        Fs[name] = torch.empty(nsys, vlen, dtype=torch.float64, device="cuda")
+        if name == "w":
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, waves=True, rows=True)
+        else:
+            batches[name] = nka_amd.nka_batch().init(nsys, vlen, mvec, flavor=nka_amd.FLAVOR_C, narrow_rows=True)
+        assert batches[name].offers_scalar_step() and batches[name].scalar_step() == nka_amd.SCALAR_ONE_THREAD, name
+        if name in ("b", "w"):
+            batches[name].set_scalar_step(nka_amd.SCALAR_WAVEFRONT)
+            assert batches[name].scalar_step() == nka_amd.SCALAR_WAVEFRONT
+        assert batches[name].kind() == (nka_amd.KIND_WAVES if name == "w" else nka_amd.KIND_NARROW), name
+        hs[name] = batches[name]._handle()
+    ld = int(Fs["a"].stride(0)) if nsys > 1 else vlen
+    upd = L.nka_hip_batch_accel_update
+    it = [0]
+
+    def run(name, reps):
+        F = Fs[name]
+        p = C.c_void_p(F.data_ptr())
+        for _ in range(reps):
+            F.copy_(pool[it[0] % npool])
+            it[0] += 1
+            assert upd(hs[name], p, ld, None) == 0
+
+    def timed(name, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run(name, reps)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / reps
+
+    reps, ts = {}, {name: [] for name in names}
+    for name in names:                             # warm: fill the lists (steady state), settle clocks and caches
+        it[0] = 0
+        run(name, mvec + 4)
+    torch.cuda.synchronize()
+    assert torch.equal(Fs["a"], Fs["b"]) and torch.equal(Fs["a"], Fs["a2"])      # the same bits, whichever step ran
+    for name in names:
+        reps[name] = max(3, int(window / timed(name, 3)) + 1)
+    for _ in range(repeats):                       # alternate the contenders
+        for name in names:
+            ts[name].append(timed(name, reps[name]))
+    out = dict(nsys=nsys, vlen=vlen, mvec=mvec)
+    for name in names:
+        assert (batches[name].num_vec() == mvec).all(), name
+        med = statistics.median(ts[name])
+        out[name], out["spread_" + name] = med, (max(ts[name]) - min(ts[name])) / med
+    for b in batches.values():
+        b.delete()
+    del pool, Fs
+    torch.cuda.empty_cache()
+    return out
+
+
+ROWS_CONDITION_AT = (256, 4096, 20)
+
+
+def rows_main(args, torch, nka_amd, L, emit):
+    ints = lambda s: [int(v) for v in s.split(",") if v]                             # noqa: E731
+    wcap, _ = nka_amd.batch_waves_rows_limits()
+    _, wvlen = nka_amd.batch_waves_limits()
+    points = [(n, v, m) for v in ints(args.vlens) for m in ints(args.mvecs) for n in ints(args.nsys)]
+    # (the condition stands at the head of the record)
+    emit(f"# CONDITION, fixed before the run, at {ROWS_CONDITION_AT}: a - b > |a - a'| + the largest window spread of the three (x a); "
+         f"every other point is recorded and judged won / lost / inside the noise by the same rule, b/w without a bar")
+    emit(f"# one update of (a) a narrow batch of nka_hip_batch_create_rows left at the one-thread scalar step, (a') a second one of the "
+         f"same shape -- the control -- and (b) a third with nka_hip_batch_set_scalar_step(NKA_HIP_BATCH_SCALAR_WAVEFRONT); (w) at vlen <= "
+         f"{wvlen} and mvec <= {wcap}: a wave batch of nka_hip_batch_create_waves_rows with the wavefront step; "
+         f"{torch.cuda.get_device_name(0)}; windows >= {args.window} s, median of {args.repeats}, the contenders alternated on the same "
+         f"inputs; flavour C, full lists, the fast sums; dynamic LDS of a wavefront-step launch: {nka_amd.batch_rows_limits(5)} / "
+         f"{nka_amd.batch_rows_limits(10)} / {nka_amd.batch_rows_limits(20)} / {nka_amd.batch_rows_limits(32)} bytes at mvec 5 / 10 / 20 / 32")
+    emit(f"{'nsys':>6} {'vlen':>5} {'mvec':>4} {'a us':>10} {'a2 us':>10} {'b us':>10} {'b/a':>6} {'|a-a2|/a':>8} {'w us':>10} {'b/w':>6}  condition")
+    t0 = time.time()
+    verdicts, wins, losses, noise, skipped = [], [], [], [], []
+    for n, v, m in points:
+        r = measure_rows(torch, nka_amd, L, n, v, m, args.window, args.repeats, args.mem_gb * 1e9, waves=(v <= wvlen and m <= wcap))
+        if r is None:
+            skipped.append((n, v, m))
+            emit(f"{n:6d} {v:5d} {m:4d}   EXCLUDED: needs more than {args.mem_gb:g} GB of device memory")
+            continue
+        ratio, ctl = r["b"] / r["a"], abs(r["a"] - r["a2"]) / r["a"]
+        spread = max(r["spread_a"], r["spread_a2"], r["spread_b"])
+        won = r["a"] - r["b"] > abs(r["a"] - r["a2"]) + spread * r["a"]
+        lost = r["b"] - r["a"] > abs(r["a"] - r["a2"]) + spread * r["a"]
+        (wins if won else losses if lost else noise).append((n, v, m))
+        cond = "-"
+        if (n, v, m) == ROWS_CONDITION_AT:
+            cond = "HELD" if won else "MISSED"
+            verdicts.append(f"{cond} at {(n, v, m)}")
+        w_us = f"{r['w'] * 1e6:10.1f} {r['b'] / r['w']:6.2f}" if "w" in r else f"{'-':>10} {'-':>6}"
+        emit(f"{n:6d} {v:5d} {m:4d} {r['a'] * 1e6:10.1f} {r['a2'] * 1e6:10.1f} {r['b'] * 1e6:10.1f} {ratio:6.3f} {ctl:8.3f} {w_us}  {cond}   "
+             f"({'won' if won else 'lost' if lost else 'inside the noise'}; spread a {100 * r['spread_a']:.1f} % a' {100 * r['spread_a2']:.1f} % "
+             f"b {100 * r['spread_b']:.1f} %)")
+    emit(f"# condition: {'; '.join(verdicts) if verdicts else 'not measured (no point at ' + str(ROWS_CONDITION_AT) + ')'}; won "
+         f"{len(wins)}: {wins}; lost {len(losses)}: {losses}; inside the noise {len(noise)}: {noise}; skipped: {skipped if skipped else 'none'}; "
+         f"{len(points)} points in {time.time() - t0:.0f} s")
     return 0
 
 
@@ -1623,6 +1746,11 @@ def main():
                          "nka_hip_batch_set_scalar_step) against the one-lane wave batch and a second one as a control, at nsys = 256 also "
                          "against the narrow batch; without --nsys / --vlens / --mvecs / --mem-gb: nsys 256,4096,65536 x vlen 65,256,1024 x "
                          "mvec 5,10,20,cap, then accel_step at 4096 x 256 x 10,20, 40 GB")
+    ap.add_argument("--rows", action="store_true",
+                    help="time the scalar step of a narrow batch on one wavefront (nka_hip_batch_create_rows, nka_hip_batch_set_scalar_step) "
+                         "against the one-thread step and a second one-thread batch as a control, at vlen <= 1024 also against the wave "
+                         "batch of nka_hip_batch_create_waves_rows; without --nsys / --vlens / --mvecs / --mem-gb: nsys 16,256,4096 x vlen "
+                         "256,1024,4096,16384 x mvec 5,10,20,32, 40 GB")
     ap.add_argument("--no-waves-rows-steps", dest="waves_rows_steps", action="store_false", help="--waves-rows: leave the two steps out")
     ap.add_argument("--no-store32-extra", dest="store32_extra", action="store_false", help="--store32: leave 4096 x 64 x 10 out")
     ap.add_argument("--no-lengths-wide", dest="lengths_wide", action="store_false", help="--lengths: leave the wide points out")
@@ -1635,6 +1763,10 @@ def main():
     if args.waves_rows:      # (ahead of the grid below: the last mvec of this mode is the library's cap)
         for name, grid_w in (("nsys", "256,4096,65536"), ("vlens", "65,256,1024"), ("mvecs", f"5,10,20,{nka_amd.batch_waves_rows_limits()[0]}"),
                              ("mem_gb", 40.0)):
+            if getattr(args, name) == ap.get_default(name):
+                setattr(args, name, grid_w)
+    if args.rows:
+        for name, grid_w in (("nsys", "16,256,4096"), ("vlens", "256,1024,4096,16384"), ("mvecs", "5,10,20,32"), ("mem_gb", 40.0)):
             if getattr(args, name) == ap.get_default(name):
                 setattr(args, name, grid_w)
     cap = nka_amd.BATCH_MAX_VLEN
@@ -1654,6 +1786,8 @@ def main():
 
     if args.waves_rows:
         return waves_rows_main(args, torch, nka_amd, L, emit)
+    if args.rows:
+        return rows_main(args, torch, nka_amd, L, emit)
     if args.wide_rows:
         for name, grid_w in (("nsys", "4,16,64,256"), ("vlens", "32768,65536,262144"), ("mvecs", "5,10,20,32"), ("mem_gb", 40.0)):
             if getattr(args, name) == ap.get_default(name):
